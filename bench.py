@@ -18,11 +18,16 @@ N ranks (fresh child processes, before anything touches the GPU) when it was not
 a rank that fails — the RCCL broadcast included: it raises on every rank, and there is no fallback unless
 --allow-rccl-fallback is given — makes the whole run exit non-zero.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
-  roofline     — the decode gate/up GEMV (half of the decoder's HBM bytes) timed live with HIP events
-                 on its launch stream inside the timed region, against the 8 TB/s HBM peak;
+Prints ONE JSON line (rank 0) with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step) and the
+phases of the timed steps.  A plain run does only that: set up, warm up, time --steps steps, print.  --full adds
+  decode_roofline, roofline — the decode step against the HBM roofline, and the decode gate/up GEMV (half of the decoder's
+                 HBM bytes) timed live with HIP events on its launch stream (one eager step per --profile-every inside the
+                 timed steps, then a chain of its own), against the 8 TB/s HBM peak;
   cpu_baseline — the oracle (numpy restatement, kind "port") timed on the host cores on a bounded
-                 sample of the same workload.
+                 sample of the same workload, and `parity`: the engine against that oracle run;
+  secondary*   — Qwen2-VL-7B, Qwen2-VL-2B at 32 rows and the corpus through the API, each in a fresh child process.
+--dump-outputs DIR writes what the last timed step returned (GenerateResult: tokens, prompt_tokens, log-probabilities
+with --logprobs) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -455,6 +460,41 @@ def pmc_traffic():
     return None, why
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> list:
+    """`--dump-outputs`: {name: array with the pages on axis 0} -> out_dir/<name>.npy, token ids as float64 (exact), everything
+    else as float32.  When the arrays hold more than `limit` bytes together, the same seeded sample of pages is kept from each
+    of them and the sampled page indices go to pages.npy.  Returns the names written."""
+    conv = {k: np.asarray(v).astype(np.float64 if np.issubdtype(np.asarray(v).dtype, np.integer) else np.float32)
+            for k, v in arrays.items()}
+    n = min(len(a) for a in conv.values())
+    per_page = sum(a.nbytes for a in conv.values()) / max(n, 1) + 8       # + the page's entry in pages.npy
+    budget = limit - 4096 * (len(conv) + 1)                               # .npy headers
+    if per_page * n > budget:
+        keep = int(budget // per_page)
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: one page's outputs alone exceed {limit} bytes")
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        conv = {k: a[idx] for k, a in conv.items()}
+        conv["pages"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(conv)
+
+
+def result_arrays(r) -> dict:
+    """The arrays a caller of Engine.generate receives (finish_reasons are strings; with ignore_eos every page runs to
+    T_out, so the per-page rows stack)."""
+    out = {"tokens": np.stack([np.asarray(t) for t in r.tokens]), "prompt_tokens": np.asarray(r.prompt_tokens)}
+    if r.logprobs is not None and all(lp is not None for lp in r.logprobs):
+        for k in ("token", "top", "top_ids"):
+            out["logprob_" + k] = np.stack([lp[k] for lp in r.logprobs])
+    return out
+
+
 class stdout_to_stderr:
     """File-descriptor level: native libraries (gloo's "[Gloo] Rank 0 is connected ..." banner) print to fd 1, and
     rank 0's stdout must carry exactly ONE line, the JSON."""
@@ -570,14 +610,21 @@ def main():
     ap.add_argument("--page", type=int, default=1024, help="synthetic page side in pixels")
     ap.add_argument("--page-width", type=int, default=None, help="page width when not square (config 5: --page 2200 --page-width 1700)")
     ap.add_argument("--max-pixels", type=int, default=1003520, help="grid A (transformers class default)")
-    ap.add_argument("--profile-every", type=int, default=1000, help="one eager decode step with HIP events around the gate/up launch every N steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--profile-every", type=int, default=None,
+                    help="one eager decode step with HIP events around the gate/up launch every N steps (default: 1000 with --full, "
+                         "else 0: none)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure beyond the headline: decode roofline, live kernel timing, CPU baseline + parity and, at N = 1, the "
+                         "secondary runs (a plain run sets up, warms up, times --steps steps and prints the result line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity block")
     ap.add_argument("--allow-rccl-fallback", action="store_true",
                     help="N > 1: when the RCCL weight broadcast fails, report rccl_error / rccl_ranks null, let every rank generate the "
                          "seeded weights and still measure (default: the run exits non-zero — a failed broadcast is a failed N-GPU run)")
     ap.add_argument("--strict-rccl", action="store_true", help="(the default since round 4; accepted for older command lines)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the runs that follow the headline at N = 1 (Qwen2-VL-7B at BASELINE config 3's per-GPU shapes + its full-depth "
+                    help="with --full: skip the runs that follow the headline at N = 1 (Qwen2-VL-7B at BASELINE config 3's per-GPU shapes + its full-depth "
                          "parity, Qwen2-VL-2B at 32 rows, the corpus through the API): each is a fresh child process")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--guided", action="store_true",
@@ -596,6 +643,10 @@ def main():
                     help="CPU rehearsal of the N-rank control plane (self-launch, rendezvous, barriers, max-over-ranks timing, "
                          "rank 0's JSON line, exit codes) with no engine: the line carries \"dry_run\": true and no measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.profile_every is None:
+        args.profile_every = 1000 if args.full else 0
 
     if args.secondary_child:
         print(json.dumps(secondary_child(args.secondary_child, args)), flush=True)
@@ -647,7 +698,7 @@ def main():
     for i in range(B):
         im = IP.synthetic_page(rank * B + i, args.page, args.page_width or args.page)
         page_imgs.append(im)
-        if i == 0 and rank == 0:      # host-side patches of page 0: the CPU baseline's input (same pixels as the GPU's)
+        if i == 0 and rank == 0 and args.full:   # host-side patches of page 0: the CPU baseline's input (same pixels as the GPU's)
             pv, g = IP.image_to_patches(im, max_pixels=args.max_pixels)
             pvs.append(pv)
         else:
@@ -703,13 +754,14 @@ def main():
 
     for _ in range(args.warmup):
         one_step()
-    eng.kernel_profile(reset=True)
-    # dispatch gap of a dependent launch in a replayed graph on this stream (what a rocprofv3 kernel
-    # span contains on top of the kernel's execution: spans are contiguous in a graph replay)
     import ctypes as C
-    floor_us = C.c_float()
-    lib().kr_probe_launch_floor(eng.s, 200, 256, 0, C.byref(floor_us))
-    floor_us = float(floor_us.value)
+    if args.full:
+        eng.kernel_profile(reset=True)
+        # dispatch gap of a dependent launch in a replayed graph on this stream (what a rocprofv3 kernel
+        # span contains on top of the kernel's execution: spans are contiguous in a graph replay)
+        floor_us = C.c_float()
+        lib().kr_probe_launch_floor(eng.s, 200, 256, 0, C.byref(floor_us))
+        floor_us = float(floor_us.value)
 
     def barrier():
         torch.cuda.synchronize()
@@ -735,13 +787,22 @@ def main():
         rates = [None] * world
         dist.all_gather_object(rates, per_rank_pps[0])
         per_rank_pps = rates
-    prof = eng.kernel_profile()
-    chain = eng.gate_up_chain_profile(B)   # live, HIP events on the launch stream, right after the timed steps
-    # what a read-only stream reaches on THIS device (achieved-vs-measured-stream next to the vendor peak): the
-    # weight arena (GBs: far beyond the 256 MB Infinity Cache) read once with 16-byte nontemporal loads, best of 3
-    stream_gbs = C.c_float()
-    lib().kr_probe_stream_read(eng.w.arena.data_ptr(), min(int(eng.w.nbytes), 4 << 30) // 16 * 16, 2048, 3, eng.s, C.byref(stream_gbs))
-    stream_gbs = float(stream_gbs.value)
+    if args.dump_outputs:
+        arrays = result_arrays(r)            # the last timed step's result; the pages of all ranks, in rank order
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, arrays)
+            arrays = {k: np.concatenate([p[k] for p in parts]) for k in arrays}
+        if rank == 0:
+            log(f"outputs of the last timed step -> {args.dump_outputs}: {dump_outputs(args.dump_outputs, arrays)}")
+    if args.full:
+        prof = eng.kernel_profile()
+        chain = eng.gate_up_chain_profile(B)   # live, HIP events on the launch stream, right after the timed steps
+        # what a read-only stream reaches on THIS device (achieved-vs-measured-stream next to the vendor peak): the
+        # weight arena (GBs: far beyond the 256 MB Infinity Cache) read once with 16-byte nontemporal loads, best of 3
+        stream_gbs = C.c_float()
+        lib().kr_probe_stream_read(eng.w.arena.data_ptr(), min(int(eng.w.nbytes), 4 << 30) // 16 * 16, 2048, 3, eng.s, C.byref(stream_gbs))
+        stream_gbs = float(stream_gbs.value)
 
     if rank == 0:
         pages_total = world * B * args.steps
@@ -751,12 +812,6 @@ def main():
         bytes_step = cfg.decoder_weight_bytes(args.weights) + sum(p + T_out / 2 for p in P) * kvb
         t_step_roof = bytes_step / (HBM_PEAK_GBS * 1e9)
         decode_step_s = phase["decode_s"] / max(T_out - 1, 1)
-        # kernel launches of one decode step: 6 per layer (7 above 16 rows with the separate residual-sum + RMSNorm launch) + lm_head + sampling
-        per_layer = 6 + (1 if (B > 16 and (eng.resnorm_qkv or (eng.family32 and eng.resnorm32_qkv))) else 0)
-        launches_per_step = per_layer * cfg.text.num_layers + 2
-        traffic, traffic_src = pmc_traffic()   # the committed PMC pass is of the default workload: not quoted for other shapes
-        if traffic is not None and abs(traffic / chain["bytes_per_launch"] - 1.0) > 0.25:
-            traffic = None
         out = {
             "metric": "pages_per_sec", "value": round(value, 4), "unit": "pages/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 2),
@@ -778,18 +833,26 @@ def main():
             "p50_latency_s": round(float(np.median(step_times)), 4),
             "phases_s": {k: round(v, 4) for k, v in phase.items()},
             "decode_step_ms": round(1e3 * decode_step_s, 4),
-            "decode_roofline": {"bytes_per_step": int(bytes_step), "t_step_roof_ms": round(1e3 * t_step_roof, 4),
-                                "frac_of_hbm_peak": round(t_step_roof / decode_step_s, 4) if decode_step_s > 0 else None,
-                                "pages_per_s_roof_per_gpu": round(B / (T_out * t_step_roof), 3),
-                                # how much of the step is seams, and what the fraction is against what a stream reaches here
-                                # (VERDICT r3 next #5): launches per step x the measured dependent-launch gap; the read-only
-                                # streaming rate of this device measured by kr_probe_stream_read just after the timed steps
-                                "launches_per_step": launches_per_step, "dispatch_gap_us": round(floor_us, 3),
-                                "launch_floor_ms": round(launches_per_step * floor_us * 1e-3, 4),
-                                "hbm_stream_measured_GBps": round(stream_gbs, 1),
-                                "frac_of_measured_stream": (round(bytes_step / (stream_gbs * 1e9) / decode_step_s, 4)
-                                                            if decode_step_s > 0 and stream_gbs > 0 else None)},
-            "roofline": {
+        }
+        if args.full:
+            # kernel launches of one decode step: 6 per layer (7 above 16 rows with the separate residual-sum + RMSNorm launch) + lm_head + sampling
+            per_layer = 6 + (1 if (B > 16 and (eng.resnorm_qkv or (eng.family32 and eng.resnorm32_qkv))) else 0)
+            launches_per_step = per_layer * cfg.text.num_layers + 2
+            traffic, traffic_src = pmc_traffic()   # the committed PMC pass is of the default workload: not quoted for other shapes
+            if traffic is not None and abs(traffic / chain["bytes_per_launch"] - 1.0) > 0.25:
+                traffic = None
+            out["decode_roofline"] = {"bytes_per_step": int(bytes_step), "t_step_roof_ms": round(1e3 * t_step_roof, 4),
+                                      "frac_of_hbm_peak": round(t_step_roof / decode_step_s, 4) if decode_step_s > 0 else None,
+                                      "pages_per_s_roof_per_gpu": round(B / (T_out * t_step_roof), 3),
+                                      # how much of the step is seams, and what the fraction is against what a stream reaches here
+                                      # (VERDICT r3 next #5): launches per step x the measured dependent-launch gap; the read-only
+                                      # streaming rate of this device measured by kr_probe_stream_read just after the timed steps
+                                      "launches_per_step": launches_per_step, "dispatch_gap_us": round(floor_us, 3),
+                                      "launch_floor_ms": round(launches_per_step * floor_us * 1e-3, 4),
+                                      "hbm_stream_measured_GBps": round(stream_gbs, 1),
+                                      "frac_of_measured_stream": (round(bytes_step / (stream_gbs * 1e9) / decode_step_s, 4)
+                                                                  if decode_step_s > 0 and stream_gbs > 0 else None)}
+            out["roofline"] = {
                 "kernel": "dec_wide_kernel<4, K/64> = <SILU8> (decode gate/up projection + fused RMSNorm + SiLU*mul, one wave per weight tile)",
                 "bound": "hbm",
                 "achieved": round(chain["bytes_per_launch"] / (chain["avg_us"] * 1e-6) / 1e9, 1),
@@ -806,8 +869,7 @@ def main():
                 # the same launch bracketed by events inside the timed decode steps (eager steps every --profile-every):
                 "in_step": {"event_bracket_us": round(prof["bracket_us"], 3), "empty_bracket_us": round(prof["null_bracket_us"], 3),
                             "dispatch_gap_us": round(floor_us, 3), "launches_timed": prof["launches"]},
-            },
-        }
+            }
         out["timed_region"] = ("uint8 RGB pages resident in HBM -> GPU image front end -> ViT -> prefill -> "
                                f"{T_out} decode steps (host-side PNG decode and the 3 MB/page H2D copy are outside)")
         if rccl_error is not None:
@@ -826,7 +888,7 @@ def main():
             out["per_rank_pages_per_s"] = [round(float(x), 3) for x in per_rank_pps]
             if os.environ.get("KARANTA_BENCH_SHARE_GPUS") == "1" and n_dev < world:
                 out["config"]["WARNING"] = f"control-flow rehearsal: {world} ranks on {n_dev} GPU(s) — not an N-GPU measurement"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("timing the CPU baseline (oracle, bounded sample) ...")
             out["cpu_baseline"], oracle_run = cpu_baseline(cfg, pvs[0], grids[0], pages[0].input_ids, T_out, weights=host_weights)
             if oracle_run is not None:
@@ -839,7 +901,7 @@ def main():
         del host_weights
         default_workload = (args.model == "Qwen2-VL-2B" and args.batch == 8 and args.weights == "bf16" and args.page == 1024
                             and args.page_width is None)
-        if world == 1 and default_workload and not args.no_secondary:
+        if args.full and world == 1 and default_workload and not args.no_secondary:
             # each in a FRESH child process, after this process has released its engine: a fault, hang or OOM kill there
             # cannot take the (complete) headline record down
             import gc

@@ -151,3 +151,37 @@ def test_failed_rccl_broadcast_is_reported_and_every_rank_generates_the_seeded_w
     eng2 = _FakeArenaEngine(fill=0)
     s, ranks, err = bench.distribute_weights(eng2, 1, 2, good, gather, lambda: {"fill": 7}, strict=False)
     assert (s, ranks, err) == (0.25, 2, None) and eng2.loaded is None
+
+
+def test_dump_outputs_writes_what_generate_returned_as_float_arrays(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's GenerateResult as DIR/<name>.npy — token ids as exact float64,
+    log-probabilities as float32 — and, over the size limit, the same seeded sample of pages from every array."""
+    import types
+
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    B, T, k = 6, 40, 3
+    toks = [rng.integers(0, 151000, T) for _ in range(B)]
+    lps = [{"token": rng.standard_normal(T).astype(np.float32), "top": rng.standard_normal((T, k)).astype(np.float32),
+            "top_ids": rng.integers(0, 151000, (T, k))} for _ in range(B)]
+    r = types.SimpleNamespace(tokens=toks, prompt_tokens=[1394] * B, logprobs=lps)
+    arrays = bench.result_arrays(r)
+    names = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert names == ["logprob_token", "logprob_top", "logprob_top_ids", "prompt_tokens", "tokens"]
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in names}
+    assert got["tokens"].dtype == np.float64 and (got["tokens"] == np.stack(toks)).all()
+    assert got["logprob_top_ids"].dtype == np.float64 and got["logprob_top"].dtype == np.float32
+    assert (got["logprob_top"] == np.stack([lp["top"] for lp in lps])).all()
+    assert bench.result_arrays(types.SimpleNamespace(tokens=toks, prompt_tokens=[1] * B, logprobs=None)).keys() == {"tokens", "prompt_tokens"}
+
+    per_page = T * 8 + 8 + T * 4 + T * k * 4 + T * k * 8 + 8                  # tokens, prompt_tokens, log-probs, pages.npy entry
+    limit = 4096 * 6 + 3 * per_page                                             # room for the headers and 3 of the 6 pages
+    names = bench.dump_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, limit=limit)
+    pages = np.load(tmp_path / "a" / "pages.npy")
+    assert "pages" in names and len(pages) == 3 and (np.diff(pages) > 0).all()
+    assert (np.load(tmp_path / "b" / "pages.npy") == pages).all()                 # seeded: the same sample every run
+    assert (np.load(tmp_path / "a" / "tokens.npy") == np.stack(toks)[pages.astype(int)]).all()
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in names) <= limit
