@@ -516,6 +516,40 @@ int kr_gumbel_argmax_guided(const float* logits, int64_t ld_logits, int vocab, c
                             int32_t* amax_idx, int n_part, int batch, const uint64_t* guide_masks,
                             const int32_t* guide_state, int mask_words, int fallback_token, kr_stream s);
 
+/* ------------------------------------------------------------------ sampling controls (vLLM's top_k / top_p / min_p and
+ * repetition / frequency / presence penalties).  Per row b, params[b * 8 + j]: j = 0 top_k (<= 0: off), 1 top_p (>= 1: off),
+ * 2 min_p (<= 0: off), 3 repetition_penalty (1: off), 4 frequency_penalty, 5 presence_penalty (0: off), 6-7 unused.
+ * counts [batch][ld_counts]: how often each token occurs in the row's output so far (kr_sample_count);
+ * prompt_bits [batch][bits_words]: bit i set <=> token i occurs in the row's prompt.  The score of an allowed token
+ * (guide mask as in kr_gumbel_argmax_guided) is v = l' * (1 / T) with l' = the logit after the penalties, in fp32:
+ * l' = (in prompt or c > 0) ? (l > 0 ? l / r : l * r) : l, then l' -= f * c + p * (c > 0).  Logits are read, never written.
+ *
+ * kr_sample_threshold: per row with T > 0 and any truncation on, threshold[b] = the order-preserving key
+ * (sign-flipped float bits) of the smallest kept score: the largest of v_max + ln(min_p), the top_k-th largest v (ties kept)
+ * and the top_p cut (the v of the first token, by descending v, at which the cumulative probability of what min_p / top_k
+ * kept reaches top_p; ties kept).  0: keep every allowed token (T == 0 or neutral truncation).  Deterministic (integer
+ * histograms).  work [batch][ld_work] fp32 is scratch.  live[b] = whether this step appends a real token to row b
+ * (ignore_eos bit 0 set or finished[b] == 0): what kr_sample_count counts after kr_sample_greedy. */
+int kr_sample_threshold(const float* logits, int64_t ld_logits, int vocab, const float* temperature, const float* params,
+                        const int32_t* counts, int64_t ld_counts, const uint32_t* prompt_bits, int bits_words,
+                        const uint64_t* guide_masks, const int32_t* guide_state, int mask_words, const int32_t* finished,
+                        int ignore_eos, float* work, int64_t ld_work, uint32_t* threshold, int32_t* live, int batch,
+                        kr_stream s);
+
+/* kr_gumbel_argmax_guided over the penalised scores, restricted to the tokens whose score key is >= threshold[b] (rows
+ * with T > 0; a T == 0 row is the plain argmax of l').  Same [batch][n_part] partials for kr_sample_greedy; a row with
+ * neutral params gets the partials of kr_gumbel_argmax_guided bit for bit. */
+int kr_gumbel_argmax_processed(const float* logits, int64_t ld_logits, int vocab, const float* temperature,
+                               const uint32_t* seed, const int32_t* ctx_len, const int32_t* prompt_len, float* amax_val,
+                               int32_t* amax_idx, int n_part, int batch, const uint64_t* guide_masks,
+                               const int32_t* guide_state, int mask_words, int fallback_token, const float* params,
+                               const int32_t* counts, int64_t ld_counts, const uint32_t* prompt_bits, int bits_words,
+                               const uint32_t* threshold, kr_stream s);
+
+/* After kr_sample_greedy: counts[b][tokens[b]] += 1 for the rows with live[b] != 0 (kr_sample_threshold of this step). */
+int kr_sample_count(const int32_t* tokens, const int32_t* live, int32_t* counts, int64_t ld_counts, int vocab, int batch,
+                    kr_stream s);
+
 /* After the sampler: guide_state[b] <- walk(guide_state[b], bytes(tokens[b])) through the table at device address
  * guide_trans[b] (0: row unconstrained); rows with finished[b] != 0 keep their state. */
 int kr_guide_advance(const int32_t* tokens, const int32_t* finished, const uint64_t* guide_trans, int32_t* guide_state,

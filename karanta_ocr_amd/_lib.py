@@ -80,6 +80,10 @@ SIGNATURES = {
     "kr_gumbel_argmax": [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, c_p],
     "kr_gumbel_argmax_guided": [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, c_p, c_p, i32, i32, c_p],
     "kr_guide_build_masks": [c_p, c_p, i32, c_p, c_p, i32, c_p, i32, c_p, i32, c_p],
+    "kr_sample_threshold": [c_p, i64, i32, c_p, c_p, c_p, i64, c_p, i32, c_p, c_p, i32, c_p, i32, c_p, i64, c_p, c_p, i32, c_p],
+    "kr_gumbel_argmax_processed": [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, c_p, c_p, i32, i32, c_p, c_p, i64, c_p,
+                                   i32, c_p, c_p],
+    "kr_sample_count": [c_p, c_p, c_p, i64, i32, i32, c_p],
     "kr_guide_advance": [c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, c_p],
     "kr_logprobs_topk": [c_p, i64, i32, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, c_p],
     "kr_linear_decode_narrow": [i32, c_p, i64, c_p, i32, c_p, i64, c_p, c_p, c_p, f32, c_p, i64, c_p, c_p, i64,

@@ -26,6 +26,7 @@ from . import positions as POS
 from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_GELU_ERF, EPI_NONE, EPI_QUICK_GELU, EPI_SILU_MUL8,
                    KarantaHipError, lib, narrow_opts, ptr)
 from .config import ModelConfig
+from .sampling import has_penalties, needs_processing, sampling_params
 from .weights import pack_w16x64, to_bf16_bits
 
 BF16 = torch.bfloat16
@@ -243,6 +244,14 @@ class PageRequest:
     #                                            (numpy arrays, or torch uint8 tensors already resident in HBM)
     guide: Any = None                          # guided.Guide / DeviceGuide: the output must match this pattern
     logprobs: Optional[int] = None             # None: off; k >= 0: log-prob of every token + the k most probable (<= 20)
+    # vLLM's sampling controls (kr_sample_threshold / kr_gumbel_argmax_processed); the defaults are "off"
+    top_k: int = 0                             # 0 or -1: off; k: keep the k largest scores (ties kept)
+    top_p: float = 1.0                         # 1: off; keep the smallest top set whose probability reaches top_p
+    min_p: float = 0.0                         # 0: off; keep p_i >= min_p * p_max
+    repetition_penalty: float = 1.0            # 1: off; tokens of the prompt or the output so far: l > 0 ? l / r : l * r
+    frequency_penalty: float = 0.0             # l -= frequency_penalty * (count in the output so far)
+    presence_penalty: float = 0.0              # l -= presence_penalty * (count > 0)
+
 
 
 @dataclass
@@ -286,6 +295,8 @@ class Engine:
         self.n_split = decode_splits
         self._ignore_eos = self._freeze_finished = self._want_logits = self._sampling = False
         self._guided = False          # the decode graph masks logits by the slots' DFA states and advances them
+        self._processing = False      # ... and applies the sampling controls (penalties, min_p / top_k / top_p; needs_processing)
+        self._cap_processing = False
         # what the current mode ALLOWS (begin_slots(sampling=, guided=); generate(): what its pages need): _sampling / _guided say
         # what the next decode step RUNS — in slot mode they follow the requests that are actually in the slots (set_step_features)
         self._cap_sampling = self._cap_guided = False
@@ -460,6 +471,15 @@ class Engine:
         self.d_gmasks = z(B, dtype=torch.int64)
         self.d_gstate = z(B, dtype=torch.int32)
         self.mask_words = 2 * ((t.vocab_size + 63) // 64)
+        # sampling controls: per-slot params (sampling_params), output-token counts, prompt-token bit set, the threshold pass's
+        # scratch scores, threshold keys and live flags (kr_sample_threshold / kr_gumbel_argmax_processed / kr_sample_count)
+        self.d_sp = torch.tensor(np.tile(sampling_params(PageRequest(np.zeros(0, np.int64))), (B, 1)), device=dev)
+        self.d_counts = z(B, t.vocab_size, dtype=torch.int32)
+        self.bits_words = (t.vocab_size + 31) // 32
+        self.d_pbits = z(B, self.bits_words, dtype=torch.int32)
+        self.d_work = z(B, t.vocab_size, dtype=torch.float32)
+        self.d_thr = z(B, dtype=torch.int32)
+        self.d_live = z(B, dtype=torch.int32)
         self.d_voc_off = self.d_voc_bytes = None   # set_vocab()
         self._guides: Dict[str, DeviceGuide] = {}
         self._slot_guides: Dict[int, DeviceGuide] = {}   # keeps the tables of the running requests alive
@@ -1010,6 +1030,7 @@ class Engine:
                                           "(generate() decides from its pages; begin_slots(sampling=True) for slot mode)")
                 self._sampling = True
             grows = self._guide_rows(pages)
+            procs = self._processing_rows(pages)
             if whole_batch:
                 tb, sb = np.zeros(self.B, np.float32), np.zeros(self.B, np.int32)
                 tb[:B], sb[:B] = temps, seeds
@@ -1031,8 +1052,10 @@ class Engine:
                 self._h2d(self.d_plen, plen)
                 self._h2d(self.d_cs, cs)
                 self.d_fin.zero_()
+                if procs is not None:
+                    self._write_processing(list(range(B)), procs)
             elif not defer_activation:
-                self._write_slot_state(slots, lens, deltas, cs, temps, seeds, grows)
+                self._write_slot_state(slots, lens, deltas, cs, temps, seeds, grows, procs)
             self._h2d(self.d_last, last_rows)
             t_ = lambda a: torch.from_numpy(a).to(dev)
             blk_tok0, blk_ntok, blk_kr, blk_vb = t_(plan.blk_tok0), t_(plan.blk_ntok), t_(plan.blk_k_row0), t_(plan.blk_vt_blk)
@@ -1064,10 +1087,43 @@ class Engine:
             elif not defer_activation:
                 self._first_tokens(slots)
         if defer_activation:
-            return {"slots": slots, "lens": lens, "deltas": deltas, "cs": cs, "temps": temps, "seeds": seeds, "guides": grows}
+            return {"slots": slots, "lens": lens, "deltas": deltas, "cs": cs, "temps": temps, "seeds": seeds, "guides": grows,
+                    "procs": procs}
         return lens
 
-    def _write_slot_state(self, slots, lens, deltas, cs, temps, seeds, guides=None):
+    def _processing_rows(self, pages):
+        """Per page (params row, prompt bit set or None, penalised) when the engine may run the processing launches, else None;
+        raises for a page that uses the sampling controls where it may not."""
+        need = [needs_processing(p) for p in pages]
+        if any(need):
+            if not self._cap_processing:
+                raise KarantaHipError("a page asks for top_k / top_p / min_p / penalties but the engine is in its greedy "
+                                      "configuration (generate() decides from its pages; begin_slots(sampling=True) for slot mode)")
+            self._processing = True       # from this admission on the steps carry the processing launches
+        if not self._cap_processing:
+            return None
+        V, rows = self.cfg.text.vocab_size, []
+        for p, nd in zip(pages, need):
+            sp = sampling_params(p)
+            bits = None
+            if nd and sp[3] != 1.0:       # repetition penalty: the prompt's tokens (image placeholders included)
+                ids = np.asarray(p.input_ids, np.int64).reshape(-1)
+                ids = ids[(ids >= 0) & (ids < V)]
+                bits = np.zeros(self.bits_words, np.uint32)
+                np.bitwise_or.at(bits, ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
+            rows.append((sp, bits, nd))
+        return rows
+
+    def _write_processing(self, slots, procs):
+        """Sampling-control state of newly admitted slots: params, prompt bits, output counts cleared."""
+        for (sp, bits, nd), j in zip(procs, slots):
+            self._h2d(self.d_sp[j], sp)
+            if bits is not None:
+                self._h2d(self.d_pbits[j], bits.view(np.int32))
+            if nd:
+                self.d_counts[j].zero_()
+
+    def _write_slot_state(self, slots, lens, deltas, cs, temps, seeds, guides=None, procs=None):
         for b, j in enumerate(slots):
             a_t, a_m, st, dg = guides[b] if guides is not None else (0, 0, 0, None)
             self._h2d(self.d_gtrans[j:j + 1], np.asarray([a_t], np.int64))
@@ -1084,6 +1140,8 @@ class Engine:
             self._h2d(self.d_temp[j:j + 1], temps[b:b + 1])
             self._h2d(self.d_seed[j:j + 1], seeds[b:b + 1])
             self.d_fin[j:j + 1].zero_()
+        if procs is not None:
+            self._write_processing(slots, procs)
 
     def _first_tokens(self, slots):
         """Last prompt position of every prefilled sequence (p_x rows d_last) -> its slot's x -> lm_head -> first token."""
@@ -1100,14 +1158,28 @@ class Engine:
         t, L, w, s = self.cfg.text, self.L, self.w, self.s
         x = self.d_x if x is None else x
         j = slot0  # rows j .. j+B-1 of every per-sequence array (the slot scheduler prefills single slots)
-        logits = self.d_logits[j:] if (self._want_logits or self._sampling or self._logprobs is not None) else None
+        logits = self.d_logits[j:] if (self._want_logits or self._sampling or self._processing or self._logprobs is not None) else None
         if self.wide_mode:
             self._dec_wide(DEC_ARGMAX, x[j:], w.view("llm.lm_head"), B, norm_w=w.view("llm.norm.w"), out_f32=logits)
         else:
             self._dec(DEC_ARGMAX, x[j:], w.view("llm.lm_head"), B, norm_w=w.view("llm.norm.w"), out_f32=logits,
                       waves=self.wv_wide)
         n_part = self._amax_parts(B) if self.wide_mode else self.n_amax   # the stride the lm_head launch wrote with
-        if self._sampling:
+        flags = (1 if self._ignore_eos else 0) | (2 if self._freeze_finished else 0)
+        gm, gs = (ptr(self.d_gmasks[j:]), ptr(self.d_gstate[j:])) if self._guided else (None, None)
+        if self._processing:
+            # sampling controls somewhere in the batch: per-row truncation threshold, then the Gumbel-max argmax over the
+            # penalised scores above it (rows with neutral controls get exactly the partials of the branch below)
+            n_part = min(64, n_part)
+            V, ld = t.vocab_size, self.d_logits.stride(0)
+            L.kr_sample_threshold(ptr(logits), ld, V, ptr(self.d_temp[j:]), ptr(self.d_sp[j:]), ptr(self.d_counts[j:]), V,
+                                  ptr(self.d_pbits[j:]), self.bits_words, gm, gs, self.mask_words, ptr(self.d_fin[j:]), flags,
+                                  ptr(self.d_work[j:]), V, ptr(self.d_thr[j:]), ptr(self.d_live[j:]), B, s)
+            L.kr_gumbel_argmax_processed(ptr(logits), ld, V, ptr(self.d_temp[j:]), ptr(self.d_seed[j:]), ptr(self.d_ctx[j:]),
+                                         ptr(self.d_plen[j:]), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, B, gm, gs,
+                                         self.mask_words, int(self.cfg.eos_token_ids[0]), ptr(self.d_sp[j:]),
+                                         ptr(self.d_counts[j:]), V, ptr(self.d_pbits[j:]), self.bits_words, ptr(self.d_thr[j:]), s)
+        elif self._sampling:
             # temperature > 0 somewhere in the batch: the partial argmax is redone on logits / T + Gumbel noise
             # (rows with T = 0 get their plain argmax back)
             n_part = min(64, n_part)
@@ -1119,11 +1191,12 @@ class Engine:
             else:
                 L.kr_gumbel_argmax(ptr(logits), self.d_logits.stride(0), t.vocab_size, ptr(self.d_temp[j:]), ptr(self.d_seed[j:]),
                                    ptr(self.d_ctx[j:]), ptr(self.d_plen[j:]), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, B, s)
-        flags = (1 if self._ignore_eos else 0) | (2 if self._freeze_finished else 0)
         L.kr_sample_greedy(ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(w.view("llm.embed")), t.hidden_size,
                            ptr(self.d_tok[j:]), ptr(self.d_hist[:, j:]), self.d_hist.stride(0), ptr(self.d_plen[j:]),
                            ptr(self.d_ctx[j:]), ptr(self.d_fin[j:]), ptr(self.d_eos), self.d_eos.numel(),
                            self.cfg.pad_token_id, flags, ptr(self.d_x[j:]), B, s)
+        if self._processing:
+            L.kr_sample_count(ptr(self.d_tok[j:]), ptr(self.d_live[j:]), ptr(self.d_counts[j:]), t.vocab_size, t.vocab_size, B, s)
         if self._guided:
             L.kr_guide_advance(ptr(self.d_tok[j:]), ptr(self.d_fin[j:]), ptr(self.d_gtrans[j:]), ptr(self.d_gstate[j:]),
                                ptr(self.d_voc_off), ptr(self.d_voc_bytes), t.vocab_size, B, s)
@@ -1321,7 +1394,7 @@ class Engine:
         return {"launches": n, "avg_us": ms.value * 1e3 / n, "bytes_per_launch": nbytes}
 
     def _graph_key(self, B: int):
-        return (B, self._ignore_eos, self._freeze_finished, self._sampling, self._guided, self._logprobs)
+        return (B, self._ignore_eos, self._freeze_finished, self._sampling, self._guided, self._logprobs, self._processing)
 
     def _graph_for(self, B: int) -> int:
         key = self._graph_key(B)
@@ -1367,6 +1440,10 @@ class Engine:
         # a guided row is masked in the sampling pass, so that pass runs (rows with T = 0 stay a plain argmax)
         self._sampling = self._guided or any(float(getattr(p, "temperature", 0.0) or 0.0) > 0 for p in pages)
         self._cap_sampling, self._cap_guided = self._sampling, self._guided
+        self._processing = self._cap_processing = any(needs_processing(p) for p in pages)
+        if force_tokens is not None and any(has_penalties(p) for p in pages):
+            raise KarantaHipError("force_tokens with repetition / frequency / presence penalties: the output counts would follow "
+                                  "the engine's own tokens, not the forced ones")
         ks = [int(p.logprobs) for p in pages if getattr(p, "logprobs", None) is not None]
         if ks and not 0 <= max(ks) <= 20:
             raise KarantaHipError("logprobs must be in 0..20")
@@ -1478,6 +1555,8 @@ class Engine:
         self._guided = bool(guided)
         self._sampling = bool(sampling) or self._guided
         self._cap_sampling, self._cap_guided = self._sampling, self._guided
+        # the sampling controls come with the sampling configuration; the steps carry them while a request needs them
+        self._processing, self._cap_processing = False, self._sampling
         self._logprobs = None if logprobs is None else int(logprobs)
         self._last_batch = self.B
         self._ensure_history(max_new_tokens)
@@ -1568,15 +1647,17 @@ class Engine:
         self.stream.wait_event(handle["done"])
         with torch.cuda.stream(self.stream):
             self._write_slot_state(rec["slots"], rec["lens"], rec["deltas"], rec["cs"], rec["temps"], rec["seeds"],
-                                   rec.get("guides"))
+                                   rec.get("guides"), rec.get("procs"))
             self._first_tokens(rec["slots"])
         return rec["lens"]
 
-    def set_step_features(self, sampling: bool, guided: bool):
+    def set_step_features(self, sampling: bool, guided: bool, processing: bool = False):
         """Slot mode: which passes the NEXT decode steps carry, within what begin_slots() allowed.  The scheduler calls it with what
         the requests in the slots need: a server that accepts guided / sampled requests runs the plain argmax graph (no f32 logits
         written and re-read, no DFA advance) while none is decoding — rows with temperature 0 and no guide get the same token from
-        either graph.  An admission that brings a guide or a temperature switches the passes on by itself (prefill)."""
+        either graph.  An admission that brings a guide or a temperature switches the passes on by itself (prefill).
+        processing: the sampling-control launches (top_k / top_p / min_p / penalties; needs_processing), same rules."""
+        self._processing = bool(processing) and self._cap_processing
         guided = bool(guided) and self._cap_guided
         self._guided = guided
         self._sampling = (bool(sampling) and self._cap_sampling) or guided

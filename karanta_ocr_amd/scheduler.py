@@ -19,6 +19,8 @@ from typing import Any, Deque, Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
 
+from .sampling import needs_processing
+
 
 @dataclass
 class SlotRequest:
@@ -172,9 +174,13 @@ class SlotScheduler:
         if self._features:      # the passes the steps carry follow the requests that are in the slots right now
             need_g = any(getattr(r.page, "guide", None) is not None for r in self.active.values())
             need_s = need_g or any(float(getattr(r.page, "temperature", 0.0) or 0.0) > 0 for r in self.active.values())
-            if (need_s, need_g) != self._features_now:
-                self.engine.set_step_features(need_s, need_g)
-                self._features_now = (need_s, need_g)
+            # the sampling controls also count the admission in flight: its first token is sampled on the decode stream
+            # (admit_end) with whatever the steps carry then
+            pending = list(self._inflight[1]) if self._inflight is not None else []
+            need_p = any(needs_processing(r.page) for r in list(self.active.values()) + pending)
+            if (need_s, need_g, need_p) != self._features_now:
+                self.engine.set_step_features(need_s, need_g, need_p)
+                self._features_now = (need_s, need_g, need_p)
         self.engine.decode_steps(self.chunk)
         self.steps += self.chunk
         self.slot_steps_busy += self.chunk * len(self.active)

@@ -15,7 +15,9 @@ request: caller skips the attempt), 500 (internal error: caller retries).
 ``temperature`` is honoured (0 or absent: greedy — the reference's ``build_page_query`` default, pipeline.py:170;
 ``process_page`` sends 0.1 on its first attempt, :281,:301): Gumbel-max sampling from softmax(logits / T)
 (kr_gumbel_argmax), reproducible through the OpenAI ``seed`` field, a random seed per request otherwise.
-``top_p`` / ``top_k`` are not applied.  ``guided_regex`` / ``response_format`` / ``logprobs``: guided.py, engine.
+``top_k`` / ``top_p`` / ``min_p`` / ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` are applied with
+vLLM's semantics and validation (sampling.py; kr_sample_threshold / kr_gumbel_argmax_processed); ``honor_temperature=False``
+(``--greedy``) ignores them with the temperature.  ``guided_regex`` / ``response_format`` / ``logprobs``: guided.py, engine.
 
 Prompt text: the checkpoint's own ``chat_template`` when the model directory ships one (``chat_template.json`` /
 ``chat_template.jinja`` / ``tokenizer_config.json`` — what vLLM applies, pipeline.py:707-734), rendered with jinja2; the
@@ -35,6 +37,7 @@ import numpy as np
 
 from . import image_processing as IP
 from .config import ModelConfig
+from .sampling import NEUTRAL, parse_request_fields
 
 DEFAULT_SYSTEM = "You are a helpful assistant."
 
@@ -129,6 +132,13 @@ class ParsedRequest:
     images: Optional[List[np.ndarray]] = None   # device_images front end: decoded HWC uint8 pages instead of pixel_values
     guide: Any = None               # guided.Guide compiled from guided_regex / response_format (None: unconstrained)
     logprobs: Optional[int] = None  # None: not asked; k: log-prob of every token + top_logprobs = k alternatives
+    # vLLM's sampling controls (sampling.parse_request_fields: validated, neutral when absent)
+    top_k: int = 0
+    top_p: float = 1.0
+    min_p: float = 0.0
+    repetition_penalty: float = 1.0
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
 
 
 class ChatFrontend:
@@ -340,9 +350,13 @@ class ChatFrontend:
                 raise BadRequest(f"top_logprobs: {e}") from e
             if not 0 <= logprobs <= 20:
                 raise BadRequest("top_logprobs must be in 0..20")
+        try:
+            controls = parse_request_fields(req)
+        except ValueError as e:
+            raise BadRequest(str(e)) from e
         return ParsedRequest(np.asarray(ids, np.int64), np.concatenate(pvs, 0) if pvs else None, grids, max_tokens,
                              str(req.get("model", "karantaocr")), temperature, seed, images or None,
-                             self._guide_for(req), logprobs)
+                             self._guide_for(req), logprobs, **controls)
 
 
 # ----------------------------------------------------------------------------- in-process server
@@ -546,6 +560,9 @@ class LocalServer:
         if self.honor_temperature and r.temperature > 0:
             page.temperature = r.temperature
             page.seed = r.seed if r.seed is not None else random.getrandbits(32)
+        if self.honor_temperature:        # --greedy: the plain greedy path, sampling controls ignored as well
+            for name in NEUTRAL:
+                setattr(page, name, getattr(r, name, NEUTRAL[name]))
         return page
 
     def _finish(self, s: Dict[str, Any], toks, reason: str):
