@@ -2083,61 +2083,20 @@ __device__ __forceinline__ unsigned kr_mix32(unsigned x) {
     return x;
 }
 
-__global__ void __launch_bounds__(256) gumbel_argmax_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
-                                                            const float* __restrict__ temperature,
-                                                            const unsigned* __restrict__ seed,
-                                                            const int32_t* __restrict__ ctx_len,
-                                                            const int32_t* __restrict__ prompt_len,
-                                                            float* __restrict__ amax_val, int32_t* __restrict__ amax_idx,
-                                                            const uint64_t* __restrict__ guide_masks,
-                                                            const int32_t* __restrict__ guide_state, int mask_words,
-                                                            int fallback_token) {
-    __shared__ float s_v[4];
-    __shared__ int s_i[4];
-    const int p = blockIdx.x, n_part = gridDim.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (((vocab + n_part - 1) / n_part) + 3) & ~3;
-    const int i0 = p * per, i1 = min(vocab, i0 + per);
-    const float T = temperature[b];
-    const float inv_t = T > 0.f ? 1.0f / T : 1.0f;
-    const unsigned base = kr_mix32(seed[b] ^ ((unsigned)(ctx_len[b] + 1 - prompt_len[b]) * 0x9E3779B1u));
-    const float* row = logits + (int64_t)b * ld;
-    // guided slot: allowed-token bits of its DFA state (kr_guide_build_masks); 0 pointer = unconstrained
-    const uint32_t* allow = nullptr;
-    if (guide_masks != nullptr && guide_masks[b] != 0)
-        allow = reinterpret_cast<const uint32_t*>(guide_masks[b]) + (int64_t)guide_state[b] * mask_words;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = i0 + tid; i < i1; i += 256) {
-        if (allow != nullptr && !((allow[i >> 5] >> (i & 31)) & 1u)) continue;
-        float v = row[i] * inv_t;
-        if (T > 0.f) {
-            const unsigned h = kr_mix32(base + (unsigned)i);
-            // 23-bit integer + 0.5 is exact in f32 (24 significant bits): u in [2^-24, 1 - 2^-24], never 0 or 1
-            // (a 24-bit integer + 0.5 rounds to 2^24 at the top code: u = 1, noise = +inf)
-            const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;  // 2^-23
-            v += -logf(-logf(u));
-        }
-        better(bv, bi, v, i);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        better(bv, bi, ov, oi);
-    }
-    if (lane == 0) {
-        s_v[wave] = bv;
-        s_i[wave] = bi;
-    }
-    __syncthreads();
-    if (tid == 0) {
-#pragma unroll
-        for (int w = 1; w < 4; ++w) better(bv, bi, s_v[w], s_i[w]);
-        // a row whose mask allows nothing (cannot happen for a live DFA state) must still yield a valid token id
-        if (p == 0 && bi == 0x7fffffff) bi = fallback_token;
-        amax_val[(int64_t)b * n_part + p] = bv;
-        amax_idx[(int64_t)b * n_part + p] = bi;
-    }
+// guided slot: allowed-token bits of row b's DFA state (kr_guide_build_masks); nullptr = unconstrained
+__device__ __forceinline__ const uint32_t* kr_guide_row(const uint64_t* guide_masks, const int32_t* guide_state, int mask_words,
+                                                        int b) {
+    if (guide_masks == nullptr || guide_masks[b] == 0) return nullptr;
+    return reinterpret_cast<const uint32_t*>(guide_masks[b]) + (int64_t)guide_state[b] * mask_words;
+}
+
+// G_i of token i for the row whose counter base is `base` (kr_mix32 of its seed and step)
+__device__ __forceinline__ float kr_gumbel_noise(unsigned base, int i) {
+    const unsigned h = kr_mix32(base + (unsigned)i);
+    // 23-bit integer + 0.5 is exact in f32 (24 significant bits): u in [2^-24, 1 - 2^-24], never 0 or 1
+    // (a 24-bit integer + 0.5 rounds to 2^24 at the top code: u = 1, noise = +inf)
+    const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;  // 2^-23
+    return -logf(-logf(u));
 }
 
 // =====================================================================================
@@ -2299,9 +2258,7 @@ __global__ void __launch_bounds__(SEL_T) sample_threshold_kernel(const float* __
     const int32_t* cnt = counts + (int64_t)b * ld_counts;
     const uint32_t* pb = prompt_bits + (int64_t)b * bits_words;
     float* wr = work + (int64_t)b * ld_work;
-    const uint32_t* allow = nullptr;
-    if (guide_masks != nullptr && guide_masks[b] != 0)
-        allow = reinterpret_cast<const uint32_t*>(guide_masks[b]) + (int64_t)guide_state[b] * mask_words;
+    const uint32_t* allow = kr_guide_row(guide_masks, guide_state, mask_words, b);
     float m = -INFINITY;
     for (int i = tid; i < vocab; i += SEL_T) {
         float v = -INFINITY;
@@ -2336,20 +2293,19 @@ __global__ void __launch_bounds__(SEL_T) sample_threshold_kernel(const float* __
     if (tid == 0) thr[b] = lo;
 }
 
-// gumbel_argmax_kernel with the penalties and the truncation threshold: same [batch][n_part] partials.  A row with
-// neutral parameters runs the same value expression as gumbel_argmax_kernel (no penalty, threshold 0): identical partials.
-__global__ void __launch_bounds__(256) gumbel_argmax_proc_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
-                                                                 const float* __restrict__ temperature,
-                                                                 const unsigned* __restrict__ seed,
-                                                                 const int32_t* __restrict__ ctx_len,
-                                                                 const int32_t* __restrict__ prompt_len,
-                                                                 float* __restrict__ amax_val, int32_t* __restrict__ amax_idx,
-                                                                 const uint64_t* __restrict__ guide_masks,
-                                                                 const int32_t* __restrict__ guide_state, int mask_words,
-                                                                 int fallback_token, const float* __restrict__ params,
-                                                                 const int32_t* __restrict__ counts, int64_t ld_counts,
-                                                                 const uint32_t* __restrict__ prompt_bits, int bits_words,
-                                                                 const uint32_t* __restrict__ thr) {
+// =====================================================================================
+// the Gumbel-max partial argmax: [batch][n_part] partials for kr_sample_greedy's reduction
+// =====================================================================================
+// One body for both launches.  PROC (gumbel_argmax_proc_kernel) adds the penalties and the truncation threshold of
+// sample_threshold_kernel; a row with neutral parameters (no penalty, threshold 0) runs the value expression of the plain
+// launch and gets its partials bit for bit.
+template <bool PROC>
+__device__ __forceinline__ void gumbel_argmax_body(const float* logits, int64_t ld, int vocab, const float* temperature,
+                                                   const unsigned* seed, const int32_t* ctx_len, const int32_t* prompt_len,
+                                                   float* amax_val, int32_t* amax_idx, const uint64_t* guide_masks,
+                                                   const int32_t* guide_state, int mask_words, int fallback_token,
+                                                   const float* params, const int32_t* counts, int64_t ld_counts,
+                                                   const uint32_t* prompt_bits, int bits_words, const uint32_t* thr) {
     __shared__ float s_v[4];
     __shared__ int s_i[4];
     const int p = blockIdx.x, n_part = gridDim.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2359,28 +2315,29 @@ __global__ void __launch_bounds__(256) gumbel_argmax_proc_kernel(const float* __
     const float inv_t = T > 0.f ? 1.0f / T : 1.0f;
     const unsigned base = kr_mix32(seed[b] ^ ((unsigned)(ctx_len[b] + 1 - prompt_len[b]) * 0x9E3779B1u));
     const float* row = logits + (int64_t)b * ld;
-    const float* prm = params + (int64_t)b * KR_SP_STRIDE;
-    const bool pen = kr_sp_penalised(prm);
-    const float rep = prm[3], freq = prm[4], pres = prm[5];
-    const int32_t* cnt = counts + (int64_t)b * ld_counts;
-    const uint32_t* pb = prompt_bits + (int64_t)b * bits_words;
-    const uint32_t th = T > 0.f ? thr[b] : 0u;    // greedy rows: truncation cannot move the argmax
-    const uint32_t* allow = nullptr;
-    if (guide_masks != nullptr && guide_masks[b] != 0)
-        allow = reinterpret_cast<const uint32_t*>(guide_masks[b]) + (int64_t)guide_state[b] * mask_words;
+    bool pen = false;
+    float rep = 1.0f, freq = 0.0f, pres = 0.0f;
+    const int32_t* cnt = nullptr;
+    const uint32_t* pb = nullptr;
+    uint32_t th = 0u;
+    if constexpr (PROC) {
+        const float* prm = params + (int64_t)b * KR_SP_STRIDE;
+        pen = kr_sp_penalised(prm);
+        rep = prm[3], freq = prm[4], pres = prm[5];
+        cnt = counts + (int64_t)b * ld_counts;
+        pb = prompt_bits + (int64_t)b * bits_words;
+        th = T > 0.f ? thr[b] : 0u;    // greedy rows: truncation cannot move the argmax
+    }
+    const uint32_t* allow = kr_guide_row(guide_masks, guide_state, mask_words, b);
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = i0 + tid; i < i1; i += 256) {
         if (allow != nullptr && !((allow[i >> 5] >> (i & 31)) & 1u)) continue;
         float lp = row[i];
-        if (pen) lp = kr_penalise(lp, (pb[i >> 5] >> (i & 31)) & 1u, cnt[i], rep, freq, pres);
+        if (PROC && pen) lp = kr_penalise(lp, (pb[i >> 5] >> (i & 31)) & 1u, cnt[i], rep, freq, pres);
         float v = lp * inv_t;
-        if (th != 0u && kr_fkey(v) < th) continue;
-        if (T > 0.f) {
-            const unsigned h = kr_mix32(base + (unsigned)i);
-            const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;  // 2^-23 (gumbel_argmax_kernel)
-            v += -logf(-logf(u));
-        }
+        if (PROC && th != 0u && kr_fkey(v) < th) continue;
+        if (T > 0.f) v += kr_gumbel_noise(base, i);
         better(bv, bi, v, i);
     }
 #pragma unroll
@@ -2397,10 +2354,40 @@ __global__ void __launch_bounds__(256) gumbel_argmax_proc_kernel(const float* __
     if (tid == 0) {
 #pragma unroll
         for (int w = 1; w < 4; ++w) better(bv, bi, s_v[w], s_i[w]);
+        // a row whose mask allows nothing (cannot happen for a live DFA state) must still yield a valid token id
         if (p == 0 && bi == 0x7fffffff) bi = fallback_token;
         amax_val[(int64_t)b * n_part + p] = bv;
         amax_idx[(int64_t)b * n_part + p] = bi;
     }
+}
+
+__global__ void __launch_bounds__(256) gumbel_argmax_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
+                                                            const float* __restrict__ temperature,
+                                                            const unsigned* __restrict__ seed,
+                                                            const int32_t* __restrict__ ctx_len,
+                                                            const int32_t* __restrict__ prompt_len,
+                                                            float* __restrict__ amax_val, int32_t* __restrict__ amax_idx,
+                                                            const uint64_t* __restrict__ guide_masks,
+                                                            const int32_t* __restrict__ guide_state, int mask_words,
+                                                            int fallback_token) {
+    gumbel_argmax_body<false>(logits, ld, vocab, temperature, seed, ctx_len, prompt_len, amax_val, amax_idx, guide_masks,
+                              guide_state, mask_words, fallback_token, nullptr, nullptr, 0, nullptr, 0, nullptr);
+}
+
+__global__ void __launch_bounds__(256) gumbel_argmax_proc_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
+                                                                 const float* __restrict__ temperature,
+                                                                 const unsigned* __restrict__ seed,
+                                                                 const int32_t* __restrict__ ctx_len,
+                                                                 const int32_t* __restrict__ prompt_len,
+                                                                 float* __restrict__ amax_val, int32_t* __restrict__ amax_idx,
+                                                                 const uint64_t* __restrict__ guide_masks,
+                                                                 const int32_t* __restrict__ guide_state, int mask_words,
+                                                                 int fallback_token, const float* __restrict__ params,
+                                                                 const int32_t* __restrict__ counts, int64_t ld_counts,
+                                                                 const uint32_t* __restrict__ prompt_bits, int bits_words,
+                                                                 const uint32_t* __restrict__ thr) {
+    gumbel_argmax_body<true>(logits, ld, vocab, temperature, seed, ctx_len, prompt_len, amax_val, amax_idx, guide_masks,
+                             guide_state, mask_words, fallback_token, params, counts, ld_counts, prompt_bits, bits_words, thr);
 }
 
 // after kr_sample_greedy: counts[b][tokens[b]] += 1 where live[b] (sample_threshold_kernel)

@@ -26,7 +26,7 @@ from . import positions as POS
 from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_GELU_ERF, EPI_NONE, EPI_QUICK_GELU, EPI_SILU_MUL8,
                    KarantaHipError, lib, narrow_opts, ptr)
 from .config import ModelConfig
-from .sampling import has_penalties, needs_processing, sampling_params
+from .sampling import StepFeatures, has_penalties, needs_processing, sampling_params, temperature
 from .weights import pack_w16x64, to_bf16_bits
 
 BF16 = torch.bfloat16
@@ -293,13 +293,11 @@ class Engine:
         self.max_patches = max_patches
         self.max_tokens = max_prompt_tokens
         self.n_split = decode_splits
-        self._ignore_eos = self._freeze_finished = self._want_logits = self._sampling = False
-        self._guided = False          # the decode graph masks logits by the slots' DFA states and advances them
-        self._processing = False      # ... and applies the sampling controls (penalties, min_p / top_k / top_p; needs_processing)
-        self._cap_processing = False
-        # what the current mode ALLOWS (begin_slots(sampling=, guided=); generate(): what its pages need): _sampling / _guided say
-        # what the next decode step RUNS — in slot mode they follow the requests that are actually in the slots (set_step_features)
-        self._cap_sampling = self._cap_guided = False
+        self._ignore_eos = self._freeze_finished = self._want_logits = False
+        # _caps: the passes the current mode ALLOWS (begin_slots(sampling=, guided=); generate(): what its pages need);
+        # _step: the passes the next decode step RUNS — in slot mode they follow the requests that are actually in the slots
+        # (set_step_features), and an admission switches on what it needs (_admit_features)
+        self._caps = self._step = StepFeatures()
         self._logprobs = None         # None or k: the decode graph records log-probabilities (kr_logprobs_topk)
         self._adm_stream = None                          # second stream of the overlapped admission (slot mode)
         # overlapped admissions run on a stream restricted to this many compute units (kr_stream_create_cu_mask), so the
@@ -914,10 +912,6 @@ class Engine:
             if g is None:
                 rows.append((0, 0, 0, None))
                 continue
-            if not self._cap_guided:
-                raise KarantaHipError("a page carries a guide but the engine is not in its guided configuration "
-                                      "(generate() decides from its pages; begin_slots(guided=True) for slot mode)")
-            self._guided = self._sampling = True      # from this admission on the steps carry the masked sampling pass
             dg = self.compile_guide(g)
             rows.append((dg.trans.data_ptr(), dg.masks.data_ptr(), dg.start, dg))
         return rows
@@ -1016,21 +1010,17 @@ class Engine:
         cfg, t, L, s, w, dev = self.cfg, self.cfg.text, self.L, self.s, self.w, self.device
         if prep is None or prep["n_img"] != n_image_tokens_total:
             prep = self._prefill_prepare(pages, n_image_tokens_total, slots)
+        need = self._admit_features(pages)
         B, whole_batch, slots, lens, M = prep["B"], prep["whole_batch"], prep["slots"], prep["lens"], prep["M"]
         src, cos, sin, deltas, plan, last_rows, cs = (prep[k] for k in ("src", "cos", "sin", "deltas", "plan", "last_rows", "cs"))
         with torch.cuda.stream(self.stream):
             self._h2d(self.p_src, src)
             self._h2d(self.p_cos, cos)
             self._h2d(self.p_sin, sin)
-            temps = np.asarray([float(getattr(p, "temperature", 0.0) or 0.0) for p in pages], np.float32)
+            temps = np.asarray([temperature(p) for p in pages], np.float32)
             seeds = np.asarray([int(getattr(p, "seed", 0) or 0) & 0xFFFFFFFF for p in pages], np.uint32).view(np.int32)
-            if temps.max(initial=0.0) > 0:
-                if not self._cap_sampling:
-                    raise KarantaHipError("a page asks for temperature > 0 but the engine is in its greedy configuration "
-                                          "(generate() decides from its pages; begin_slots(sampling=True) for slot mode)")
-                self._sampling = True
             grows = self._guide_rows(pages)
-            procs = self._processing_rows(pages)
+            procs = self._control_rows(pages)
             if whole_batch:
                 tb, sb = np.zeros(self.B, np.float32), np.zeros(self.B, np.int32)
                 tb[:B], sb[:B] = temps, seeds
@@ -1088,23 +1078,32 @@ class Engine:
                 self._first_tokens(slots)
         if defer_activation:
             return {"slots": slots, "lens": lens, "deltas": deltas, "cs": cs, "temps": temps, "seeds": seeds, "guides": grows,
-                    "procs": procs}
+                    "procs": procs, "need": need}
         return lens
 
-    def _processing_rows(self, pages):
-        """Per page (params row, prompt bit set or None, penalised) when the engine may run the processing launches, else None;
-        raises for a page that uses the sampling controls where it may not."""
-        need = [needs_processing(p) for p in pages]
-        if any(need):
-            if not self._cap_processing:
-                raise KarantaHipError("a page asks for top_k / top_p / min_p / penalties but the engine is in its greedy "
-                                      "configuration (generate() decides from its pages; begin_slots(sampling=True) for slot mode)")
-            self._processing = True       # from this admission on the steps carry the processing launches
-        if not self._cap_processing:
+    def _admit_features(self, pages) -> StepFeatures:
+        """What an admission's pages need: raises where the mode does not allow it, else the next steps carry it (from this
+        admission on: its first token included).  Returns the need."""
+        need, caps = StepFeatures.of(pages), self._caps
+        if need.guided and not caps.guided:
+            raise KarantaHipError("a page carries a guide but the engine is not in its guided configuration "
+                                  "(generate() decides from its pages; begin_slots(guided=True) for slot mode)")
+        if need.sampling and not caps.sampling:
+            raise KarantaHipError("a page asks for temperature > 0 but the engine is in its greedy configuration "
+                                  "(generate() decides from its pages; begin_slots(sampling=True) for slot mode)")
+        if need.processing and not caps.processing:
+            raise KarantaHipError("a page asks for top_k / top_p / min_p / penalties but the engine is in its greedy "
+                                  "configuration (generate() decides from its pages; begin_slots(sampling=True) for slot mode)")
+        self._step |= need
+        return need
+
+    def _control_rows(self, pages):
+        """Per page (params row, prompt bit set or None, penalised) when the engine may run the processing launches, else None."""
+        if not self._caps.processing:
             return None
         V, rows = self.cfg.text.vocab_size, []
-        for p, nd in zip(pages, need):
-            sp = sampling_params(p)
+        for p in pages:
+            sp, nd = sampling_params(p), needs_processing(p)
             bits = None
             if nd and sp[3] != 1.0:       # repetition penalty: the prompt's tokens (image placeholders included)
                 ids = np.asarray(p.input_ids, np.int64).reshape(-1)
@@ -1158,7 +1157,8 @@ class Engine:
         t, L, w, s = self.cfg.text, self.L, self.w, self.s
         x = self.d_x if x is None else x
         j = slot0  # rows j .. j+B-1 of every per-sequence array (the slot scheduler prefills single slots)
-        logits = self.d_logits[j:] if (self._want_logits or self._sampling or self._processing or self._logprobs is not None) else None
+        step = self._step
+        logits = self.d_logits[j:] if (self._want_logits or step.sampling or step.processing or self._logprobs is not None) else None
         if self.wide_mode:
             self._dec_wide(DEC_ARGMAX, x[j:], w.view("llm.lm_head"), B, norm_w=w.view("llm.norm.w"), out_f32=logits)
         else:
@@ -1166,8 +1166,8 @@ class Engine:
                       waves=self.wv_wide)
         n_part = self._amax_parts(B) if self.wide_mode else self.n_amax   # the stride the lm_head launch wrote with
         flags = (1 if self._ignore_eos else 0) | (2 if self._freeze_finished else 0)
-        gm, gs = (ptr(self.d_gmasks[j:]), ptr(self.d_gstate[j:])) if self._guided else (None, None)
-        if self._processing:
+        gm, gs = (ptr(self.d_gmasks[j:]), ptr(self.d_gstate[j:])) if step.guided else (None, None)
+        if step.processing:
             # sampling controls somewhere in the batch: per-row truncation threshold, then the Gumbel-max argmax over the
             # penalised scores above it (rows with neutral controls get exactly the partials of the branch below)
             n_part = min(64, n_part)
@@ -1179,25 +1179,22 @@ class Engine:
                                          ptr(self.d_plen[j:]), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, B, gm, gs,
                                          self.mask_words, int(self.cfg.eos_token_ids[0]), ptr(self.d_sp[j:]),
                                          ptr(self.d_counts[j:]), V, ptr(self.d_pbits[j:]), self.bits_words, ptr(self.d_thr[j:]), s)
-        elif self._sampling:
+        elif step.sampling:
             # temperature > 0 somewhere in the batch: the partial argmax is redone on logits / T + Gumbel noise
-            # (rows with T = 0 get their plain argmax back)
+            # (rows with T = 0 get their plain argmax back); guided slots: only the tokens their DFA state allows take part
+            # (unguided steps: null masks, as kr_gumbel_argmax passes them)
             n_part = min(64, n_part)
-            if self._guided:   # guided slots: only the tokens their DFA state allows take part
-                L.kr_gumbel_argmax_guided(ptr(logits), self.d_logits.stride(0), t.vocab_size, ptr(self.d_temp[j:]),
-                                          ptr(self.d_seed[j:]), ptr(self.d_ctx[j:]), ptr(self.d_plen[j:]), ptr(self.d_amax_v),
-                                          ptr(self.d_amax_i), n_part, B, ptr(self.d_gmasks[j:]), ptr(self.d_gstate[j:]),
-                                          self.mask_words, int(self.cfg.eos_token_ids[0]), s)
-            else:
-                L.kr_gumbel_argmax(ptr(logits), self.d_logits.stride(0), t.vocab_size, ptr(self.d_temp[j:]), ptr(self.d_seed[j:]),
-                                   ptr(self.d_ctx[j:]), ptr(self.d_plen[j:]), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, B, s)
+            mw, fb = (self.mask_words, int(self.cfg.eos_token_ids[0])) if step.guided else (0, 0)
+            L.kr_gumbel_argmax_guided(ptr(logits), self.d_logits.stride(0), t.vocab_size, ptr(self.d_temp[j:]), ptr(self.d_seed[j:]),
+                                      ptr(self.d_ctx[j:]), ptr(self.d_plen[j:]), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, B,
+                                      gm, gs, mw, fb, s)
         L.kr_sample_greedy(ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(w.view("llm.embed")), t.hidden_size,
                            ptr(self.d_tok[j:]), ptr(self.d_hist[:, j:]), self.d_hist.stride(0), ptr(self.d_plen[j:]),
                            ptr(self.d_ctx[j:]), ptr(self.d_fin[j:]), ptr(self.d_eos), self.d_eos.numel(),
                            self.cfg.pad_token_id, flags, ptr(self.d_x[j:]), B, s)
-        if self._processing:
+        if step.processing:
             L.kr_sample_count(ptr(self.d_tok[j:]), ptr(self.d_live[j:]), ptr(self.d_counts[j:]), t.vocab_size, t.vocab_size, B, s)
-        if self._guided:
+        if step.guided:
             L.kr_guide_advance(ptr(self.d_tok[j:]), ptr(self.d_fin[j:]), ptr(self.d_gtrans[j:]), ptr(self.d_gstate[j:]),
                                ptr(self.d_voc_off), ptr(self.d_voc_bytes), t.vocab_size, B, s)
         if self._logprobs is not None:
@@ -1394,7 +1391,7 @@ class Engine:
         return {"launches": n, "avg_us": ms.value * 1e3 / n, "bytes_per_launch": nbytes}
 
     def _graph_key(self, B: int):
-        return (B, self._ignore_eos, self._freeze_finished, self._sampling, self._guided, self._logprobs, self._processing)
+        return (B, self._ignore_eos, self._freeze_finished, self._logprobs, self._step)
 
     def _graph_for(self, B: int) -> int:
         key = self._graph_key(B)
@@ -1436,11 +1433,7 @@ class Engine:
         self._ignore_eos = bool(ignore_eos)
         self._freeze_finished = False
         self._want_logits = bool(return_logits)
-        self._guided = any(getattr(p, "guide", None) is not None for p in pages)
-        # a guided row is masked in the sampling pass, so that pass runs (rows with T = 0 stay a plain argmax)
-        self._sampling = self._guided or any(float(getattr(p, "temperature", 0.0) or 0.0) > 0 for p in pages)
-        self._cap_sampling, self._cap_guided = self._sampling, self._guided
-        self._processing = self._cap_processing = any(needs_processing(p) for p in pages)
+        self._caps = self._step = StepFeatures.of(pages)
         if force_tokens is not None and any(has_penalties(p) for p in pages):
             raise KarantaHipError("force_tokens with repetition / frequency / presence penalties: the output counts would follow "
                                   "the engine's own tokens, not the forced ones")
@@ -1552,11 +1545,9 @@ class Engine:
         if guided and self.d_voc_off is None:
             raise KarantaHipError("guided decoding needs the vocabulary's byte strings: call Engine.set_vocab() first")
         self._ignore_eos, self._freeze_finished, self._want_logits = False, True, False
-        self._guided = bool(guided)
-        self._sampling = bool(sampling) or self._guided
-        self._cap_sampling, self._cap_guided = self._sampling, self._guided
-        # the sampling controls come with the sampling configuration; the steps carry them while a request needs them
-        self._processing, self._cap_processing = False, self._sampling
+        # the sampling controls come with the sampling configuration; the steps carry each pass while a request needs it
+        sampled = bool(sampling) or bool(guided)
+        self._caps, self._step = StepFeatures(sampled, bool(guided), sampled), StepFeatures()
         self._logprobs = None if logprobs is None else int(logprobs)
         self._last_batch = self.B
         self._ensure_history(max_new_tokens)
@@ -1645,6 +1636,8 @@ class Engine:
         rec = handle["rec"]
         self._adm_inflight = max(0, self._adm_inflight - 1)
         self.stream.wait_event(handle["done"])
+        # the first tokens are sampled with the passes this admission needs, whatever set_step_features did since admit_begin
+        self._step |= rec["need"]
         with torch.cuda.stream(self.stream):
             self._write_slot_state(rec["slots"], rec["lens"], rec["deltas"], rec["cs"], rec["temps"], rec["seeds"],
                                    rec.get("guides"), rec.get("procs"))
@@ -1655,12 +1648,9 @@ class Engine:
         """Slot mode: which passes the NEXT decode steps carry, within what begin_slots() allowed.  The scheduler calls it with what
         the requests in the slots need: a server that accepts guided / sampled requests runs the plain argmax graph (no f32 logits
         written and re-read, no DFA advance) while none is decoding — rows with temperature 0 and no guide get the same token from
-        either graph.  An admission that brings a guide or a temperature switches the passes on by itself (prefill).
+        either graph.  An admission switches on what its pages need by itself (prefill, admit_end).
         processing: the sampling-control launches (top_k / top_p / min_p / penalties; needs_processing), same rules."""
-        self._processing = bool(processing) and self._cap_processing
-        guided = bool(guided) and self._cap_guided
-        self._guided = guided
-        self._sampling = (bool(sampling) and self._cap_sampling) or guided
+        self._step = StepFeatures(bool(sampling), bool(guided), bool(processing)) & self._caps
 
     def decode_steps(self, n: int):
         """n decode steps over all slots (asynchronous on the engine's stream).  While an admission is in flight on a CU-masked

@@ -1,13 +1,13 @@
 """vLLM's sampling controls on a page: top_k, top_p, min_p and the repetition / frequency / presence penalties.
 
-Host side only (no torch): the kr_sample_threshold params row of a page, whether a page uses any control (the decode
-steps then carry the processing launches: Engine._lm_head_and_sample), and the request validation of the server, which
-follows vLLM's SamplingParams checks.  The device semantics are documented in include/karanta_hip.h and DESIGN.md §5c.
+Host side only (no torch): the kr_sample_threshold params row of a page, whether a page uses any control, which passes the
+decode steps of a set of pages carry (StepFeatures: Engine._lm_head_and_sample, SlotScheduler), and the request validation of
+the server, which follows vLLM's SamplingParams checks.  The device semantics are documented in include/karanta_hip.h and DESIGN.md §5c.
 """
 from __future__ import annotations
 
 import math
-from typing import Any, Dict
+from typing import Any, Dict, Iterable, NamedTuple
 
 import numpy as np
 
@@ -34,6 +34,35 @@ def needs_processing(p) -> bool:
     """Whether a page uses any of the sampling controls."""
     sp = sampling_params(p)
     return bool(sp[0] > 0 or sp[1] != 1.0 or sp[2] != 0.0 or has_penalties(p))
+
+
+def temperature(p) -> float:
+    """A page's sampling temperature; None, missing or 0 all mean greedy (0.0)."""
+    return float(getattr(p, "temperature", 0.0) or 0.0)
+
+
+class StepFeatures(NamedTuple):
+    """The optional passes of a decode step (part of Engine's graph key): `sampling` the Gumbel-max argmax, `guided` its
+    guide mask and the DFA advance, `processing` the sampling-control launches.  A guided row is masked in the sampling
+    pass, so `guided` implies `sampling`."""
+    sampling: bool = False
+    guided: bool = False
+    processing: bool = False
+
+    @classmethod
+    def of(cls, pages: Iterable) -> "StepFeatures":
+        """What a set of pages needs; the one place that decides it."""
+        pages = list(pages)
+        guided = any(getattr(p, "guide", None) is not None for p in pages)
+        return cls(guided or any(temperature(p) > 0 for p in pages), guided, any(needs_processing(p) for p in pages))
+
+    def __or__(self, other: "StepFeatures") -> "StepFeatures":
+        return StepFeatures(*(a or b for a, b in zip(self, other)))
+
+    def __and__(self, caps: "StepFeatures") -> "StepFeatures":
+        """The clamp to what `caps` allows; a guided row that stays guided keeps the sampling pass it is masked in."""
+        guided = self.guided and caps.guided
+        return StepFeatures((self.sampling and caps.sampling) or guided, guided, self.processing and caps.processing)
 
 
 def parse_request_fields(req: Dict[str, Any]) -> Dict[str, Any]:

@@ -19,7 +19,7 @@ from typing import Any, Deque, Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
 
-from .sampling import needs_processing
+from .sampling import StepFeatures
 
 
 @dataclass
@@ -171,16 +171,14 @@ class SlotScheduler:
         return seq, self.engine.snapshot_slots()
 
     def _decode_chunk(self):
-        if self._features:      # the passes the steps carry follow the requests that are in the slots right now
-            need_g = any(getattr(r.page, "guide", None) is not None for r in self.active.values())
-            need_s = need_g or any(float(getattr(r.page, "temperature", 0.0) or 0.0) > 0 for r in self.active.values())
-            # the sampling controls also count the admission in flight: its first token is sampled on the decode stream
-            # (admit_end) with whatever the steps carry then
-            pending = list(self._inflight[1]) if self._inflight is not None else []
-            need_p = any(needs_processing(r.page) for r in list(self.active.values()) + pending)
-            if (need_s, need_g, need_p) != self._features_now:
-                self.engine.set_step_features(need_s, need_g, need_p)
-                self._features_now = (need_s, need_g, need_p)
+        if self._features:
+            # the passes the steps carry follow the requests in the slots and the admission in flight, whose first token is
+            # sampled on the decode stream (admit_end)
+            pending = self._inflight[1] if self._inflight is not None else []
+            need = StepFeatures.of(r.page for r in [*self.active.values(), *pending])
+            if need != self._features_now:
+                self.engine.set_step_features(*need)
+                self._features_now = need
         self.engine.decode_steps(self.chunk)
         self.steps += self.chunk
         self.slot_steps_busy += self.chunk * len(self.active)

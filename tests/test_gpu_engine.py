@@ -486,9 +486,11 @@ def test_guided_generation_and_logprobs_match_oracle(engines, tiny_models, name)
 
 
 @pytest.mark.gpu
-def test_slot_scheduler_guided_and_logprobs_equal_solo(engines, tiny_models):
+@pytest.mark.parametrize("overlap", [False, True])
+def test_slot_scheduler_guided_and_logprobs_equal_solo(engines, tiny_models, overlap):
     """Continuous batching with guides and log-probabilities: patterns, DFA states and log-prob histories are per slot
-    and reset on admission — every request equals its solo `generate`, whatever held its slot before."""
+    and reset on admission — every request equals its solo `generate`, whatever held its slot before.  overlap: the
+    admissions run beside the decode chunks, and a guided one's first token keeps its guided pass."""
     from karanta_ocr_amd.scheduler import SlotRequest, SlotScheduler
     from karanta_ocr_amd.serving import ByteTokenizer
     cfg, w, P = tiny_models["tiny"]
@@ -505,7 +507,7 @@ def test_slot_scheduler_guided_and_logprobs_equal_solo(engines, tiny_models):
                                  temperature=(0.8 if i == 5 else 0.0), seed=5))
     limits = [16, 7, 16, 16, 5, 16]
     solo = [eng.generate([pg], mt) for pg, mt in zip(pages, limits)]
-    sch = SlotScheduler(eng, max_tokens_cap=16, chunk=3, sampling=True, guided=True, logprobs=4)
+    sch = SlotScheduler(eng, max_tokens_cap=16, chunk=3, sampling=True, guided=True, logprobs=4, overlap=overlap)
     res = sch.run([SlotRequest(pg, mt, tag=i) for i, (pg, mt) in enumerate(zip(pages, limits))])
     for i, (r, s) in enumerate(zip(res, solo)):
         assert r.error is None

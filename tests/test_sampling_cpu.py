@@ -1,6 +1,6 @@
 """Sampling controls on the host (no GPU): the six vLLM fields reach PageRequest through the server with vLLM's validation,
---greedy ignores them, and the slot scheduler switches the processing launches with the requests in the slots, the
-overlapped admission in flight included."""
+--greedy ignores them, StepFeatures decides the passes a set of pages needs, and the slot scheduler switches the passes with
+the requests in the slots, the overlapped admission in flight included."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -9,7 +9,7 @@ import pytest
 from karanta_ocr_amd import serving as S
 from karanta_ocr_amd.config import CONFIGS
 from karanta_ocr_amd.engine import PageRequest
-from karanta_ocr_amd.sampling import NEUTRAL, needs_processing, sampling_params
+from karanta_ocr_amd.sampling import NEUTRAL, StepFeatures, needs_processing, sampling_params
 from karanta_ocr_amd.scheduler import SlotRequest, SlotScheduler
 
 CFG = CONFIGS["tiny"]
@@ -90,7 +90,35 @@ def test_honor_temperature_off_ignores_the_fields():
     assert not needs_processing(p) and p.temperature == 0.0
 
 
-# ----------------------------------------------------------------------------- scheduler: the processing feature
+# ----------------------------------------------------------------------------- StepFeatures
+def test_step_features_of_pages():
+    of = lambda **kw: StepFeatures.of([SimpleNamespace(**kw)])
+    assert StepFeatures.of([]) == of() == StepFeatures(False, False, False)
+    for t in (None, 0, 0.0):
+        assert of(temperature=t) == StepFeatures()
+    assert of(temperature=0.5) == StepFeatures(True, False, False)
+    assert of(guide="x") == of(guide="x", temperature=0.0) == StepFeatures(True, True, False)     # guided implies sampling
+    assert of(guide=None, temperature=None) == StepFeatures()
+    for k, v in FIELDS.items():
+        assert of(**{k: v}) == StepFeatures(False, False, True), k
+        assert of(**{k: NEUTRAL[k]}) == of(**{k: None}) == StepFeatures(), k
+    assert of(top_k=-1) == StepFeatures()
+
+
+def test_step_features_union_and_clamp():
+    S_, G, P = StepFeatures(True, False, False), StepFeatures(True, True, False), StepFeatures(False, False, True)
+    assert S_ | P == StepFeatures(True, False, True) and G | S_ == G and StepFeatures() | P == P
+    pages = [SimpleNamespace(temperature=0.3), SimpleNamespace(guide="x"), SimpleNamespace(min_p=0.1)]
+    assert StepFeatures.of(pages) == StepFeatures.of(pages[:1]) | StepFeatures.of(pages[1:2]) | StepFeatures.of(pages[2:])
+    everything = StepFeatures(True, True, True)
+    assert everything & StepFeatures() == StepFeatures()
+    assert everything & StepFeatures(True, False, True) == StepFeatures(True, False, True)
+    assert StepFeatures(False, True, False) & everything == G             # a guided step keeps the pass it is masked in
+    assert StepFeatures(False, True, False) & StepFeatures(True, False, True) == StepFeatures()
+    assert P & G == StepFeatures() and G & G == G
+
+
+# ----------------------------------------------------------------------------- scheduler: the step features
 class Page:
     def __init__(self, key, **kw):
         self.input_ids = np.asarray([key, 0])
@@ -100,8 +128,8 @@ class Page:
 
 
 class FeatureEngine:
-    """Slot engine with the overlapped-admission API and set_step_features(s, g, processing); sequence j of a page emits
-    `length` tokens then EOS.  Records the features every decode chunk runs with."""
+    """Slot engine with the overlapped-admission API and set_step_features(s, g, processing); a page emits input_ids[0]
+    tokens then EOS.  Records the StepFeatures every decode chunk and every admission's first token run with."""
     class cfg:
         eos_token_ids = (99,)
 
@@ -109,16 +137,16 @@ class FeatureEngine:
 
     def __init__(self, n_slots):
         self.B = n_slots
-        self.features = (False, False, False)
-        self.log = []
+        self.features = StepFeatures()
+        self.log, self.eos_at = [], []
 
     def begin_slots(self, max_new, sampling=False, guided=False, logprobs=None):
         self.seq, self.gen, self.fin = [None] * self.B, [0] * self.B, [True] * self.B
         self.hist = [[] for _ in range(self.B)]
 
     def set_step_features(self, sampling, guided, processing=False):
-        self.features = (sampling, guided, processing)
-        self.log.append(("features", processing))
+        self.features = StepFeatures(sampling, guided, processing)
+        self.log.append(("features", self.features))
 
     def admit(self, pages, slots):
         for p, j in zip(pages, slots):
@@ -128,10 +156,9 @@ class FeatureEngine:
         return [len(p.input_ids) for p in pages]
 
     def admit_begin(self, pages, slots):
-        need = any(needs_processing(p) for p in pages)
-        self.log.append(("begin", need))
-        if need:        # like Engine.prefill: an admission that needs the launches switches them on by itself
-            self.features = self.features[:2] + (True,)
+        need = StepFeatures.of(pages)
+        self.log.append(("begin", need, list(slots)))
+        self.features |= need       # like Engine.prefill: an admission switches on what it needs by itself
         return {"pages": pages, "slots": list(slots), "polls": 0}
 
     def admit_ready(self, h):
@@ -140,7 +167,7 @@ class FeatureEngine:
 
     def admit_end(self, h):
         # the first token of the admission is sampled with the features the steps carry now
-        self.log.append(("end", self.features[2], any(needs_processing(p) for p in h["pages"])))
+        self.log.append(("end", self.features, StepFeatures.of(h["pages"])))
         return self.admit(h["pages"], h["slots"])
 
     def _emit(self, j):
@@ -150,9 +177,11 @@ class FeatureEngine:
         self.hist[j].append(tok)
         self.gen[j] += 1
         self.fin[j] = tok == 99
+        if self.fin[j]:
+            self.eos_at.append((len(self.log), j))    # (log position, slot)
 
     def decode_steps(self, n):
-        self.log.append(("steps", self.features[2]))
+        self.log.append(("steps", self.features))
         for _ in range(n):
             for j in range(self.B):
                 self._emit(j)
@@ -177,19 +206,43 @@ def test_processing_follows_the_slots_and_the_admission_in_flight():
     assert all(r.error is None for r in res)
     # every processed admission's first token ran with processing on, although the slots held no processed request
     ends = [e for e in eng.log if e[0] == "end"]
-    assert any(e[2] for e in ends) and all(e[1] for e in ends if e[2])
+    assert any(e[2].processing for e in ends) and all(e[1].processing for e in ends if e[2].processing)
     # a processed admission begun while only plain requests decode switches processing on for the chunks in between
-    i = next(k for k, e in enumerate(eng.log) if e == ("begin", True))
+    i = next(k for k, e in enumerate(eng.log) if e[0] == "begin" and e[1].processing)
     j = next(k for k in range(i, len(eng.log)) if eng.log[k][0] == "end")
-    assert all(e[1] for e in eng.log[i:j] if e[0] == "steps")
+    assert all(e[1].processing for e in eng.log[i:j] if e[0] == "steps")
     # ... and off again once the last processed request has left (the long plain one keeps decoding)
-    steps = [e[1] for e in eng.log if e[0] == "steps"]
+    steps = [e[1].processing for e in eng.log if e[0] == "steps"]
     assert True in steps and steps[-1] is False
-    assert eng.log[-1][0] == "steps" and not eng.features[2]
+    assert eng.log[-1][0] == "steps" and not eng.features.processing
 
 
 def test_processing_stays_off_for_plain_traffic():
     eng = FeatureEngine(2)
     sch = SlotScheduler(eng, max_tokens_cap=64, chunk=2, sampling=True, overlap=True)
     sch.run([SlotRequest(Page(3, temperature=0.5), 8, tag=i) for i in range(3)])
-    assert not any(e[1] for e in eng.log if e[0] == "steps")
+    assert not any(e[1].processing for e in eng.log if e[0] == "steps")
+
+
+def test_guided_admission_in_flight_keeps_its_passes():
+    """guided C finishes while guided B is between admit_begin and admit_end and plain A decodes.  The
+    chunks in between must keep the guided / sampling passes that B's first token needs, not switch them off with C."""
+    eng = FeatureEngine(3)
+    sch = SlotScheduler(eng, max_tokens_cap=64, chunk=2, sampling=True, guided=True, overlap=True)
+    a, c, b = (SlotRequest(Page(30), 40, tag="plain-A"), SlotRequest(Page(5, guide="x"), 10, tag="guided-C"),
+               SlotRequest(Page(6, guide="y", temperature=0.7), 10, tag="guided-B"))
+    sch.submit(a)
+    sch.submit(c)
+    done = []
+    while len(sch.active) < 2:
+        done += sch.step()
+    sch.submit(b)
+    while not sch.idle:
+        done += sch.step()
+    assert sorted(r.tag for r in done) == ["guided-B", "guided-C", "plain-A"] and all(r.error is None for r in done)
+    i = next(k for k, e in enumerate(eng.log) if e[0] == "begin" and e[2] == [2])     # B's admission (A, C: slots 0, 1)
+    j = next(k for k in range(i, len(eng.log)) if eng.log[k][0] == "end")
+    assert any(i < k <= j and slot == 1 for k, slot in eng.eos_at), "the scenario needs C (slot 1) to finish while B is in flight"
+    assert eng.log[j][2] == StepFeatures(True, True, False)
+    assert eng.log[j][1].guided and eng.log[j][1].sampling, eng.log[i:j + 1]
+    assert all(e[1].guided for e in eng.log[i:j] if e[0] == "steps")
