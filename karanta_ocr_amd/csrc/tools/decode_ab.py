@@ -19,11 +19,13 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))))
 from karanta_ocr_amd._lib import lib  # noqa: E402
 from karanta_ocr_amd.config import CONFIGS  # noqa: E402
-from karanta_ocr_amd.engine import Engine  # noqa: E402
+from karanta_ocr_amd.engine import SEQUENCE_SWITCHES, Engine  # noqa: E402
 from karanta_ocr_amd.csrc.tools.experiment_engine import ExperimentEngine  # noqa: E402
 
-EXPERIMENT_KEYS = {"fast_residual", "attn_fused_merge", "merge_in_o_proj", "_prefetch_mode", "_extra_nulls", "experiment"}
-EXPERIMENT_ENV = {"KARANTA_PREFETCH", "KARANTA_FAST_RESIDUAL", "KARANTA_ATTN_FUSED", "KARANTA_MERGE_IN_OPROJ", "KARANTA_EXTRA_NULLS"}
+EXPERIMENT_KEYS = {"fast_residual", "attn_fused_merge", "merge_in_o_proj", "_prefetch_mode", "_extra_nulls", "experiment",
+                   "narrow_mode", "narrow_o", "defer_down", "atomic_slab", "resnorm_qkv"}   # only ExperimentEngine branches on these
+EXPERIMENT_ENV = {"KARANTA_PREFETCH", "KARANTA_FAST_RESIDUAL", "KARANTA_ATTN_FUSED", "KARANTA_MERGE_IN_OPROJ", "KARANTA_EXTRA_NULLS",
+                  "KARANTA_RESNORM_QKV", *SEQUENCE_SWITCHES}      # the superseded launch sequences: the product engine refuses them
 
 
 def fill_random(arena: torch.Tensor):
@@ -73,6 +75,8 @@ def main():
                 env[k] = v
             else:
                 over[k] = v
+        if "wide_mode" in over:
+            raise SystemExit("wide_mode sizes the argmax partials at construction: use KARANTA_WIDE=0")
         old = {k: os.environ.get(k) for k in env}
         os.environ.update(env)
         cls = ExperimentEngine if (EXPERIMENT_KEYS & set(over) or EXPERIMENT_ENV & set(env)) else Engine
@@ -271,7 +275,7 @@ def chains(a, engines, reset):
                 eng._dec_wide(DEC_SILU8, None, w.view(p + "gate_up.w"), B, out=eng.d_act, norm_w=w.view(p + "ln2.w"), x_f32=eng.d_xacc,
                               x_out=eng.d_x, **eng._w8kw(p + "gate_up.w"))
             elif kind == "down":
-                eng._dec_narrow(DEC_PLAIN, eng.d_act, w.view(p + "down.w"), B, out_f32=eng.d_part, waves=eng._down_waves(B), ksplit=2,
+                eng._dec_narrow(DEC_PLAIN, eng.d_act, w.view(p + "down.w"), B, out_f32=eng.d_part, waves=eng.down_waves_small if B <= 16 else 8, ksplit=2,
                                 **eng._w8kw(p + "down.w"))
             else:
                 raise SystemExit(f"unknown chain kind {kind}")

@@ -1,8 +1,13 @@
 """The measured-and-not-adopted variants of the decode step (rounds 1-3), kept runnable for A/B timing
 (csrc/tools/decode_ab.py) and for their tests — NOT part of the product path.
 
-`ExperimentEngine` is `karanta_ocr_amd.engine.Engine` with the round-3 launch sequence of one decode step, which interleaves the
-product launches with:
+`ExperimentEngine` is `karanta_ocr_amd.engine.Engine` with the round-3 launch sequence of one decode step and the switches that
+select its superseded forms (the product engine refuses them):
+  KARANTA_NARROW=0 / _NARROW_O=0 / KARANTA_WIDE=0   first-generation kr_linear_decode for qkv + down_proj / o_proj / gate/up + lm_head
+  KARANTA_DEFER_DOWN=0 / KARANTA_ATOMIC_SLAB=0      down_proj + residual in one launch / two-slab form of the deferred split
+  KARANTA_RESNORM_QKV=0 / 1    > 16 rows: the fused qkv launch (per 16-row range at the 7B width) / kr_decode_resnorm + one direct qkv launch
+  KARANTA_DEC32=0              names this engine: its > 16-row steps are round 3's two-column-tile narrow launches
+It interleaves the launches with:
   KARANTA_PREFETCH=1..6        Infinity-Cache prefetch of a layer's MLP weights (serial / second graph branch / idle-CU workgroups
                                riding on the qkv launch)                                   DESIGN.md 5-r2: all slower
   fast_residual                o_proj split by attention head + float atomics into an f32 residual accumulator, no merge launch
@@ -21,7 +26,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from karanta_ocr_amd._lib import DEC_ARGMAX, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, KarantaHipError, ptr
+from karanta_ocr_amd._lib import DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, KarantaHipError, narrow_opts, ptr
 from karanta_ocr_amd.engine import Engine
 
 
@@ -40,6 +45,20 @@ class ExperimentEngine(Engine):
             raise KarantaHipError("KARANTA_PREFETCH / KARANTA_FAST_RESIDUAL / KARANTA_ATTN_FUSED need a library built with "
                                   "-DKR_EXPERIMENTS (csrc/tools/build_variant.py), loaded through KARANTA_HIP_LIB")
         self.family32 = False          # round 3's sequence: row-major narrow launches at every batch size
+        on = lambda k: os.environ.get(k, "1") == "1"
+        self.narrow_mode = on("KARANTA_NARROW")
+        self.narrow_o = self.narrow_mode and on("KARANTA_NARROW_O")
+        self.defer_down = self.defer_down and self.narrow_mode and on("KARANTA_DEFER_DOWN")
+        self.atomic_slab = on("KARANTA_ATOMIC_SLAB")
+        if "KARANTA_RESNORM_QKV" in os.environ:
+            self.resnorm_qkv = on("KARANTA_RESNORM_QKV")
+        if self.wide_mode and not on("KARANTA_WIDE"):
+            # the lm_head launch of kr_linear_decode leaves one argmax partial per workgroup pair of tiles
+            self.wide_mode, self.n_amax = False, (t.vocab_size // 16 + 1) // 2
+            self.d_amax_v = torch.zeros(B, self.n_amax, dtype=torch.float32, device=dev)
+            self.d_amax_i = torch.zeros(B, self.n_amax, dtype=torch.int32, device=dev)
+        if (B > 16 or self.fp8) and not (self.wide_mode and self.narrow_mode and (self.narrow_o or B <= 16)):
+            raise KarantaHipError("max_batch > 16 and fp8 weights need the wide / narrow decode kernels")
         self.d_xacc = torch.zeros(B, t.hidden_size, dtype=torch.float32, device=dev)      # fast-residual mode: f32 residual accumulator
         self.d_cnt = torch.zeros(B * t.num_kv_heads, dtype=torch.int32, device=dev)       # arrival counters of the in-launch merge
         self.fast_residual = want_fast and self.narrow_mode and self.wide_mode and not self.row_split
@@ -57,18 +76,54 @@ class ExperimentEngine(Engine):
             ev = self._pf_ev[layer] = (a, b)
         return ev
 
-    def _dec_narrow_experiment(self, head, tail, W, w8, w_scale, x_out_f32=None, prefetch=None):
-        """kr_linear_decode_narrow_x32: workgroup 0 also stores x_new as the f32 accumulator's start value (fast-residual mode);
-        prefetch = (address, bytes, blocks): prefetch workgroups ride on the launch."""
-        if x_out_f32 is None and prefetch is None:
-            if w8 is not None:
-                self.L.kr_linear_decode_narrow_fp8(*head, ptr(w8), ptr(w_scale), *tail, self.s)
-            else:
-                self.L.kr_linear_decode_narrow(*head, ptr(W), *tail, self.s)
-            return
-        pf = prefetch or (0, 0, 0)
-        self.L.kr_linear_decode_narrow_x32(*head, ptr(x_out_f32), x_out_f32.stride(0) if x_out_f32 is not None else 0,
-                                           ptr(w8 if w8 is not None else W), ptr(w_scale), *tail, int(pf[0]), int(pf[1]), int(pf[2]), self.s)
+    def _down_waves(self, B: int) -> int:
+        return self.down_waves_small if B <= 16 else 8   # two batch column tiles double the x fragments: 8-wave workgroups only
+
+    def _row_ranges(self, B: int):
+        """(first row, rows) of the qkv launches: the whole batch, or 16-row ranges when 32 x rows do not fit (row_split)."""
+        if self.row_split and B > 16:
+            return [(0, 16), (16, B - 16)]
+        return [(0, B)]
+
+    def _dec(self, mode, x, W, M, out=None, out_f32=None, bias=None, norm_w=None, res=None, waves=4, kc=0, vc=0,
+             attn_partials=None):
+        """kr_linear_decode in full: bias, residual, the M-RoPE + KV append epilogue, the split-KV merge prologue (x = None)."""
+        t = self.cfg.text
+        N, K = W.shape
+        o = out if out is not None else out_f32
+        self.L.kr_linear_decode(mode, ptr(x), x.stride(0) if x is not None else 0, ptr(W), ptr(bias), ptr(norm_w),
+                                t.rms_norm_eps, ptr(res), res.stride(0) if res is not None else 0, ptr(out), ptr(out_f32),
+                                o.stride(0) if o is not None else 0, M, N, K, waves, self.persist_blocks, 1, 0, 0,
+                                ptr(attn_partials), self.n_split, ptr(self.d_cs), self.max_new, ptr(self.d_plen),
+                                ptr(self.d_ctx), ptr(self.d_q), kc, vc, t.num_heads, t.num_kv_heads, self.s_max,
+                                ptr(self.d_amax_v), ptr(self.d_amax_i), self.s)
+
+    def _dec_narrow(self, mode, x, W, M, out=None, out_f32=None, bias=None, norm_w=None, res=None, waves=8, ksplit=1,
+                    part_in=None, x_out=None, kc=0, vc=0, w8=None, w_scale=None, part_rows=0, row0=0, zero=None,
+                    atomic_out=False, x_out_f32=None, prefetch=None):
+        """The product launch, plus: row0 (the launch covers batch rows row0 .. row0 + M - 1: every per-sequence array is handed
+        over from that row; part_rows: the row count the slabs of part_in were packed with); x_out_f32 / prefetch
+        (kr_linear_decode_narrow_x32: workgroup 0 also stores x_new as the f32 accumulator's start value, fast-residual mode;
+        prefetch = (address, bytes, blocks): prefetch workgroups ride on the launch)."""
+        t = self.cfg.text
+        N, K = W.shape
+        o = out if out is not None else out_f32
+        head = (mode, ptr(x), x.stride(0), ptr(part_in), int(part_in.shape[0]) if part_in is not None else 0, ptr(x_out),
+                x_out.stride(0) if x_out is not None else 0)
+        cache0 = 2 * row0 * t.num_kv_heads * self.s_max * t.head_dim
+        args = (ptr(bias), ptr(norm_w), t.rms_norm_eps, ptr(res), res.stride(0) if res is not None else 0, ptr(out),
+                ptr(out_f32), o.stride(-2) if o is not None else 0, M, N, K, waves, ksplit,
+                ptr(self.d_cs[row0:]) if self.d_cs is not None else 0, self.max_new, ptr(self.d_plen[row0:]), ptr(self.d_ctx[row0:]),
+                ptr(self.d_q[row0:]), kc + cache0 if kc else 0, vc + cache0 if vc else 0, t.num_heads, t.num_kv_heads, self.s_max,
+                narrow_opts(ptr(zero), zero.numel() * 4 if zero is not None else 0, atomic_out, part_rows))
+        if x_out_f32 is not None or prefetch is not None:
+            pf = prefetch or (0, 0, 0)
+            self.L.kr_linear_decode_narrow_x32(*head, ptr(x_out_f32), x_out_f32.stride(0) if x_out_f32 is not None else 0,
+                                               ptr(w8 if w8 is not None else W), ptr(w_scale), *args, int(pf[0]), int(pf[1]), int(pf[2]), self.s)
+        elif w8 is not None:
+            self.L.kr_linear_decode_narrow_fp8(*head, ptr(w8), ptr(w_scale), *args, self.s)
+        else:
+            self.L.kr_linear_decode_narrow(*head, ptr(W), *args, self.s)
 
     def _dec_wide_x32(self, mode, x_f32, x_out, W, M, out=None, out_f32=None, norm_w=None, w8=None, w_scale=None):
         """kr_linear_decode_wide_x32 (fast-residual mode): the rows come from the f32 residual accumulator; x_out receives their
@@ -149,22 +204,18 @@ class ExperimentEngine(Engine):
                         pending = False
                     self._dec_narrow(DEC_ROPE_KV, self.d_h, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), kc=kc, vc=vc, zero=zero,
                                      **self._w8kw(p + "qkv.w"))
-                elif pending:
-                    for k, (r0, m) in enumerate(ranges):
-                        pin = slabs[i & 1:(i & 1) + 1, r0:] if one_slab else slabs[:, r0:]
-                        self._dec_narrow(DEC_ROPE_KV, x[r0:], w.view(p + "qkv.w"), m, bias=w.view(p + "qkv.b"),
-                                         norm_w=w.view(p + "ln1.w"), part_in=pin, x_out=x_other[r0:], kc=kc, vc=vc,
-                                         x_out_f32=None if xacc is None else xacc[r0:], part_rows=B if len(ranges) > 1 else 0,
-                                         row0=r0, zero=zero if k == 0 else None, prefetch=pf if k == 0 else None,
-                                         **self._w8kw(p + "qkv.w"))
-                    x, x_other = x_other, x
-                    pending = False
                 else:
                     for k, (r0, m) in enumerate(ranges):
+                        pin = (slabs[i & 1:(i & 1) + 1, r0:] if one_slab else slabs[:, r0:]) if pending else None
                         self._dec_narrow(DEC_ROPE_KV, x[r0:], w.view(p + "qkv.w"), m, bias=w.view(p + "qkv.b"),
-                                         norm_w=w.view(p + "ln1.w"), kc=kc, vc=vc, x_out_f32=None if xacc is None else xacc[r0:],
+                                         norm_w=w.view(p + "ln1.w"), part_in=pin, x_out=x_other[r0:] if pending else None, kc=kc, vc=vc,
+                                         x_out_f32=None if xacc is None else xacc[r0:],
+                                         part_rows=B if (pending and len(ranges) > 1) else 0,
                                          row0=r0, zero=zero if k == 0 else None, prefetch=pf if k == 0 else None,
                                          **self._w8kw(p + "qkv.w"))
+                    if pending:
+                        x, x_other = x_other, x
+                        pending = False
             else:
                 self._dec(DEC_ROPE_KV, x, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), norm_w=w.view(p + "ln1.w"),
                           waves=self.wv_qkv, kc=kc, vc=vc)
@@ -179,16 +230,12 @@ class ExperimentEngine(Engine):
                 w8o, sco = self._w8(p + "o.w")
                 L.kr_oproj_heads(ptr(self.d_ws), self.n_split, ptr(w8o if w8o is not None else w.view(p + "o.w")), ptr(sco),
                                  ptr(self.d_xacc), self.d_xacc.stride(0), B, t.hidden_size, H, s)
-            elif self.attn_fused_merge:
-                if self.narrow_o:
-                    self._dec_narrow(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, out=x, res=x, waves=self.o_waves if B <= 16 else 8, **self._w8kw(p + "o.w"))
-                else:
-                    self._dec(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, out=x, res=x, waves=self.wv_o)
-            elif self.merge_in_o_proj:
+            elif self.merge_in_o_proj and not self.attn_fused_merge:
                 self._dec(DEC_PLAIN, None, w.view(p + "o.w"), B, out=x, res=x, waves=self.wv_o,
                           attn_partials=self.d_ws)
             else:
-                L.kr_attn_decode_merge(ptr(self.d_ws), ptr(self.d_o), B, H, hd, self.n_split, s)
+                if not self.attn_fused_merge:
+                    L.kr_attn_decode_merge(ptr(self.d_ws), ptr(self.d_o), B, H, hd, self.n_split, s)
                 if self.narrow_o:
                     self._dec_narrow(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, out=x, res=x, waves=self.o_waves if B <= 16 else 8, **self._w8kw(p + "o.w"))
                 else:
@@ -214,13 +261,9 @@ class ExperimentEngine(Engine):
                 L.kr_event_record(e2, s)
             if self.defer_down and i + 1 < nl:
                 # 2 workgroups per tile; the slabs are added to x by the next layer's qkv prologue
-                if self.atomic_slab:
-                    acc = self.d_part.view(-1)[: 2 * B * t.hidden_size].view(2, B, t.hidden_size)[(i + 1) & 1]
-                    self._dec_narrow(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, out_f32=acc, waves=self._down_waves(B), ksplit=2,
-                                     atomic_out=True, **self._w8kw(p + "down.w"))
-                else:
-                    self._dec_narrow(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, out_f32=self.d_part, waves=self._down_waves(B),
-                                     ksplit=2, **self._w8kw(p + "down.w"))
+                acc = slabs[(i + 1) & 1] if self.atomic_slab else self.d_part
+                self._dec_narrow(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, out_f32=acc, waves=self._down_waves(B), ksplit=2,
+                                 atomic_out=self.atomic_slab, **self._w8kw(p + "down.w"))
                 pending = True
             elif self.narrow_mode:
                 self._dec_narrow(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, out=x, res=x, waves=self._down_waves(B),
@@ -230,7 +273,6 @@ class ExperimentEngine(Engine):
             for _ in range(self._extra_nulls):  # diagnostic: price of one more (empty) launch in the chain
                 L.kr_launch_null(s)
         self._lm_head_and_sample(B, x)
-
 
     def set_fast_residual(self, on: bool):
         """Switch between the deterministic decode step (split-KV merge launch + slab reductions) and the fast-residual

@@ -32,6 +32,8 @@ from .weights import pack_w16x64, to_bf16_bits
 BF16 = torch.bfloat16
 GEMM_SCRATCH_BYTES = 512 * 65536   # include/karanta_hip.h: KR_GEMM_SCRATCH_BYTES
 FP8_ACT_DEFAULT = False            # fp8 engines: W8A8 prefill on by default? (measured error and speed)
+# default-on switches of csrc/tools/experiment_engine.ExperimentEngine that select a superseded decode launch sequence
+SEQUENCE_SWITCHES = ("KARANTA_NARROW", "KARANTA_NARROW_O", "KARANTA_DEFER_DOWN", "KARANTA_WIDE", "KARANTA_ATOMIC_SLAB", "KARANTA_DEC32")
 
 
 def _bits(w: np.ndarray) -> np.ndarray:
@@ -319,6 +321,14 @@ class Engine:
             raise KarantaHipError("KARANTA_PREFETCH / KARANTA_FAST_RESIDUAL / KARANTA_ATTN_FUSED / KARANTA_MERGE_IN_OPROJ are decode "
                                   "experiments: they run on csrc/tools/experiment_engine.ExperimentEngine with a -DKR_EXPERIMENTS "
                                   "library (csrc/tools/build_variant.py, KARANTA_HIP_LIB), not on the product engine")
+        # the switches that used to select a superseded launch sequence: refused, not ignored (an A/B of two identical runs)
+        if os.environ.get("KARANTA_RESNORM32_QKV", "1") != "1":
+            raise KarantaHipError("KARANTA_RESNORM32_QKV is retired: the packed family with the fused row-major qkv launch was "
+                                  "measured and dropped (profiles/r04_decode32_chains.txt)")
+        moved = [k for k in SEQUENCE_SWITCHES if os.environ.get(k, "1") != "1"] + [k for k in ("KARANTA_RESNORM_QKV",) if k in os.environ]
+        if type(self) is Engine and moved:
+            raise KarantaHipError(" / ".join(moved) + ": superseded decode launch sequences run on csrc/tools/experiment_engine."
+                                  "ExperimentEngine (csrc/tools/decode_ab.py builds it for such a variant), not on the product engine")
         v, t = cfg.vision, cfg.text
         if v.head_dim not in (80, 128) or t.head_dim != 128:
             raise KarantaHipError(f"unsupported head dims vit={v.head_dim} llm={t.head_dim}")
@@ -386,10 +396,9 @@ class Engine:
         self.d_x2 = z(B, t.hidden_size)  # the other residual buffer (deferred split-K ping-pong)
         # down_proj slabs of the deferred split: [2][B][hidden]; > 16 rows with the group-split down_proj: two PAIRS (layer parity)
         self.d_part = z(4 if B > 16 else 2, B, t.hidden_size, dtype=torch.float32)
-        # ONE-slab form of the deferred split (KARANTA_ATOMIC_SLAB, default on): down_proj's two K ranges add into one f32
-        # accumulator with float atomics (a + b onto zero: order-free, reproducible); two accumulators alternate by layer
-        # parity, layer L's qkv launch zeroes the one layer L's down_proj adds into.  d_part doubles as the pair.
-        self.atomic_slab = os.environ.get("KARANTA_ATOMIC_SLAB", "1") == "1"
+        # ONE-slab form of the deferred split: down_proj's two K ranges add into one f32 accumulator with float atomics
+        # (a + b onto zero: order-free, reproducible); two accumulators alternate by layer parity, layer L's qkv launch
+        # zeroes the one layer L's down_proj adds into.  d_part doubles as the pair.
         # down_proj at >= 192 weight tiles (7B widths) runs two tiles per workgroup (kr_decode.hip, launch_narrow_direct):
         # 8-wave workgroups with a 5-deep ring then beat 16-wave ones (7B step 2.992 -> 2.975 ms)
         if t.hidden_size // 16 >= 192:
@@ -414,40 +423,27 @@ class Engine:
             v_ = os.environ.get("KARANTA_WV_" + name.upper())
             if v_:
                 setattr(self, "wv_" + name, int(v_))
-        # qkv / o_proj / down_proj: kr_linear_decode_narrow; down_proj split over 2 workgroups per tile with the
-        # reduction deferred to the next layer's qkv prologue (K = 1536 / 2048 / 3584 only)
-        self.narrow_mode = os.environ.get("KARANTA_NARROW", "1") == "1"
-        self.narrow_o = self.narrow_mode and os.environ.get("KARANTA_NARROW_O", "1") == "1"
-        self.defer_down = (self.narrow_mode and os.environ.get("KARANTA_DEFER_DOWN", "1") == "1"
-                           and t.hidden_size in (1536, 2048, 3584))
+        # down_proj split over 2 workgroups per tile with the reduction deferred to the next layer's qkv prologue
+        # (K = 1536 / 2048 / 3584 only)
+        self.defer_down = t.hidden_size in (1536, 2048, 3584)
         # gate/up and lm_head: one wave per 16-row tile (kr_linear_decode_wide) when K allows it
-        self.wide_mode = os.environ.get("KARANTA_WIDE", "1") == "1" and t.hidden_size % 512 == 0 and t.hidden_size <= 4096
+        self.wide_mode = t.hidden_size % 512 == 0 and t.hidden_size <= 4096
         self.wide_blocks = int(os.environ.get("KARANTA_WIDE_BLOCKS", "256"))
         self.wide_waves = int(os.environ.get("KARANTA_WIDE_WAVES", "0"))  # 0: ceil(tiles / blocks), at most 8
         self.wide_spread32 = os.environ.get("KARANTA_WIDE_SPREAD32", "1") == "1"   # > 16 rows: tiles dealt as at <= 16 rows (_wide_geometry)
-        if self.B > 16 and not (self.wide_mode and self.narrow_mode and self.narrow_o and t.intermediate_size % 64 == 0):
+        if self.B > 16 and not (self.wide_mode and t.intermediate_size % 64 == 0):
             raise KarantaHipError("max_batch > 16 needs the wide / narrow decode kernels (hidden_size % 512 == 0) and hidden_size <= 2048 or == 3584")
-        # Above 16 rows the decode linears hold two 16-row column tiles per weight fragment, with all 32 normalised x rows
-        # in LDS — which fits up to hidden_size 2048 (Qwen2-VL-2B, Qwen2.5-VL-3B).  At the 7B width (32 x 3584 bf16 = 229 KB
-        # against 160 KB of LDS) the wide launches (gate/up, lm_head) stage K in two halves (dec_wide_kh_kernel: weights
-        # still read once) and the qkv launch, whose norm prologue keeps whole rows per wave, runs ONCE PER 16-ROW RANGE
-        # (33 MB of 14 GB streamed twice); o_proj / down_proj read their x fragments straight from L2 on two column tiles.
+        # Above 16 rows the narrow linears (qkv behind kr_decode_resnorm32, o_proj, down_proj) run as the packed-activation
+        # family (kr_linear_decode32) and the wide launches (gate/up, lm_head) hold two 16-row column tiles per weight
+        # fragment, with all 32 normalised x rows in LDS — which fits up to hidden_size 2048 (Qwen2-VL-2B, Qwen2.5-VL-3B).
+        # At the 7B width (32 x 3584 bf16 = 229 KB against 160 KB of LDS) they stage K in two halves (dec_wide_kh_kernel:
+        # weights still read once): row_split.
         self.row_split = self.B > 16 and t.hidden_size > 2048
-        # > 16 rows: kr_decode_resnorm + ONE direct qkv launch.  On where the fused launch would have to run per 16-row range
-        # (the 7B width: 4.73 -> 4.47 ms per step); at widths whose 32 rows fit the fused launch's LDS it is 1 % slower
-        # (Qwen2-VL-2B, same-box A/B: 1.957 vs 1.979 ms) and stays off.  KARANTA_RESNORM_QKV = 0 / 1 forces either.
-        env_rn = os.environ.get("KARANTA_RESNORM_QKV")
-        self.resnorm_qkv = (env_rn == "1") if env_rn is not None else self.row_split
-        # > 16 rows: the packed-activation family (kr_linear_decode32) for qkv (behind kr_decode_resnorm32), o_proj and
-        # down_proj; KARANTA_DEC32=0: round 3's two-column-tile instantiations of the narrow kernel (row-major x fragments)
-        # ... with kr_decode_resnorm32 + the packed qkv launch also at the widths whose fused qkv launch fits (KARANTA_RESNORM32_QKV)
-        self.resnorm32_qkv = os.environ.get("KARANTA_RESNORM32_QKV", "1") == "1"
+        self.family32, self.resnorm_qkv = self.B > 16, self.row_split     # what bench.py --full counts launches from
         self.group_split_down = int(os.environ.get("KARANTA_DOWN_GS", "1"))   # 0 off, 1 at 16-atom partitions (2B widths), 2 always
-        self.family32 = (self.B > 16 and self.narrow_mode and self.narrow_o and t.intermediate_size % 64 == 0 and t.q_dim % 64 == 0
-                         and t.hidden_size % 64 == 0 and os.environ.get("KARANTA_DEC32", "1") == "1")
         if self.row_split and t.hidden_size != 3584:
             raise KarantaHipError("max_batch > 16: hidden_size <= 2048 or == 3584 (the 7B width) only")
-        if self.fp8 and not (self.wide_mode and self.narrow_mode):
+        if self.fp8 and not self.wide_mode:
             raise KarantaHipError("fp8 weights need the wide / narrow decode kernels: hidden_size % 512 == 0 and <= 4096")
         # one argmax partial per wave of the lm_head launch; the launch geometry depends on the row count (8 waves above
         # 16 rows), so the buffers are sized for the larger one and the sampler is told the launch's own count
@@ -522,44 +518,35 @@ class Engine:
                                ptr(C_), C_.stride(0), M, N, K, epi, 1 if packed else 0, ptr(self.gemm_scratch),
                                self.gemm_scratch.numel() * 4, self.s)
 
-    def _dec(self, mode, x, W, M, out=None, out_f32=None, bias=None, norm_w=None, res=None, waves=4, kc=0, vc=0,
-             attn_partials=None):
-        """kr_linear_decode on packed weights (no cross-workgroup split on the engine's path)."""
+    def _dec(self, mode, x, W, M, out=None, out_f32=None, norm_w=None, waves=4):
+        """kr_linear_decode on packed weights: gate/up and lm_head at the widths without the wide kernels."""
         t = self.cfg.text
         N, K = W.shape
         o = out if out is not None else out_f32
-        self.L.kr_linear_decode(mode, ptr(x), x.stride(0) if x is not None else 0, ptr(W), ptr(bias), ptr(norm_w),
-                                t.rms_norm_eps, ptr(res), res.stride(0) if res is not None else 0, ptr(out), ptr(out_f32),
+        self.L.kr_linear_decode(mode, ptr(x), x.stride(0), ptr(W), 0, ptr(norm_w), t.rms_norm_eps, 0, 0, ptr(out), ptr(out_f32),
                                 o.stride(0) if o is not None else 0, M, N, K, waves, self.persist_blocks, 1, 0, 0,
-                                ptr(attn_partials), self.n_split, ptr(self.d_cs), self.max_new, ptr(self.d_plen),
-                                ptr(self.d_ctx), ptr(self.d_q), kc, vc, t.num_heads, t.num_kv_heads, self.s_max,
+                                0, self.n_split, ptr(self.d_cs), self.max_new, ptr(self.d_plen),
+                                ptr(self.d_ctx), ptr(self.d_q), 0, 0, t.num_heads, t.num_kv_heads, self.s_max,
                                 ptr(self.d_amax_v), ptr(self.d_amax_i), self.s)
 
     def _dec_narrow(self, mode, x, W, M, out=None, out_f32=None, bias=None, norm_w=None, res=None, waves=8, ksplit=1,
-                    part_in=None, x_out=None, kc=0, vc=0, w8=None, w_scale=None, part_rows=0, row0=0,
-                    zero=None, atomic_out=False, **experiment):
-        """kr_linear_decode_narrow: one workgroup per tile (pair); ksplit > 1 = deferred split-K slabs in out_f32.
+                    part_in=None, x_out=None, kc=0, vc=0, w8=None, w_scale=None, zero=None, atomic_out=False):
+        """kr_linear_decode_narrow: one workgroup per tile (pair); ksplit > 1 = deferred split-K sums in out_f32.
         w8 / w_scale: the fp8 copy of W and its row scales (kr_linear_decode_narrow_fp8).  zero (an f32 tensor the launch
-        also zeroes), atomic_out, part_rows: the launch's kr_narrow_opts."""
+        also zeroes), atomic_out: the launch's kr_narrow_opts."""
         t = self.cfg.text
         N, K = W.shape
         o = out if out is not None else out_f32
-        ldc = o.stride(-2) if o is not None else 0  # slabs of the deferred split are [ksplit][M][ldc] with the CURRENT M, packed in d_part
         head = (mode, ptr(x), x.stride(0), ptr(part_in), int(part_in.shape[0]) if part_in is not None else 0, ptr(x_out),
                 x_out.stride(0) if x_out is not None else 0)
-        opts = narrow_opts(ptr(zero) if zero is not None else 0, zero.numel() * 4 if zero is not None else 0, atomic_out, part_rows)
-        # row0: the launch covers batch rows row0 .. row0 + M - 1 (every per-sequence array is handed over from that row)
-        tail = (ptr(bias), ptr(norm_w), t.rms_norm_eps, ptr(res), res.stride(0) if res is not None else 0, ptr(out),
-                ptr(out_f32), ldc, M, N, K, waves, ksplit, ptr(self.d_cs[row0:]) if self.d_cs is not None else 0, self.max_new,
-                ptr(self.d_plen[row0:]), ptr(self.d_ctx[row0:]), ptr(self.d_q[row0:]),
-                kc + 2 * row0 * t.num_kv_heads * self.s_max * t.head_dim if kc else 0,
-                vc + 2 * row0 * t.num_kv_heads * self.s_max * t.head_dim if vc else 0, t.num_heads, t.num_kv_heads, self.s_max, opts)
-        if experiment:      # csrc/tools/experiment_engine.py (x_out_f32, prefetch: kr_linear_decode_narrow_x32)
-            self._dec_narrow_experiment(head, tail, W, w8, w_scale, **experiment)
-        elif w8 is not None:
-            self.L.kr_linear_decode_narrow_fp8(*head, ptr(w8), ptr(w_scale), *tail, self.s)
+        args = (ptr(bias), ptr(norm_w), t.rms_norm_eps, ptr(res), res.stride(0) if res is not None else 0, ptr(out),
+                ptr(out_f32), o.stride(-2) if o is not None else 0, M, N, K, waves, ksplit, ptr(self.d_cs), self.max_new,
+                ptr(self.d_plen), ptr(self.d_ctx), ptr(self.d_q), kc, vc, t.num_heads, t.num_kv_heads, self.s_max,
+                narrow_opts(ptr(zero), zero.numel() * 4 if zero is not None else 0, atomic_out), self.s)
+        if w8 is not None:
+            self.L.kr_linear_decode_narrow_fp8(*head, ptr(w8), ptr(w_scale), *args)
         else:
-            self.L.kr_linear_decode_narrow(*head, ptr(W), *tail, self.s)
+            self.L.kr_linear_decode_narrow(*head, ptr(W), *args)
 
     def _dec32(self, mode, xp, W, M, waves_ref, out=None, out_f32=None, bias=None, res=None, ksplit=1, atomic_out=False, zero=None,
                kc=0, vc=0, w8=None, w_scale=None, tiles_per_wg=0, group_split=False):
@@ -577,12 +564,13 @@ class Engine:
                   t.num_heads, t.num_kv_heads, self.s_max)
         self.L.kr_linear_decode32(mode, C.byref(a), self.s)
 
+    # the shipped sequence; ExperimentEngine overrides these per instance; bench.py --full reads resnorm_qkv, family32,
+    # resnorm32_qkv (the instance's wide_mode, defer_down, row_split, family32, resnorm_qkv follow from its config: _alloc)
+    narrow_mode = narrow_o = atomic_slab = resnorm32_qkv = True
+
     down_waves_small = 16         # waves per down_proj workgroup at <= 16 rows (instance attribute for sweeps)
     down_gs_tiles = 0             # weight tiles per workgroup of the group-split down_proj (0: 4 at 8-atom partitions, else 2)
     o_waves = 8                   # waves per o_proj workgroup at <= 16 rows
-
-    def _down_waves(self, B: int) -> int:
-        return self.down_waves_small if B <= 16 else 8   # two batch column tiles double the x fragments: 8-wave workgroups only
 
     def _w8kw(self, name: str) -> dict:
         w8, sc = self._w8(name)
@@ -610,25 +598,18 @@ class Engine:
         waves = self.wide_waves or (8 if M > 16 else min(8, -(-tiles // self.wide_blocks)))
         return min(self.wide_blocks, -(-tiles // waves)), waves
 
-    def _row_ranges(self, B: int):
-        """(first row, rows) of the qkv launches: the whole batch, or 16-row ranges when 32 x rows do not fit (row_split)."""
-        if self.row_split and B > 16:
-            return [(0, 16), (16, B - 16)]
-        return [(0, B)]
-
     def _amax_parts(self, M: int) -> int:
         """Argmax partials the lm_head launch writes per row at batch M (= its stride in d_amax_*): workgroups x waves."""
         wb, ww = self._wide_geometry(self.cfg.text.vocab_size, M)
         return wb * ww
 
-    def _dec_wide(self, mode, x, W, M, out=None, out_f32=None, norm_w=None, w8=None, w_scale=None, amax_row0: int = 0):
+    def _dec_wide(self, mode, x, W, M, out=None, out_f32=None, norm_w=None, w8=None, w_scale=None):
         """kr_linear_decode_wide: `wide_blocks` workgroups (one per CU), each wave an independent weight stream."""
         N, K = W.shape
         blocks, waves = self._wide_geometry(N, M)
         o = out if out is not None else out_f32
-        av, ai = self.d_amax_v.view(-1)[amax_row0 * blocks * waves:], self.d_amax_i.view(-1)[amax_row0 * blocks * waves:]
         tail = (0, ptr(norm_w), self.cfg.text.rms_norm_eps, 0, 0, ptr(out), ptr(out_f32), o.stride(0) if o is not None else 0,
-                M, N, K, blocks, waves, ptr(av), ptr(ai), self.s)
+                M, N, K, blocks, waves, ptr(self.d_amax_v), ptr(self.d_amax_i), self.s)
         if w8 is not None:
             self.L.kr_linear_decode_wide_fp8(mode, ptr(x), x.stride(0), ptr(w8), ptr(w_scale), *tail)
         else:
@@ -1205,80 +1186,64 @@ class Engine:
 
     # ------------------------------------------------------------------ decode
     def _decode_step_launches(self, B: int):
-        """One decode step = 6 launches per layer + 2 (Qwen2VLDecoderLayer TF:559-624, final norm TF:839, lm_head
-        TF:1320-1323): [(down_proj slab +) RMSNorm + QKV + bias + M-RoPE + KV append] -> attention partials -> merge ->
-        [o_proj + residual] -> [RMSNorm + gate/up + SiLU*mul] -> [down_proj (+ residual | slab)].  Above 16 rows the residual
-        sum + RMSNorm may run as a launch of their own (kr_decode_resnorm32) and the narrow linears read PACKED activations
-        (kr_linear_decode32): same sums, row for row.  The measured-and-not-adopted variants of this sequence (prefetch
-        branches, fast-residual mode, in-launch merges) live in csrc/tools/experiment_engine.py."""
+        """One decode step = 6 (<= 16 rows) or 7 (17..32 rows) launches per layer + 2 (Qwen2VLDecoderLayer TF:559-624, final norm
+        TF:839, lm_head TF:1320-1323).
+        <= 16 rows: [(x += down_proj sums) + RMSNorm + QKV + bias + M-RoPE + KV append] (kr_linear_decode_narrow) -> attention
+        partials -> merge -> [o_proj + residual] (narrow) -> [RMSNorm + gate/up + SiLU*mul] (kr_linear_decode_wide) ->
+        [down_proj (+ residual | deferred split-K sums)] (narrow).
+        17..32 rows: the residual sum + RMSNorm are a launch of their own (kr_decode_resnorm32) and qkv, o_proj and down_proj
+        read PACKED activations (kr_linear_decode32; written by kr_decode_resnorm32, kr_attn_decode_merge32 and gate/up with
+        DEC_OUT_XP): same sums, row for row.  The superseded and the measured-and-not-adopted sequences (kr_linear_decode
+        everywhere, two slabs, row-major launches above 16 rows, prefetch branches, fast-residual mode, in-launch merges)
+        live in csrc/tools/experiment_engine.py."""
         t, L, w, s = self.cfg.text, self.L, self.w, self.s
         H, KVH, hd = t.num_heads, t.num_kv_heads, t.head_dim
         nl = t.num_layers
-        f32 = B > 16 and self.family32            # packed-activation family of 17..32-row batches
+        big = B > 16                              # packed-activation family of 17..32-row batches
         x, x_other = self.d_x, self.d_x2          # residual stream: swaps buffers at every deferred reduction
         pending = False                           # down_proj's split-K sums of the previous layer waiting in d_part
+        # deferred split-K: down_proj's two K ranges add into one f32 accumulator; two accumulators alternate by layer parity
         slabs = self.d_part.view(-1)[: 2 * B * t.hidden_size].view(2, B, t.hidden_size)   # as down_proj packs them
-        one_slab = self.atomic_slab and self.defer_down
         # > 16 rows, bf16 weights: down_proj's K ranges each in TWO workgroups (kr_dec32.group_split) adding into a slab per range;
         # the pair of a layer parity replaces the one slab, and kr_decode_resnorm32 adds x + (slab 0 + slab 1): the same bits
         # (measured, profiles/r04_down_group_split.txt: 2B / 32 rows 1.691 -> 1.678 ms per step; at the 7B width, where two tiles
         # per workgroup already share the x fragments, 3.968 -> 3.983: there it stays off unless KARANTA_DOWN_GS=2)
-        gs = (f32 and one_slab and self.resnorm32_qkv and not self.fp8
+        gs = (big and self.defer_down and not self.fp8
               and (self.group_split_down == 2 or self.group_split_down == 1 and self.down_waves_small == 16)
               and (t.hidden_size // 16) % (4 if self.down_waves_small == 8 else 2) == 0)
-        pairs = self.d_part.view(-1)[: 4 * B * t.hidden_size].view(2, 2, B, t.hidden_size) if gs else None
+        if gs:
+            slabs = self.d_part.view(-1)[: 4 * B * t.hidden_size].view(2, 2, B, t.hidden_size)
         for i in range(nl):
             p = f"llm.{i}."
             kc, vc = ptr(self.kcache[i]), ptr(self.vtcache[i])     # the cache tensors are [layers, max_batch, ...]
+            defer = self.defer_down and i + 1 < nl
             # ---- 1. (x += down_proj sums of layer i - 1) -> RMSNorm -> QKV + bias + M-RoPE + KV append
-            if not self.narrow_mode:
-                self._dec(DEC_ROPE_KV, x, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), norm_w=w.view(p + "ln1.w"),
-                          waves=self.wv_qkv, kc=kc, vc=vc)
+            # this layer's down_proj will ADD into accumulator (i + 1) & 1: the qkv launch zeroes it (it was last read by
+            # layer i - 1's qkv launch, which is complete)
+            acc = slabs[(i + 1) & 1] if defer else None
+            pin = (slabs[i & 1] if gs else slabs[i & 1:(i & 1) + 1]) if pending else None
+            if big:
+                # the residual sum + RMSNorm ONCE for the batch (bit-identical rows), then ONE qkv launch over all rows
+                L.kr_decode_resnorm32(ptr(x), x.stride(0), ptr(pin), int(pin.shape[0]) if pending else 0, B, ptr(x_other),
+                                      x_other.stride(0), ptr(w.view(p + "ln1.w")), t.rms_norm_eps, ptr(self.d_h), B, t.hidden_size,
+                                      1 if (gs and pending) else 0, s)
+                self._dec32(DEC_ROPE_KV, self.d_h, w.view(p + "qkv.w"), B, 8, bias=w.view(p + "qkv.b"), kc=kc, vc=vc,
+                            zero=acc, **self._w8kw(p + "qkv.w"))
             else:
-                # this layer's down_proj will ADD into accumulator (i + 1) & 1: the qkv launch zeroes it (it was last read by
-                # layer i - 1's qkv launch, which is complete)
-                zero = slabs[(i + 1) & 1] if (one_slab and i + 1 < nl) else None
-                pin = ((slabs[i & 1:(i & 1) + 1] if one_slab else slabs) if pending else None)
-                if gs:
-                    zero = pairs[(i + 1) & 1] if i + 1 < nl else None
-                    pin = pairs[i & 1] if pending else None
-                if B > 16 and (self.resnorm_qkv or f32 and self.resnorm32_qkv):
-                    # the residual sum + RMSNorm ONCE for the batch (bit-identical rows), then ONE qkv launch over all rows
-                    args = (ptr(x), x.stride(0), ptr(pin), int(pin.shape[0]) if pin is not None else 0, B, ptr(x_other),
-                            x_other.stride(0), ptr(w.view(p + "ln1.w")), t.rms_norm_eps, ptr(self.d_h))
-                    if f32:
-                        L.kr_decode_resnorm32(*args, B, t.hidden_size, 1 if (gs and pin is not None) else 0, s)
-                        self._dec32(DEC_ROPE_KV, self.d_h, w.view(p + "qkv.w"), B, 8, bias=w.view(p + "qkv.b"), kc=kc, vc=vc,
-                                    zero=zero, **self._w8kw(p + "qkv.w"))
-                    else:
-                        L.kr_decode_resnorm(*args, self.d_h.stride(0), B, t.hidden_size, s)
-                        self._dec_narrow(DEC_ROPE_KV, self.d_h, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), kc=kc, vc=vc,
-                                         zero=zero, **self._w8kw(p + "qkv.w"))
-                else:
-                    for k, (r0, m) in enumerate(self._row_ranges(B)):     # one launch, or one per 16-row range (row_split)
-                        self._dec_narrow(DEC_ROPE_KV, x[r0:], w.view(p + "qkv.w"), m, bias=w.view(p + "qkv.b"),
-                                         norm_w=w.view(p + "ln1.w"), part_in=pin[:, r0:] if pin is not None else None,
-                                         x_out=x_other[r0:] if pin is not None else None, kc=kc, vc=vc,
-                                         part_rows=B if (pin is not None and self.row_split and B > 16) else 0, row0=r0,
-                                         zero=zero if k == 0 else None, **self._w8kw(p + "qkv.w"))
-                if pending:
-                    x, x_other = x_other, x
-                    pending = False
+                self._dec_narrow(DEC_ROPE_KV, x, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), norm_w=w.view(p + "ln1.w"),
+                                 part_in=pin, x_out=x_other if pending else None, kc=kc, vc=vc, zero=acc,
+                                 **self._w8kw(p + "qkv.w"))
+            if pending:
+                x, x_other = x_other, x
             # ---- 2. split-KV attention partials, 3. their merge
             L.kr_attn_decode_slots(ptr(self.d_q), kc, vc, ptr(self.d_ctx), ptr(self.d_fin), ptr(self.d_ws), B, H, KVH, hd, self.s_max,
                                    self.n_split, hd ** -0.5, s)
-            if f32:
-                L.kr_attn_decode_merge32(ptr(self.d_ws), ptr(self.d_o), B, H, hd, self.n_split, s)
-            else:
-                L.kr_attn_decode_merge(ptr(self.d_ws), ptr(self.d_o), B, H, hd, self.n_split, s)
+            (L.kr_attn_decode_merge32 if big else L.kr_attn_decode_merge)(ptr(self.d_ws), ptr(self.d_o), B, H, hd, self.n_split, s)
             # ---- 4. o_proj + residual
-            if f32:
+            if big:
                 self._dec32(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, self.o_waves, out=x, res=x, **self._w8kw(p + "o.w"))
-            elif self.narrow_o:
-                self._dec_narrow(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, out=x, res=x, waves=self.o_waves if B <= 16 else 8,
-                                 **self._w8kw(p + "o.w"))
             else:
-                self._dec(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, out=x, res=x, waves=self.wv_o)
+                self._dec_narrow(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, out=x, res=x, waves=self.o_waves, **self._w8kw(p + "o.w"))
             # ---- 5. RMSNorm + gate/up + SiLU*mul (the kernel bench.py's roofline object is measured on)
             if self._prof_on:
                 # [e0][e1] gate/up [e2]: the empty bracket e0..e1 measures what two back-to-back event
@@ -1287,7 +1252,7 @@ class Engine:
                 L.kr_event_record(e0, s)
                 L.kr_event_record(e1, s)
             if self.wide_mode:
-                self._dec_wide(DEC_SILU8 | (DEC_OUT_XP if f32 else 0), x, w.view(p + "gate_up.w"), B, out=self.d_act,
+                self._dec_wide(DEC_SILU8 | (DEC_OUT_XP if big else 0), x, w.view(p + "gate_up.w"), B, out=self.d_act,
                                norm_w=w.view(p + "ln2.w"), **self._w8kw(p + "gate_up.w"))
             else:
                 self._dec(DEC_SILU8, x, w.view(p + "gate_up.w"), B, out=self.d_act, norm_w=w.view(p + "ln2.w"), waves=self.wv_wide)
@@ -1295,23 +1260,15 @@ class Engine:
                 L.kr_event_record(e2, s)
             # ---- 6. down_proj: two K ranges per tile whose sums the next layer's first launch adds to x (deferred split-K),
             # or (last layer / widths without the deferral) down_proj + residual
-            defer = self.defer_down and i + 1 < nl
-            acc = slabs[(i + 1) & 1] if (defer and self.atomic_slab) else (self.d_part if defer else None)
-            if f32 and gs and defer:
-                self._dec32(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, self.down_waves_small, ksplit=2, out_f32=pairs[(i + 1) & 1],
-                            atomic_out=True, group_split=True, tiles_per_wg=self.down_gs_tiles)
-            elif f32:
-                self._dec32(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, self.down_waves_small, ksplit=2 if defer else 1,
-                            out_f32=acc, atomic_out=defer and self.atomic_slab, out=None if defer else x, res=None if defer else x,
-                            **self._w8kw(p + "down.w"))
-            elif defer:
-                self._dec_narrow(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, out_f32=acc, waves=self._down_waves(B), ksplit=2,
-                                 atomic_out=self.atomic_slab, **self._w8kw(p + "down.w"))
-            elif self.narrow_mode:
-                self._dec_narrow(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, out=x, res=x, waves=self._down_waves(B),
-                                 **self._w8kw(p + "down.w"))
+            down = dict(ksplit=2, out_f32=acc, atomic_out=True) if defer else dict(out=x, res=x)
+            if gs and defer:
+                self._dec32(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, self.down_waves_small, group_split=True,
+                            tiles_per_wg=self.down_gs_tiles, **down)
+            elif big:
+                self._dec32(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, self.down_waves_small, **down, **self._w8kw(p + "down.w"))
             else:
-                self._dec(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, out=x, res=x, waves=self.wv_down)
+                self._dec_narrow(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, waves=self.down_waves_small, **down,
+                                 **self._w8kw(p + "down.w"))
             pending = defer
         self._lm_head_and_sample(B, x)
 

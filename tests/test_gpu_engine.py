@@ -332,13 +332,15 @@ def test_fp8_weight_engine_matches_oracle_on_dequantised_weights():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["tiny-w512", "tiny-w3584", "tiny-w512+resnorm", "tiny-w3584+fp8"])
-def test_batches_above_16_rows_equal_solo_generation(name, monkeypatch):
+def test_batches_above_16_rows_equal_solo_generation(name):
     """max_batch up to 32: 21 ragged pages decoded together give each page the tokens it gets alone; the slot scheduler
     runs 20 slots.  tiny-w512: two 16-row column tiles per weight fragment, all x rows in LDS (hidden_size <= 2048).
     tiny-w3584 (the 7B decoder width, BASELINE config 3's 32-rows-per-GPU variant): 32 x rows of 3584 do not fit the LDS,
     gate/up and lm_head stage K in two halves (dec_wide_kh_kernel), the qkv launch runs once per 16-row range, o_proj /
     down_proj on two column tiles; round 3: there the residual sum + RMSNorm run once (kr_decode_resnorm) and ONE direct qkv
-    launch covers all rows.  "+resnorm": that two-launch form forced on at the width where the fused launch is the default."""
+    launch covers all rows.  "+resnorm": that two-launch form forced on at the width where the fused launch is the default
+    (round 3's sequence: csrc/tools/experiment_engine.ExperimentEngine on the product library, no experiment mode).  The other
+    three cases run the product engine, whose > 16-row steps are the packed family (kr_decode_resnorm32 + kr_linear_decode32)."""
     from karanta_ocr_amd._lib import KarantaHipError
     from karanta_ocr_amd.config import CONFIGS
     from karanta_ocr_amd.scheduler import SlotRequest, SlotScheduler
@@ -346,15 +348,16 @@ def test_batches_above_16_rows_equal_solo_generation(name, monkeypatch):
     weight_dtype = "bf16"
     if name.endswith("+fp8"):          # fp8 weights through the same >16-row launches (direct qkv on e4m3 codes)
         name, weight_dtype = name[:-len("+fp8")], "fp8"
+    engine_cls, want_resnorm = Engine, name == "tiny-w3584"
     if name.endswith("+resnorm"):
-        name = name[:-len("+resnorm")]
-        monkeypatch.setenv("KARANTA_RESNORM_QKV", "1")
-        want_resnorm = True
-    else:
-        want_resnorm = name == "tiny-w3584"
+        from karanta_ocr_amd.csrc.tools.experiment_engine import ExperimentEngine
+        name, engine_cls, want_resnorm = name[:-len("+resnorm")], ExperimentEngine, True
     cfg = CONFIGS[name]
     w = random_weights(cfg, 909)
-    eng = Engine(cfg, max_batch=21, s_max=512, max_patches=4096, max_prompt_tokens=4096, decode_splits=2, weight_dtype=weight_dtype)
+    eng = engine_cls(cfg, max_batch=21, s_max=512, max_patches=4096, max_prompt_tokens=4096, decode_splits=2, weight_dtype=weight_dtype)
+    if engine_cls is not Engine:
+        eng.resnorm_qkv = True
+        assert not (eng.family32 or eng.fast_residual or eng.attn_fused_merge or eng.merge_in_o_proj or eng._prefetch_mode)
     eng.load_weights(w)
     if weight_dtype == "fp8":
         from karanta_ocr_amd.weights import fp8_dequantized_weights
