@@ -484,7 +484,7 @@ int kr_image_normalize_patchify(const uint8_t* img, int rh, int rw, const float*
 
 /* Temperature sampling as an argmax (Gumbel-max): per row b, partial argmax over n_part vocabulary slices of
  * logits[b][i] / T_b + G(seed_b, n_b, i), n_b = ctx_len[b] + 1 - prompt_len[b] (index of the token being
- * generated), G = -ln(-ln(u)) from a counter-based hash (definition in kr_decode.hip, restated in the oracle);
+ * generated), G = -ln(-ln(u)) from a counter-based hash (definition in kr_sample.hip, restated in the oracle);
  * T_b == 0: plain argmax.  Writes amax_val / amax_idx [batch][n_part] for kr_sample_greedy, replacing the
  * greedy partials of the lm_head.  Replaces vLLM's sampler for requests with temperature > 0
  * (/root/reference/karanta/pipeline.py:281,301; bulk_processing/workers/vllm_client.py:155). */

@@ -1,6 +1,6 @@
 /* karanta_hip_experiments.h — entry points of the decode experiments that were built, measured and NOT adopted
  * (profiles/r02_decode_experiments.txt).  They are compiled only with -DKR_EXPERIMENTS
- * (python karanta_ocr_amd/csrc/tools/build_variant.py exp kr_decode.hip kr_selftest.hip -DKR_EXPERIMENTS); the shipped
+ * (python karanta_ocr_amd/csrc/tools/build_variant.py exp kr_decode.hip,kr_attn_decode.hip,kr_selftest.hip -DKR_EXPERIMENTS); the shipped
  * libkaranta_hip.so does not export them (tests/test_abi.py asserts that).  Same conventions as karanta_hip.h. */
 #ifndef KARANTA_HIP_EXPERIMENTS_H
 #define KARANTA_HIP_EXPERIMENTS_H

@@ -1,0 +1,383 @@
+// Decode attention (one query token per live sequence); the ViT and prefill attention are in kr_attention.hip.
+//   attn_decode2_kernel  split-KV MFMA attention: one (o[128], m, l) record per (sequence, head, split).  The engine passes
+//                        out == NULL and merges with a launch of its own; the in-launch merge by the last-arriving
+//                        workgroup of each (sequence, kv head) is an experiment build (-DKR_EXPERIMENTS).
+//   attn_merge_kernel    the merge launch: row-major rows (kr_attn_decode_merge) or the packed XP layout of 17..32-row
+//                        batches (kr_attn_decode_merge32).
+#include "kr_decode_common.h"
+
+namespace {
+
+// grid = (n_split, kv_heads, batch); WAVES waves; wave `part` = split*WAVES + wave walks 32-key units
+// part, part + WAVES*n_split, ...   Layouts as in kr_attention.hip (K rows, V^T 64-key blocks).
+#ifndef KR_ATTN_DEC_LD        // -DKR_ATTN_DEC_LD=ld8: default-policy K / V^T loads (A/B builds, csrc/tools/build_variant.py)
+#define KR_ATTN_DEC_LD ld8_nt
+#endif
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16* __restrict__ q, const kr_bf16* __restrict__ kcache,
+                                                                  const kr_bf16* __restrict__ vtcache,
+                                                                  const int32_t* __restrict__ ctx_len,
+                                                                  const int32_t* __restrict__ finished, int heads, int kv_heads,
+                                                                  int group, int n_split, int s_max, float scale_log2e,
+                                                                  kr_bf16* __restrict__ out, float* __restrict__ ws,
+                                                                  int* __restrict__ counters, int ws_bytes) {
+    // argument order: everything the first loads need sits in the 16 preloaded dwords (kernarg preload), so the
+    // scalar load of ctx_len[b] leaves at once instead of behind a load of the argument tail
+    constexpr int HD = 128, DT = HD / 16, REC = HD + 4;
+    __shared__ __attribute__((aligned(16))) float o_s[WAVES][16][HD];
+    __shared__ float m_s[WAVES][16], l_s[WAVES][16];
+    __shared__ int last_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fg = lane >> 4;
+    // group (= heads / kv_heads) and n_split (= gridDim.x) are arguments: a runtime division and a read of the dispatch
+    // packet would both sit in front of the first loads
+    const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
+    const int n_part = n_split * WAVES, part = split * WAVES + wave;
+    const int ctx = ctx_len[b] + 1;
+    // a sequence that has finished (EOS flag set by the sampling launch, or retired by the host): nothing downstream reads its rows
+    // any more — its workgroups leave without touching its cache (a server's idle slots: ~18 % of the rows in the corpus run)
+    if (finished != nullptr && finished[b] != 0) return;
+
+    const int g = fr < group ? fr : 0;
+    // MFMA k-step i pairs K[key][32i + 8fg + j] with Q[g][32i + 8fg + j]: per load instruction the
+    // four lane groups cover 64 contiguous bytes of each of 16 key rows
+    const kr_bf16* qp = q + ((int64_t)b * heads + kvh * group + g) * HD + fg * 8;
+    bf16x8 qf[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) qf[i] = ld8(qp + i * 32);
+    const int64_t kv_base = (int64_t)b * kv_heads + kvh;
+    const kr_bf16* kc = kcache + kv_base * s_max * HD;
+    const kr_bf16* vc = vtcache + kv_base * (int64_t)(s_max >> 6) * (HD * 64);
+
+    f32x4 o[DT];
+#pragma unroll
+    for (int t = 0; t < DT; ++t) o[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float m_run = -1e30f, l_run = 0.f;
+    // unit = 32 keys (half a V^T block); wave `part` takes units part, part + n_part, ...: at the contexts of a page
+    // (1.4k .. 2.4k keys = 44 .. 76 units) 64 parts leave one unit — one memory round trip — per wave; a wave with
+    // more requests unit u + n_part before it computes unit u
+    const int nu = (ctx + 31) >> 5;
+    bf16x8 kf[2][4], vf[DT], kf2[2][4], vf2[DT];
+    auto load_unit = [&](int u, bf16x8 (&kk)[2][4], bf16x8 (&vv)[DT]) {
+        const int key0 = u * 32;
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) {
+            const kr_bf16* kp = kc + (int64_t)(key0 + 8 * (fr >> 2) + 4 * kt + (fr & 3)) * HD + fg * 8;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) kk[kt][i] = KR_ATTN_DEC_LD(kp + i * 32);
+        }
+        // the unit's half of its V^T block is contiguous ([2][HD][32]: kr_common.h): 16 channel rows x 64 B per instruction = 1 KiB of
+        // whole lines (rounds 1-3: [HD][64], half of every line — 4.0 against 6.5 TB/s for this shape, profiles/r04_halfline_read.txt)
+        const kr_bf16* vp = vc + (int64_t)(u >> 1) * (HD * 64) + (u & 1) * (HD * 32) + fg * 8;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) vv[dt] = KR_ATTN_DEC_LD(vp + (dt * 16 + fr) * 32);
+    };
+    int u = part;
+    if (u < nu) load_unit(u, kf, vf);
+    while (u < nu) {
+        const int un = u + n_part;
+        if (un < nu) load_unit(un, kf2, vf2);
+        {
+            const int key0 = u * 32;
+            f32x4 s[2];
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+                s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][i], qf[i], s[kt], 0, 0, 0);
+            }
+            float mx = -INFINITY;
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int key = key0 + 8 * fg + 4 * kt + r;
+                    const float v = key < ctx ? s[kt][r] * scale_log2e : -INFINITY;
+                    s[kt][r] = v;
+                    mx = fmaxf(mx, v);
+                }
+            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float m_new = fmaxf(m_run, mx);
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+            m_run = m_new;
+            bf16x8 pf;
+            float psum = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const __bf16 pb = f2bf(__builtin_amdgcn_exp2f(s[kt][r] - m_new));
+                    psum += bf2f(pb);
+                    pf[kt * 4 + r] = pb;
+                }
+            l_run = l_run * alpha + psum;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt], pf, o[dt], 0, 0, 0);
+            }
+        }
+        if (un < nu) {
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) kf[kt][i] = kf2[kt][i];
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) vf[dt] = vf2[dt];
+        }
+        u = un;
+    }
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
+    // ---- merge the waves through LDS
+    if (fr < group) {
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4*>(&o_s[wave][fr][dt * 16 + fg * 4]) = o[dt];
+        if (fg == 0) {
+            m_s[wave][fr] = m_run;
+            l_s[wave][fr] = l_run;
+        }
+    }
+    __syncthreads();
+    // element t < group * 32 = 4 consecutive channels d4 .. d4+3 of head gg: one 16-byte piece of the record
+    // [o[128], m, l, 0, 0] (REC floats) of this (sequence, head, split); a thread owns elements tid, tid + NTHR, ...
+    constexpr int NTHR = WAVES * 64, IT = (16 * 32 + NTHR - 1) / NTHR;
+    const int bh0 = b * heads + kvh * group;
+    const int nq = group * (HD / 4);
+    f32x4 acc4[IT];
+    float mm[IT], ll[IT];
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const int t = tid + it * NTHR, gg = t >> 5, d4 = (t & 31) << 2;
+        acc4[it] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        mm[it] = -1e30f;
+        ll[it] = 0.f;
+        if (t < nq) {
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) mm[it] = fmaxf(mm[it], m_s[w][gg]);
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) {
+                const float sc = __builtin_amdgcn_exp2f(m_s[w][gg] - mm[it]);
+                const f32x4 ow = *reinterpret_cast<const f32x4*>(&o_s[w][gg][d4]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc4[it][j] += ow[j] * sc;
+                ll[it] += l_s[w][gg] * sc;
+            }
+        }
+    }
+    auto store_out = [&](int t, const f32x4& a, float l) {
+        const float inv = l > 0.f ? 1.0f / l : 0.f;
+        bf16x4 ov;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ov[j] = f2bf(a[j] * inv);
+        *reinterpret_cast<bf16x4*>(out + (int64_t)(bh0 + (t >> 5)) * HD + ((t & 31) << 2)) = ov;
+    };
+    auto rec_of = [&](int t) { return ((int64_t)(bh0 + (t >> 5)) * n_split) * REC; };   // first record of element t's head (floats)
+    if (n_split == 1 && out) {
+#pragma unroll
+        for (int it = 0; it < IT; ++it)
+            if (tid + it * NTHR < nq) store_out(tid + it * NTHR, acc4[it], ll[it]);
+        return;
+    }
+    if (!KR_EXP || !out) {  // a later launch (kr_attn_decode_merge) merges the partials: plain stores
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            const int t = tid + it * NTHR, d4 = (t & 31) << 2;
+            if (t < nq) {
+                float* w = ws + rec_of(t) + (int64_t)split * REC;
+                *reinterpret_cast<f32x4*>(w + d4) = acc4[it];
+                if (d4 == 0) *reinterpret_cast<f32x4*>(w + HD) = (f32x4){mm[it], ll[it], 0.f, 0.f};
+            }
+        }
+        return;
+    }
+    // ---- in-launch merge by the last-arriving split of this (sequence, kv head).  Hand-off in the form the guide
+    // measures (MI355X_MICROARCH.md, visibility, "Valid forms" row 1): every payload byte leaves as a 16-byte sc1
+    // (write-through) store, every storing wave drains its stores (vmcnt(0)) before the workgroup barrier, ONE lane
+    // then adds to the group's counter; the workgroup whose add returns n_split - 1 is the last one and reads all
+    // records with 16-byte sc1 loads (never a plain load of these bytes), all requested at once.  Nobody waits:
+    // the other workgroups just leave.  Correct for any placement of the splits on XCDs / CUs.
+    // (Measured r2: 1.2200 ms per step against 1.2033 with the separate merge launch — the hand-off costs what the
+    // launch costs; kept for the ABI and as the tested example of the protocol.  CAUTION before reusing it: the same form
+    // with 64 KB payloads per workgroup — a split-K GEMM fix-up, profiles/r02_decode_experiments.txt — let the last arriver
+    // read a few 16-byte pieces too early in 1 of ~10^6; nothing on the default path depends on an in-launch hand-off.)
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(ws, 0, ws_bytes, 0x00020000);
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const int t = tid + it * NTHR, d4 = (t & 31) << 2;
+        if (t < nq) {
+            const int off = (int)((rec_of(t) + (int64_t)split * REC + d4) * 4);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc4[it]), rsrc, off, 0, 16);
+            if (d4 == 0)
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, (f32x4){mm[it], ll[it], 0.f, 0.f}), rsrc,
+                                                       (int)((rec_of(t) + (int64_t)split * REC + HD) * 4), 0, 16);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's record stores have been acknowledged
+    __syncthreads();
+    if (tid == 0) {
+        const int old = __hip_atomic_fetch_add(counters + b * kv_heads + kvh, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last_s = (old == n_split - 1);
+        if (old == n_split - 1) __hip_atomic_store(counters + b * kv_heads + kvh, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!last_s) return;
+    constexpr int MAXS = 16;
+    for (int it = 0; it < IT; ++it) {
+        const int t = tid + it * NTHR, d4 = (t & 31) << 2;
+        if (t >= nq) continue;
+        u32x4 ro[MAXS], rm[MAXS];
+#pragma unroll
+        for (int p = 0; p < MAXS; ++p) {
+            if (p < n_split) {
+                ro[p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((rec_of(t) + (int64_t)p * REC + d4) * 4), 0, 16);
+                rm[p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((rec_of(t) + (int64_t)p * REC + HD) * 4), 0, 16);
+            }
+        }
+        float mt = -1e30f;
+#pragma unroll
+        for (int p = 0; p < MAXS; ++p)
+            if (p < n_split) mt = fmaxf(mt, __builtin_bit_cast(f32x4, rm[p])[0]);
+        f32x4 at = {0.f, 0.f, 0.f, 0.f};
+        float lt = 0.f;
+#pragma unroll
+        for (int p = 0; p < MAXS; ++p) {
+            if (p < n_split) {
+                const f32x4 mlp = __builtin_bit_cast(f32x4, rm[p]), op = __builtin_bit_cast(f32x4, ro[p]);
+                const float sc = __builtin_amdgcn_exp2f(mlp[0] - mt);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) at[j] += op[j] * sc;
+                lt += mlp[1] * sc;
+            }
+        }
+        store_out(t, at, lt);
+    }
+}
+
+// Merge of the split-KV partials as a launch of its own: one 128-thread workgroup per (sequence, head).
+// (Cheaper end-to-end than replicating the merge in every o_proj workgroup's prologue: measured.)
+// NS > 0: all n_split records are requested at once (one memory round trip instead of two dependent loops).
+template <int NS>
+__global__ void __launch_bounds__(128) attn_merge_kernel(const float* __restrict__ ws, kr_bf16* __restrict__ out, int n_split, int heads_xp) {
+    // heads_xp > 0: out is the XP layout of a 17..32-row batch (row = sequence, column = head * 128 + d), heads_xp = heads
+    constexpr int HD = 128, REC = HD + 4;
+    const int bh = blockIdx.x, d = threadIdx.x;
+    float acc = 0.f, ll = 0.f;
+    if constexpr (NS > 0) {
+        const float* w = ws + (int64_t)bh * NS * REC;
+        float m[NS], l[NS], o[NS];
+#pragma unroll
+        for (int p = 0; p < NS; ++p) {
+            m[p] = w[p * REC + HD];
+            l[p] = w[p * REC + HD + 1];
+            o[p] = w[p * REC + d];
+        }
+        float mm = -1e30f;
+#pragma unroll
+        for (int p = 0; p < NS; ++p) mm = fmaxf(mm, m[p]);
+#pragma unroll
+        for (int p = 0; p < NS; ++p) {
+            const float sc = __builtin_amdgcn_exp2f(m[p] - mm);
+            acc += o[p] * sc;
+            ll += l[p] * sc;
+        }
+    } else {
+        const float* w = ws + (int64_t)bh * n_split * REC;
+        float mm = -1e30f;
+        for (int p = 0; p < n_split; ++p) mm = fmaxf(mm, w[p * REC + HD]);
+        for (int p = 0; p < n_split; ++p) {
+            const float sc = __builtin_amdgcn_exp2f(w[p * REC + HD] - mm);
+            acc += w[p * REC + d] * sc;
+            ll += w[p * REC + HD + 1] * sc;
+        }
+    }
+    const kr_bf16 r = __builtin_bit_cast(kr_bf16, f2bf(ll > 0.f ? acc / ll : 0.f));
+    if (heads_xp > 0) {
+        const int b = bh / heads_xp, hh = bh - b * heads_xp;
+        *reinterpret_cast<kr_bf16*>(reinterpret_cast<char*>(out) + kr_xp_byte_offset(b, hh * HD + d)) = r;
+    } else {
+        out[(int64_t)bh * HD + d] = r;
+    }
+}
+
+}  // namespace
+
+static int attn_decode_impl(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
+                            const int32_t* finished, kr_bf16* out, float* workspace, int32_t* counters, int batch, int heads,
+                            int kv_heads, int hd, int s_max, int n_split, float scale, kr_stream s) {
+    KR_CHECK_ARG(q && kcache && vtcache && ctx_len && (out || workspace), "kr_attn_decode_fused: null pointer");
+    KR_CHECK_ARG(hd == 128, "kr_attn_decode_fused: hd=%d (only 128)", hd);
+    KR_CHECK_ARG(heads % kv_heads == 0 && heads / kv_heads <= 16, "kr_attn_decode_fused: GQA group must be <= 16");
+    KR_CHECK_ARG(batch > 0 && n_split > 0 && s_max % 64 == 0, "kr_attn_decode_fused: bad sizes");
+    KR_CHECK_ARG(KR_EXP || !out || n_split == 1,
+                 "kr_attn_decode_fused: the in-launch merge (out != NULL with n_split > 1) is an experiment build (-DKR_EXPERIMENTS); "
+                 "pass out = NULL and run kr_attn_decode_merge");
+    KR_CHECK_ARG(!out || n_split <= 16, "kr_attn_decode_fused: the in-launch merge takes at most 16 splits");
+    KR_CHECK_ARG(!out || n_split == 1 || (workspace && counters), "kr_attn_decode_fused: split needs workspace + counters");
+    KR_CHECK_ARG(workspace || n_split == 1, "kr_attn_decode_fused: the split partials need a workspace");
+    // Workgroup shape: n_split x WAVES parts of 32-key units, so that at page contexts (1.4k .. 2.4k keys = 44 .. 76 units)
+    // a wave fetches ONE unit (one memory round trip).  r2 chain timings (B = 8, ctx 1906, launch + dependent-launch gap):
+    // 8 splits x 8 waves (128 workgroups) 7.8 us; 16 splits x 4 waves (256 workgroups, every CU loads) 5.8 us;
+    // 6 x 8 (two units per wave) 12.7 us.  Hence: up to 8 splits 8 waves, up to 16 splits 4 waves, beyond 2 waves
+    // (KARANTA_ATTN_WAVES = 2 / 4 / 8 overrides for A/B runs).
+    static const int waves_env = [] { const char* e = getenv("KARANTA_ATTN_WAVES"); return e ? atoi(e) : 0; }();
+    const int waves = waves_env ? waves_env : (n_split <= 8 ? 8 : n_split <= 16 ? 4 : 2);
+    KR_CHECK_ARG(waves == 2 || waves == 4 || waves == 8, "kr_attn_decode_fused: KARANTA_ATTN_WAVES=%d (2, 4 or 8)", waves);
+    const int64_t ws_bytes = (int64_t)batch * heads * n_split * (hd + 4) * 4;
+    KR_CHECK_ARG(ws_bytes < ((int64_t)1 << 31), "kr_attn_decode_fused: workspace of %lld bytes", (long long)ws_bytes);
+    const dim3 grid(n_split, kv_heads, batch);
+    const float sl2 = scale * 1.4426950408889634f;
+    const int group = heads / kv_heads;
+    if (waves == 8)
+        attn_decode2_kernel<8><<<grid, 512, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
+                                                           workspace, counters, (int)ws_bytes);
+    else if (waves == 4)
+        attn_decode2_kernel<4><<<grid, 256, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
+                                                           workspace, counters, (int)ws_bytes);
+    else
+        attn_decode2_kernel<2><<<grid, 128, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
+                                                           workspace, counters, (int)ws_bytes);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_attn_decode_fused(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
+                                    kr_bf16* out, float* workspace, int32_t* counters, int batch, int heads, int kv_heads,
+                                    int hd, int s_max, int n_split, float scale, kr_stream s) {
+    return attn_decode_impl(q, kcache, vtcache, ctx_len, nullptr, out, workspace, counters, batch, heads, kv_heads, hd, s_max, n_split, scale, s);
+}
+
+extern "C" int kr_attn_decode_slots(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
+                                    const int32_t* finished, float* workspace, int batch, int heads, int kv_heads, int hd, int s_max,
+                                    int n_split, float scale, kr_stream s) {
+    KR_CHECK_ARG(finished && workspace, "kr_attn_decode_slots: null pointer");
+    return attn_decode_impl(q, kcache, vtcache, ctx_len, finished, nullptr, workspace, nullptr, batch, heads, kv_heads, hd, s_max, n_split, scale, s);
+}
+
+static int merge_impl(const float* workspace, kr_bf16* out, int batch, int heads, int hd, int n_split, int xp, kr_stream s) {
+    KR_CHECK_ARG(workspace && out && batch > 0 && heads > 0 && n_split > 0, "kr_attn_decode_merge: bad args");
+    KR_CHECK_ARG(hd == 128, "kr_attn_decode_merge: hd=%d (only 128)", hd);
+    KR_CHECK_ARG(!xp || (batch <= 32 && ((uintptr_t)out & 15) == 0), "kr_attn_decode_merge32: batch=%d (<= 32)", batch);
+    const int hx = xp ? heads : 0;
+    switch (n_split) {
+        case 4: attn_merge_kernel<4><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
+        case 8: attn_merge_kernel<8><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
+        case 16: attn_merge_kernel<16><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
+        case 32: attn_merge_kernel<32><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
+        default: attn_merge_kernel<0><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx);
+    }
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_attn_decode_merge(const float* workspace, kr_bf16* out, int batch, int heads, int hd, int n_split,
+                                    kr_stream s) {
+    return merge_impl(workspace, out, batch, heads, hd, n_split, 0, s);
+}
+
+extern "C" int kr_attn_decode_merge32(const float* workspace, kr_bf16* out_xp, int batch, int heads, int hd, int n_split,
+                                      kr_stream s) {
+    return merge_impl(workspace, out_xp, batch, heads, hd, n_split, 1, s);
+}

@@ -1,44 +1,27 @@
-// Decode-step kernels (one new token per live sequence): 5 launches per decoder layer + 2 per step.
+// Decode-step linears (one new token per live sequence) and the residual sum + RMSNorm launch of 17..32-row batches.
 //
-//   dec_linear_kernel   y[M<=16, N] = epi(x W^T): the weight matrix is read from HBM exactly once, as
-//                       one linear stream — weights are stored PACKED as [N/16][K/32][4][16][8]: one
-//                       (16 x 32) block is an MFMA fragment set in lane order, so every wave-level load
-//                       is 1 KiB of contiguous memory (8 full 128-byte lines); K is split over
-//                       the 4 / 8 / 16 waves of a workgroup (narrow layers get more waves per workgroup
-//                       instead of a cross-workgroup split: every fence / atomic hop between workgroups
-//                       costs microseconds, measured, and a decode step is a chain of 142 launches).
-//                       An optional cross-workgroup split-K with a deterministic in-launch reduction
-//                       (slabs + arrival counter, agent-scope release/acquire) is kept for wide-K shapes.
-//                       Fused prologues: Qwen2VLRMSNorm, or the merge of the attention split partials.
-//                       Fused epilogues:
-//                         PLAIN   (+bias, +residual, bf16 or fp32 out)        o_proj, down_proj
-//                         SILU    silu(gate)*up                              gate/up projection
-//                         ROPE_KV +bias, M-RoPE, q -> q buffer, k/v -> KV cache (V transposed)
-//                         ARGMAX  per-workgroup (max, index) partials [+ fp32 logits]   lm_head
-//   attn_decode2_kernel split-KV MFMA attention; the split partials are merged either by the consumer
-//                       (the o_proj prologue, out == NULL: the engine's path) or in-launch by the
-//                       last-arriving workgroup of each (sequence, kv head).
-//   sample_greedy_kernel final argmax over the lm_head partials, token history, EOS bookkeeping,
-//                       next-token embedding gather, context advance.  (The rotary table of every
-//                       decode position is built once per request on the host.)
-//   sample_threshold_kernel / gumbel_argmax_proc_kernel / sample_count_kernel  vLLM's sampling controls (top_k, top_p,
-//                       min_p, repetition / frequency / presence penalties) around the Gumbel-max argmax; DESIGN.md §5c.
-#include "kr_common.h"
+// A decode step is 6 (<= 16 rows) or 7 (17..32 rows) launches per decoder layer + 2 (engine.py, _decode_step_launches):
+//   <= 16 rows   [(x += down_proj sums) + RMSNorm + QKV + bias + M-RoPE + KV append] (kr_linear_decode_narrow) -> attention
+//                partials -> merge (kr_attn_decode.hip) -> [o_proj + residual] (narrow) -> [RMSNorm + gate/up + SiLU*mul]
+//                (kr_linear_decode_wide) -> [down_proj (+ residual | deferred split-K sums)] (narrow)
+//   17..32 rows  the residual sum + RMSNorm are a launch of their own (kr_decode_resnorm32); qkv, o_proj and down_proj read
+//                packed activations (kr_decode32.hip); gate/up stays kr_linear_decode_wide
+//   per step     [final RMSNorm + lm_head + ARGMAX partials] (kr_linear_decode_wide) -> the sampler (kr_sample.hip)
+//
+// Weights are stored PACKED as [N/16][K/32][4][16][8]: one (16 x 32) block is an MFMA fragment set in lane order, so every
+// wave-level load is 1 KiB of contiguous memory (8 full 128-byte lines) and a weight matrix is read from HBM exactly once.
+// dec_wide_kernel, dec_wide_kh_kernel, dec_narrow_kernel and dec_resnorm_kernel are described where they stand;
+// dec_linear_kernel (kr_linear_decode) is the general fallback: K split over the 4 / 8 / 16 waves of a workgroup, an
+// optional cross-workgroup split-K with a deterministic in-launch reduction (slabs + arrival counter, agent-scope
+// release/acquire), prologues RMSNorm or the merge of the attention partials.  Fused epilogues:
+//   PLAIN   (+bias, +residual, bf16 or fp32 out)        o_proj, down_proj
+//   SILU    silu(gate)*up                              gate/up projection
+//   ROPE_KV +bias, M-RoPE, q -> q buffer, k/v -> KV cache (V transposed)
+//   ARGMAX  per-workgroup (max, index) partials [+ fp32 logits]   lm_head
+// -DKR_EXPERIMENTS (kr_decode_common.h) adds the per-head o_proj (dec_oproj_heads_kernel) and the _x32 entry points.
+#include "kr_decode_common.h"
 
 namespace {
-
-// -DKR_EXPERIMENTS (csrc/tools/build_variant.py): the measured-and-not-adopted decode experiments of rounds 1-2 — Infinity-Cache
-// prefetch workgroups riding on the qkv launch, the fast-residual mode (per-head o_proj with float atomics: dec_oproj_heads_kernel,
-// f32 x rows in the wide / narrow kernels), the in-launch split-KV merge of the attention kernel.  The shipped library holds the
-// product path and the general dec_linear_kernel fallback only; the experiment entry points are declared in
-// include/karanta_hip_experiments.h.
-#ifdef KR_EXPERIMENTS
-constexpr bool KR_EXP = true;
-#else
-constexpr bool KR_EXP = false;
-#endif
-
-constexpr int DEPI_PLAIN = 0, DEPI_SILU = 1, DEPI_ROPE_KV = 2, DEPI_ARGMAX = 3, DEPI_SILU8 = 4;
 
 struct DecLinArgs {
     const kr_bf16* x; int64_t ldx;
@@ -91,55 +74,6 @@ struct DecLinArgs {
     // batch (kr_linear_decode32) reads its x fragments as whole cache lines
     int out_xp;
 };
-
-// One 64-wide K chunk of a 16-row weight tile in registers, and where its operands sit.
-//  bf16 : 2 KiB per chunk, two 16-byte loads per lane; lane (r, g) holds k = 32h + 8g .. +7 of k-step h
-//  fp8  : 1 KiB per chunk, ONE 16-byte load per lane; lane (r, g) holds k = 16g .. 16g+15, k-step h takes 16g + 8h .. +7
-//         (x is read in the same order, a dot product does not care), converted to bf16 in registers
-//         (v_cvt_scalef32_pk_bf16_fp8: every e4m3 value is exact in bf16; the per-row scale is applied in the epilogue)
-template <bool W8> struct WChunk;
-template <> struct WChunk<false> {
-    static constexpr int BYTES = 2048;
-    bf16x8 v[2];
-    __device__ __forceinline__ void load(const char* p, int64_t c) {
-        v[0] = ld8_nt(reinterpret_cast<const kr_bf16*>(p + c * BYTES));
-        v[1] = ld8_nt(reinterpret_cast<const kr_bf16*>(p + c * BYTES + 1024));
-    }
-    __device__ __forceinline__ bf16x8 frag(int h) const { return v[h]; }
-    static __device__ __forceinline__ int x_byte(int h, int fg) { return h * 64 + fg * 16; }  // inside the chunk's 128 B of x
-};
-template <> struct WChunk<true> {
-    static constexpr int BYTES = 1024;
-    u32x4 q;
-    __device__ __forceinline__ void load(const char* p, int64_t c) {
-        q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + c * BYTES));
-    }
-    __device__ __forceinline__ bf16x8 frag(int h) const {
-        // each conversion yields two bf16 packed in one register; they are moved as 32-bit words (element-wise
-        // extraction of the builtin's 2 x bf16 result is mis-lowered by this compiler: both halves read the low one)
-        u32x4 o;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int w = (int)q[2 * h + i];
-            o[2 * i + 0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
-            o[2 * i + 1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true));
-        }
-        return __builtin_bit_cast(bf16x8, o);
-    }
-    static __device__ __forceinline__ int x_byte(int h, int fg) { return fg * 32 + h * 16; }
-};
-
-__device__ __forceinline__ void apply_w_scale(const float* w_scale, int n, f32x4& acc) {
-    if (w_scale) {
-        const f32x4 sc = *reinterpret_cast<const f32x4*>(w_scale + n);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] *= sc[j];
-    }
-}
-
-__device__ __forceinline__ void better(float& bv, int& bi, float v, int i) {
-    if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-}
 
 template <int NT, int EPI, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) dec_linear_kernel(const DecLinArgs a) {
@@ -1124,7 +1058,6 @@ template <int NCH> struct NarrowCfg { static constexpr int RL = 8; };
 template <> struct NarrowCfg<24> { static constexpr int RL = 3; };
 template <> struct NarrowCfg<32> { static constexpr int RL = 4; };
 template <> struct NarrowCfg<56> { static constexpr int RL = 7; };
-constexpr int DEPI_PARTIAL = 16;  // internal: PLAIN with deferred split-K slabs
 
 // U = ring depth in 64-wide K chunks: the host picks the smallest instantiated U that covers a wave's share of K
 // (then every chunk is requested up front and at most one request per wave is redundant), else the deepest ring.
@@ -1771,707 +1704,6 @@ int launch_oproj_heads(const float* ws, const void* wp, const float* w_scale, fl
 }
 #endif  // KR_EXPERIMENTS
 
-// =====================================================================================
-// decode attention with in-launch merge
-// =====================================================================================
-// grid = (n_split, kv_heads, batch); WAVES waves; wave `part` = split*WAVES + wave walks 32-key units
-// part, part + WAVES*n_split, ...   Layouts as in kr_attention.hip (K rows, V^T 64-key blocks).
-#ifndef KR_ATTN_DEC_LD        // -DKR_ATTN_DEC_LD=ld8: default-policy K / V^T loads (A/B builds, csrc/tools/build_variant.py)
-#define KR_ATTN_DEC_LD ld8_nt
-#endif
-template <int WAVES>
-__global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16* __restrict__ q, const kr_bf16* __restrict__ kcache,
-                                                                  const kr_bf16* __restrict__ vtcache,
-                                                                  const int32_t* __restrict__ ctx_len,
-                                                                  const int32_t* __restrict__ finished, int heads, int kv_heads,
-                                                                  int group, int n_split, int s_max, float scale_log2e,
-                                                                  kr_bf16* __restrict__ out, float* __restrict__ ws,
-                                                                  int* __restrict__ counters, int ws_bytes) {
-    // argument order: everything the first loads need sits in the 16 preloaded dwords (kernarg preload), so the
-    // scalar load of ctx_len[b] leaves at once instead of behind a load of the argument tail
-    constexpr int HD = 128, DT = HD / 16, REC = HD + 4;
-    __shared__ __attribute__((aligned(16))) float o_s[WAVES][16][HD];
-    __shared__ float m_s[WAVES][16], l_s[WAVES][16];
-    __shared__ int last_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int fr = lane & 15, fg = lane >> 4;
-    // group (= heads / kv_heads) and n_split (= gridDim.x) are arguments: a runtime division and a read of the dispatch
-    // packet would both sit in front of the first loads
-    const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
-    const int n_part = n_split * WAVES, part = split * WAVES + wave;
-    const int ctx = ctx_len[b] + 1;
-    // a sequence that has finished (EOS flag set by the sampling launch, or retired by the host): nothing downstream reads its rows
-    // any more — its workgroups leave without touching its cache (a server's idle slots: ~18 % of the rows in the corpus run)
-    if (finished != nullptr && finished[b] != 0) return;
-
-    const int g = fr < group ? fr : 0;
-    // MFMA k-step i pairs K[key][32i + 8fg + j] with Q[g][32i + 8fg + j]: per load instruction the
-    // four lane groups cover 64 contiguous bytes of each of 16 key rows
-    const kr_bf16* qp = q + ((int64_t)b * heads + kvh * group + g) * HD + fg * 8;
-    bf16x8 qf[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) qf[i] = ld8(qp + i * 32);
-    const int64_t kv_base = (int64_t)b * kv_heads + kvh;
-    const kr_bf16* kc = kcache + kv_base * s_max * HD;
-    const kr_bf16* vc = vtcache + kv_base * (int64_t)(s_max >> 6) * (HD * 64);
-
-    f32x4 o[DT];
-#pragma unroll
-    for (int t = 0; t < DT; ++t) o[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float m_run = -1e30f, l_run = 0.f;
-    // unit = 32 keys (half a V^T block); wave `part` takes units part, part + n_part, ...: at the contexts of a page
-    // (1.4k .. 2.4k keys = 44 .. 76 units) 64 parts leave one unit — one memory round trip — per wave; a wave with
-    // more requests unit u + n_part before it computes unit u
-    const int nu = (ctx + 31) >> 5;
-    bf16x8 kf[2][4], vf[DT], kf2[2][4], vf2[DT];
-    auto load_unit = [&](int u, bf16x8 (&kk)[2][4], bf16x8 (&vv)[DT]) {
-        const int key0 = u * 32;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-            const kr_bf16* kp = kc + (int64_t)(key0 + 8 * (fr >> 2) + 4 * kt + (fr & 3)) * HD + fg * 8;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) kk[kt][i] = KR_ATTN_DEC_LD(kp + i * 32);
-        }
-        // the unit's half of its V^T block is contiguous ([2][HD][32]: kr_common.h): 16 channel rows x 64 B per instruction = 1 KiB of
-        // whole lines (rounds 1-3: [HD][64], half of every line — 4.0 against 6.5 TB/s for this shape, profiles/r04_halfline_read.txt)
-        const kr_bf16* vp = vc + (int64_t)(u >> 1) * (HD * 64) + (u & 1) * (HD * 32) + fg * 8;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) vv[dt] = KR_ATTN_DEC_LD(vp + (dt * 16 + fr) * 32);
-    };
-    int u = part;
-    if (u < nu) load_unit(u, kf, vf);
-    while (u < nu) {
-        const int un = u + n_part;
-        if (un < nu) load_unit(un, kf2, vf2);
-        {
-            const int key0 = u * 32;
-            f32x4 s[2];
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-                s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][i], qf[i], s[kt], 0, 0, 0);
-            }
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key = key0 + 8 * fg + 4 * kt + r;
-                    const float v = key < ctx ? s[kt][r] * scale_log2e : -INFINITY;
-                    s[kt][r] = v;
-                    mx = fmaxf(mx, v);
-                }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-            m_run = m_new;
-            bf16x8 pf;
-            float psum = 0.f;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const __bf16 pb = f2bf(__builtin_amdgcn_exp2f(s[kt][r] - m_new));
-                    psum += bf2f(pb);
-                    pf[kt * 4 + r] = pb;
-                }
-            l_run = l_run * alpha + psum;
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt], pf, o[dt], 0, 0, 0);
-            }
-        }
-        if (un < nu) {
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) kf[kt][i] = kf2[kt][i];
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) vf[dt] = vf2[dt];
-        }
-        u = un;
-    }
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
-    // ---- merge the waves through LDS
-    if (fr < group) {
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4*>(&o_s[wave][fr][dt * 16 + fg * 4]) = o[dt];
-        if (fg == 0) {
-            m_s[wave][fr] = m_run;
-            l_s[wave][fr] = l_run;
-        }
-    }
-    __syncthreads();
-    // element t < group * 32 = 4 consecutive channels d4 .. d4+3 of head gg: one 16-byte piece of the record
-    // [o[128], m, l, 0, 0] (REC floats) of this (sequence, head, split); a thread owns elements tid, tid + NTHR, ...
-    constexpr int NTHR = WAVES * 64, IT = (16 * 32 + NTHR - 1) / NTHR;
-    const int bh0 = b * heads + kvh * group;
-    const int nq = group * (HD / 4);
-    f32x4 acc4[IT];
-    float mm[IT], ll[IT];
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-        const int t = tid + it * NTHR, gg = t >> 5, d4 = (t & 31) << 2;
-        acc4[it] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        mm[it] = -1e30f;
-        ll[it] = 0.f;
-        if (t < nq) {
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) mm[it] = fmaxf(mm[it], m_s[w][gg]);
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) {
-                const float sc = __builtin_amdgcn_exp2f(m_s[w][gg] - mm[it]);
-                const f32x4 ow = *reinterpret_cast<const f32x4*>(&o_s[w][gg][d4]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc4[it][j] += ow[j] * sc;
-                ll[it] += l_s[w][gg] * sc;
-            }
-        }
-    }
-    auto store_out = [&](int t, const f32x4& a, float l) {
-        const float inv = l > 0.f ? 1.0f / l : 0.f;
-        bf16x4 ov;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ov[j] = f2bf(a[j] * inv);
-        *reinterpret_cast<bf16x4*>(out + (int64_t)(bh0 + (t >> 5)) * HD + ((t & 31) << 2)) = ov;
-    };
-    auto rec_of = [&](int t) { return ((int64_t)(bh0 + (t >> 5)) * n_split) * REC; };   // first record of element t's head (floats)
-    if (n_split == 1 && out) {
-#pragma unroll
-        for (int it = 0; it < IT; ++it)
-            if (tid + it * NTHR < nq) store_out(tid + it * NTHR, acc4[it], ll[it]);
-        return;
-    }
-    if (!KR_EXP || !out) {  // a later launch (kr_attn_decode_merge) merges the partials: plain stores
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int t = tid + it * NTHR, d4 = (t & 31) << 2;
-            if (t < nq) {
-                float* w = ws + rec_of(t) + (int64_t)split * REC;
-                *reinterpret_cast<f32x4*>(w + d4) = acc4[it];
-                if (d4 == 0) *reinterpret_cast<f32x4*>(w + HD) = (f32x4){mm[it], ll[it], 0.f, 0.f};
-            }
-        }
-        return;
-    }
-    // ---- in-launch merge by the last-arriving split of this (sequence, kv head).  Hand-off in the form the guide
-    // measures (MI355X_MICROARCH.md, visibility, "Valid forms" row 1): every payload byte leaves as a 16-byte sc1
-    // (write-through) store, every storing wave drains its stores (vmcnt(0)) before the workgroup barrier, ONE lane
-    // then adds to the group's counter; the workgroup whose add returns n_split - 1 is the last one and reads all
-    // records with 16-byte sc1 loads (never a plain load of these bytes), all requested at once.  Nobody waits:
-    // the other workgroups just leave.  Correct for any placement of the splits on XCDs / CUs.
-    // (Measured r2: 1.2200 ms per step against 1.2033 with the separate merge launch — the hand-off costs what the
-    // launch costs; kept for the ABI and as the tested example of the protocol.  CAUTION before reusing it: the same form
-    // with 64 KB payloads per workgroup — a split-K GEMM fix-up, profiles/r02_decode_experiments.txt — let the last arriver
-    // read a few 16-byte pieces too early in 1 of ~10^6; nothing on the default path depends on an in-launch hand-off.)
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(ws, 0, ws_bytes, 0x00020000);
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-        const int t = tid + it * NTHR, d4 = (t & 31) << 2;
-        if (t < nq) {
-            const int off = (int)((rec_of(t) + (int64_t)split * REC + d4) * 4);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc4[it]), rsrc, off, 0, 16);
-            if (d4 == 0)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, (f32x4){mm[it], ll[it], 0.f, 0.f}), rsrc,
-                                                       (int)((rec_of(t) + (int64_t)split * REC + HD) * 4), 0, 16);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's record stores have been acknowledged
-    __syncthreads();
-    if (tid == 0) {
-        const int old = __hip_atomic_fetch_add(counters + b * kv_heads + kvh, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_s = (old == n_split - 1);
-        if (old == n_split - 1) __hip_atomic_store(counters + b * kv_heads + kvh, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!last_s) return;
-    constexpr int MAXS = 16;
-    for (int it = 0; it < IT; ++it) {
-        const int t = tid + it * NTHR, d4 = (t & 31) << 2;
-        if (t >= nq) continue;
-        u32x4 ro[MAXS], rm[MAXS];
-#pragma unroll
-        for (int p = 0; p < MAXS; ++p) {
-            if (p < n_split) {
-                ro[p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((rec_of(t) + (int64_t)p * REC + d4) * 4), 0, 16);
-                rm[p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((rec_of(t) + (int64_t)p * REC + HD) * 4), 0, 16);
-            }
-        }
-        float mt = -1e30f;
-#pragma unroll
-        for (int p = 0; p < MAXS; ++p)
-            if (p < n_split) mt = fmaxf(mt, __builtin_bit_cast(f32x4, rm[p])[0]);
-        f32x4 at = {0.f, 0.f, 0.f, 0.f};
-        float lt = 0.f;
-#pragma unroll
-        for (int p = 0; p < MAXS; ++p) {
-            if (p < n_split) {
-                const f32x4 mlp = __builtin_bit_cast(f32x4, rm[p]), op = __builtin_bit_cast(f32x4, ro[p]);
-                const float sc = __builtin_amdgcn_exp2f(mlp[0] - mt);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) at[j] += op[j] * sc;
-                lt += mlp[1] * sc;
-            }
-        }
-        store_out(t, at, lt);
-    }
-}
-
-// Merge of the split-KV partials as a launch of its own: one 128-thread workgroup per (sequence, head).
-// (Cheaper end-to-end than replicating the merge in every o_proj workgroup's prologue: measured.)
-// NS > 0: all n_split records are requested at once (one memory round trip instead of two dependent loops).
-template <int NS>
-__global__ void __launch_bounds__(128) attn_merge_kernel(const float* __restrict__ ws, kr_bf16* __restrict__ out, int n_split, int heads_xp) {
-    // heads_xp > 0: out is the XP layout of a 17..32-row batch (row = sequence, column = head * 128 + d), heads_xp = heads
-    constexpr int HD = 128, REC = HD + 4;
-    const int bh = blockIdx.x, d = threadIdx.x;
-    float acc = 0.f, ll = 0.f;
-    if constexpr (NS > 0) {
-        const float* w = ws + (int64_t)bh * NS * REC;
-        float m[NS], l[NS], o[NS];
-#pragma unroll
-        for (int p = 0; p < NS; ++p) {
-            m[p] = w[p * REC + HD];
-            l[p] = w[p * REC + HD + 1];
-            o[p] = w[p * REC + d];
-        }
-        float mm = -1e30f;
-#pragma unroll
-        for (int p = 0; p < NS; ++p) mm = fmaxf(mm, m[p]);
-#pragma unroll
-        for (int p = 0; p < NS; ++p) {
-            const float sc = __builtin_amdgcn_exp2f(m[p] - mm);
-            acc += o[p] * sc;
-            ll += l[p] * sc;
-        }
-    } else {
-        const float* w = ws + (int64_t)bh * n_split * REC;
-        float mm = -1e30f;
-        for (int p = 0; p < n_split; ++p) mm = fmaxf(mm, w[p * REC + HD]);
-        for (int p = 0; p < n_split; ++p) {
-            const float sc = __builtin_amdgcn_exp2f(w[p * REC + HD] - mm);
-            acc += w[p * REC + d] * sc;
-            ll += w[p * REC + HD + 1] * sc;
-        }
-    }
-    const kr_bf16 r = __builtin_bit_cast(kr_bf16, f2bf(ll > 0.f ? acc / ll : 0.f));
-    if (heads_xp > 0) {
-        const int b = bh / heads_xp, hh = bh - b * heads_xp;
-        *reinterpret_cast<kr_bf16*>(reinterpret_cast<char*>(out) + kr_xp_byte_offset(b, hh * HD + d)) = r;
-    } else {
-        out[(int64_t)bh * HD + d] = r;
-    }
-}
-
-// =====================================================================================
-// temperature sampling as an argmax (Gumbel-max): token = argmax_i( logit_i / T + G_i )
-// =====================================================================================
-// G_i = -ln(-ln(u_i)), u_i = ((h_i >> 9) + 0.5) * 2^-23, h_i = mix(mix(seed ^ n * 0x9E3779B1) + i) with
-// mix = the "lowbias32" integer finaliser and n = the index of the token being generated in its sequence
-// (ctx_len + 1 - prompt_len).  A counter-based generator: no state, any (sequence, step, token) draw can be
-// recomputed — the oracle does exactly that.  T == 0 rows get no noise: plain argmax, ties to the lowest index.
-// The reference's requests carry temperature 0.1 (first attempt, karanta/pipeline.py:281,301) or 0.7
-// (VLLMClient.generate default, bulk_processing/workers/vllm_client.py:155); vLLM's own sampler draws from the
-// same softmax(logits / T) distribution with a different generator.
-__device__ __forceinline__ unsigned kr_mix32(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
-// guided slot: allowed-token bits of row b's DFA state (kr_guide_build_masks); nullptr = unconstrained
-__device__ __forceinline__ const uint32_t* kr_guide_row(const uint64_t* guide_masks, const int32_t* guide_state, int mask_words,
-                                                        int b) {
-    if (guide_masks == nullptr || guide_masks[b] == 0) return nullptr;
-    return reinterpret_cast<const uint32_t*>(guide_masks[b]) + (int64_t)guide_state[b] * mask_words;
-}
-
-// G_i of token i for the row whose counter base is `base` (kr_mix32 of its seed and step)
-__device__ __forceinline__ float kr_gumbel_noise(unsigned base, int i) {
-    const unsigned h = kr_mix32(base + (unsigned)i);
-    // 23-bit integer + 0.5 is exact in f32 (24 significant bits): u in [2^-24, 1 - 2^-24], never 0 or 1
-    // (a 24-bit integer + 0.5 rounds to 2^24 at the top code: u = 1, noise = +inf)
-    const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;  // 2^-23
-    return -logf(-logf(u));
-}
-
-// =====================================================================================
-// sampling controls: penalties, min_p / top_k / top_p truncation (vLLM's sampling parameters)
-// =====================================================================================
-// Per row, on the fp32 lm_head logits l, after the guide mask: repetition penalty r on every token of the prompt set or
-// with an output count c > 0 (l > 0 ? l / r : l * r), then l -= f * c + p * (c > 0); v = l * (1 / T); truncation keeps
-// v >= a per-row threshold (min_p: v_max + ln(min_p); top_k: the k-th largest v; top_p: the v at which the mass of the
-// descending v reaches p, over what min_p / top_k kept; the largest of the three), and the Gumbel-max argmax runs over
-// the kept tokens with the noise of gumbel_argmax_kernel unchanged: a draw from the renormalised truncated softmax.
-// params[b][KR_SP_STRIDE] = {top_k (<= 0: off), top_p (>= 1: off), min_p (<= 0: off), repetition, frequency, presence}.
-constexpr int KR_SP_STRIDE = 8;
-
-__device__ __forceinline__ uint32_t kr_fkey(float v) {   // order-preserving: a < b <=> key(a) < key(b) (-0 < +0)
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ bool kr_sp_penalised(const float* prm) {
-    return prm[3] != 1.0f || prm[4] != 0.0f || prm[5] != 0.0f;
-}
-
-// fp32, this operation order, no fused multiply-add: the numpy restatement matches bit for bit
-__device__ __forceinline__ float kr_penalise(float l, uint32_t in_prompt, int c, float rep, float freq, float pres) {
-#pragma clang fp contract(off)
-    if (in_prompt != 0u || c > 0) l = l > 0.f ? l / rep : l * rep;
-    const float cf = (float)c;
-    const float sub = freq * cf + pres * (c > 0 ? 1.0f : 0.0f);
-    return l - sub;
-}
-
-__device__ __forceinline__ unsigned long long wave_incl_scan_u64(unsigned long long x, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned lo = (unsigned)__shfl_up((int)(unsigned)x, o, 64);
-        const unsigned hi = (unsigned)__shfl_up((int)(unsigned)(x >> 32), o, 64);
-        if (lane >= o) x += ((unsigned long long)hi << 32) | lo;
-    }
-    return x;
-}
-
-__device__ __forceinline__ unsigned long long shfl_u64(unsigned long long x, int src) {
-    const unsigned lo = (unsigned)__shfl((int)(unsigned)x, src, 64), hi = (unsigned)__shfl((int)(unsigned)(x >> 32), src, 64);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-constexpr int SEL_T = 1024;
-
-// Radix select over the keys of one row's scores w (excluded tokens hold -inf): the largest key t >= lo whose weight
-// sum over keys >= t reaches the target, in three histogram passes (11 / 11 / 10 key bits).  Weights: 1 (count mode,
-// target = k), or exp(v - vmax) in 32.32 fixed point (mass mode, target = ceil(frac * mass of the keys >= lo)).  Integer
-// LDS atomics: the histograms, and so the result, do not depend on the order the threads add in.  Returns lo when the
-// keys >= lo weigh less than the target (k above the surviving count).
-__device__ uint32_t radix_select(const float* __restrict__ w, int vocab, uint32_t lo, bool mass, float vmax, double want,
-                                 unsigned long long* hist, unsigned long long* s_misc) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t prefix = 0, hi_mask = 0;
-    unsigned long long target = 0;
-    for (int lvl = 0; lvl < 3; ++lvl) {
-        const int shift = lvl == 0 ? 21 : lvl == 1 ? 10 : 0;
-        const int nb = lvl == 2 ? 1024 : 2048;
-        for (int j = tid; j < 2048; j += SEL_T) hist[j] = 0ull;
-        __syncthreads();
-        for (int i0 = tid; i0 < vocab; i0 += 4 * SEL_T) {
-            float v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = i0 + u * SEL_T;
-                v[u] = i < vocab ? w[i] : -INFINITY;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint32_t k = kr_fkey(v[u]);
-                if (k >= lo && (k & hi_mask) == prefix) {
-                    const unsigned long long wt = mass ? (unsigned long long)(__expf(v[u] - vmax) * 4294967296.0f) : 1ull;
-                    // a zero weight never moves the crossing bin: the LDS atomic (the pass's cost) is skipped
-                    if (wt != 0ull) atomicAdd(&hist[(k >> shift) & (nb - 1)], wt);
-                }
-            }
-        }
-        __syncthreads();
-        if (wave == 0) {
-            // lane l owns nb / 64 bins, highest keys first; the first lane whose inclusive sum reaches the target holds the bin
-            const int per = nb / 64;
-            const int top = nb - 1 - lane * per;
-            unsigned long long sl = 0;
-            for (int q = 0; q < per; ++q) sl += hist[top - q];
-            const unsigned long long incl = wave_incl_scan_u64(sl, lane);
-            if (lvl == 0) {
-                const unsigned long long total = shfl_u64(incl, 63);
-                if (mass) {
-                    const double t = ceil(want * (double)total);
-                    target = t < 1.0 ? 1ull : (t > (double)total ? total : (unsigned long long)t);
-                } else {
-                    target = (unsigned long long)want;
-                }
-            }
-            const unsigned long long bal = __ballot(incl >= target);
-            if (bal == 0ull) {
-                if (lane == 0) s_misc[0] = 1ull;
-            } else {
-                const int L = __ffsll((long long)bal) - 1;
-                const unsigned long long before = shfl_u64(incl - sl, L);
-                const int topL = nb - 1 - L * per;
-                const unsigned long long hq = lane < per ? hist[topL - lane] : 0ull;
-                const unsigned long long inc2 = wave_incl_scan_u64(hq, lane) + before;
-                const unsigned long long bal2 = __ballot(lane < per && inc2 >= target);
-                const int Q = __ffsll((long long)bal2) - 1;
-                const unsigned long long before2 = shfl_u64(inc2 - hq, Q);
-                if (lane == 0) {
-                    s_misc[0] = 0ull;
-                    s_misc[1] = (unsigned long long)(topL - Q);
-                    s_misc[2] = target - before2;
-                }
-            }
-        }
-        __syncthreads();
-        if (s_misc[0] != 0ull) return lo;
-        prefix |= (uint32_t)s_misc[1] << shift;
-        hi_mask |= (uint32_t)(nb - 1) << shift;
-        target = s_misc[2];
-        __syncthreads();
-    }
-    return prefix;
-}
-
-// One workgroup per row: the row's scores (penalised, tempered, guide-masked; -inf where excluded) go to work once,
-// v_max, then the min_p / top_k / top_p threshold key -> thr[b] (0: keep every allowed token).  Rows with T == 0 or
-// neutral truncation stop after writing 0.  live[b]: whether kr_sample_greedy appends a real token to this row in this
-// step (not a finished row's pad token) — what kr_sample_count counts.
-__global__ void __launch_bounds__(SEL_T) sample_threshold_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
-                                                                 const float* __restrict__ temperature,
-                                                                 const float* __restrict__ params,
-                                                                 const int32_t* __restrict__ counts, int64_t ld_counts,
-                                                                 const uint32_t* __restrict__ prompt_bits, int bits_words,
-                                                                 const uint64_t* __restrict__ guide_masks,
-                                                                 const int32_t* __restrict__ guide_state, int mask_words,
-                                                                 const int32_t* __restrict__ finished, int ignore_eos,
-                                                                 float* __restrict__ work, int64_t ld_work,
-                                                                 uint32_t* __restrict__ thr, int32_t* __restrict__ live) {
-    __shared__ unsigned long long hist[2048];
-    __shared__ unsigned long long s_misc[4];
-    __shared__ float s_m[SEL_T / 64];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* prm = params + (int64_t)b * KR_SP_STRIDE;
-    if (tid == 0) live[b] = ((ignore_eos & 1) != 0 || finished[b] == 0) ? 1 : 0;
-    const float T = temperature[b];
-    const int top_k = (int)prm[0];
-    const float top_p = prm[1], min_p = prm[2];
-    const bool use_k = top_k > 0 && top_k < vocab, use_p = top_p < 1.0f, use_m = min_p > 0.0f;
-    if (!(T > 0.f) || !(use_k || use_p || use_m)) {
-        if (tid == 0) thr[b] = 0u;
-        return;
-    }
-    const float inv_t = 1.0f / T;
-    const bool pen = kr_sp_penalised(prm);
-    const float rep = prm[3], freq = prm[4], pres = prm[5];
-    const float* row = logits + (int64_t)b * ld;
-    const int32_t* cnt = counts + (int64_t)b * ld_counts;
-    const uint32_t* pb = prompt_bits + (int64_t)b * bits_words;
-    float* wr = work + (int64_t)b * ld_work;
-    const uint32_t* allow = kr_guide_row(guide_masks, guide_state, mask_words, b);
-    float m = -INFINITY;
-    for (int i = tid; i < vocab; i += SEL_T) {
-        float v = -INFINITY;
-        if (allow == nullptr || ((allow[i >> 5] >> (i & 31)) & 1u)) {
-            float lp = row[i];
-            if (pen) lp = kr_penalise(lp, (pb[i >> 5] >> (i & 31)) & 1u, cnt[i], rep, freq, pres);
-            v = lp * inv_t;
-        }
-        wr[i] = v;
-        m = fmaxf(m, v);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if (lane == 0) s_m[wave] = m;
-    __syncthreads();   // also orders this workgroup's work-row writes before its reads below
-    m = s_m[0];
-#pragma unroll
-    for (int q = 1; q < SEL_T / 64; ++q) m = fmaxf(m, s_m[q]);
-    uint32_t lo = kr_fkey(-INFINITY) + 1u;        // every allowed (finite) score
-    if (use_m) {
-        const uint32_t km = kr_fkey(m + logf(min_p));
-        lo = km > lo ? km : lo;
-    }
-    if (use_k) {
-        const uint32_t kk = radix_select(wr, vocab, lo, false, m, (double)top_k, hist, s_misc);
-        lo = kk > lo ? kk : lo;
-    }
-    if (use_p) {
-        const uint32_t kp = radix_select(wr, vocab, lo, true, m, (double)top_p, hist, s_misc);
-        lo = kp > lo ? kp : lo;
-    }
-    if (tid == 0) thr[b] = lo;
-}
-
-// =====================================================================================
-// the Gumbel-max partial argmax: [batch][n_part] partials for kr_sample_greedy's reduction
-// =====================================================================================
-// One body for both launches.  PROC (gumbel_argmax_proc_kernel) adds the penalties and the truncation threshold of
-// sample_threshold_kernel; a row with neutral parameters (no penalty, threshold 0) runs the value expression of the plain
-// launch and gets its partials bit for bit.
-template <bool PROC>
-__device__ __forceinline__ void gumbel_argmax_body(const float* logits, int64_t ld, int vocab, const float* temperature,
-                                                   const unsigned* seed, const int32_t* ctx_len, const int32_t* prompt_len,
-                                                   float* amax_val, int32_t* amax_idx, const uint64_t* guide_masks,
-                                                   const int32_t* guide_state, int mask_words, int fallback_token,
-                                                   const float* params, const int32_t* counts, int64_t ld_counts,
-                                                   const uint32_t* prompt_bits, int bits_words, const uint32_t* thr) {
-    __shared__ float s_v[4];
-    __shared__ int s_i[4];
-    const int p = blockIdx.x, n_part = gridDim.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (((vocab + n_part - 1) / n_part) + 3) & ~3;
-    const int i0 = p * per, i1 = min(vocab, i0 + per);
-    const float T = temperature[b];
-    const float inv_t = T > 0.f ? 1.0f / T : 1.0f;
-    const unsigned base = kr_mix32(seed[b] ^ ((unsigned)(ctx_len[b] + 1 - prompt_len[b]) * 0x9E3779B1u));
-    const float* row = logits + (int64_t)b * ld;
-    bool pen = false;
-    float rep = 1.0f, freq = 0.0f, pres = 0.0f;
-    const int32_t* cnt = nullptr;
-    const uint32_t* pb = nullptr;
-    uint32_t th = 0u;
-    if constexpr (PROC) {
-        const float* prm = params + (int64_t)b * KR_SP_STRIDE;
-        pen = kr_sp_penalised(prm);
-        rep = prm[3], freq = prm[4], pres = prm[5];
-        cnt = counts + (int64_t)b * ld_counts;
-        pb = prompt_bits + (int64_t)b * bits_words;
-        th = T > 0.f ? thr[b] : 0u;    // greedy rows: truncation cannot move the argmax
-    }
-    const uint32_t* allow = kr_guide_row(guide_masks, guide_state, mask_words, b);
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = i0 + tid; i < i1; i += 256) {
-        if (allow != nullptr && !((allow[i >> 5] >> (i & 31)) & 1u)) continue;
-        float lp = row[i];
-        if (PROC && pen) lp = kr_penalise(lp, (pb[i >> 5] >> (i & 31)) & 1u, cnt[i], rep, freq, pres);
-        float v = lp * inv_t;
-        if (PROC && th != 0u && kr_fkey(v) < th) continue;
-        if (T > 0.f) v += kr_gumbel_noise(base, i);
-        better(bv, bi, v, i);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        better(bv, bi, ov, oi);
-    }
-    if (lane == 0) {
-        s_v[wave] = bv;
-        s_i[wave] = bi;
-    }
-    __syncthreads();
-    if (tid == 0) {
-#pragma unroll
-        for (int w = 1; w < 4; ++w) better(bv, bi, s_v[w], s_i[w]);
-        // a row whose mask allows nothing (cannot happen for a live DFA state) must still yield a valid token id
-        if (p == 0 && bi == 0x7fffffff) bi = fallback_token;
-        amax_val[(int64_t)b * n_part + p] = bv;
-        amax_idx[(int64_t)b * n_part + p] = bi;
-    }
-}
-
-__global__ void __launch_bounds__(256) gumbel_argmax_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
-                                                            const float* __restrict__ temperature,
-                                                            const unsigned* __restrict__ seed,
-                                                            const int32_t* __restrict__ ctx_len,
-                                                            const int32_t* __restrict__ prompt_len,
-                                                            float* __restrict__ amax_val, int32_t* __restrict__ amax_idx,
-                                                            const uint64_t* __restrict__ guide_masks,
-                                                            const int32_t* __restrict__ guide_state, int mask_words,
-                                                            int fallback_token) {
-    gumbel_argmax_body<false>(logits, ld, vocab, temperature, seed, ctx_len, prompt_len, amax_val, amax_idx, guide_masks,
-                              guide_state, mask_words, fallback_token, nullptr, nullptr, 0, nullptr, 0, nullptr);
-}
-
-__global__ void __launch_bounds__(256) gumbel_argmax_proc_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
-                                                                 const float* __restrict__ temperature,
-                                                                 const unsigned* __restrict__ seed,
-                                                                 const int32_t* __restrict__ ctx_len,
-                                                                 const int32_t* __restrict__ prompt_len,
-                                                                 float* __restrict__ amax_val, int32_t* __restrict__ amax_idx,
-                                                                 const uint64_t* __restrict__ guide_masks,
-                                                                 const int32_t* __restrict__ guide_state, int mask_words,
-                                                                 int fallback_token, const float* __restrict__ params,
-                                                                 const int32_t* __restrict__ counts, int64_t ld_counts,
-                                                                 const uint32_t* __restrict__ prompt_bits, int bits_words,
-                                                                 const uint32_t* __restrict__ thr) {
-    gumbel_argmax_body<true>(logits, ld, vocab, temperature, seed, ctx_len, prompt_len, amax_val, amax_idx, guide_masks,
-                             guide_state, mask_words, fallback_token, params, counts, ld_counts, prompt_bits, bits_words, thr);
-}
-
-// after kr_sample_greedy: counts[b][tokens[b]] += 1 where live[b] (sample_threshold_kernel)
-__global__ void __launch_bounds__(64) sample_count_kernel(const int32_t* __restrict__ tokens, const int32_t* __restrict__ live,
-                                                          int32_t* __restrict__ counts, int64_t ld_counts, int vocab, int batch) {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= batch || live[b] == 0) return;
-    const int t = tokens[b];
-    if (t >= 0 && t < vocab) counts[(int64_t)b * ld_counts + t] += 1;
-}
-
-// =====================================================================================
-// greedy sampling from the lm_head partials + per-step bookkeeping
-// =====================================================================================
-__global__ void __launch_bounds__(256) sample_greedy_kernel(const float* __restrict__ amax_val,
-                                                            const int32_t* __restrict__ amax_idx, int n_part,
-                                                            const kr_bf16* __restrict__ table, int d,
-                                                            int32_t* __restrict__ tokens_out, int32_t* __restrict__ history,
-                                                            int hist_stride, const int32_t* __restrict__ prompt_len,
-                                                            int32_t* __restrict__ ctx_len, int32_t* __restrict__ finished,
-                                                            const int32_t* __restrict__ eos, int n_eos, int pad_id,
-                                                            int ignore_eos, kr_bf16* __restrict__ x_next) {
-    __shared__ float s_v[4];
-    __shared__ int s_i[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    // eight partials per thread requested at once (clamped indices, no branch around the loads): the lm_head leaves up to 2048
-    // partials per row, and one load pair per loop iteration was eight dependent L2 round trips in a 6 us launch
-    for (int i0 = tid; i0 < n_part; i0 += 256 * 8) {
-        float v[8];
-        int ix[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = min(i0 + u * 256, n_part - 1);
-            v[u] = amax_val[(int64_t)b * n_part + i];
-            ix[u] = amax_idx[(int64_t)b * n_part + i];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (i0 + u * 256 < n_part) better(bv, bi, v[u], ix[u]);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        better(bv, bi, ov, oi);
-    }
-    if (lane == 0) {
-        s_v[wave] = bv;
-        s_i[wave] = bi;
-    }
-    __syncthreads();
-    bv = s_v[0];
-    bi = s_i[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) better(bv, bi, s_v[w], s_i[w]);
-    int tok = bi;
-    const int was_finished = finished[b];
-    const bool freeze = (ignore_eos & 2) != 0;  // bit 1: a finished sequence stops advancing (slot scheduler)
-    ignore_eos &= 1;
-    if (was_finished && !ignore_eos) tok = pad_id;
-    const int new_ctx = ctx_len[b] + 1;  // tokens cached once the sampled token has been fed back
-    __syncthreads();
-    if (freeze && was_finished && !ignore_eos) {
-        // the slot idles at its last position (its KV row is rewritten in place, its history stays as it is)
-        // until the host admits a new request into it
-        if (tid == 0) tokens_out[b] = tok;
-        for (int c = tid; c < (d >> 3); c += 256) st8(x_next + (int64_t)b * d + c * 8, ld8(table + (int64_t)tok * d + c * 8));
-        return;
-    }
-    if (tid == 0) {
-        tokens_out[b] = tok;
-        history[(int64_t)(new_ctx - prompt_len[b]) * hist_stride + b] = tok;  // generated-token index of this sequence
-        ctx_len[b] = new_ctx;
-        if (!ignore_eos && !was_finished) {
-            int hit = 0;
-            for (int i = 0; i < n_eos; ++i) hit |= (tok == eos[i]);
-            if (hit) finished[b] = 1;
-        }
-    }
-    for (int c = tid; c < (d >> 3); c += 256) st8(x_next + (int64_t)b * d + c * 8, ld8(table + (int64_t)tok * d + c * 8));
-}
-
 template <int NT, int EPI, int WAVES>
 int launch_dec(DecLinArgs& a, int groups, int max_blocks, kr_stream s) {
     a.groups = groups;
@@ -2725,58 +1957,6 @@ extern "C" int kr_linear_decode_narrow_fp8(int mode, const kr_bf16* x, int64_t l
                        heads, kv_heads, s_max, opts, s);
 }
 
-static int attn_decode_impl(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
-                            const int32_t* finished, kr_bf16* out, float* workspace, int32_t* counters, int batch, int heads,
-                            int kv_heads, int hd, int s_max, int n_split, float scale, kr_stream s) {
-    KR_CHECK_ARG(q && kcache && vtcache && ctx_len && (out || workspace), "kr_attn_decode_fused: null pointer");
-    KR_CHECK_ARG(hd == 128, "kr_attn_decode_fused: hd=%d (only 128)", hd);
-    KR_CHECK_ARG(heads % kv_heads == 0 && heads / kv_heads <= 16, "kr_attn_decode_fused: GQA group must be <= 16");
-    KR_CHECK_ARG(batch > 0 && n_split > 0 && s_max % 64 == 0, "kr_attn_decode_fused: bad sizes");
-    KR_CHECK_ARG(KR_EXP || !out || n_split == 1,
-                 "kr_attn_decode_fused: the in-launch merge (out != NULL with n_split > 1) is an experiment build (-DKR_EXPERIMENTS); "
-                 "pass out = NULL and run kr_attn_decode_merge");
-    KR_CHECK_ARG(!out || n_split <= 16, "kr_attn_decode_fused: the in-launch merge takes at most 16 splits");
-    KR_CHECK_ARG(!out || n_split == 1 || (workspace && counters), "kr_attn_decode_fused: split needs workspace + counters");
-    KR_CHECK_ARG(workspace || n_split == 1, "kr_attn_decode_fused: the split partials need a workspace");
-    // Workgroup shape: n_split x WAVES parts of 32-key units, so that at page contexts (1.4k .. 2.4k keys = 44 .. 76 units)
-    // a wave fetches ONE unit (one memory round trip).  r2 chain timings (B = 8, ctx 1906, launch + dependent-launch gap):
-    // 8 splits x 8 waves (128 workgroups) 7.8 us; 16 splits x 4 waves (256 workgroups, every CU loads) 5.8 us;
-    // 6 x 8 (two units per wave) 12.7 us.  Hence: up to 8 splits 8 waves, up to 16 splits 4 waves, beyond 2 waves
-    // (KARANTA_ATTN_WAVES = 2 / 4 / 8 overrides for A/B runs).
-    static const int waves_env = [] { const char* e = getenv("KARANTA_ATTN_WAVES"); return e ? atoi(e) : 0; }();
-    const int waves = waves_env ? waves_env : (n_split <= 8 ? 8 : n_split <= 16 ? 4 : 2);
-    KR_CHECK_ARG(waves == 2 || waves == 4 || waves == 8, "kr_attn_decode_fused: KARANTA_ATTN_WAVES=%d (2, 4 or 8)", waves);
-    const int64_t ws_bytes = (int64_t)batch * heads * n_split * (hd + 4) * 4;
-    KR_CHECK_ARG(ws_bytes < ((int64_t)1 << 31), "kr_attn_decode_fused: workspace of %lld bytes", (long long)ws_bytes);
-    const dim3 grid(n_split, kv_heads, batch);
-    const float sl2 = scale * 1.4426950408889634f;
-    const int group = heads / kv_heads;
-    if (waves == 8)
-        attn_decode2_kernel<8><<<grid, 512, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
-                                                           workspace, counters, (int)ws_bytes);
-    else if (waves == 4)
-        attn_decode2_kernel<4><<<grid, 256, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
-                                                           workspace, counters, (int)ws_bytes);
-    else
-        attn_decode2_kernel<2><<<grid, 128, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
-                                                           workspace, counters, (int)ws_bytes);
-    KR_CHECK_LAUNCH();
-    return KR_OK;
-}
-
-extern "C" int kr_attn_decode_fused(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
-                                    kr_bf16* out, float* workspace, int32_t* counters, int batch, int heads, int kv_heads,
-                                    int hd, int s_max, int n_split, float scale, kr_stream s) {
-    return attn_decode_impl(q, kcache, vtcache, ctx_len, nullptr, out, workspace, counters, batch, heads, kv_heads, hd, s_max, n_split, scale, s);
-}
-
-extern "C" int kr_attn_decode_slots(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
-                                    const int32_t* finished, float* workspace, int batch, int heads, int kv_heads, int hd, int s_max,
-                                    int n_split, float scale, kr_stream s) {
-    KR_CHECK_ARG(finished && workspace, "kr_attn_decode_slots: null pointer");
-    return attn_decode_impl(q, kcache, vtcache, ctx_len, finished, nullptr, workspace, nullptr, batch, heads, kv_heads, hd, s_max, n_split, scale, s);
-}
-
 // ---- residual sum + RMSNorm ONCE per batch (decode batches above 16 rows)
 namespace {
 // x_new = bf16(x + slab_0 + slab_1 + ...) (in that order), h = norm_w * bf16(x_new * rsqrt(mean(x_new^2) + eps)).
@@ -2919,120 +2099,6 @@ extern "C" int kr_decode_resnorm32(const kr_bf16* x, int64_t ldx, const float* p
                                    int64_t ldxo, const kr_bf16* norm_w, float norm_eps, kr_bf16* h_xp, int M, int K, int sum_slabs_first,
                                    kr_stream s) {
     return resnorm_impl(x, ldx, part_in, n_part_in, part_rows, x_out, ldxo, norm_w, norm_eps, h_xp, 0, M, K, 1 | (sum_slabs_first ? 2 : 0), s);
-}
-
-static int merge_impl(const float* workspace, kr_bf16* out, int batch, int heads, int hd, int n_split, int xp, kr_stream s) {
-    KR_CHECK_ARG(workspace && out && batch > 0 && heads > 0 && n_split > 0, "kr_attn_decode_merge: bad args");
-    KR_CHECK_ARG(hd == 128, "kr_attn_decode_merge: hd=%d (only 128)", hd);
-    KR_CHECK_ARG(!xp || (batch <= 32 && ((uintptr_t)out & 15) == 0), "kr_attn_decode_merge32: batch=%d (<= 32)", batch);
-    const int hx = xp ? heads : 0;
-    switch (n_split) {
-        case 4: attn_merge_kernel<4><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
-        case 8: attn_merge_kernel<8><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
-        case 16: attn_merge_kernel<16><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
-        case 32: attn_merge_kernel<32><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
-        default: attn_merge_kernel<0><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx);
-    }
-    KR_CHECK_LAUNCH();
-    return KR_OK;
-}
-
-extern "C" int kr_attn_decode_merge(const float* workspace, kr_bf16* out, int batch, int heads, int hd, int n_split,
-                                    kr_stream s) {
-    return merge_impl(workspace, out, batch, heads, hd, n_split, 0, s);
-}
-
-extern "C" int kr_attn_decode_merge32(const float* workspace, kr_bf16* out_xp, int batch, int heads, int hd, int n_split,
-                                      kr_stream s) {
-    return merge_impl(workspace, out_xp, batch, heads, hd, n_split, 1, s);
-}
-
-extern "C" int kr_gumbel_argmax_guided(const float* logits, int64_t ld_logits, int vocab, const float* temperature,
-                                       const uint32_t* seed, const int32_t* ctx_len, const int32_t* prompt_len,
-                                       float* amax_val, int32_t* amax_idx, int n_part, int batch,
-                                       const uint64_t* guide_masks, const int32_t* guide_state, int mask_words,
-                                       int fallback_token, kr_stream s) {
-    KR_CHECK_ARG(logits && temperature && seed && ctx_len && prompt_len && amax_val && amax_idx, "kr_gumbel_argmax: null pointer");
-    KR_CHECK_ARG(vocab > 0 && ld_logits >= vocab && n_part > 0 && n_part <= 65535 && batch > 0, "kr_gumbel_argmax: bad sizes");
-    KR_CHECK_ARG(guide_masks == nullptr || (guide_state != nullptr && (int64_t)mask_words * 32 >= vocab),
-                 "kr_gumbel_argmax_guided: guide_state missing or mask_words * 32 < vocab");
-    KR_CHECK_ARG(fallback_token >= 0 && fallback_token < vocab, "kr_gumbel_argmax_guided: fallback_token out of vocabulary");
-    gumbel_argmax_kernel<<<dim3(n_part, batch), 256, 0, kr_hs(s)>>>(logits, ld_logits, vocab, temperature, seed, ctx_len, prompt_len,
-                                                                    amax_val, amax_idx, guide_masks, guide_state, mask_words,
-                                                                    fallback_token);
-    KR_CHECK_LAUNCH();
-    return KR_OK;
-}
-
-extern "C" int kr_gumbel_argmax(const float* logits, int64_t ld_logits, int vocab, const float* temperature,
-                                const uint32_t* seed, const int32_t* ctx_len, const int32_t* prompt_len, float* amax_val,
-                                int32_t* amax_idx, int n_part, int batch, kr_stream s) {
-    return kr_gumbel_argmax_guided(logits, ld_logits, vocab, temperature, seed, ctx_len, prompt_len, amax_val, amax_idx, n_part,
-                                   batch, nullptr, nullptr, 0, 0, s);
-}
-
-extern "C" int kr_sample_greedy(const float* amax_val, const int32_t* amax_idx, int n_part, const kr_bf16* embed_table,
-                                int d, int32_t* tokens_out, int32_t* history, int hist_stride, const int32_t* prompt_len,
-                                int32_t* ctx_len, int32_t* finished, const int32_t* eos, int n_eos, int pad_id,
-                                int ignore_eos, kr_bf16* x_next, int batch, kr_stream s) {
-    KR_CHECK_ARG(amax_val && amax_idx && embed_table && tokens_out && history && prompt_len && ctx_len && finished && x_next,
-                 "kr_sample_greedy: null pointer");
-    KR_CHECK_ARG(n_part > 0 && batch > 0 && (d & 7) == 0 && hist_stride >= batch && (n_eos == 0 || eos),
-                 "kr_sample_greedy: bad sizes");
-    sample_greedy_kernel<<<batch, 256, 0, kr_hs(s)>>>(amax_val, amax_idx, n_part, embed_table, d, tokens_out, history,
-                                                      hist_stride, prompt_len, ctx_len, finished, eos, n_eos, pad_id,
-                                                      ignore_eos, x_next);
-    KR_CHECK_LAUNCH();
-    return KR_OK;
-}
-
-
-extern "C" int kr_sample_threshold(const float* logits, int64_t ld_logits, int vocab, const float* temperature, const float* params,
-                                   const int32_t* counts, int64_t ld_counts, const uint32_t* prompt_bits, int bits_words,
-                                   const uint64_t* guide_masks, const int32_t* guide_state, int mask_words, const int32_t* finished,
-                                   int ignore_eos, float* work, int64_t ld_work, uint32_t* threshold, int32_t* live, int batch,
-                                   kr_stream s) {
-    KR_CHECK_ARG(logits && temperature && params && counts && prompt_bits && finished && work && threshold && live,
-                 "kr_sample_threshold: null pointer");
-    KR_CHECK_ARG(vocab > 0 && ld_logits >= vocab && ld_counts >= vocab && ld_work >= vocab && (int64_t)bits_words * 32 >= vocab &&
-                 batch > 0, "kr_sample_threshold: bad sizes");
-    KR_CHECK_ARG(guide_masks == nullptr || (guide_state != nullptr && (int64_t)mask_words * 32 >= vocab),
-                 "kr_sample_threshold: guide_state missing or mask_words * 32 < vocab");
-    sample_threshold_kernel<<<batch, SEL_T, 0, kr_hs(s)>>>(logits, ld_logits, vocab, temperature, params, counts, ld_counts,
-                                                           prompt_bits, bits_words, guide_masks, guide_state, mask_words, finished,
-                                                           ignore_eos, work, ld_work, threshold, live);
-    KR_CHECK_LAUNCH();
-    return KR_OK;
-}
-
-extern "C" int kr_gumbel_argmax_processed(const float* logits, int64_t ld_logits, int vocab, const float* temperature,
-                                          const uint32_t* seed, const int32_t* ctx_len, const int32_t* prompt_len, float* amax_val,
-                                          int32_t* amax_idx, int n_part, int batch, const uint64_t* guide_masks,
-                                          const int32_t* guide_state, int mask_words, int fallback_token, const float* params,
-                                          const int32_t* counts, int64_t ld_counts, const uint32_t* prompt_bits, int bits_words,
-                                          const uint32_t* threshold, kr_stream s) {
-    KR_CHECK_ARG(logits && temperature && seed && ctx_len && prompt_len && amax_val && amax_idx && params && counts && prompt_bits &&
-                 threshold, "kr_gumbel_argmax_processed: null pointer");
-    KR_CHECK_ARG(vocab > 0 && ld_logits >= vocab && ld_counts >= vocab && (int64_t)bits_words * 32 >= vocab && n_part > 0 &&
-                 n_part <= 65535 && batch > 0, "kr_gumbel_argmax_processed: bad sizes");
-    KR_CHECK_ARG(guide_masks == nullptr || (guide_state != nullptr && (int64_t)mask_words * 32 >= vocab),
-                 "kr_gumbel_argmax_processed: guide_state missing or mask_words * 32 < vocab");
-    KR_CHECK_ARG(fallback_token >= 0 && fallback_token < vocab, "kr_gumbel_argmax_processed: fallback_token out of vocabulary");
-    gumbel_argmax_proc_kernel<<<dim3(n_part, batch), 256, 0, kr_hs(s)>>>(logits, ld_logits, vocab, temperature, seed, ctx_len,
-                                                                         prompt_len, amax_val, amax_idx, guide_masks, guide_state,
-                                                                         mask_words, fallback_token, params, counts, ld_counts,
-                                                                         prompt_bits, bits_words, threshold);
-    KR_CHECK_LAUNCH();
-    return KR_OK;
-}
-
-extern "C" int kr_sample_count(const int32_t* tokens, const int32_t* live, int32_t* counts, int64_t ld_counts, int vocab, int batch,
-                               kr_stream s) {
-    KR_CHECK_ARG(tokens && live && counts, "kr_sample_count: null pointer");
-    KR_CHECK_ARG(vocab > 0 && ld_counts >= vocab && batch > 0, "kr_sample_count: bad sizes");
-    sample_count_kernel<<<(batch + 63) / 64, 64, 0, kr_hs(s)>>>(tokens, live, counts, ld_counts, vocab, batch);
-    KR_CHECK_LAUNCH();
-    return KR_OK;
 }
 
 #ifdef KR_EXPERIMENTS

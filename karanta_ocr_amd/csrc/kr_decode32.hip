@@ -19,46 +19,12 @@
 //     kr_linear_decode32 with kr_linear_decode_narrow row for row).
 //   * epilogues spread over (column tile, weight tile) waves instead of wave 0 alone; bias / residual / rotary operands are
 //     requested ahead of the weight ring as in the narrow kernel.
-#include "kr_common.h"
+#include "kr_decode_common.h"
 
 namespace {
 
-constexpr int D32_PLAIN = 0, D32_ROPE_KV = 2, D32_PARTIAL = 16;
+constexpr int D32_PLAIN = DEPI_PLAIN, D32_ROPE_KV = DEPI_ROPE_KV, D32_PARTIAL = DEPI_PARTIAL;   // the modes this family has
 constexpr int MT = 2;   // 16-row column tiles of the batch
-
-// One 64-wide K chunk of a 16-row weight tile in registers (formats of kr_decode.hip's WChunk) and where its x operand sits
-// inside a column tile's 2 KiB of a packed chunk.
-template <bool W8> struct WCh;
-template <> struct WCh<false> {
-    static constexpr int BYTES = 2048;
-    bf16x8 v[2];
-    __device__ __forceinline__ void load(const char* p, int64_t c) {
-        v[0] = ld8_nt(reinterpret_cast<const kr_bf16*>(p + c * BYTES));
-        v[1] = ld8_nt(reinterpret_cast<const kr_bf16*>(p + c * BYTES + 1024));
-    }
-    __device__ __forceinline__ bf16x8 frag(int h) const { return v[h]; }
-    // lane (fr, fg) of k-step h holds k = 32h + 8fg .. +7: block h, lane's own 16 bytes
-    static __device__ __forceinline__ int xp_off(int h, int fr, int fg) { return h * 1024 + (fg * 16 + fr) * 16; }
-};
-template <> struct WCh<true> {
-    static constexpr int BYTES = 1024;
-    u32x4 q;
-    __device__ __forceinline__ void load(const char* p, int64_t c) {
-        q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + c * BYTES));
-    }
-    __device__ __forceinline__ bf16x8 frag(int h) const {
-        u32x4 o;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int w = (int)q[2 * h + i];
-            o[2 * i + 0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
-            o[2 * i + 1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true));
-        }
-        return __builtin_bit_cast(bf16x8, o);
-    }
-    // fp8 chunk: lane (fr, fg) of k-step h holds k = 16fg + 8h .. +7 = block (fg >> 1), lane group 2 (fg & 1) + h
-    static __device__ __forceinline__ int xp_off(int h, int fr, int fg) { return (fg >> 1) * 1024 + ((((fg & 1) << 1) | h) * 16 + fr) * 16; }
-};
 
 struct D32Args {
     const float* w_scale;
@@ -81,7 +47,7 @@ template <int NT, int EPI, int WAVES, int VW, int U, bool W8, bool GS = false>
 __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, const char* hwp, int hM, int hN, int hK, int hcpb,
                                                            const D32Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    using WC = WCh<W8>;
+    using WC = WChunk<W8>;
     constexpr int WLOC = WAVES * VW;                 // atoms of this workgroup
     constexpr int WREF = GS ? 2 * WLOC : WLOC;       // atoms of the reference partition of one K range
     static_assert(!GS || EPI == D32_PARTIAL, "group split feeds atomic slabs");

@@ -6,7 +6,7 @@
 // (karanta/data/create_batch_data_prompts.py:117-118).  Here the host compiles the pattern to a byte DFA
 // (karanta_ocr_amd/guided.py) and everything per token stays on the GPU, inside the replayed decode graph:
 //   guide_build_masks_kernel   once per pattern: allowed-token bits of every DFA state      (HBM: S x V/8 bytes written)
-//   gumbel_argmax_kernel       (kr_decode.hip) skips the tokens whose bit is clear in the row of the slot's state
+//   gumbel_argmax_kernel       (kr_sample.hip) skips the tokens whose bit is clear in the row of the slot's state
 //   guide_advance_kernel       after the sampler: state <- walk(state, bytes(token))
 //   logprob_partial_kernel     per vocabulary slice (LDS resident): max, sum exp, top-k by k rounds of block argmax
 //   logprob_merge_kernel       per sequence: log-sum-exp, log-prob of the sampled token, merged top-k -> history

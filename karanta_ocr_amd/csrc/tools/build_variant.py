@@ -1,8 +1,9 @@
 """Build a VARIANT of libkaranta_hip.so with extra -D switches on one or more sources, for same-box A/B measurements.
 
     python karanta_ocr_amd/csrc/tools/build_variant.py NAME kr_attention.hip '-DKR_ATTN_VPRE(HD)=0' ...
-    python karanta_ocr_amd/csrc/tools/build_variant.py exp kr_decode.hip,kr_selftest.hip -DKR_EXPERIMENTS
-        (the decode experiments of rounds 1-2 and their entry points, include/karanta_hip_experiments.h)
+    python karanta_ocr_amd/csrc/tools/build_variant.py exp kr_decode.hip,kr_attn_decode.hip,kr_selftest.hip -DKR_EXPERIMENTS
+        (the decode experiments of rounds 1-2 and their entry points, include/karanta_hip_experiments.h; every source that
+        reads KR_EXP, csrc/kr_decode_common.h, has to be named)
 
 writes karanta_ocr_amd/csrc/_build/variants/libkaranta_hip.NAME.so (built artefact: git-ignored, travels with gpurun);
 run any tool against it with KARANTA_HIP_LIB=<that path>.  The other objects are the ones of the regular build.

@@ -14,8 +14,9 @@ It interleaves the launches with:
   KARANTA_ATTN_FUSED=1         split-KV merge inside the attention launch (last-arriving workgroup)
   KARANTA_MERGE_IN_OPROJ=1     split-KV merge in the o_proj prologue (general dec_linear_kernel)
   KARANTA_EXTRA_NULLS=n        n empty launches per layer (the price of a launch in the chain)
-Most of them need a library built with -DKR_EXPERIMENTS (csrc/tools/build_variant.py exp kr_decode.hip,kr_selftest.hip
--DKR_EXPERIMENTS; load it through KARANTA_HIP_LIB): include/karanta_hip_experiments.h.  The 17..32-row packed family
+Most of them need a library built with -DKR_EXPERIMENTS (csrc/tools/build_variant.py exp
+kr_decode.hip,kr_attn_decode.hip,kr_selftest.hip -DKR_EXPERIMENTS; load it through KARANTA_HIP_LIB):
+include/karanta_hip_experiments.h.  The 17..32-row packed family
 (kr_linear_decode32) is not wired in here: this sequence keeps round 3's row-major narrow launches at every batch size."""
 from __future__ import annotations
 

@@ -1,5 +1,5 @@
 // Micro-benchmark (round 4): does the SHAPE of the decode attention's K / V^T loads cost HBM bandwidth?
-// The decode attention (kr_decode.hip, attn_decode2_kernel) reads a 32-key unit as
+// The decode attention (kr_attn_decode.hip, attn_decode2_kernel) reads a 32-key unit as
 //   K   : 8 wave-instructions of 16 key rows x 64 B (row stride 256 B): two instructions share every 128-B line,
 //   V^T : 8 wave-instructions of 16 channel rows x 64 B (row stride 128 B) = one HALF of every line of a 16 KiB block; the other
 //         half belongs to the neighbouring unit = the next wave of the same workgroup.

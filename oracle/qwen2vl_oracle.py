@@ -616,7 +616,7 @@ def _mix32(x: np.ndarray) -> np.ndarray:
 
 
 def gumbel_noise(seed: int, n: int, vocab: int) -> np.ndarray:
-    """G_i of the build's sampler (kr_gumbel_argmax, kr_decode.hip): -ln(-ln(u_i)), u_i = ((h_i >> 9) + 0.5) 2^-23,
+    """G_i of the build's sampler (kr_gumbel_argmax, kr_sample.hip): -ln(-ln(u_i)), u_i = ((h_i >> 9) + 0.5) 2^-23,
     h_i = mix(mix(seed ^ n * 0x9E3779B1) + i), n = index of the token being generated.  fp32 like the kernel.
     (23 bits + 0.5 is exact in fp32, so u stays inside [2^-24, 1 - 2^-24] and the noise is finite: see gumbel_u.)"""
     base = _mix32(np.uint64((int(seed) ^ ((int(n) * 0x9E3779B1) & 0xFFFFFFFF)) & 0xFFFFFFFF))
