@@ -14,7 +14,9 @@
 //                     non-temporal 16-byte loads, 8+ loads in flight per wave; x (<= 16 rows) is staged
 //                     (optionally RMS-normalised) in LDS.  HBM-bound; roofline = 8 TB/s.
 #include <algorithm>
+#include <cstdlib>
 #include <mutex>
+#include <optional>
 
 #include "kr_common.h"
 
@@ -1051,11 +1053,118 @@ __global__ void __launch_bounds__(512) gemm_pipe_mx_kernel(const uint8_t* __rest
     }
 }
 
+// Compute units of the current device (cached per device): the round size of a one-workgroup-per-CU launch.
+inline int kr_cu_count() {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (cus[dev] == 0) {
+        int n = 0;
+        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
+    }
+    return cus[dev];
+}
+
+inline std::optional<int> env_int(const char* name) {
+    const char* v = getenv(name);
+    return v ? std::optional<int>(atoi(v)) : std::nullopt;
+}
+constexpr bool MX_TWO_DEFAULT = false;   // set by measurement (profiles/r03_fp8_gemm_bench.txt)
+
+// The switches of one GEMM call.  Constructing one reads the environment; every extern "C" entry does
+// that once per call and nothing is cached: the tests and the A/B sweeps flip the variables between launches of one process.
+struct GemmTuning {
+    int tile = env_int("KARANTA_GEMM_TILE").value_or(0);   // 128 / 256 / 512 (= pipelined 256x256) force the geometry (tests, tuning sweeps)
+    bool tail = env_int("KARANTA_GEMM_TAIL").value_or(1) != 0;           // 0: a pipelined launch keeps its last round whole
+    int tail_min_k = env_int("KARANTA_GEMM_TAIL_MINK").value_or(0);      // tuning sweeps: the K from which any tail of <= cus / 2 tiles is split
+    int tail_ksplit = env_int("KARANTA_GEMM_TAIL_KSPLIT").value_or(16);  // 0 / 1: never split the tail along K (A/B, tests); n: at most n ranges
+    std::optional<int> group_m = env_int("KARANTA_GEMM_GROUP_M");        // m tiles per group of the pipelined kernels' tile order
+    int stagger = env_int("KARANTA_GEMM_STAGGER").value_or(0);           // experiment, see gemm_pipe_kernel
+    std::optional<int> stages = env_int("KARANTA_GEMM_STAGES");          // 2 / 4: the ring depth of every 128x128 launch (A/B, tests)
+    // 1 (default) = kr_gemm_fp8a on the block-scaled instruction v_mfma_scale_f32_32x32x64_f8f6f4 (twice the bf16 rate); 0 =
+    // v_mfma_f32_16x16x32_fp8_fp8 in the bf16 kernel's pipeline (the bf16 rate).  Same products (exact in f32), another summation order.
+    bool mx = env_int("KARANTA_FP8_MX").value_or(1) != 0;
+    bool mx2 = env_int("KARANTA_FP8_MX2").value_or(MX_TWO_DEFAULT) != 0;   // 1: two K-tiles per barrier pair where K % 128 == 0 (A/B, tests flip it)
+#ifdef KR_GEMM_PERSIST_EXPERIMENT
+    // experiment build (tools/build_variant.py persist kr_gemm.hip -DKR_GEMM_PERSIST_EXPERIMENT): 0 (A/B, tests) selects the
+    // product launch in the same library
+    bool persist = env_int("KARANTA_GEMM_PERSIST").value_or(1) != 0;
+#endif
+
+    // measured (tools/gemm_microbench.py, r2): groups of 8 m tiles against m-major rows — ViT qkv (15 n tiles) 373 -> 350 us,
+    // fc1 (20) 518 -> 496, prefill gate/up (70) 581 -> 562, 8192^3 856 -> 1390 TFLOP/s; with 5-6 n tiles an m-major run of
+    // 32 ids is already a compact patch and groups are neutral (proj, down_proj) or worse (ViT fc2, K = 5120: 467 -> 495)
+    int group_m_for(int tiles_n) const { return group_m.value_or(tiles_n >= 8 ? 8 : 1); }
+    // 128x128 launches of at most one workgroup per CU take the 4-deep ring (see gemm_kernel)
+    bool deep_ring(int64_t nwg) const { return stages ? *stages == 4 : nwg <= kr_cu_count(); }
+};
+
+// One entry-point call: filled once by the extern "C" function (in its argument order) and passed down the launch chain.  The
+// fp8 entries pass their code bytes as kr_bf16 (A of kr_gemm_fp8a, W of both).  scratch is the CALLER-OWNED split-K scratch
+// of the tail launches (kr_gemm_bf16_ws: 128x128 f32 per partial workgroup, KR_GEMM_SCRATCH_BYTES in all).  The library
+// allocates nothing: a call without scratch runs its tail unsplit.
+struct GemmCall {
+    const kr_bf16* A;
+    int64_t lda;
+    const kr_bf16 *W, *bias, *R;
+    int64_t ldr;
+    kr_bf16* C;
+    int64_t ldc, M;
+    int N, K;
+    const float *w_scale, *a_scale;
+    float* scratch;
+    kr_stream s;
+    GemmTuning tune;   // = GemmTuning(): this call's reading of the environment
+};
+constexpr int TAIL_MAX_WGS = 512, TAIL_WG_BYTES = 256 * 16 * 16;   // 128x128 f32 per workgroup
+static_assert((size_t)TAIL_MAX_WGS * TAIL_WG_BYTES == KR_GEMM_SCRATCH_BYTES, "karanta_hip.h: KR_GEMM_SCRATCH_BYTES");
+
+template <int EPI, bool WPACK, typename G, int STAGES>
+int launch_gemm_kernel(const GemmCall& c, unsigned nwg, int tiles_n, int ptiles_n, unsigned qbase, int group_m, int ksplit = 1,
+                       int ks_mode = 0, float* ws = nullptr) {
+    constexpr int LDS = STAGES * (G::BM + G::BN) * BK * 2;
+    static KrPerDeviceOnce attr_set;
+    if (attr_set.need()) {
+        KR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<EPI, WPACK, G, STAGES>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    }
+    gemm_kernel<EPI, WPACK, G, STAGES><<<nwg, G::WM * G::WN * 64, LDS, kr_hs(c.s)>>>(
+        c.A, c.lda, c.W, c.bias, c.R, c.ldr, c.C, c.ldc, c.M, c.N, c.K, tiles_n, nwg, ptiles_n, qbase, group_m, ksplit, ks_mode, ws);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+template <int EPI, bool WPACK, typename G>
+int launch_gemm3(const GemmCall& c) {
+    const int64_t tiles_m = (c.M + G::BM - 1) / G::BM;
+    const int tiles_n = (c.N + G::BN - 1) / G::BN;
+    const int64_t nwg = tiles_m * tiles_n;
+    KR_CHECK_ARG(nwg < (1ll << 31), "kr_gemm_bf16: grid too large");
+    if constexpr (G::BM == 128) {
+        if (c.tune.deep_ring(nwg)) return launch_gemm_kernel<EPI, WPACK, G, 4>(c, (unsigned)nwg, tiles_n, 0, 0u, 0);
+    }
+    return launch_gemm_kernel<EPI, WPACK, G, 2>(c, (unsigned)nwg, tiles_n, 0, 0u, 0);
+}
+
+// The quarters of the 256x256 tiles [tile0, tile0 + n_tiles) of a launch_gemm_pipe tile list, as 128x128 workgroups; with a
+// long K (>= 4096) and few tail tiles each quarter is cut into K ranges (partials launch + reduce-and-epilogue launch, see
+// gemm_kernel) so that the tail's bytes are pulled by ~256-512 workgroups instead of 4 per tail tile.
 template <int EPI, bool WPACK>
-int launch_gemm_tail(const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_bf16* bias, const kr_bf16* R, int64_t ldr,
-                     kr_bf16* C, int64_t ldc, int64_t M, int N, int K, int ptiles_n, unsigned tile0, unsigned n_tiles, int group_m,
-                     kr_stream s);
-inline int kr_cu_count();
+int launch_gemm_tail(const GemmCall& c, int ptiles_n, unsigned tile0, unsigned n_tiles, int group_m) {
+    const unsigned nq = 4 * n_tiles;
+    const int cap = c.tune.tail_ksplit;
+    int ksplit = 1;
+    // one round of workgroups (4-deep ring: one per CU), at least 8 K steps each
+    if (cap > 1 && c.K >= 4096) ksplit = std::max(1, std::min(std::min(cap, (c.K / BK) / 8), (int)(kr_cu_count() / nq)));
+    float* ws = (ksplit > 1 && nq * (unsigned)ksplit <= (unsigned)TAIL_MAX_WGS) ? c.scratch : nullptr;
+    if (ws) {
+        int rc = launch_gemm_kernel<EPI, WPACK, G128, 4>(c, nq * ksplit, 1, ptiles_n, tile0, group_m, ksplit, 1, ws);
+        if (rc != KR_OK) return rc;
+        return launch_gemm_kernel<EPI, WPACK, G128, 2>(c, nq, 1, ptiles_n, tile0, group_m, ksplit, 2, ws);
+    }
+    if (c.tune.deep_ring(nq)) return launch_gemm_kernel<EPI, WPACK, G128, 4>(c, nq, 1, ptiles_n, tile0, group_m);
+    return launch_gemm_kernel<EPI, WPACK, G128, 2>(c, nq, 1, ptiles_n, tile0, group_m);
+}
 
 // One 512-thread workgroup per CU at a time: a launch of T tiles takes ceil(T / CUs) ROUNDS, and the page-sized GEMMs
 // sit badly on that grid — ViT proj / fc2 at 8 pages are 770 tiles = 3 rounds + 2 tiles (a fourth round for 0.3 % of
@@ -1063,18 +1172,15 @@ inline int kr_cu_count();
 // tiles are cut into 128x128 quarters and run as a second launch of the two-barrier kernel (same k order: the same
 // bits), which fills the chip with 4x as many, co-resident, short workgroups.  KARANTA_GEMM_TAIL=0 disables it.
 template <int EPI, bool WPACK, bool W8 = false, bool A8 = false>
-int launch_gemm_pipe(const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_bf16* bias, const kr_bf16* R, int64_t ldr,
-                     kr_bf16* C, int64_t ldc, int64_t M, int N, int K, kr_stream s, const float* w_scale = nullptr,
-                     const float* a_scale = nullptr) {
+int launch_gemm_pipe(const GemmCall& c) {
     constexpr int LDS = PSTAGES * PBUF;
-    const int64_t tiles_m = (M + 255) / 256;
-    const int tiles_n = (N + 255) / 256;
+    const int64_t tiles_m = (c.M + 255) / 256;
+    const int tiles_n = (c.N + 255) / 256;
     int64_t nwg = tiles_m * tiles_n;
     KR_CHECK_ARG(nwg < (1ll << 31), "kr_gemm_bf16: grid too large");
     unsigned tail = 0;
     if constexpr (!W8) {
         const int cus = kr_cu_count();
-        const char* env = getenv("KARANTA_GEMM_TAIL");
         const int64_t t = nwg % cus;
         // measured (tools/gemm_microbench.py, r2): a lone last round is cheaper than a full one (its few tiles have the
         // chip's clocks and memory system to themselves), so the split pays most where a tile is long — prefill down_proj
@@ -1082,9 +1188,8 @@ int launch_gemm_pipe(const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_b
         // tail on the 4-deep ring kernel, admission batches of 1..8 pages): at K = 1280 too every tail of <= cus / 2 tiles is
         // neutral or better split — proj 3 pages (34 tail tiles) 64.7 -> 59.3 us, qkv 1 page (44) 65.0 -> 58.4, fc1 2 pages
         // (12) 146.2 -> 136.5, fc1 8 pages (8) 499.7 -> 481.9 — so the round-2 condition "K >= 1536 or <= 4 tail tiles" is gone
-        const char* kenv = getenv("KARANTA_GEMM_TAIL_MINK");   // tuning sweeps: the K from which any tail of <= cus / 2 tiles is split
-        const int min_k = kenv ? atoi(kenv) : 0;
-        if (nwg > cus && t > 0 && 2 * t <= cus && (K >= min_k || t <= 4) && !(env && atoi(env) == 0)) {
+        // (tail_min_k = 0 unless a sweep sets it)
+        if (nwg > cus && t > 0 && 2 * t <= cus && (c.K >= c.tune.tail_min_k || t <= 4) && c.tune.tail) {
             tail = (unsigned)t;
             nwg -= t;
         }
@@ -1098,43 +1203,28 @@ int launch_gemm_pipe(const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_b
                                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS + 8 * 4096));
 #endif
     }
-    // measured (tools/gemm_microbench.py, r2): groups of 8 m tiles against m-major rows — ViT qkv (15 n tiles) 373 -> 350 us,
-    // fc1 (20) 518 -> 496, prefill gate/up (70) 581 -> 562, 8192^3 856 -> 1390 TFLOP/s; with 5-6 n tiles an m-major run of
-    // 32 ids is already a compact patch and groups are neutral (proj, down_proj) or worse (ViT fc2, K = 5120: 467 -> 495)
-    const char* genv = getenv("KARANTA_GEMM_GROUP_M");
-    const int group_m = genv ? atoi(genv) : (tiles_n >= 8 ? 8 : 1);
-    const char* senv = getenv("KARANTA_GEMM_STAGGER");
-    const int stagger = senv ? atoi(senv) : 0;
+    const int group_m = c.tune.group_m_for(tiles_n);
 #ifdef KR_GEMM_PERSIST_EXPERIMENT
-    // experiment build (tools/build_variant.py persist kr_gemm.hip -DKR_GEMM_PERSIST_EXPERIMENT): KARANTA_GEMM_PERSIST=0 (read per
-    // call: A/B, tests) selects the product launch in the same library
-    const char* penv = getenv("KARANTA_GEMM_PERSIST");
-    const bool persist = (penv ? atoi(penv) != 0 : true) && nwg > kr_cu_count();
-    if (persist)
-        gemm_pipe_kernel<EPI, WPACK, W8, A8, true><<<(unsigned)kr_cu_count(), 512, LDS + 8 * 4096, kr_hs(s)>>>(
-            A, lda, W, bias, R, ldr, C, ldc, M, N, K, tiles_n, (unsigned)nwg, w_scale, group_m, a_scale, 0);
+    if (c.tune.persist && nwg > kr_cu_count())
+        gemm_pipe_kernel<EPI, WPACK, W8, A8, true><<<(unsigned)kr_cu_count(), 512, LDS + 8 * 4096, kr_hs(c.s)>>>(
+            c.A, c.lda, c.W, c.bias, c.R, c.ldr, c.C, c.ldc, c.M, c.N, c.K, tiles_n, (unsigned)nwg, c.w_scale, group_m, c.a_scale, 0);
     else
 #endif
-        gemm_pipe_kernel<EPI, WPACK, W8, A8><<<(unsigned)nwg, 512, LDS, kr_hs(s)>>>(A, lda, W, bias, R, ldr, C, ldc, M, N, K, tiles_n,
-                                                                                    (unsigned)nwg, w_scale, group_m, a_scale, stagger);
+        gemm_pipe_kernel<EPI, WPACK, W8, A8><<<(unsigned)nwg, 512, LDS, kr_hs(c.s)>>>(
+            c.A, c.lda, c.W, c.bias, c.R, c.ldr, c.C, c.ldc, c.M, c.N, c.K, tiles_n, (unsigned)nwg, c.w_scale, group_m, c.a_scale,
+            c.tune.stagger);
     KR_CHECK_LAUNCH();
     if constexpr (!W8) {
-        if (tail)
-            return launch_gemm_tail<EPI, WPACK>(A, lda, W, bias, R, ldr, C, ldc, M, N, K, tiles_n, (unsigned)nwg, tail, group_m, s);
+        if (tail) return launch_gemm_tail<EPI, WPACK>(c, tiles_n, (unsigned)nwg, tail, group_m);
     }
     return KR_OK;
 }
 
-inline int kr_cu_count();
-
-constexpr bool MX_TWO_DEFAULT = false;   // set by measurement (profiles/r03_fp8_gemm_bench.txt)
-
 template <int EPI>
-int launch_gemm_pipe_mx(const uint8_t* A8, int64_t lda, const uint8_t* W8, const kr_bf16* bias, const kr_bf16* R, int64_t ldr, kr_bf16* C,
-                        int64_t ldc, int64_t M, int N, int K, kr_stream s, const float* w_scale, const float* a_scale) {
+int launch_gemm_pipe_mx(const GemmCall& c) {
     constexpr int LDS = 4 * 32768;
-    const int64_t tiles_m = (M + 255) / 256;
-    const int tiles_n = (N + 255) / 256;
+    const int64_t tiles_m = (c.M + 255) / 256;
+    const int tiles_n = (c.N + 255) / 256;
     const int64_t nwg = tiles_m * tiles_n;
     KR_CHECK_ARG(nwg < (1ll << 31), "kr_gemm_fp8a: grid too large");
     static KrPerDeviceOnce attr_set;
@@ -1142,139 +1232,42 @@ int launch_gemm_pipe_mx(const uint8_t* A8, int64_t lda, const uint8_t* W8, const
         KR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pipe_mx_kernel<EPI, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         KR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pipe_mx_kernel<EPI, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
     }
-    const char* genv = getenv("KARANTA_GEMM_GROUP_M");
-    const int group_m = genv ? atoi(genv) : (tiles_n >= 8 ? 8 : 1);
-    const char* tenv = getenv("KARANTA_FP8_MX2");   // 1: two K-tiles per barrier pair where K % 128 == 0 (A/B, tests flip it)
-    const bool two = (tenv ? atoi(tenv) != 0 : MX_TWO_DEFAULT) && (K % 128) == 0;
-    if (two)
-        gemm_pipe_mx_kernel<EPI, true><<<(unsigned)nwg, 512, LDS, kr_hs(s)>>>(A8, lda, W8, bias, R, ldr, C, ldc, M, N, K, tiles_n, (unsigned)nwg,
-                                                                              w_scale, group_m, a_scale);
-    else
-        gemm_pipe_mx_kernel<EPI, false><<<(unsigned)nwg, 512, LDS, kr_hs(s)>>>(A8, lda, W8, bias, R, ldr, C, ldc, M, N, K, tiles_n, (unsigned)nwg,
-                                                                               w_scale, group_m, a_scale);
+    const auto fn = (c.tune.mx2 && (c.K % 128) == 0) ? &gemm_pipe_mx_kernel<EPI, true> : &gemm_pipe_mx_kernel<EPI, false>;
+    fn<<<(unsigned)nwg, 512, LDS, kr_hs(c.s)>>>(reinterpret_cast<const uint8_t*>(c.A), c.lda, reinterpret_cast<const uint8_t*>(c.W), c.bias,
+                                                c.R, c.ldr, c.C, c.ldc, c.M, c.N, c.K, tiles_n, (unsigned)nwg, c.w_scale,
+                                                c.tune.group_m_for(tiles_n), c.a_scale);
     KR_CHECK_LAUNCH();
     return KR_OK;
 }
 
-template <int EPI, bool WPACK, typename G, int STAGES>
-int launch_gemm_kernel(unsigned nwg, const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_bf16* bias, const kr_bf16* R,
-                       int64_t ldr, kr_bf16* C, int64_t ldc, int64_t M, int N, int K, int tiles_n, int ptiles_n, unsigned qbase,
-                       int group_m, kr_stream s, int ksplit = 1, int ks_mode = 0, float* ws = nullptr) {
-    constexpr int LDS = STAGES * (G::BM + G::BN) * BK * 2;
-    static KrPerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        KR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<EPI, WPACK, G, STAGES>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    }
-    gemm_kernel<EPI, WPACK, G, STAGES><<<nwg, G::WM * G::WN * 64, LDS, kr_hs(s)>>>(A, lda, W, bias, R, ldr, C, ldc, M, N, K, tiles_n,
-                                                                                  nwg, ptiles_n, qbase, group_m, ksplit, ks_mode, ws);
-    KR_CHECK_LAUNCH();
-    return KR_OK;
-}
-
-// 128x128 launches of at most one workgroup per CU take the 4-deep ring (see gemm_kernel); KARANTA_GEMM_STAGES=2 forces
-// the two-buffer form (A/B, tests).
-inline bool gemm_deep_ring(int64_t nwg) {
-    const char* env = getenv("KARANTA_GEMM_STAGES");
-    if (env) return atoi(env) == 4;
-    return nwg <= kr_cu_count();
-}
-
-template <int EPI, bool WPACK, typename G>
-int launch_gemm3(const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_bf16* bias, const kr_bf16* R, int64_t ldr,
-                 kr_bf16* C, int64_t ldc, int64_t M, int N, int K, kr_stream s) {
-    const int64_t tiles_m = (M + G::BM - 1) / G::BM;
-    const int tiles_n = (N + G::BN - 1) / G::BN;
-    const int64_t nwg = tiles_m * tiles_n;
-    KR_CHECK_ARG(nwg < (1ll << 31), "kr_gemm_bf16: grid too large");
-    if constexpr (G::BM == 128) {
-        if (gemm_deep_ring(nwg))
-            return launch_gemm_kernel<EPI, WPACK, G, 4>((unsigned)nwg, A, lda, W, bias, R, ldr, C, ldc, M, N, K, tiles_n, 0, 0u, 0, s);
-    }
-    return launch_gemm_kernel<EPI, WPACK, G, 2>((unsigned)nwg, A, lda, W, bias, R, ldr, C, ldc, M, N, K, tiles_n, 0, 0u, 0, s);
-}
-
-// Split-K scratch of the tail launches: CALLER-OWNED (kr_gemm_bf16_ws: 128x128 f32 per partial workgroup, KR_GEMM_SCRATCH_BYTES in
-// all).  The library allocates nothing: a call without scratch (kr_gemm_bf16) runs its tail unsplit, a call with scratch splits
-// it — the same call gives the same bits whatever ran before it, in a stream capture or not (the lazily
-// allocated per-stream scratch made the accumulation order depend on call history).  The scratch of the current entry-point
-// call, valid only while that call is on this thread's stack:
-constexpr int TAIL_MAX_WGS = 512, TAIL_WG_BYTES = 256 * 16 * 16;   // 128x128 f32 per workgroup
-static_assert((size_t)TAIL_MAX_WGS * TAIL_WG_BYTES == KR_GEMM_SCRATCH_BYTES, "karanta_hip.h: KR_GEMM_SCRATCH_BYTES");
-static thread_local float* t_call_scratch = nullptr;
-struct CallScratch {
-    explicit CallScratch(float* p) { t_call_scratch = p; }
-    ~CallScratch() { t_call_scratch = nullptr; }
-};
-
-// The quarters of the 256x256 tiles [tile0, tile0 + n_tiles) of a launch_gemm_pipe tile list, as 128x128 workgroups; with a
-// long K (>= 4096) and few tail tiles each quarter is cut into K ranges (partials launch + reduce-and-epilogue launch, see
-// gemm_kernel) so that the tail's bytes are pulled by ~256-512 workgroups instead of 4 per tail tile.
 template <int EPI, bool WPACK>
-int launch_gemm_tail(const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_bf16* bias, const kr_bf16* R, int64_t ldr,
-                     kr_bf16* C, int64_t ldc, int64_t M, int N, int K, int ptiles_n, unsigned tile0, unsigned n_tiles, int group_m,
-                     kr_stream s) {
-    const unsigned nq = 4 * n_tiles;
-    const char* env = getenv("KARANTA_GEMM_TAIL_KSPLIT");   // 0 / 1: never split (A/B, tests); n: at most n ranges
-    const int cap = env ? atoi(env) : 16;
-    int ksplit = 1;
-    // one round of workgroups (4-deep ring: one per CU), at least 8 K steps each
-    if (cap > 1 && K >= 4096) ksplit = std::max(1, std::min(std::min(cap, (K / BK) / 8), (int)(kr_cu_count() / nq)));
-    float* ws = (ksplit > 1 && nq * (unsigned)ksplit <= (unsigned)TAIL_MAX_WGS) ? t_call_scratch : nullptr;
-    if (ws) {
-        int rc = launch_gemm_kernel<EPI, WPACK, G128, 4>(nq * ksplit, A, lda, W, bias, R, ldr, C, ldc, M, N, K, 1, ptiles_n, tile0,
-                                                         group_m, s, ksplit, 1, ws);
-        if (rc != KR_OK) return rc;
-        return launch_gemm_kernel<EPI, WPACK, G128, 2>(nq, A, lda, W, bias, R, ldr, C, ldc, M, N, K, 1, ptiles_n, tile0, group_m, s,
-                                                       ksplit, 2, ws);
+int launch_gemm2(const GemmCall& c) {
+    int tile = c.tune.tile;
+    if (tile != 128 && tile != 256 && tile != 512) {
+        // the 256x256 tile (pipelined kernel) wants about one workgroup per CU or more and no N padding; measured on the
+        // ViT / prefill / merger shapes (gemm_microbench.py) it beats the 128x128 tile by 10-40 % from 234 workgroups up
+        const int64_t wgs = ((c.M + 255) / 256) * ((c.N + 255) / 256);
+        tile = (wgs >= 192 && c.N % 256 == 0) ? 512 : 128;
     }
-    if (gemm_deep_ring(nq))
-        return launch_gemm_kernel<EPI, WPACK, G128, 4>(nq, A, lda, W, bias, R, ldr, C, ldc, M, N, K, 1, ptiles_n, tile0, group_m, s);
-    return launch_gemm_kernel<EPI, WPACK, G128, 2>(nq, A, lda, W, bias, R, ldr, C, ldc, M, N, K, 1, ptiles_n, tile0, group_m, s);
-}
-
-// Compute units of the current device (cached per device): the round size of a one-workgroup-per-CU launch.
-inline int kr_cu_count() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cus[dev] == 0) {
-        int n = 0;
-        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return cus[dev];
-}
-
-// 0 = automatic; 128 / 256 / 512 (= pipelined 256x256) forced by KARANTA_GEMM_TILE (tests, tuning sweeps)
-inline int gemm_tile_choice(int64_t M, int N, int K) {
-    const char* env = getenv("KARANTA_GEMM_TILE");  // read per call: the tests flip it between launches
-    const int forced = env ? atoi(env) : 0;
-    if (forced == 128 || forced == 256 || forced == 512) return forced;   // 512: the pipelined 256x256 kernel
-    // the 256x256 tile (pipelined kernel) wants about one workgroup per CU or more and no N padding; measured on the
-    // ViT / prefill / merger shapes (gemm_microbench.py) it beats the 128x128 tile by 10-40 % from 234 workgroups up
-    const int64_t wgs = ((M + 255) / 256) * ((N + 255) / 256);
-    return (wgs >= 192 && N % 256 == 0) ? 512 : 128;
-}
-
-template <int EPI, bool WPACK>
-int launch_gemm2(const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_bf16* bias, const kr_bf16* R, int64_t ldr,
-                 kr_bf16* C, int64_t ldc, int64_t M, int N, int K, kr_stream s) {
-    int tile = gemm_tile_choice(M, N, K);
     // the 256x256 kernels store C through LDS as 16-byte pieces
-    if ((ldc & 7) != 0 || (reinterpret_cast<uintptr_t>(C) & 15) != 0) tile = 128;
-    if (tile == 512) return launch_gemm_pipe<EPI, WPACK>(A, lda, W, bias, R, ldr, C, ldc, M, N, K, s);
-    if (tile == 256) return launch_gemm3<EPI, WPACK, G256>(A, lda, W, bias, R, ldr, C, ldc, M, N, K, s);
-    return launch_gemm3<EPI, WPACK, G128>(A, lda, W, bias, R, ldr, C, ldc, M, N, K, s);
+    if ((c.ldc & 7) != 0 || (reinterpret_cast<uintptr_t>(c.C) & 15) != 0) tile = 128;
+    if (tile == 512) return launch_gemm_pipe<EPI, WPACK>(c);
+    if (tile == 256) return launch_gemm3<EPI, WPACK, G256>(c);
+    return launch_gemm3<EPI, WPACK, G128>(c);
 }
 
 template <int EPI>
-int launch_gemm(const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_bf16* bias, const kr_bf16* R, int64_t ldr,
-                kr_bf16* C, int64_t ldc, int64_t M, int N, int K, int w_packed, kr_stream s) {
-    return w_packed ? launch_gemm2<EPI, true>(A, lda, W, bias, R, ldr, C, ldc, M, N, K, s)
-                    : launch_gemm2<EPI, false>(A, lda, W, bias, R, ldr, C, ldc, M, N, K, s);
+int launch_gemm(const GemmCall& c, int w_packed) {
+    return w_packed ? launch_gemm2<EPI, true>(c) : launch_gemm2<EPI, false>(c);
 }
 
 }  // namespace
+
+extern "C" int kr_gemm_bf16(const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_bf16* bias,
+                            const kr_bf16* residual, int64_t ldr, kr_bf16* C, int64_t ldc, int64_t M, int N, int K,
+                            int epilogue, int w_packed, kr_stream s) {
+    return kr_gemm_bf16_ws(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, epilogue, w_packed, nullptr, 0, s);
+}
 
 extern "C" int kr_gemm_bf16_ws(const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_bf16* bias,
                                const kr_bf16* residual, int64_t ldr, kr_bf16* C, int64_t ldc, int64_t M, int N, int K,
@@ -1282,13 +1275,6 @@ extern "C" int kr_gemm_bf16_ws(const kr_bf16* A, int64_t lda, const kr_bf16* W, 
     KR_CHECK_ARG(scratch == nullptr || (scratch_bytes >= KR_GEMM_SCRATCH_BYTES && ((uintptr_t)scratch & 15) == 0),
                  "kr_gemm_bf16_ws: scratch of %zu bytes (KR_GEMM_SCRATCH_BYTES = %zu, 16-byte aligned)", scratch_bytes,
                  (size_t)KR_GEMM_SCRATCH_BYTES);
-    CallScratch guard(scratch);
-    return kr_gemm_bf16(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, epilogue, w_packed, s);
-}
-
-extern "C" int kr_gemm_bf16(const kr_bf16* A, int64_t lda, const kr_bf16* W, const kr_bf16* bias,
-                            const kr_bf16* residual, int64_t ldr, kr_bf16* C, int64_t ldc, int64_t M, int N, int K,
-                            int epilogue, int w_packed, kr_stream s) {
     KR_CHECK_ARG(A && W && C, "kr_gemm_bf16: null pointer");
     KR_CHECK_ARG(M >= 0 && N > 0 && K > 0, "kr_gemm_bf16: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
     KR_CHECK_ARG(K % BK == 0, "kr_gemm_bf16: K=%d must be a multiple of %d", K, BK);
@@ -1298,23 +1284,24 @@ extern "C" int kr_gemm_bf16(const kr_bf16* A, int64_t lda, const kr_bf16* W, con
     KR_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)C & 7) == 0,
                  "kr_gemm_bf16: pointer alignment");
     if (M == 0) return KR_OK;
+    const GemmCall c{A, lda, W, bias, residual, ldr, C, ldc, M, N, K, nullptr, nullptr, scratch, s, GemmTuning()};
     switch (epilogue) {
         case KR_EPI_NONE:
             KR_CHECK_ARG(ldc >= N, "kr_gemm_bf16: ldc < N");
-            return launch_gemm<KR_EPI_NONE>(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, w_packed, s);
+            return launch_gemm<KR_EPI_NONE>(c, w_packed);
         case KR_EPI_QUICK_GELU:
             KR_CHECK_ARG(ldc >= N, "kr_gemm_bf16: ldc < N");
-            return launch_gemm<KR_EPI_QUICK_GELU>(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, w_packed, s);
+            return launch_gemm<KR_EPI_QUICK_GELU>(c, w_packed);
         case KR_EPI_GELU_ERF:
             KR_CHECK_ARG(ldc >= N, "kr_gemm_bf16: ldc < N");
-            return launch_gemm<KR_EPI_GELU_ERF>(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, w_packed, s);
+            return launch_gemm<KR_EPI_GELU_ERF>(c, w_packed);
         case KR_EPI_SILU_MUL:
             KR_CHECK_ARG(N % 32 == 0 && ldc >= N / 2 && !bias && !residual,
                          "kr_gemm_bf16: SILU_MUL needs N%%32==0, no bias/residual");
-            return launch_gemm<KR_EPI_SILU_MUL>(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, w_packed, s);
+            return launch_gemm<KR_EPI_SILU_MUL>(c, w_packed);
         case KR_EPI_SILU_MUL8:
             KR_CHECK_ARG(ldc >= N / 2 && !residual, "kr_gemm_bf16: SILU_MUL8 takes no residual");
-            return launch_gemm<KR_EPI_SILU_MUL8>(A, lda, W, bias, residual, ldr, C, ldc, M, N, K, w_packed, s);
+            return launch_gemm<KR_EPI_SILU_MUL8>(c, w_packed);
         default:
             kr_set_error("kr_gemm_bf16: unknown epilogue %d", epilogue);
             return KR_ERR_ARG;
@@ -1399,22 +1386,16 @@ extern "C" int kr_gemm_fp8a(const uint8_t* A8, int64_t lda, const float* a_scale
     KR_CHECK_ARG(((uintptr_t)A8 & 15) == 0 && ((uintptr_t)w_packed_fp8 & 15) == 0 && ((uintptr_t)w_scale & 15) == 0,
                  "kr_gemm_fp8a: pointer alignment");
     if (M == 0) return KR_OK;
-    const kr_bf16* Ap = reinterpret_cast<const kr_bf16*>(A8);
-    const kr_bf16* Wp = reinterpret_cast<const kr_bf16*>(w_packed_fp8);
-    // KARANTA_FP8_MX (read per call: the tests flip it): 1 (default) = the block-scaled instruction v_mfma_scale_f32_32x32x64_f8f6f4
-    // (twice the bf16 rate); 0 = v_mfma_f32_16x16x32_fp8_fp8 in the bf16 kernel's pipeline (the bf16 rate).  Same products
-    // (exact in f32), another summation order.
-    const char* mxe = getenv("KARANTA_FP8_MX");
-    const bool mx = !(mxe && atoi(mxe) == 0) && N % 32 == 0;
+    const GemmCall c{reinterpret_cast<const kr_bf16*>(A8), lda, reinterpret_cast<const kr_bf16*>(w_packed_fp8), bias, residual, ldr, C, ldc,
+                     M, N, K, w_scale, a_scale, nullptr, s, GemmTuning()};
+    const bool mx = c.tune.mx && N % 32 == 0;
     switch (epilogue) {
         case KR_EPI_NONE:
             KR_CHECK_ARG(ldc >= N, "kr_gemm_fp8a: ldc < N");
-            if (mx) return launch_gemm_pipe_mx<KR_EPI_NONE>(A8, lda, w_packed_fp8, bias, residual, ldr, C, ldc, M, N, K, s, w_scale, a_scale);
-            return launch_gemm_pipe<KR_EPI_NONE, true, true, true>(Ap, lda, Wp, bias, residual, ldr, C, ldc, M, N, K, s, w_scale, a_scale);
+            return mx ? launch_gemm_pipe_mx<KR_EPI_NONE>(c) : launch_gemm_pipe<KR_EPI_NONE, true, true, true>(c);
         case KR_EPI_SILU_MUL8:
             KR_CHECK_ARG(ldc >= N / 2 && !residual, "kr_gemm_fp8a: SILU_MUL8 takes no residual");
-            if (mx) return launch_gemm_pipe_mx<KR_EPI_SILU_MUL8>(A8, lda, w_packed_fp8, bias, residual, ldr, C, ldc, M, N, K, s, w_scale, a_scale);
-            return launch_gemm_pipe<KR_EPI_SILU_MUL8, true, true, true>(Ap, lda, Wp, bias, residual, ldr, C, ldc, M, N, K, s, w_scale, a_scale);
+            return mx ? launch_gemm_pipe_mx<KR_EPI_SILU_MUL8>(c) : launch_gemm_pipe<KR_EPI_SILU_MUL8, true, true, true>(c);
         default:
             kr_set_error("kr_gemm_fp8a: epilogue %d (NONE and SILU_MUL8 only: the decoder's prefill linears)", epilogue);
             return KR_ERR_ARG;
@@ -1433,14 +1414,15 @@ extern "C" int kr_gemm_fp8(const kr_bf16* A, int64_t lda, const uint8_t* w_packe
     KR_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)w_packed_fp8 & 15) == 0 && ((uintptr_t)w_scale & 15) == 0,
                  "kr_gemm_fp8: pointer alignment");
     if (M == 0) return KR_OK;
-    const kr_bf16* Wp = reinterpret_cast<const kr_bf16*>(w_packed_fp8);
+    const GemmCall c{A, lda, reinterpret_cast<const kr_bf16*>(w_packed_fp8), bias, residual, ldr, C, ldc, M, N, K, w_scale, nullptr, nullptr,
+                     s, GemmTuning()};
     switch (epilogue) {
         case KR_EPI_NONE:
             KR_CHECK_ARG(ldc >= N, "kr_gemm_fp8: ldc < N");
-            return launch_gemm_pipe<KR_EPI_NONE, true, true>(A, lda, Wp, bias, residual, ldr, C, ldc, M, N, K, s, w_scale);
+            return launch_gemm_pipe<KR_EPI_NONE, true, true>(c);
         case KR_EPI_SILU_MUL8:
             KR_CHECK_ARG(ldc >= N / 2 && !residual, "kr_gemm_fp8: SILU_MUL8 takes no residual");
-            return launch_gemm_pipe<KR_EPI_SILU_MUL8, true, true>(A, lda, Wp, bias, residual, ldr, C, ldc, M, N, K, s, w_scale);
+            return launch_gemm_pipe<KR_EPI_SILU_MUL8, true, true>(c);
         default:
             kr_set_error("kr_gemm_fp8: epilogue %d (NONE and SILU_MUL8 only: the decoder's prefill linears)", epilogue);
             return KR_ERR_ARG;
@@ -1627,22 +1609,33 @@ __global__ void __launch_bounds__(256) gemv_kernel(const kr_bf16* __restrict__ x
     }
 }
 
-template <int NT, int EPI, bool XLDS, bool OUTF32>
-int launch_gemv(const kr_bf16* x, int64_t ldx, const kr_bf16* W, const kr_bf16* bias, const kr_bf16* R, int64_t ldr,
-                kr_bf16* out, float* outf, int64_t ldc, int M, int N, int K, const kr_bf16* norm_w, float eps,
-                kr_stream s) {
-    const int grid = (N + NT * 16 - 1) / (NT * 16);
-    const size_t xbytes = XLDS ? (((size_t)M * (K * 2 + 16) + 127) & ~(size_t)127) : 0;
+struct GemvCall {   // one kr_gemv_bf16 call, in its argument order
+    const kr_bf16* x;
+    int64_t ldx;
+    const kr_bf16 *W, *bias, *R;
+    int64_t ldr;
+    kr_bf16* out;
+    float* outf;
+    int64_t ldc;
+    int M, N, K;
+    const kr_bf16* norm_w;
+    float eps;
+    kr_stream s;
+};
+
+template <int NT, int EPI, bool OUTF32>
+int launch_gemv(const GemvCall& c, bool xlds) {
+    const int grid = (c.N + NT * 16 - 1) / (NT * 16);
+    const size_t xbytes = xlds ? (((size_t)c.M * (c.K * 2 + 16) + 127) & ~(size_t)127) : 0;
     const size_t lds = xbytes + (size_t)4 * NT * 256 * 4 + 64;
     KR_CHECK_ARG(lds <= 160 * 1024, "kr_gemv_bf16: LDS %zu too large", lds);
-    auto fn = &gemv_kernel<NT, EPI, XLDS, OUTF32>;
-    static size_t max_set = 0;
-    if (lds > 48 * 1024 && lds > max_set) {
-        KR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         160 * 1024));
-        max_set = 160 * 1024;
+    static KrPerDeviceOnce attr_set;
+    if (attr_set.need()) {   // x in LDS can take more than 48 KiB; the other form never does
+        KR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_kernel<NT, EPI, true, OUTF32>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
-    fn<<<grid, 256, lds, kr_hs(s)>>>(x, ldx, W, bias, R, ldr, out, outf, ldc, M, N, K, norm_w, eps);
+    const auto fn = xlds ? &gemv_kernel<NT, EPI, true, OUTF32> : &gemv_kernel<NT, EPI, false, OUTF32>;
+    fn<<<grid, 256, lds, kr_hs(c.s)>>>(c.x, c.ldx, c.W, c.bias, c.R, c.ldr, c.out, c.outf, c.ldc, c.M, c.N, c.K, c.norm_w, c.eps);
     KR_CHECK_LAUNCH();
     return KR_OK;
 }
@@ -1660,12 +1653,10 @@ extern "C" int kr_gemv_bf16(const kr_bf16* x, int64_t ldx, const kr_bf16* W, con
     KR_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)W & 15) == 0, "kr_gemv_bf16: pointer alignment");
     const bool xlds = (size_t)M * (K * 2 + 16) <= 148 * 1024;
     KR_CHECK_ARG(!norm_w || xlds, "kr_gemv_bf16: fused RMSNorm needs M*(2K+16) <= 148 KiB of LDS (M=%d K=%d)", M, K);
+    const GemvCall c{x, ldx, W, bias, residual, ldr, out, out_f32, ldc, M, N, K, norm_w, norm_eps, s};
     if (epilogue == KR_EPI_SILU_MUL) {
         KR_CHECK_ARG(N % 32 == 0 && !bias && !residual && out && !out_f32 && ldc >= N / 2, "kr_gemv_bf16: SILU_MUL args");
-        return xlds ? launch_gemv<2, KR_EPI_SILU_MUL, true, false>(x, ldx, W, bias, residual, ldr, out, out_f32, ldc, M, N,
-                                                                   K, norm_w, norm_eps, s)
-                    : launch_gemv<2, KR_EPI_SILU_MUL, false, false>(x, ldx, W, bias, residual, ldr, out, out_f32, ldc, M,
-                                                                    N, K, norm_w, norm_eps, s);
+        return launch_gemv<2, KR_EPI_SILU_MUL, false>(c, xlds);
     }
     KR_CHECK_ARG(epilogue == KR_EPI_NONE, "kr_gemv_bf16: epilogue %d not supported for M<=16", epilogue);
     KR_CHECK_ARG(ldc >= N, "kr_gemv_bf16: ldc < N");
@@ -1673,23 +1664,7 @@ extern "C" int kr_gemv_bf16(const kr_bf16* x, int64_t ldx, const kr_bf16* W, con
     const bool wide = N >= 16 * 2 * 512;
     if (out_f32) {
         KR_CHECK_ARG(!residual, "kr_gemv_bf16: fp32 output has no residual path");
-        if (wide)
-            return xlds ? launch_gemv<2, KR_EPI_NONE, true, true>(x, ldx, W, bias, residual, ldr, out, out_f32, ldc, M, N, K,
-                                                                  norm_w, norm_eps, s)
-                        : launch_gemv<2, KR_EPI_NONE, false, true>(x, ldx, W, bias, residual, ldr, out, out_f32, ldc, M, N,
-                                                                   K, norm_w, norm_eps, s);
-        return xlds ? launch_gemv<1, KR_EPI_NONE, true, true>(x, ldx, W, bias, residual, ldr, out, out_f32, ldc, M, N, K,
-                                                              norm_w, norm_eps, s)
-                    : launch_gemv<1, KR_EPI_NONE, false, true>(x, ldx, W, bias, residual, ldr, out, out_f32, ldc, M, N, K,
-                                                               norm_w, norm_eps, s);
+        return wide ? launch_gemv<2, KR_EPI_NONE, true>(c, xlds) : launch_gemv<1, KR_EPI_NONE, true>(c, xlds);
     }
-    if (wide)
-        return xlds ? launch_gemv<2, KR_EPI_NONE, true, false>(x, ldx, W, bias, residual, ldr, out, out_f32, ldc, M, N, K,
-                                                               norm_w, norm_eps, s)
-                    : launch_gemv<2, KR_EPI_NONE, false, false>(x, ldx, W, bias, residual, ldr, out, out_f32, ldc, M, N, K,
-                                                                norm_w, norm_eps, s);
-    return xlds ? launch_gemv<1, KR_EPI_NONE, true, false>(x, ldx, W, bias, residual, ldr, out, out_f32, ldc, M, N, K,
-                                                           norm_w, norm_eps, s)
-                : launch_gemv<1, KR_EPI_NONE, false, false>(x, ldx, W, bias, residual, ldr, out, out_f32, ldc, M, N, K,
-                                                            norm_w, norm_eps, s);
+    return wide ? launch_gemv<2, KR_EPI_NONE, false>(c, xlds) : launch_gemv<1, KR_EPI_NONE, false>(c, xlds);
 }

@@ -185,7 +185,7 @@ def ref_linear(A, W, bias=None, res=None, epi=EPI_NONE):
 _GEMM_SCRATCH = None
 
 
-def run_gemm(L, A, W, bias=None, res=None, epi=EPI_NONE, lda_pad=0, packed=False):
+def run_gemm(L, A, W, bias=None, res=None, epi=EPI_NONE, lda_pad=0, packed=False, scratch=True):
     M, K = A.shape
     N = W.shape[0]
     Ad = dev_bf16(np.concatenate([A, np.zeros((M, lda_pad), np.float32)], 1)) if lda_pad else dev_bf16(A)
@@ -198,8 +198,12 @@ def run_gemm(L, A, W, bias=None, res=None, epi=EPI_NONE, lda_pad=0, packed=False
     global _GEMM_SCRATCH
     if _GEMM_SCRATCH is None:
         _GEMM_SCRATCH = torch.zeros(512 * 65536 // 4, dtype=torch.float32, device=DEV)
-    L.kr_gemm_bf16_ws(ptr(Ad), K + lda_pad, ptr(Wd), ptr(bd), ptr(rd), nc if res is not None else 0, ptr(Cd), nc, M, N, K,
-                      epi, 1 if packed else 0, ptr(_GEMM_SCRATCH), _GEMM_SCRATCH.numel() * 4, 0)
+    if scratch:
+        L.kr_gemm_bf16_ws(ptr(Ad), K + lda_pad, ptr(Wd), ptr(bd), ptr(rd), nc if res is not None else 0, ptr(Cd), nc, M, N, K,
+                          epi, 1 if packed else 0, ptr(_GEMM_SCRATCH), _GEMM_SCRATCH.numel() * 4, 0)
+    else:       # kr_gemm_bf16: no scratch, the tail is never cut along K
+        L.kr_gemm_bf16(ptr(Ad), K + lda_pad, ptr(Wd), ptr(bd), ptr(rd), nc if res is not None else 0, ptr(Cd), nc, M, N, K,
+                       epi, 1 if packed else 0, 0)
     return host(Cd)
 
 
@@ -310,8 +314,14 @@ def test_gemm_tail_round_as_quarter_tiles(L, M, N, K, epi, packed):
         os.environ.pop("KARANTA_GEMM_TAIL", None)
         for _ in range(3):      # reproducible: nothing depends on which workgroup finishes first
             np.testing.assert_array_equal(got, run_gemm(L, A, W, bias, res, epi, packed=packed))
+        # right after a call with scratch (its tail split along K), the same operands without: a call's bits do not depend
+        # on the call before it
+        bare = run_gemm(L, A, W, bias, res, epi, packed=packed, scratch=False) if K == 4480 else None
         os.environ["KARANTA_GEMM_TAIL_KSPLIT"] = "1"       # the unsplit tail
-        assert (run_gemm(L, A, W, bias, res, epi, packed=packed) != one).mean() < 1e-5
+        unsplit = run_gemm(L, A, W, bias, res, epi, packed=packed)
+        assert (unsplit != one).mean() < 1e-5
+        if bare is not None:
+            np.testing.assert_array_equal(bare, unsplit)
         rows = np.r_[0:300, M - 600:M]          # the head and the tail tiles' rows against the host reference
         assert_close_bf16(got[rows], ref_linear(A[rows], W, bias, None if res is None else res[rows], epi), what="tail split")
     finally:
