@@ -255,7 +255,6 @@ class PageRequest:
     presence_penalty: float = 0.0              # l -= presence_penalty * (count > 0)
 
 
-
 @dataclass
 class GenerateResult:
     tokens: List[np.ndarray]          # per page: generated ids (EOS included, nothing after it)
@@ -274,6 +273,62 @@ class DeviceGuide:
     def __init__(self, guide, trans: torch.Tensor, masks: torch.Tensor):
         self.guide, self.trans, self.masks = guide, trans, masks
         self.start = int(guide.start)
+
+
+@dataclass
+class DevicePlan:
+    """A positions.AttnPlan whose six work lists are resident in HBM (what kr_qkv_prep / kr_attn_varlen_q read)."""
+    host: POS.AttnPlan
+    blk_tok0: torch.Tensor
+    blk_ntok: torch.Tensor
+    blk_kr: torch.Tensor
+    blk_vb: torch.Tensor
+    qblk: torch.Tensor
+    qlen: torch.Tensor
+    n_blk: int
+
+
+def device_plan(plan: POS.AttnPlan, dev: torch.device) -> DevicePlan:
+    t_ = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    return DevicePlan(plan, t_(plan.blk_tok0), t_(plan.blk_ntok), t_(plan.blk_k_row0), t_(plan.blk_vt_blk), t_(plan.qblk),
+                      t_(plan.qblk_len), len(plan.blk_tok0))
+
+
+@dataclass
+class VitTables:
+    """What the vision tower needs per batch geometry (Engine._vit_tables): rotary tables (Qwen2.5-VL: in window order) and the
+    whole-image attention plan; Qwen2.5-VL also the window-order gather / its inverse and the window attention plan."""
+    cos: torch.Tensor
+    sin: torch.Tensor
+    full: DevicePlan
+    perm: Optional[torch.Tensor] = None
+    inv: Optional[torch.Tensor] = None
+    win: Optional[DevicePlan] = None
+
+
+@dataclass
+class Admission:
+    """One admission — a whole batch (`generate`) or new requests for some slots — from the host tables
+    (Engine._prefill_prepare) over the sampling state (Engine.prefill) to the activation of its sequences."""
+    B: int
+    slots: List[int]
+    whole_batch: bool
+    lens: List[int]
+    M: int
+    src: np.ndarray          # int32 [M]: token id, or -(image row + 1)
+    cos: np.ndarray          # fp32 [M, head_dim] M-RoPE tables of the prompts
+    sin: np.ndarray
+    deltas: np.ndarray       # int32 [max_batch]
+    plan: POS.AttnPlan
+    last_rows: np.ndarray    # int32 [B]: row of every prompt's last token
+    cs: np.ndarray           # fp32 [B, max_new, head_dim] rotary table of the decode positions
+    n_img: int
+    # added by prefill: what the sampler keeps per sequence
+    temps: Optional[np.ndarray] = None
+    seeds: Optional[np.ndarray] = None
+    guides: Optional[list] = None      # Engine._guide_rows
+    procs: Optional[list] = None       # Engine._control_rows
+    need: StepFeatures = StepFeatures()
 
 
 class Engine:
@@ -620,14 +675,13 @@ class Engine:
         dst.view(-1)[:src.numel()].copy_(src.view(-1), non_blocking=False)
 
     # ------------------------------------------------------------------ vision tower
-    def _vit_tables(self, grids):
+    def _vit_tables(self, grids) -> VitTables:
         """Rotary tables and attention work lists depend only on the image grids: build once per
         distinct batch geometry and keep them resident in HBM."""
         key = tuple(tuple(int(x) for x in g) for g in grids)
         hit = self._vit_cache.get(key)
         if hit is None:
             v, dev = self.cfg.vision, self.device
-            plan = POS.vit_attn_plan(key)
             t_ = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
             # the rotary tables of an image depend on its own grid only: kept per grid, so that a batch of a new COMPOSITION (every
             # admission of a corpus with mixed page sizes) costs a concatenation on the device, not ~0.7 ms of numpy per page with the
@@ -644,9 +698,7 @@ class Engine:
                 per_img.append(hit_i)
             cos = per_img[0][0] if len(per_img) == 1 else torch.cat([c for c, _ in per_img])
             sin = per_img[0][1] if len(per_img) == 1 else torch.cat([s_ for _, s_ in per_img])
-            dplan = lambda pl: (pl, t_(pl.blk_tok0), t_(pl.blk_ntok), t_(pl.blk_k_row0), t_(pl.blk_vt_blk), t_(pl.qblk),
-                                t_(pl.qblk_len))
-            extra = None
+            hit = VitTables(cos, sin, device_plan(POS.vit_attn_plan(key), dev))
             if v.variant == "qwen2_5":
                 # window order (TF25:430-446): patches move in groups of merge^2; rotary tables move with them;
                 # two attention work lists: windows, and whole images for the fullatt_block_indexes blocks
@@ -654,10 +706,9 @@ class Engine:
                 order, win_lens = POS.vision_window_order(key, v.spatial_merge_size, v.window_size, v.patch_size)
                 perm = (order[:, None] * unit + np.arange(unit)[None, :]).reshape(-1)      # patch-level gather
                 perm_long = t_(perm.astype(np.int64))
-                cos, sin = cos.index_select(0, perm_long), sin.index_select(0, perm_long)
-                extra = (t_(perm.astype(np.int32)), t_(np.argsort(order).astype(np.int32)), dplan(POS.segments_attn_plan(win_lens)))
-            hit = (plan, cos, sin, t_(plan.blk_tok0), t_(plan.blk_ntok), t_(plan.blk_k_row0),
-                   t_(plan.blk_vt_blk), t_(plan.qblk), t_(plan.qblk_len), extra)
+                hit.cos, hit.sin = cos.index_select(0, perm_long), sin.index_select(0, perm_long)
+                hit.perm, hit.inv = t_(perm.astype(np.int32)), t_(np.argsort(order).astype(np.int32))
+                hit.win = device_plan(POS.segments_attn_plan(win_lens), dev)
             if len(self._vit_cache) > 16:
                 self._vit_cache.clear()
             self._vit_cache[key] = hit
@@ -732,7 +783,7 @@ class Engine:
                 off += n
         return out, grids
 
-    def _pixels_for(self, pages: Sequence["PageRequest"], pixel_values_device):
+    def _pixels_for(self, pages: Sequence[PageRequest], pixel_values_device):
         """The pixel source of a batch of pages: caller-resident patches, the GPU front end (pages with `images`),
         or the pages' host arrays."""
         if pixel_values_device is not None:
@@ -753,7 +804,7 @@ class Engine:
         return np.concatenate(pvs, 0) if len(pvs) > 1 else pvs[0]
 
     def vit_forward(self, pixel_values, grids: Sequence[Sequence[int]]) -> torch.Tensor:
-        """Qwen2VisionTransformerPretrainedModel.forward (TF:700-731).  ``pixel_values`` is fp32
+        """Qwen2VisionTransformerPretrainedModel.forward (TF:700-731) or its Qwen2.5-VL successor.  ``pixel_values`` is fp32
         ``[n, 1176]`` — a numpy array (copied to the device here) or a torch tensor already resident
         in HBM.  Returns a view of the merged image embeddings ``[T, d]`` (bf16, device)."""
         v, L, s, w = self.cfg.vision, self.L, self.s, self.w
@@ -763,8 +814,8 @@ class Engine:
         if n > self.max_patches:
             raise KarantaHipError(f"{n} patches > max_patches {self.max_patches}")
         with torch.cuda.stream(self.stream):
-            plan, cos_d, sin_d, blk_tok0, blk_ntok, blk_kr, blk_vb, qblk, qlen, extra = self._vit_tables(grids)
-            assert plan.n_tokens == n, (plan.n_tokens, n)
+            tab = self._vit_tables(grids)
+            assert tab.full.host.n_tokens == n, (tab.full.host.n_tokens, n)
             if isinstance(pixel_values, torch.Tensor):
                 pix = pixel_values
                 if pix.dtype != torch.float32 or not pix.is_cuda or not pix.is_contiguous():
@@ -772,74 +823,57 @@ class Engine:
             else:
                 self._h2d(self.v_pix, np.asarray(pixel_values, dtype=np.float32))
                 pix = self.v_pix
-            D, H, hd = v.embed_dim, v.num_heads, v.head_dim
+            D, H, hd, d_out = v.embed_dim, v.num_heads, v.head_dim, self.cfg.text.hidden_size
+            x, h = self.v_x, self.v_h
             L.kr_cast_pad_f32_bf16(ptr(pix), ptr(self.v_in), n, v.patch_dim, v.patch_dim_padded, s)
-            self._gemm(self.v_in, w.view("vit.patch"), self.v_x, n)
-            nvb_total = self.v_vt.shape[1]
-            if plan.n_vt_blocks > nvb_total or (extra is not None and extra[2][0].n_vt_blocks > nvb_total):
+            self._gemm(self.v_in, w.view("vit.patch"), x, n)
+            if max(pl.host.n_vt_blocks for pl in (tab.full, tab.win) if pl is not None) > self.v_vt.shape[1]:
                 raise KarantaHipError("too many image segments for the V^T buffer")
-            if v.variant == "qwen2_5":
-                return self._vit_blocks_qwen2_5(n, (plan, blk_tok0, blk_ntok, blk_kr, blk_vb, qblk, qlen), cos_d, sin_d, extra)
+            # what the variant decides.  Qwen2-VL (TF:700-731): LayerNorm, fc1 / QuickGELU / fc2, attention over whole images.
+            # Qwen2.5-VL (TF25:430-472): RMSNorm, biased SwiGLU, attention inside the windows except in the
+            # fullatt_block_indexes blocks, tokens gathered into window order for the blocks and scattered back after the merger
+            v25 = v.variant == "qwen2_5"
+            if v25:
+                L.kr_embed_scatter(ptr(tab.perm), ptr(x), 0, ptr(h), n, D, s)   # image order -> window order
+                x, h = h, x
+                norm = lambda name: L.kr_rmsnorm(ptr(x), D, ptr(w.view(name + ".w")), ptr(h), n, D, 1e-6, s)
+                up, down, epi = "gate_up", "down", EPI_SILU_MUL8
+            else:
+                norm = lambda name: L.kr_layernorm(ptr(x), ptr(w.view(name + ".w")), ptr(w.view(name + ".b")), ptr(h), n, D, 1e-6, s)
+                up, down, epi = "fc1", "fc2", EPI_QUICK_GELU
             for i in range(v.depth):
                 p = f"vit.{i}."
-                L.kr_layernorm(ptr(self.v_x), ptr(w.view(p + "ln1.w")), ptr(w.view(p + "ln1.b")), ptr(self.v_h), n, D, 1e-6, s)
-                self._gemm(self.v_h, w.view(p + "qkv.w"), self.v_qkv, n, bias=w.view(p + "qkv.b"))
-                L.kr_qkv_prep(ptr(self.v_qkv), 3 * D, 0, D, 2 * D, ptr(cos_d), ptr(sin_d),
-                              ptr(blk_tok0), ptr(blk_ntok), ptr(blk_kr), ptr(blk_vb), len(plan.blk_tok0),
-                              ptr(self.v_q), self.v_q.stride(0), ptr(self.v_k), self.v_k.stride(0),
-                              ptr(self.v_vt), self.v_vt.stride(0), H, H, hd, s)
-                L.kr_attn_varlen_q(ptr(self.v_q), ptr(self.v_k), ptr(self.v_vt), ptr(self.v_o), ptr(qblk), ptr(qlen),
-                                   plan.qblk.shape[0], self.v_q.shape[1], H, H, hd, self.v_k.stride(0),
-                                   self.v_vt.stride(0), hd ** -0.5, 0, plan.q_block, s)
-                self._gemm(self.v_o, w.view(p + "proj.w"), self.v_x, n, bias=w.view(p + "proj.b"), res=self.v_x)
-                L.kr_layernorm(ptr(self.v_x), ptr(w.view(p + "ln2.w")), ptr(w.view(p + "ln2.b")), ptr(self.v_h), n, D, 1e-6, s)
-                self._gemm(self.v_h, w.view(p + "fc1.w"), self.v_f, n, bias=w.view(p + "fc1.b"), epi=EPI_QUICK_GELU)
-                self._gemm(self.v_f, w.view(p + "fc2.w"), self.v_x, n, bias=w.view(p + "fc2.b"), res=self.v_x)
-            # PatchMerger (TF:277-290): LN -> view [n/4, 4D] -> Linear+GELU -> Linear
-            L.kr_layernorm(ptr(self.v_x), ptr(w.view("vit.merger.ln.w")), ptr(w.view("vit.merger.ln.b")), ptr(self.v_h), n, D, 1e-6, s)
+                norm(p + "ln1")
+                self._gemm(h, w.view(p + "qkv.w"), self.v_qkv, n, bias=w.view(p + "qkv.b"))
+                self._attention(self.v_qkv, D, 2 * D, tab.cos, tab.sin, tab.win if v25 and i not in v.fullatt_block_indexes else tab.full,
+                                self.v_q, self.v_k, self.v_k.stride(0), self.v_vt, self.v_vt.stride(0), self.v_o, H, H, hd, causal=False)
+                self._gemm(self.v_o, w.view(p + "proj.w"), x, n, bias=w.view(p + "proj.b"), res=x)
+                norm(p + "ln2")
+                self._gemm(h, w.view(p + up + ".w"), self.v_f, n, bias=w.view(p + up + ".b"), epi=epi)
+                self._gemm(self.v_f, w.view(p + down + ".w"), x, n, bias=w.view(p + down + ".b"), res=x)
+            # PatchMerger (TF:277-290): norm -> view [n/4, 4D] -> Linear+GELU -> Linear
+            norm("vit.merger.ln")
             T = n // (v.spatial_merge_size ** 2)
-            merged_in = self.v_h.view(-1)[: T * v.merge_dim].view(T, v.merge_dim)
+            merged_in = h.view(-1)[: T * v.merge_dim].view(T, v.merge_dim)
             self._gemm(merged_in, w.view("vit.merger.fc1.w"), self.v_m1, T, bias=w.view("vit.merger.fc1.b"), epi=EPI_GELU_ERF)
-            self._gemm(self.v_m1, w.view("vit.merger.fc2.w"), self.img_embeds, T, bias=w.view("vit.merger.fc2.b"))
+            # window order: the second GEMM goes to v_o, then back to image order (reverse_indices, TF25:466-468)
+            out = self.v_o.view(-1)[: T * d_out].view(T, d_out) if v25 else self.img_embeds
+            self._gemm(self.v_m1, w.view("vit.merger.fc2.w"), out, T, bias=w.view("vit.merger.fc2.b"))
+            if v25:
+                L.kr_embed_scatter(ptr(tab.inv), ptr(out), 0, ptr(self.img_embeds), T, d_out, s)
         return self.img_embeds[:T]
 
-    def _vit_blocks_qwen2_5(self, n: int, full, cos_d, sin_d, extra) -> torch.Tensor:
-        """Qwen2_5_VisionTransformerPretrainedModel.forward after the patch embedding (TF25:430-472): tokens gathered
-        into window order, RMSNorm blocks with attention inside the windows (whole images in the
-        fullatt_block_indexes blocks) and the biased SwiGLU MLP, RMSNorm merger, merged tokens scattered back."""
-        v, L, s, w = self.cfg.vision, self.L, self.s, self.w
-        D, H, hd = v.embed_dim, v.num_heads, v.head_dim
-        perm_d, inv_d, win = extra
-        # v_x (image order) -> v_h (window order) -> the blocks run on v_x again
-        L.kr_embed_scatter(ptr(perm_d), ptr(self.v_x), 0, ptr(self.v_h), n, D, s)
-        self.v_x, self.v_h = self.v_h, self.v_x
-        for i in range(v.depth):
-            p = f"vit.{i}."
-            plan, blk_tok0, blk_ntok, blk_kr, blk_vb, qblk, qlen = full if i in v.fullatt_block_indexes else win
-            L.kr_rmsnorm(ptr(self.v_x), D, ptr(w.view(p + "ln1.w")), ptr(self.v_h), n, D, 1e-6, s)
-            self._gemm(self.v_h, w.view(p + "qkv.w"), self.v_qkv, n, bias=w.view(p + "qkv.b"))
-            L.kr_qkv_prep(ptr(self.v_qkv), 3 * D, 0, D, 2 * D, ptr(cos_d), ptr(sin_d),
-                          ptr(blk_tok0), ptr(blk_ntok), ptr(blk_kr), ptr(blk_vb), len(plan.blk_tok0),
-                          ptr(self.v_q), self.v_q.stride(0), ptr(self.v_k), self.v_k.stride(0),
-                          ptr(self.v_vt), self.v_vt.stride(0), H, H, hd, s)
-            L.kr_attn_varlen_q(ptr(self.v_q), ptr(self.v_k), ptr(self.v_vt), ptr(self.v_o), ptr(qblk), ptr(qlen),
-                               plan.qblk.shape[0], self.v_q.shape[1], H, H, hd, self.v_k.stride(0),
-                               self.v_vt.stride(0), hd ** -0.5, 0, plan.q_block, s)
-            self._gemm(self.v_o, w.view(p + "proj.w"), self.v_x, n, bias=w.view(p + "proj.b"), res=self.v_x)
-            L.kr_rmsnorm(ptr(self.v_x), D, ptr(w.view(p + "ln2.w")), ptr(self.v_h), n, D, 1e-6, s)
-            self._gemm(self.v_h, w.view(p + "gate_up.w"), self.v_f, n, bias=w.view(p + "gate_up.b"), epi=EPI_SILU_MUL8)
-            self._gemm(self.v_f, w.view(p + "down.w"), self.v_x, n, bias=w.view(p + "down.b"), res=self.v_x)
-        L.kr_rmsnorm(ptr(self.v_x), D, ptr(w.view("vit.merger.ln.w")), ptr(self.v_h), n, D, 1e-6, s)
-        T = n // (v.spatial_merge_size ** 2)
-        merged_in = self.v_h.view(-1)[: T * v.merge_dim].view(T, v.merge_dim)
-        self._gemm(merged_in, w.view("vit.merger.fc1.w"), self.v_m1, T, bias=w.view("vit.merger.fc1.b"), epi=EPI_GELU_ERF)
-        # second GEMM into v_m1's neighbour, then back to image order (reverse_indices, TF25:466-468)
-        tmp = self.v_o.view(-1)[: T * self.cfg.text.hidden_size].view(T, self.cfg.text.hidden_size)
-        self._gemm(self.v_m1, w.view("vit.merger.fc2.w"), tmp, T, bias=w.view("vit.merger.fc2.b"))
-        L.kr_embed_scatter(ptr(inv_d), ptr(tmp), 0, ptr(self.img_embeds), T, self.cfg.text.hidden_size, s)
-        return self.img_embeds[:T]
+    def _attention(self, qkv, k_off, v_off, cos, sin, dp: DevicePlan, q, k, k_stride, vt, vt_stride, out, H, KVH, hd, causal):
+        """Varlen attention of a fused [rows, q | k | v] buffer: kr_qkv_prep (rotary on q and k; q head-major, k rows and V^T
+        blocks to where the plan says) then kr_attn_varlen_q over the plan's query blocks.  k / vt with their head strides: the
+        ViT's scratch buffers, or a layer of the KV cache."""
+        L, s = self.L, self.s
+        L.kr_qkv_prep(ptr(qkv), qkv.shape[1], 0, k_off, v_off, ptr(cos), ptr(sin),
+                      ptr(dp.blk_tok0), ptr(dp.blk_ntok), ptr(dp.blk_kr), ptr(dp.blk_vb), dp.n_blk,
+                      ptr(q), q.stride(0), ptr(k), k_stride, ptr(vt), vt_stride, H, KVH, hd, s)
+        L.kr_attn_varlen_q(ptr(q), ptr(k), ptr(vt), ptr(out), ptr(dp.qblk), ptr(dp.qlen), dp.host.qblk.shape[0], q.shape[1],
+                           H, KVH, hd, k_stride, vt_stride, hd ** -0.5, 1 if causal else 0, dp.host.q_block, s)
 
-    # ------------------------------------------------------------------ prefill
     # ------------------------------------------------------------------ guided decoding
     def set_vocab(self, token_bytes: Sequence[bytes]):
         """Byte string of every token id (b"" for special tokens) — what a pattern is matched against.  Needed once
@@ -897,6 +931,7 @@ class Engine:
             rows.append((dg.trans.data_ptr(), dg.masks.data_ptr(), dg.start, dg))
         return rows
 
+    # ------------------------------------------------------------------ admission: host tables, prefill, slot state, first tokens
     def _ensure_history(self, max_new_tokens: int):
         """Token history, rotary table and (when asked for) log-prob history sized for max_new_tokens; their
         addresses are baked into captured graphs, so a reallocation drops the graphs."""
@@ -919,7 +954,7 @@ class Engine:
         return self.s_max - (1 if self._freeze_finished else 0)
 
     def _prefill_prepare(self, pages: Sequence[PageRequest], n_image_tokens_total: int, slots: Optional[Sequence[int]] = None,
-                         budgets: Optional[Sequence[int]] = None):
+                         budgets: Optional[Sequence[int]] = None) -> Admission:
         """Host side of `prefill` (numpy only: token sources, M-RoPE tables of the prompt and of every decode position,
         the varlen attention plan).  `generate` runs it while the ViT launches are still executing.
         ``budgets``: per page, the number of tokens it may generate (slot mode: its max_tokens + the scheduler's chunk
@@ -935,14 +970,11 @@ class Engine:
         M = sum(lens)
         if M > self.max_tokens:
             raise KarantaHipError(f"{M} prompt tokens > max_prompt_tokens {self.max_tokens}")
-        room = self.seq_room()
         if budgets is None:
             budgets = [self._req_max_new] * B
         if len(budgets) != B or max(budgets) > self.max_new:
             raise KarantaHipError(f"budgets {list(budgets)} do not fit {B} pages / the history of {self.max_new} tokens")
-        for n, bud in zip(lens, budgets):
-            if n + int(bud) > room:
-                raise KarantaHipError(f"prompt {n} + max_new_tokens {int(bud)} exceeds s_max {room}")
+        self._check_budgets(pages, budgets)
         src = np.empty(M, np.int32)
         cos = np.empty((M, t.head_dim), np.float32)
         sin = np.empty((M, t.head_dim), np.float32)
@@ -976,91 +1008,58 @@ class Engine:
             p1 = lens[b] + kk + int(deltas[b])
             c_, s_ = POS.mrope_tables(np.stack([p1, p1, p1]), t.head_dim, t.rope_theta, t.mrope_section)
             cs[b, :, : t.head_dim // 2], cs[b, :, t.head_dim // 2:] = c_[:, : t.head_dim // 2], s_[:, : t.head_dim // 2]
-        return {"B": B, "whole_batch": whole_batch, "slots": slots, "lens": lens, "M": M, "src": src, "cos": cos, "sin": sin,
-                "deltas": deltas, "plan": plan, "last_rows": last_rows, "cs": cs, "n_img": n_image_tokens_total}
+        return Admission(B, slots, whole_batch, lens, M, src, cos, sin, deltas, plan, last_rows, cs, n_image_tokens_total)
 
-    def prefill(self, pages: Sequence[PageRequest], n_image_tokens_total: int,
-                slots: Optional[Sequence[int]] = None, defer_activation: bool = False, prep=None):
+    def _vit_and_prepare(self, pages: Sequence[PageRequest], pixel_values_device=None, slots: Optional[Sequence[int]] = None,
+                         budgets: Optional[Sequence[int]] = None) -> Admission:
+        """Front of every admission: the pages' images through the ViT (launches only), then the host tables of the prefill
+        while those launches execute."""
+        pix = self._pixels_for(pages, pixel_values_device)
+        n_img_tok = self.vit_forward(pix, [g for p in pages for g in p.grids]).shape[0] if pix is not None else 0
+        return self._prefill_prepare(pages, n_img_tok, slots, budgets)
+
+    def prefill(self, pages: Sequence[PageRequest], n_image_tokens_total: int, slots: Optional[Sequence[int]] = None,
+                defer_activation: bool = False, adm: Optional[Admission] = None) -> Admission:
         """embed+scatter, M-RoPE, 28 x decoder layer over the flattened prompts (causal varlen
-        attention writing the KV cache), last-token logits -> first greedy token.
-        Leaves the decode state (d_x, d_ctx, d_delta, history row 0) ready.  Returns prompt lengths.
+        attention writing the KV cache), last-token logits -> first token.
+        Leaves the decode state (d_x, d_ctx, d_delta, history row 0) ready.  Returns the admission's record (`lens`: the
+        prompt lengths).  ``adm``: what `_prefill_prepare` made of these pages ahead of time.
         ``slots`` (slot scheduler): the cache / state slots the pages go to; only those slots' state is
         touched, the other sequences keep decoding from where they are.  ``defer_activation`` (overlapped
-        admission): only the layers run here (they fill the slots' KV rows); the slot state writes and the first
-        sampling step are returned as a record for `_activate` to apply on the decode stream."""
-        cfg, t, L, s, w, dev = self.cfg, self.cfg.text, self.L, self.s, self.w, self.device
-        if prep is None or prep["n_img"] != n_image_tokens_total:
-            prep = self._prefill_prepare(pages, n_image_tokens_total, slots)
-        need = self._admit_features(pages)
-        B, whole_batch, slots, lens, M = prep["B"], prep["whole_batch"], prep["slots"], prep["lens"], prep["M"]
-        src, cos, sin, deltas, plan, last_rows, cs = (prep[k] for k in ("src", "cos", "sin", "deltas", "plan", "last_rows", "cs"))
+        admission): only the layers run here (they fill the slots' KV rows); `admit_end` applies the slot state writes and
+        the first sampling step from the returned record on the decode stream."""
+        t, L, s, w = self.cfg.text, self.L, self.s, self.w
+        if adm is None or adm.n_img != n_image_tokens_total:
+            adm = self._prefill_prepare(pages, n_image_tokens_total, slots)
+        adm.need = self._admit_features(pages)
+        M, d = adm.M, t.hidden_size
         with torch.cuda.stream(self.stream):
-            self._h2d(self.p_src, src)
-            self._h2d(self.p_cos, cos)
-            self._h2d(self.p_sin, sin)
-            temps = np.asarray([temperature(p) for p in pages], np.float32)
-            seeds = np.asarray([int(getattr(p, "seed", 0) or 0) & 0xFFFFFFFF for p in pages], np.uint32).view(np.int32)
-            grows = self._guide_rows(pages)
-            procs = self._control_rows(pages)
-            if whole_batch:
-                tb, sb = np.zeros(self.B, np.float32), np.zeros(self.B, np.int32)
-                tb[:B], sb[:B] = temps, seeds
-                self._h2d(self.d_temp, tb)
-                self._h2d(self.d_seed, sb)
-                gt, gm, gs = np.zeros(self.B, np.int64), np.zeros(self.B, np.int64), np.zeros(self.B, np.int32)
-                for b, (a_t, a_m, st, dg) in enumerate(grows):
-                    gt[b], gm[b], gs[b] = a_t, a_m, st
-                self._slot_guides = {b: r[3] for b, r in enumerate(grows) if r[3] is not None}
-                self._h2d(self.d_gtrans, gt)
-                self._h2d(self.d_gmasks, gm)
-                self._h2d(self.d_gstate, gs)
-                ctx0 = np.zeros(self.B, np.int32)
-                ctx0[:B] = np.asarray(lens, np.int32) - 1  # kr_sample_greedy adds 1 -> number of cached tokens
-                plen = np.zeros(self.B, np.int32)
-                plen[:B] = lens
-                self._h2d(self.d_delta, deltas)
-                self._h2d(self.d_ctx, ctx0)
-                self._h2d(self.d_plen, plen)
-                self._h2d(self.d_cs, cs)
-                self.d_fin.zero_()
-                if procs is not None:
-                    self._write_processing(list(range(B)), procs)
-            elif not defer_activation:
-                self._write_slot_state(slots, lens, deltas, cs, temps, seeds, grows, procs)
-            self._h2d(self.d_last, last_rows)
-            t_ = lambda a: torch.from_numpy(a).to(dev)
-            blk_tok0, blk_ntok, blk_kr, blk_vb = t_(plan.blk_tok0), t_(plan.blk_ntok), t_(plan.blk_k_row0), t_(plan.blk_vt_blk)
-            qblk, qlen = t_(plan.qblk), t_(plan.qblk_len)
-            d, H, KVH, hd = t.hidden_size, t.num_heads, t.num_kv_heads, t.head_dim
+            self._h2d(self.p_src, adm.src)
+            self._h2d(self.p_cos, adm.cos)
+            self._h2d(self.p_sin, adm.sin)
+            adm.temps = np.asarray([temperature(p) for p in pages], np.float32)
+            adm.seeds = np.asarray([int(getattr(p, "seed", 0) or 0) & 0xFFFFFFFF for p in pages], np.uint32).view(np.int32)
+            adm.guides = self._guide_rows(pages)
+            adm.procs = self._control_rows(pages)
+            if not defer_activation:
+                self._write_state(adm)
+            self._h2d(self.d_last, adm.last_rows)
+            dp = device_plan(adm.plan, self.device)
             L.kr_embed_scatter(ptr(self.p_src), ptr(w.view("llm.embed")), ptr(self.img_embeds), ptr(self.p_x), M, d, s)
-            k_head_stride = self.s_max * hd
-            vt_head_stride = (self.s_max // 64) * hd * 64
             for i in range(t.num_layers):
                 p = f"llm.{i}."
                 L.kr_rmsnorm(ptr(self.p_x), d, ptr(w.view(p + "ln1.w")), ptr(self.p_h), M, d, t.rms_norm_eps, s)
                 self._gemm(self.p_h, w.view(p + "qkv.w"), self.p_qkv, M, bias=w.view(p + "qkv.b"), packed=True, **self._w8kw(p + "qkv.w"))
-                kc, vc = self.kcache[i], self.vtcache[i]
-                L.kr_qkv_prep(ptr(self.p_qkv), t.qkv_dim, 0, t.q_dim, t.q_dim + t.kv_dim, ptr(self.p_cos), ptr(self.p_sin),
-                              ptr(blk_tok0), ptr(blk_ntok), ptr(blk_kr), ptr(blk_vb), len(plan.blk_tok0),
-                              ptr(self.p_q), self.p_q.stride(0), ptr(kc), k_head_stride, ptr(vc), vt_head_stride,
-                              H, KVH, hd, s)
-                L.kr_attn_varlen_q(ptr(self.p_q), ptr(kc), ptr(vc), ptr(self.p_o), ptr(qblk), ptr(qlen),
-                                   plan.qblk.shape[0], self.p_q.shape[1], H, KVH, hd, k_head_stride, vt_head_stride,
-                                   hd ** -0.5, 1, plan.q_block, s)
+                kc, vc = self.kcache[i], self.vtcache[i]       # [max_batch, kv heads, ...]: the plan's rows count from slot 0
+                self._attention(self.p_qkv, t.q_dim, t.q_dim + t.kv_dim, self.p_cos, self.p_sin, dp, self.p_q, kc, kc.stride(1),
+                                vc, vc.stride(1), self.p_o, t.num_heads, t.num_kv_heads, t.head_dim, causal=True)
                 self._gemm(self.p_o, w.view(p + "o.w"), self.p_x, M, res=self.p_x, packed=True, **self._w8kw(p + "o.w"))
                 L.kr_rmsnorm(ptr(self.p_x), d, ptr(w.view(p + "ln2.w")), ptr(self.p_h), M, d, t.rms_norm_eps, s)
                 self._gemm(self.p_h, w.view(p + "gate_up.w"), self.p_act, M, epi=EPI_SILU_MUL8, packed=True, **self._w8kw(p + "gate_up.w"))
                 self._gemm(self.p_act, w.view(p + "down.w"), self.p_x, M, res=self.p_x, packed=True, **self._w8kw(p + "down.w"))
-            # last position of every sequence -> final norm (fused) -> lm_head -> greedy token
-            if whole_batch:
-                L.kr_embed_scatter(ptr(self.d_last), ptr(self.p_x), 0, ptr(self.d_x), B, d, s)
-                self._lm_head_and_sample(B)
-            elif not defer_activation:
-                self._first_tokens(slots)
-        if defer_activation:
-            return {"slots": slots, "lens": lens, "deltas": deltas, "cs": cs, "temps": temps, "seeds": seeds, "guides": grows,
-                    "procs": procs, "need": need}
-        return lens
+            if not defer_activation:
+                self._first_tokens(adm)
+        return adm
 
     def _admit_features(self, pages) -> StepFeatures:
         """What an admission's pages need: raises where the mode does not allow it, else the next steps carry it (from this
@@ -1094,41 +1093,49 @@ class Engine:
             rows.append((sp, bits, nd))
         return rows
 
-    def _write_processing(self, slots, procs):
-        """Sampling-control state of newly admitted slots: params, prompt bits, output counts cleared."""
-        for (sp, bits, nd), j in zip(procs, slots):
+    def _write_state(self, a: Admission):
+        """Decode state of an admission's sequences: the same fields in both modes.  Whole batch: one copy per field, padded
+        with zeros to max_batch rows.  Slots: one-row copies into the named slots only, the others keep decoding."""
+        gt, gm, gs, dgs = zip(*a.guides)
+        lens = np.asarray(a.lens, np.int32)
+        sampler = ((self.d_temp, a.temps), (self.d_seed, a.seeds))
+        fields = ((self.d_gtrans, np.asarray(gt, np.int64)), (self.d_gmasks, np.asarray(gm, np.int64)),
+                  (self.d_gstate, np.asarray(gs, np.int32)), (self.d_delta, a.deltas),
+                  (self.d_ctx, lens - 1), (self.d_plen, lens))      # kr_sample_greedy adds 1 to ctx -> number of cached tokens
+        if a.whole_batch:
+            for dst, rows in sampler + fields:
+                padded = np.zeros(self.B, rows.dtype)
+                padded[:a.B] = rows[:a.B]
+                self._h2d(dst, padded)
+            self._h2d(self.d_cs, a.cs)
+            self.d_fin.zero_()
+            self._slot_guides = {b: dg for b, dg in enumerate(dgs) if dg is not None}
+        else:
+            for b, j in enumerate(a.slots):
+                for dst, rows in fields:
+                    self._h2d(dst[j:j + 1], rows[b:b + 1])
+                self._h2d(self.d_cs[j], a.cs[b])
+                for dst, rows in sampler:
+                    self._h2d(dst[j:j + 1], rows[b:b + 1])
+                self.d_fin[j:j + 1].zero_()
+                self._slot_guides.pop(j, None)
+                if dgs[b] is not None:
+                    self._slot_guides[j] = dgs[b]
+        # sampling controls: params, prompt bits, output counts cleared
+        for (sp, bits, nd), j in zip(a.procs or (), a.slots):
             self._h2d(self.d_sp[j], sp)
             if bits is not None:
                 self._h2d(self.d_pbits[j], bits.view(np.int32))
             if nd:
                 self.d_counts[j].zero_()
 
-    def _write_slot_state(self, slots, lens, deltas, cs, temps, seeds, guides=None, procs=None):
-        for b, j in enumerate(slots):
-            a_t, a_m, st, dg = guides[b] if guides is not None else (0, 0, 0, None)
-            self._h2d(self.d_gtrans[j:j + 1], np.asarray([a_t], np.int64))
-            self._h2d(self.d_gmasks[j:j + 1], np.asarray([a_m], np.int64))
-            self._h2d(self.d_gstate[j:j + 1], np.asarray([st], np.int32))
-            if dg is None:
-                self._slot_guides.pop(j, None)
-            else:
-                self._slot_guides[j] = dg
-            self._h2d(self.d_delta[j:j + 1], deltas[b:b + 1])
-            self._h2d(self.d_ctx[j:j + 1], np.asarray([lens[b] - 1], np.int32))
-            self._h2d(self.d_plen[j:j + 1], np.asarray([lens[b]], np.int32))
-            self._h2d(self.d_cs[j], cs[b])
-            self._h2d(self.d_temp[j:j + 1], temps[b:b + 1])
-            self._h2d(self.d_seed[j:j + 1], seeds[b:b + 1])
-            self.d_fin[j:j + 1].zero_()
-        if procs is not None:
-            self._write_processing(slots, procs)
-
-    def _first_tokens(self, slots):
-        """Last prompt position of every prefilled sequence (p_x rows d_last) -> its slot's x -> lm_head -> first token."""
+    def _first_tokens(self, a: Admission):
+        """Last prompt position of every prefilled sequence (p_x rows d_last) -> its slot's x -> lm_head -> first token: the
+        whole batch in one pass, slots one by one."""
         d = self.cfg.text.hidden_size
-        for b, j in enumerate(slots):
-            self.L.kr_embed_scatter(ptr(self.d_last[b:]), ptr(self.p_x), 0, ptr(self.d_x[j:]), 1, d, self.s)
-            self._lm_head_and_sample(1, slot0=j)
+        for b, j, n in ((0, 0, a.B),) if a.whole_batch else ((b, j, 1) for b, j in enumerate(a.slots)):
+            self.L.kr_embed_scatter(ptr(self.d_last[b:]), ptr(self.p_x), 0, ptr(self.d_x[j:]), n, d, self.s)
+            self._lm_head_and_sample(n, slot0=j)
 
     def _lm_head_and_sample(self, B: int, x=None, slot0: int = 0):
         """final RMSNorm (fused) -> lm_head with per-workgroup argmax partials -> greedy token,
@@ -1401,15 +1408,10 @@ class Engine:
         self._last_batch = B
         self._ensure_history(max_new_tokens)
         self._req_max_new = int(max_new_tokens)
-        grids = [g for p in pages for g in p.grids]
-        n_img_tok = 0
-        pix = self._pixels_for(pages, pixel_values_device)
-        if pix is not None:
-            n_img_tok = self.vit_forward(pix, grids).shape[0]
-        prep = self._prefill_prepare(pages, n_img_tok)   # host work of the prefill, under the ViT launches still running
+        adm = self._vit_and_prepare(pages, pixel_values_device)
         self.stream.synchronize()
         t1 = time.perf_counter()
-        lens = self.prefill(pages, n_img_tok, prep=prep)
+        lens = self.prefill(pages, adm.n_img, adm=adm).lens
         forced = None
         if force_tokens is not None:
             ft = np.asarray(force_tokens, np.int64)
@@ -1530,11 +1532,8 @@ class Engine:
         """ViT + prefill of new requests into idle slots; their first token is sampled.  Returns prompt lengths.
         ``budgets``: tokens each page may generate before the host retires it (its max_tokens + the chunk overshoot)."""
         self._check_budgets(pages, budgets)       # before any launch: an oversized page fails the call, nothing ran
-        grids = [g for p in pages for g in p.grids]
-        pix = self._pixels_for(pages, None)
-        n_img_tok = self.vit_forward(pix, grids).shape[0] if pix is not None else 0
-        prep = self._prefill_prepare(pages, n_img_tok, slots, budgets)   # host tables while the ViT launches execute
-        return self.prefill(pages, n_img_tok, slots=slots, prep=prep)
+        adm = self._vit_and_prepare(pages, None, slots, budgets)
+        return self.prefill(pages, adm.n_img, slots=slots, adm=adm).lens
 
     def _check_budgets(self, pages, budgets):
         room = self.seq_room()
@@ -1573,11 +1572,8 @@ class Engine:
         main = (self.stream, self.s)
         self.stream, self.s = self._adm_stream, self._adm_stream.cuda_stream
         try:
-            grids = [g for p in pages for g in p.grids]
-            pix = self._pixels_for(pages, None)
-            n_img_tok = self.vit_forward(pix, grids).shape[0] if pix is not None else 0
-            rec = self.prefill(pages, n_img_tok, slots=slots, defer_activation=True,
-                               prep=self._prefill_prepare(pages, n_img_tok, slots, budgets))
+            adm = self._vit_and_prepare(pages, None, slots, budgets)
+            rec = self.prefill(pages, adm.n_img, slots=slots, defer_activation=True, adm=adm)
             done = torch.cuda.Event()
             done.record(self._adm_stream)
         finally:
@@ -1590,16 +1586,15 @@ class Engine:
 
     def admit_end(self, handle) -> List[int]:
         """Activate the admitted slots on the decode stream (waits for the admission stream there, not on the host)."""
-        rec = handle["rec"]
+        rec: Admission = handle["rec"]
         self._adm_inflight = max(0, self._adm_inflight - 1)
         self.stream.wait_event(handle["done"])
         # the first tokens are sampled with the passes this admission needs, whatever set_step_features did since admit_begin
-        self._step |= rec["need"]
+        self._step |= rec.need
         with torch.cuda.stream(self.stream):
-            self._write_slot_state(rec["slots"], rec["lens"], rec["deltas"], rec["cs"], rec["temps"], rec["seeds"],
-                                   rec.get("guides"), rec.get("procs"))
-            self._first_tokens(rec["slots"])
-        return rec["lens"]
+            self._write_state(rec)
+            self._first_tokens(rec)
+        return rec.lens
 
     def set_step_features(self, sampling: bool, guided: bool, processing: bool = False):
         """Slot mode: which passes the NEXT decode steps carry, within what begin_slots() allowed.  The scheduler calls it with what
