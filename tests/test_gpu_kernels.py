@@ -1,6 +1,9 @@
 """Parity of every HIP kernel against numpy restatements, through the C-ABI (ctypes), on a real
 MI355X.  Integer-valued inputs make the MFMA paths bit-exact (any layout slip fails exactly);
-random inputs use a stated bf16 tolerance."""
+random inputs use a stated bf16 tolerance.  The attention tests here run N(0,1) q, k, v — a flat softmax, where one key
+among thousands moves the output by less than the tolerance: they check the arithmetic (and, in the decode tests, that
+finite stale cache rows past the context change nothing); masks, row offsets and trip counts are checked to the key by
+test_gpu_attention_exact.py."""
 import ctypes as C
 import math
 
@@ -50,6 +53,16 @@ def assert_close_bf16(got, ref, rel=2 ** -7, abs_=1e-2, what=""):
     bad = err > tol
     assert not bad.any(), f"{what}: {bad.sum()} / {bad.size} out of tolerance, max err {err.max():.4g} at " \
                           f"{np.unravel_index(err.argmax(), err.shape)} (ref {ref.flat[err.argmax()]:.4g})"
+
+
+def stale_cache_tails(kc, vc, first_stale, seed):
+    """What slot reuse after a longer page leaves behind: finite K rows and V^T columns from `first_stale[b]` to the end of
+    slot b's cache, drawn from a generator of their own (the test's other draws stay what they were) and 8x the size of
+    the live values, so a kernel that lets one of them into a softmax moves its output.  In place."""
+    rng = np.random.default_rng(seed)
+    for b, c in enumerate(first_stale):
+        kc[b, :, c:] = rnd(rng, *kc[b, :, c:].shape, scale=8.0)
+        vc[b, :, c:] = rnd(rng, *vc[b, :, c:].shape, scale=8.0)
 
 
 # ----------------------------------------------------------------------------- self test
@@ -719,6 +732,7 @@ def test_decode_prep_and_attention(L, H, KVH, ctxs):
     for b, c in enumerate(ctxs):
         kc[b, :, :c] = rnd(rng, KVH, c, hd)
         vc[b, :, :c] = rnd(rng, KVH, c, hd)
+    stale_cache_tails(kc, vc, [c + 1 for c in ctxs], 9001)   # the prep writes row ctx; the rows after it are a longer earlier page's
     vt = POS.vt_blocks(vc)
     kc_d, vt_d = dev_bf16(kc), dev_bf16(vt)
     qkv = rnd(rng, B, (H + 2 * KVH) * hd)
@@ -1841,6 +1855,7 @@ def test_attn_partials_merged_by_o_proj_prologue(L, H, KVH, n_split):
     for b, c in enumerate(ctxs):
         kc[b, :, :c + 1] = rnd(rng, KVH, c + 1, hd)
         vc[b, :, :c + 1] = rnd(rng, KVH, c + 1, hd)
+    stale_cache_tails(kc, vc, [c + 1 for c in ctxs], 9002)
     vt = POS.vt_blocks(vc)
     q = rnd(rng, B, H, hd)
     Wo, X = rnd(rng, d, H * hd, scale=(H * hd) ** -0.5), rnd(rng, B, d)
@@ -1871,6 +1886,7 @@ def test_attn_decode_partials_then_merge_launch(L, H, KVH, n_split, config5):
     for b, c in enumerate(ctxs):
         kc[b, :, :c + 1] = rnd(rng, KVH, c + 1, hd)
         vc[b, :, :c + 1] = rnd(rng, KVH, c + 1, hd)
+    stale_cache_tails(kc, vc, [c + 1 for c in ctxs], 9003)
     vt = POS.vt_blocks(vc)
     q = rnd(rng, B, H, hd)
     kc_d, vt_d, q_d = dev_bf16(kc), dev_bf16(vt), dev_bf16(q)
@@ -1908,6 +1924,7 @@ def test_attn_decode_fused(L, H, KVH, n_split, long_ctx):
     for b, c in enumerate(ctxs):
         kc[b, :, :c + 1] = rnd(rng, KVH, c + 1, hd)
         vc[b, :, :c + 1] = rnd(rng, KVH, c + 1, hd)
+    stale_cache_tails(kc, vc, [c + 1 for c in ctxs], 9004)
     vt = POS.vt_blocks(vc)
     q = rnd(rng, B, H, hd)
     kc_d, vt_d, q_d = dev_bf16(kc), dev_bf16(vt), dev_bf16(q)
