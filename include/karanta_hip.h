@@ -39,7 +39,7 @@ typedef uint16_t kr_bf16;
 /* kr_version() of the library this header describes: major * 100 + minor.  The major changes with every incompatible
  * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family); a caller built
  * against major X must refuse a library whose kr_version() / 100 != X. */
-#define KR_ABI_VERSION 402
+#define KR_ABI_VERSION 403
 
 #define KR_OK 0
 #define KR_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -549,6 +549,34 @@ int kr_gumbel_argmax_processed(const float* logits, int64_t ld_logits, int vocab
 /* After kr_sample_greedy: counts[b][tokens[b]] += 1 for the rows with live[b] != 0 (kr_sample_threshold of this step). */
 int kr_sample_count(const int32_t* tokens, const int32_t* live, int32_t* counts, int64_t ld_counts, int vocab, int batch,
                     kr_stream s);
+
+/* ------------------------------------------------------------------ per-request logit adjustments (vLLM's logit_bias,
+ * min_tokens and stop_token_ids).  Per row b a table of adj_meta[b * 4 + 0] = n_entries <= KR_ADJ_CAP entries, every token id
+ * at most once in a row (the host merges bias keys, stop ids and the model's EOS ids); entry e of row b, at
+ * [b * KR_ADJ_CAP + e]: adj_ids (token id), adj_val (the bias, fp32, 0 where none; -inf allowed), adj_flag (bit 0 = stop
+ * entry: one of the row's stop_token_ids or an EOS id).  adj_meta[b * 4 + 1] = min_tokens, [2..3] unused.  n_entries above
+ * KR_ADJ_CAP counts as KR_ADJ_CAP and an id outside [0, vocab) is skipped.  vLLM's order: these run on the lm_head's fp32
+ * logits BEFORE the penalties, temperature and truncation of the sampler; log-probabilities and returned logits stay raw.
+ *
+ * kr_logits_adjust: saved[b][e] = logits[b][id]; then, with n = ctx_len[b] + 1 - prompt_len[b] (the index of the token being
+ * generated, as in kr_gumbel_argmax): logits[b][id] = -inf on a stop entry while n < min_tokens (the mask wins over a bias,
+ * nothing is masked at n == min_tokens), else logits[b][id] + adj_val in fp32.  Rows with n_entries == 0 are not touched.
+ * saved [batch][KR_ADJ_CAP] fp32 belongs to the step: kr_logits_restore reads it. */
+#define KR_ADJ_CAP 320   /* OpenAI's 300 logit_bias entries + 16 stop ids + the EOS ids */
+int kr_logits_adjust(float* logits, int64_t ld_logits, int vocab, const int32_t* adj_ids, const float* adj_val,
+                     const int32_t* adj_flag, const int32_t* adj_meta, const int32_t* ctx_len, const int32_t* prompt_len,
+                     float* saved, int batch, kr_stream s);
+
+/* After the sampler: logits[b][id] = saved[b][e] for every entry — the buffer equals what the lm_head wrote, bit for bit
+ * (kr_logprobs_topk and returned logits report the unadjusted values). */
+int kr_logits_restore(float* logits, int64_t ld_logits, int vocab, const int32_t* adj_ids, const int32_t* adj_meta,
+                      const float* saved, int batch, kr_stream s);
+
+/* After kr_sample_greedy: finished[b] = 1 where the row was still live (finished[b] == 0: it appended a sampled token, not a
+ * pad) and tokens[b] is one of its stop entries — from here on the row is what an EOS row is (frozen in slot mode, no
+ * log-prob for the finishing step).  ignore_eos bit 0 (kr_sample_greedy's): nothing finishes. */
+int kr_stop_tokens(const int32_t* tokens, const int32_t* adj_ids, const int32_t* adj_flag, const int32_t* adj_meta,
+                   int32_t* finished, int ignore_eos, int batch, kr_stream s);
 
 /* After the sampler: guide_state[b] <- walk(guide_state[b], bytes(tokens[b])) through the table at device address
  * guide_trans[b] (0: row unconstrained); rows with finished[b] != 0 keep their state. */

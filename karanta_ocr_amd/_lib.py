@@ -84,6 +84,9 @@ SIGNATURES = {
     "kr_gumbel_argmax_processed": [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, c_p, c_p, i32, i32, c_p, c_p, i64, c_p,
                                    i32, c_p, c_p],
     "kr_sample_count": [c_p, c_p, c_p, i64, i32, i32, c_p],
+    "kr_logits_adjust": [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p],
+    "kr_logits_restore": [c_p, i64, i32, c_p, c_p, c_p, i32, c_p],
+    "kr_stop_tokens": [c_p, c_p, c_p, c_p, c_p, i32, i32, c_p],
     "kr_guide_advance": [c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, c_p],
     "kr_logprobs_topk": [c_p, i64, i32, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, c_p],
     "kr_linear_decode_narrow": [i32, c_p, i64, c_p, i32, c_p, i64, c_p, c_p, c_p, f32, c_p, i64, c_p, c_p, i64,
@@ -141,6 +144,7 @@ class Dec32(C.Structure):
 
 ABI_MAJOR = 4              # include/karanta_hip.h KR_ABI_VERSION / 100: the header this binding was written against
 DEC_OUT_XP = 0x100         # KR_DEC_OUT_XP
+ADJ_CAP = 320              # KR_ADJ_CAP: entries per row of the logit-adjustment tables (kr_logits_adjust)
 EPI_NONE, EPI_QUICK_GELU, EPI_GELU_ERF, EPI_SILU_MUL, EPI_SILU_MUL8 = 0, 1, 2, 3, 4
 DEC_PLAIN, DEC_SILU, DEC_ROPE_KV, DEC_ARGMAX, DEC_SILU8 = 0, 1, 2, 3, 4
 

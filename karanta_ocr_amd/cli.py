@@ -59,7 +59,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--max-pixels", type=int, default=None,
                     help="override the checkpoint's preprocessor_config.json (default without one: 1003520)")
     ap.add_argument("--min-pixels", type=int, default=None)
-    ap.add_argument("--greedy", action="store_true", help="ignore request temperatures")
+    ap.add_argument("--greedy", action="store_true", help="ignore request temperatures, sampling controls, logit_bias, min_tokens, stop_token_ids and stop strings")
     ap.add_argument("--admit-min", type=int, default=1,
                     help="while sequences decode, wait for this many free slots + waiting requests before an admission "
                          "(6: +8 %% pages/s on a saturated server, profiles/r03_corpus_sweep.txt; 1: lowest latency)")

@@ -23,10 +23,10 @@ import torch
 
 from . import image_processing as IP
 from . import positions as POS
-from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_GELU_ERF, EPI_NONE, EPI_QUICK_GELU, EPI_SILU_MUL8,
+from ._lib import (ADJ_CAP, DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_GELU_ERF, EPI_NONE, EPI_QUICK_GELU, EPI_SILU_MUL8,
                    KarantaHipError, lib, narrow_opts, ptr)
 from .config import ModelConfig
-from .sampling import StepFeatures, has_penalties, needs_processing, sampling_params, temperature
+from .sampling import StepFeatures, adjust_table, has_penalties, needs_processing, sampling_params, temperature
 from .weights import pack_w16x64, to_bf16_bits
 
 BF16 = torch.bfloat16
@@ -253,6 +253,10 @@ class PageRequest:
     repetition_penalty: float = 1.0            # 1: off; tokens of the prompt or the output so far: l > 0 ? l / r : l * r
     frequency_penalty: float = 0.0             # l -= frequency_penalty * (count in the output so far)
     presence_penalty: float = 0.0              # l -= presence_penalty * (count > 0)
+    # vLLM's logit adjustments (kr_logits_adjust / kr_stop_tokens), applied before the penalties; the defaults are "off"
+    logit_bias: Optional[Dict[int, float]] = None   # token id -> value added to its logit (fp32)
+    min_tokens: int = 0                        # while fewer tokens are generated, EOS and the stop_token_ids cannot be chosen
+    stop_token_ids: Tuple[int, ...] = ()       # a generated token among these ends the sequence as EOS does
 
 
 @dataclass
@@ -328,6 +332,7 @@ class Admission:
     seeds: Optional[np.ndarray] = None
     guides: Optional[list] = None      # Engine._guide_rows
     procs: Optional[list] = None       # Engine._control_rows
+    adjs: Optional[list] = None        # Engine._adjust_rows
     need: StepFeatures = StepFeatures()
 
 
@@ -529,6 +534,13 @@ class Engine:
         self.d_work = z(B, t.vocab_size, dtype=torch.float32)
         self.d_thr = z(B, dtype=torch.int32)
         self.d_live = z(B, dtype=torch.int32)
+        # logit adjustments: per-slot tables (sampling.adjust_table; a row with n_entries == 0 is left alone) and the values
+        # kr_logits_adjust saves for kr_logits_restore
+        self.d_adj_ids = z(B, ADJ_CAP, dtype=torch.int32)
+        self.d_adj_val = z(B, ADJ_CAP, dtype=torch.float32)
+        self.d_adj_flag = z(B, ADJ_CAP, dtype=torch.int32)
+        self.d_adj_meta = z(B, 4, dtype=torch.int32)
+        self.d_adj_saved = z(B, ADJ_CAP, dtype=torch.float32)
         self.d_voc_off = self.d_voc_bytes = None   # set_vocab()
         self._guides: Dict[str, DeviceGuide] = {}
         self._slot_guides: Dict[int, DeviceGuide] = {}   # keeps the tables of the running requests alive
@@ -1041,6 +1053,7 @@ class Engine:
             adm.seeds = np.asarray([int(getattr(p, "seed", 0) or 0) & 0xFFFFFFFF for p in pages], np.uint32).view(np.int32)
             adm.guides = self._guide_rows(pages)
             adm.procs = self._control_rows(pages)
+            adm.adjs = self._adjust_rows(pages)
             if not defer_activation:
                 self._write_state(adm)
             self._h2d(self.d_last, adm.last_rows)
@@ -1068,6 +1081,9 @@ class Engine:
         if need.guided and not caps.guided:
             raise KarantaHipError("a page carries a guide but the engine is not in its guided configuration "
                                   "(generate() decides from its pages; begin_slots(guided=True) for slot mode)")
+        if need.adjust and not caps.adjust:
+            raise KarantaHipError("a page asks for logit_bias / min_tokens / stop_token_ids but the engine is in its greedy "
+                                  "configuration (generate() decides from its pages; begin_slots(sampling=True) for slot mode)")
         if need.sampling and not caps.sampling:
             raise KarantaHipError("a page asks for temperature > 0 but the engine is in its greedy configuration "
                                   "(generate() decides from its pages; begin_slots(sampling=True) for slot mode)")
@@ -1092,6 +1108,16 @@ class Engine:
                 np.bitwise_or.at(bits, ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
             rows.append((sp, bits, nd))
         return rows
+
+    def _adjust_rows(self, pages):
+        """Per page its logit-adjustment table (sampling.adjust_table) or None, when the engine may run the adjustment launches,
+        else None."""
+        if not self._caps.adjust:
+            return None
+        try:
+            return [adjust_table(p, self.cfg.eos_token_ids, self.cfg.text.vocab_size) for p in pages]
+        except ValueError as e:
+            raise KarantaHipError(str(e)) from e
 
     def _write_state(self, a: Admission):
         """Decode state of an admission's sequences: the same fields in both modes.  Whole batch: one copy per field, padded
@@ -1128,6 +1154,16 @@ class Engine:
                 self._h2d(self.d_pbits[j], bits.view(np.int32))
             if nd:
                 self.d_counts[j].zero_()
+        # logit adjustments: the row's table; n_entries = 0 where the page has none, so a slot never keeps its predecessor's
+        if a.adjs is not None and a.whole_batch:
+            self.d_adj_meta.zero_()
+        for tab, j in zip(a.adjs or (), a.slots):
+            if tab is None:
+                if not a.whole_batch:
+                    self.d_adj_meta[j].zero_()
+                continue
+            for dst, rows in zip((self.d_adj_ids, self.d_adj_val, self.d_adj_flag, self.d_adj_meta), tab):
+                self._h2d(dst[j], rows)
 
     def _first_tokens(self, a: Admission):
         """Last prompt position of every prefilled sequence (p_x rows d_last) -> its slot's x -> lm_head -> first token: the
@@ -1155,6 +1191,11 @@ class Engine:
         n_part = self._amax_parts(B) if self.wide_mode else self.n_amax   # the stride the lm_head launch wrote with
         flags = (1 if self._ignore_eos else 0) | (2 if self._freeze_finished else 0)
         gm, gs = (ptr(self.d_gmasks[j:]), ptr(self.d_gstate[j:])) if step.guided else (None, None)
+        if step.adjust:
+            # logit_bias / min_tokens somewhere in the batch: applied in place before the sampler (vLLM's order), undone after it
+            adj = (ptr(self.d_adj_ids[j:]), ptr(self.d_adj_val[j:]), ptr(self.d_adj_flag[j:]), ptr(self.d_adj_meta[j:]))
+            L.kr_logits_adjust(ptr(logits), self.d_logits.stride(0), t.vocab_size, *adj, ptr(self.d_ctx[j:]), ptr(self.d_plen[j:]),
+                               ptr(self.d_adj_saved[j:]), B, s)
         if step.processing:
             # sampling controls somewhere in the batch: per-row truncation threshold, then the Gumbel-max argmax over the
             # penalised scores above it (rows with neutral controls get exactly the partials of the branch below)
@@ -1180,11 +1221,15 @@ class Engine:
                            ptr(self.d_tok[j:]), ptr(self.d_hist[:, j:]), self.d_hist.stride(0), ptr(self.d_plen[j:]),
                            ptr(self.d_ctx[j:]), ptr(self.d_fin[j:]), ptr(self.d_eos), self.d_eos.numel(),
                            self.cfg.pad_token_id, flags, ptr(self.d_x[j:]), B, s)
+        if step.adjust:
+            L.kr_stop_tokens(ptr(self.d_tok[j:]), adj[0], adj[2], adj[3], ptr(self.d_fin[j:]), flags, B, s)
         if step.processing:
             L.kr_sample_count(ptr(self.d_tok[j:]), ptr(self.d_live[j:]), ptr(self.d_counts[j:]), t.vocab_size, t.vocab_size, B, s)
         if step.guided:
             L.kr_guide_advance(ptr(self.d_tok[j:]), ptr(self.d_fin[j:]), ptr(self.d_gtrans[j:]), ptr(self.d_gstate[j:]),
                                ptr(self.d_voc_off), ptr(self.d_voc_bytes), t.vocab_size, B, s)
+        if step.adjust:     # log-probabilities and returned logits report what the lm_head wrote
+            L.kr_logits_restore(ptr(logits), self.d_logits.stride(0), t.vocab_size, adj[0], adj[3], ptr(self.d_adj_saved[j:]), B, s)
         if self._logprobs is not None:
             L.kr_logprobs_topk(ptr(logits), self.d_logits.stride(0), t.vocab_size, int(self._logprobs), self.lp_part,
                                ptr(self.d_lp_pv), ptr(self.d_lp_pi), ptr(self.d_lp_ms), ptr(self.d_tok[j:]), ptr(self.d_ctx[j:]),
@@ -1467,8 +1512,8 @@ class Engine:
         for b in range(B):
             row = hist[b]
             cut, reason = len(row), "length"
-            if not ignore_eos:
-                hit = np.flatnonzero(np.isin(row, list(eos)))
+            if not ignore_eos:       # a row's own stop ids end it as EOS does (kr_stop_tokens)
+                hit = np.flatnonzero(np.isin(row, list(eos | set(int(x) for x in getattr(pages[b], "stop_token_ids", None) or ()))))
                 if hit.size:
                     cut, reason = int(hit[0]) + 1, "stop"
             toks.append(row[:cut].astype(np.int64))
@@ -1506,7 +1551,7 @@ class Engine:
         self._ignore_eos, self._freeze_finished, self._want_logits = False, True, False
         # the sampling controls come with the sampling configuration; the steps carry each pass while a request needs it
         sampled = bool(sampling) or bool(guided)
-        self._caps, self._step = StepFeatures(sampled, bool(guided), sampled), StepFeatures()
+        self._caps, self._step = StepFeatures(sampled, bool(guided), sampled, sampled), StepFeatures()
         self._logprobs = None if logprobs is None else int(logprobs)
         self._last_batch = self.B
         self._ensure_history(max_new_tokens)
@@ -1522,6 +1567,7 @@ class Engine:
             self.d_temp.zero_()
             self.d_gtrans.zero_()
             self.d_gmasks.zero_()
+            self.d_adj_meta.zero_()
             self._slot_guides = {}
             self.d_ctx.zero_()
             self.d_plen.zero_()
@@ -1596,13 +1642,14 @@ class Engine:
             self._first_tokens(rec)
         return rec.lens
 
-    def set_step_features(self, sampling: bool, guided: bool, processing: bool = False):
+    def set_step_features(self, sampling: bool, guided: bool, processing: bool = False, adjust: bool = False):
         """Slot mode: which passes the NEXT decode steps carry, within what begin_slots() allowed.  The scheduler calls it with what
         the requests in the slots need: a server that accepts guided / sampled requests runs the plain argmax graph (no f32 logits
         written and re-read, no DFA advance) while none is decoding — rows with temperature 0 and no guide get the same token from
         either graph.  An admission switches on what its pages need by itself (prefill, admit_end).
-        processing: the sampling-control launches (top_k / top_p / min_p / penalties; needs_processing), same rules."""
-        self._step = StepFeatures(bool(sampling), bool(guided), bool(processing)) & self._caps
+        processing: the sampling-control launches (top_k / top_p / min_p / penalties; needs_processing), same rules.
+        adjust: the logit-adjustment launches (logit_bias / min_tokens / stop_token_ids; needs_adjust), same rules."""
+        self._step = StepFeatures(bool(sampling), bool(guided), bool(processing), bool(adjust)) & self._caps
 
     def decode_steps(self, n: int):
         """n decode steps over all slots (asynchronous on the engine's stream).  While an admission is in flight on a CU-masked

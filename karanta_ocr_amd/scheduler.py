@@ -4,7 +4,8 @@ The reference leaves scheduling to vLLM (one server per GPU, `scripts/start_mult
 pipeline only watches its `Running: n reqs, Waiting: m reqs` lines, `karanta/pipeline.py:769-800`).  Here the decode
 hipGraph always steps all `max_batch` slots; a sequence that hits EOS (device flag) or its `max_tokens` (host) frees
 its slot, and the next waiting request is prefilled into that slot while the other sequences keep their state —
-instead of the whole batch waiting for its longest member (`Engine.generate`, static batching).
+instead of the whole batch waiting for its longest member (`Engine.generate`, static batching).  A request's own
+`stop_token_ids` end it on the device as EOS does; its stop strings (`SlotRequest.stop_check`) are looked for at each harvest.
 
 Only the host logic lives here; it drives `Engine.begin_slots / admit / decode_steps / poll_slots / slot_tokens /
 retire`, and any object with those six methods (the CPU tests use a fake) can stand in for the engine.
@@ -15,7 +16,7 @@ import collections
 import os
 import time
 from dataclasses import dataclass
-from typing import Any, Deque, Dict, Iterable, List, Optional, Sequence
+from typing import Any, Callable, Deque, Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
 
@@ -27,6 +28,9 @@ class SlotRequest:
     page: Any                 # engine.PageRequest
     max_tokens: int
     tag: Any = None           # returned untouched with the result
+    # stop strings: called at every harvest with the tokens generated so far; returns how many to keep (through the token that
+    # completed a match) or None.  Requests without one cause no token reads before they finish.
+    stop_check: Optional[Callable[[np.ndarray], Optional[int]]] = None
 
 
 @dataclass
@@ -177,7 +181,8 @@ class SlotScheduler:
             pending = self._inflight[1] if self._inflight is not None else []
             need = StepFeatures.of(r.page for r in [*self.active.values(), *pending])
             if need != self._features_now:
-                self.engine.set_step_features(*need)
+                # (engines older than the adjustment pass take three arguments: it is only named when a request needs it)
+                self.engine.set_step_features(need.sampling, need.guided, need.processing, **({"adjust": True} if need.adjust else {}))
                 self._features_now = need
         self.engine.decode_steps(self.chunk)
         self.steps += self.chunk
@@ -300,20 +305,30 @@ class SlotScheduler:
                 continue
             r = self.active[j]
             limit = min(int(r.max_tokens), self.cap)
-            if not (fin[j] or gen[j] >= limit):
-                continue
             n = int(min(gen[j], limit))
+            over = bool(fin[j] or gen[j] >= limit)
+            if not over and (r.stop_check is None or n < 1):
+                continue
             toks = np.asarray(self.engine.slot_tokens(j, n), np.int64)
-            reason = "length"
-            hit = np.flatnonzero(np.isin(toks, list(self.eos))) if self.eos else np.zeros(0, np.int64)
-            if hit.size:
-                toks, reason = toks[: int(hit[0]) + 1], "stop"
+            reason, on_token = "length", False
+            if over:
+                stops = self.eos | set(int(t) for t in getattr(r.page, "stop_token_ids", None) or ())
+                hit = np.flatnonzero(np.isin(toks, list(stops))) if stops else np.zeros(0, np.int64)
+                if hit.size:
+                    toks, reason, on_token = toks[: int(hit[0]) + 1], "stop", True
+            if r.stop_check is not None:
+                keep = r.stop_check(toks)
+                if keep is not None and keep <= len(toks):
+                    on_token = on_token and keep == len(toks)
+                    toks, reason = toks[:int(keep)], "stop"
+                elif not over:
+                    continue
             if not fin[j]:
                 self.engine.retire(j)
             lps = None
             k = getattr(r.page, "logprobs", None)
             if k is not None and self.logprobs is not None:
-                n_lp = len(toks) - (1 if reason == "stop" else 0)     # the EOS step records nothing
+                n_lp = len(toks) - (1 if on_token else 0)     # the step that finishes on EOS / a stop id records nothing
                 lps = self.engine.slot_logprobs(j, n_lp, int(k))
             out.append(SlotResult(r.tag, toks, reason, self.prompt_len.pop(j), request=r, logprobs=lps))
             del self.active[j]

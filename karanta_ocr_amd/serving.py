@@ -17,7 +17,10 @@ request: caller skips the attempt), 500 (internal error: caller retries).
 (kr_gumbel_argmax), reproducible through the OpenAI ``seed`` field, a random seed per request otherwise.
 ``top_k`` / ``top_p`` / ``min_p`` / ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` are applied with
 vLLM's semantics and validation (sampling.py; kr_sample_threshold / kr_gumbel_argmax_processed); ``honor_temperature=False``
-(``--greedy``) ignores them with the temperature.  ``guided_regex`` / ``response_format`` / ``logprobs``: guided.py, engine.
+(``--greedy``) ignores them with the temperature.  ``logit_bias`` / ``min_tokens`` / ``stop_token_ids`` are applied on the device
+(sampling.parse_adjust_fields; kr_logits_adjust / kr_stop_tokens) and ``stop`` strings (``include_stop_str_in_output``) by the
+scheduler between decode chunks (sampling.StopStrings); ``--greedy`` ignores all of these too.  ``n > 1`` is not served.
+``guided_regex`` / ``response_format`` / ``logprobs``: guided.py, engine.
 
 Prompt text: the checkpoint's own ``chat_template`` when the model directory ships one (``chat_template.json`` /
 ``chat_template.jinja`` / ``tokenizer_config.json`` — what vLLM applies, pipeline.py:707-734), rendered with jinja2; the
@@ -37,7 +40,7 @@ import numpy as np
 
 from . import image_processing as IP
 from .config import ModelConfig
-from .sampling import NEUTRAL, parse_request_fields
+from .sampling import NEUTRAL, StopStrings, parse_adjust_fields, parse_request_fields
 
 DEFAULT_SYSTEM = "You are a helpful assistant."
 
@@ -139,6 +142,15 @@ class ParsedRequest:
     repetition_penalty: float = 1.0
     frequency_penalty: float = 0.0
     presence_penalty: float = 0.0
+    # vLLM's logit adjustments and stop conditions (sampling.parse_adjust_fields: validated, off when absent)
+    logit_bias: Optional[Dict[int, float]] = None
+    min_tokens: int = 0
+    stop_token_ids: Tuple[int, ...] = ()
+    stop: Tuple[str, ...] = ()
+    include_stop_str_in_output: bool = False
+
+
+ADJUST_FIELDS = ("logit_bias", "min_tokens", "stop_token_ids")
 
 
 class ChatFrontend:
@@ -352,11 +364,16 @@ class ChatFrontend:
                 raise BadRequest("top_logprobs must be in 0..20")
         try:
             controls = parse_request_fields(req)
+            guide = self._guide_for(req)
+            controls.update(parse_adjust_fields(req, self.cfg.text.vocab_size, max_tokens, guided=guide is not None,
+                                                eos_token_ids=self.cfg.eos_token_ids))
+        except BadRequest:
+            raise
         except ValueError as e:
             raise BadRequest(str(e)) from e
         return ParsedRequest(np.asarray(ids, np.int64), np.concatenate(pvs, 0) if pvs else None, grids, max_tokens,
                              str(req.get("model", "karantaocr")), temperature, seed, images or None,
-                             self._guide_for(req), logprobs, **controls)
+                             guide, logprobs, **controls)
 
 
 # ----------------------------------------------------------------------------- in-process server
@@ -392,6 +409,7 @@ class LocalServer:
         # other slots keep decoding (SlotScheduler(overlap=True))
         self.overlap_admissions = bool(overlap_admissions)
         self.launch_ahead = bool(launch_ahead)
+        self._tok_bytes = None       # the tokenizer's byte strings, fetched once for the stop-string matchers
         self._q: "queue.Queue" = queue.Queue()
         self._running = 0
         self._stop = False
@@ -460,7 +478,7 @@ class LocalServer:
             kind = "BadRequestError" if code == 400 else "InternalServerError"
             return code, {"error": {"message": slot["error"], "type": kind, "code": code}}
         toks, reason = slot["tokens"], slot["reason"]
-        text = self.frontend.tok.decode(toks)
+        text = slot["text"] if slot.get("text") is not None else self.frontend.tok.decode(toks)   # "text": cut at a stop string
         self.latencies.append(time.time() - t0)
         if len(self.latencies) > 20000:          # bounded: /metrics reads the last 10000
             del self.latencies[:10000]
@@ -549,6 +567,18 @@ class LocalServer:
                 groups.append([s])
         return groups
 
+    def _stop_strings(self, r: ParsedRequest) -> Optional[StopStrings]:
+        """The matcher of a request's `stop` strings, on the tokenizer's byte strings where it has them (None: no stop strings,
+        or --greedy, which ignores them with the other generation controls)."""
+        stops = getattr(r, "stop", None)
+        if not stops or not self.honor_temperature:
+            return None
+        tok = self.frontend.tok
+        if self._tok_bytes is None and hasattr(tok, "token_bytes"):
+            self._tok_bytes = tok.token_bytes()
+        return StopStrings(stops, getattr(r, "include_stop_str_in_output", False), self._tok_bytes,
+                           None if self._tok_bytes is not None else tok.decode)
+
     def _page(self, r: ParsedRequest):
         from .engine import PageRequest
         import random
@@ -563,6 +593,9 @@ class LocalServer:
         if self.honor_temperature:        # --greedy: the plain greedy path, sampling controls ignored as well
             for name in NEUTRAL:
                 setattr(page, name, getattr(r, name, NEUTRAL[name]))
+            for name in ADJUST_FIELDS:
+                if getattr(r, name, None):
+                    setattr(page, name, getattr(r, name))
         return page
 
     def _finish(self, s: Dict[str, Any], toks, reason: str):
@@ -570,8 +603,19 @@ class LocalServer:
         if len(toks) > mt:
             toks, reason = toks[:mt], "length"
         eos = set(int(e) for e in self.engine.cfg.eos_token_ids)
+        if self.honor_temperature:
+            eos |= set(int(t) for t in getattr(s["req"], "stop_token_ids", None) or ())
         if reason == "stop" and len(toks) and int(toks[-1]) in eos:
-            toks = toks[:-1]  # the EOS token is not part of the message content
+            toks = toks[:-1]  # the EOS token (or the stop id that ended the sequence) is not part of the message content
+        # stop strings: the earliest match cuts the text; usage counts through the token that completed it.  (Continuous mode:
+        # the scheduler has already stopped the sequence there with this matcher; static mode: generation ran on.)
+        m = s.get("stop")
+        if m is None:
+            m = self._stop_strings(s["req"])
+        if m is not None:
+            keep = m.check(toks)
+            if keep is not None:
+                toks, reason, s["text"] = toks[:keep], "stop", m.text
         s["tokens"], s["reason"] = toks, reason
 
     def _loop_continuous(self):
@@ -607,7 +651,8 @@ class LocalServer:
                     s["done"].set()
                 else:
                     r = s["req"]
-                    sch.submit(SlotRequest(self._page(r), max(1, int(r.max_tokens)), tag=s))
+                    s["stop"] = self._stop_strings(r)
+                    sch.submit(SlotRequest(self._page(r), max(1, int(r.max_tokens)), tag=s, stop_check=s["stop"]))
             if self._stop or sch is None:
                 continue
             try:
