@@ -39,7 +39,7 @@ typedef uint16_t kr_bf16;
 /* kr_version() of the library this header describes: major * 100 + minor.  The major changes with every incompatible
  * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family); a caller built
  * against major X must refuse a library whose kr_version() / 100 != X. */
-#define KR_ABI_VERSION 403
+#define KR_ABI_VERSION 404
 
 #define KR_OK 0
 #define KR_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -593,6 +593,34 @@ int kr_logprobs_topk(const float* logits, int64_t ld_logits, int vocab, int k, i
                      int32_t* part_idx, float* part_ms, const int32_t* tokens, const int32_t* ctx_len,
                      const int32_t* prompt_len, const int32_t* finished, float* out_lp, int32_t* out_idx, int hist_len,
                      int hist_batch, int k_stride, int batch, kr_stream s);
+
+/* Fork of prefilled KV-cache slots (n > 1 of a request, a repeated page): for every group of the plan, every layer and KV head,
+ * rows [0, n_tokens) of kcache and V^T blocks [0, ceil(n_tokens / 64)) of vtcache are copied from slot `src` to each slot of
+ * `dst`.  The partial last V^T block is copied whole: a decode step appends column by column into it, and its columns at or
+ * beyond n_tokens are masked by ctx_len.  Nothing else is written: destination rows / blocks beyond the span, the other slots
+ * and the sources keep their bytes.  One launch; a source piece (64 tokens of one head: hd x 128 bytes) is loaded once and
+ * stored to every destination of its group.
+ * The caches arrive as explicit ELEMENT strides of (layer, slot, head); a head holds [s_max][hd] (kcache) or
+ * [s_max / 64][2][hd][32] (vtcache) contiguously; all offsets are 64-bit.  hd % 8 == 0, s_max % 64 == 0, 1 <= slots <= 32,
+ * strides multiples of 8 and at least the extent below them.
+ * `plan` is HOST memory, read during the call only and carried in the kernel arguments (no device table, copy or allocation).
+ * KR_ERR_ARG, and nothing launches: a slot outside [0, slots), n_tokens outside [1, s_max], a destination listed twice (in any
+ * group), a destination equal to any group's source, a group without destinations, n_groups outside [1, 32]. */
+#define KR_FORK_MAX_GROUPS 32
+#define KR_FORK_MAX_SLOTS 32
+typedef struct kr_fork_group {
+    int32_t src;                       /* source slot */
+    int32_t n_tokens;                  /* prompt length: rows [0, n_tokens) */
+    int32_t n_dst;                     /* 1 .. KR_FORK_MAX_SLOTS */
+    int32_t dst[KR_FORK_MAX_SLOTS];    /* destination slots */
+} kr_fork_group;
+typedef struct kr_fork_plan {
+    int32_t n_groups;                  /* 1 .. KR_FORK_MAX_GROUPS */
+    kr_fork_group groups[KR_FORK_MAX_GROUPS];
+} kr_fork_plan;
+int kr_kv_fork(kr_bf16* kcache, kr_bf16* vtcache, int64_t k_layer_stride, int64_t k_slot_stride, int64_t k_head_stride,
+               int64_t vt_layer_stride, int64_t vt_slot_stride, int64_t vt_head_stride, int layers, int kv_heads, int hd,
+               int slots, int s_max, const kr_fork_plan* plan, kr_stream s);
 
 /* Greedy sampling from the ARGMAX partials + per-step bookkeeping: token -> tokens_out[b] and
  * history[(ctx_len[b] + 1 - prompt_len[b]) * hist_stride + b] (= this sequence's generated-token

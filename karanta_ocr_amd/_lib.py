@@ -88,6 +88,7 @@ SIGNATURES = {
     "kr_logits_restore": [c_p, i64, i32, c_p, c_p, c_p, i32, c_p],
     "kr_stop_tokens": [c_p, c_p, c_p, c_p, c_p, i32, i32, c_p],
     "kr_guide_advance": [c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, c_p],
+    "kr_kv_fork": [c_p, c_p, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, c_p, c_p],
     "kr_logprobs_topk": [c_p, i64, i32, i32, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, c_p],
     "kr_linear_decode_narrow": [i32, c_p, i64, c_p, i32, c_p, i64, c_p, c_p, c_p, f32, c_p, i64, c_p, c_p, i64,
                                 i32, i32, i32, i32, i32, c_p, i32, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, c_p, c_p],
@@ -140,6 +141,32 @@ class Dec32(C.Structure):
                 ("group_split", C.c_int32), ("reserved0", C.c_int32), ("zero_ptr", c_p), ("zero_bytes", C.c_uint64),
                 ("cs_table", c_p), ("cs_stride", C.c_int32), ("prompt_len", c_p), ("ctx_len", c_p),
                 ("q_out", c_p), ("kcache", c_p), ("vtcache", c_p), ("heads", C.c_int32), ("kv_heads", C.c_int32), ("s_max", C.c_int32)]
+
+
+FORK_MAX_GROUPS = FORK_MAX_SLOTS = 32    # KR_FORK_MAX_GROUPS / KR_FORK_MAX_SLOTS
+
+
+class ForkGroup(C.Structure):
+    """kr_fork_group (include/karanta_hip.h)."""
+    _fields_ = [("src", C.c_int32), ("n_tokens", C.c_int32), ("n_dst", C.c_int32), ("dst", C.c_int32 * FORK_MAX_SLOTS)]
+
+
+class ForkPlan(C.Structure):
+    """kr_fork_plan (include/karanta_hip.h): what kr_kv_fork copies."""
+    _fields_ = [("n_groups", C.c_int32), ("groups", ForkGroup * FORK_MAX_GROUPS)]
+
+
+def fork_plan(groups):
+    """A kr_fork_plan* from [(source slot, n_tokens, [destination slots]), ...].  Like kr_narrow_opts it is read during the call
+    only.  What the struct cannot hold (too many groups / destinations) is passed on as a count the library rejects."""
+    p = ForkPlan()
+    p.n_groups = len(groups) if len(groups) <= FORK_MAX_GROUPS else -1
+    for g, (src, n_tokens, dst) in zip(p.groups, groups):
+        g.src, g.n_tokens = int(src), int(n_tokens)
+        g.n_dst = len(dst) if len(dst) <= FORK_MAX_SLOTS else -1
+        for i, j in enumerate(list(dst)[:FORK_MAX_SLOTS]):
+            g.dst[i] = int(j)
+    return C.byref(p)
 
 
 ABI_MAJOR = 4              # include/karanta_hip.h KR_ABI_VERSION / 100: the header this binding was written against

@@ -66,6 +66,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--admit-max-wait", type=int, default=48, help="... but at most this many scheduler steps of 2 decode steps")
     ap.add_argument("--quantization", default=None, choices=("fp8",),
                     help="decoder Linears as fp8 codes + row scales (vLLM's flag; implied by a checkpoint with a quantization_config)")
+    ap.add_argument("--enable-prefix-caching", action="store_true",
+                    help="vLLM's flag: a request whose whole prompt (ids, grids, image bytes) is still resident in a decode slot "
+                         "starts from that slot's KV rows, without ViT or prefill (continuous mode)")
     ap.add_argument("--max-logprobs", type=int, default=None,
                     help="record log-probabilities in the decode graph: the largest top_logprobs a request may ask for (0..20)")
     return ap
@@ -186,7 +189,8 @@ def make_server(args, log=print):
                          upload_device=None if args.host_images else "cuda:0")
     return LocalServer(eng, front, served_model_name=args.served_model_name, log=log, continuous=not args.static_batching,
                        max_tokens_cap=min(args.max_tokens_cap, args.max_model_len), honor_temperature=not args.greedy,
-                       max_logprobs=args.max_logprobs, admit_min=args.admit_min, admit_max_wait=args.admit_max_wait)
+                       max_logprobs=args.max_logprobs, admit_min=args.admit_min, admit_max_wait=args.admit_max_wait,
+                       prefix_cache=bool(getattr(args, "enable_prefix_caching", False)))
 
 
 def main(argv: Optional[List[str]] = None, make=make_server, on_ready=None) -> int:

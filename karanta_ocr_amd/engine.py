@@ -11,6 +11,7 @@ prompt each, any mix of sizes); pages of different requests never interact (SURV
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import math
 import os
@@ -24,7 +25,7 @@ import torch
 from . import image_processing as IP
 from . import positions as POS
 from ._lib import (ADJ_CAP, DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_GELU_ERF, EPI_NONE, EPI_QUICK_GELU, EPI_SILU_MUL8,
-                   KarantaHipError, lib, narrow_opts, ptr)
+                   KarantaHipError, fork_plan, lib, narrow_opts, ptr)
 from .config import ModelConfig
 from .sampling import StepFeatures, adjust_table, has_penalties, needs_processing, sampling_params, temperature
 from .weights import pack_w16x64, to_bf16_bits
@@ -257,11 +258,34 @@ class PageRequest:
     logit_bias: Optional[Dict[int, float]] = None   # token id -> value added to its logit (fp32)
     min_tokens: int = 0                        # while fewer tokens are generated, EOS and the stop_token_ids cannot be chosen
     stop_token_ids: Tuple[int, ...] = ()       # a generated token among these ends the sequence as EOS does
+    # parallel sampling (OpenAI's n): the page starts n sequences, exactly what n copies of it with seeds (seed + c) & 0xFFFFFFFF,
+    # c = 0..n-1, start (vLLM's seeds for the children of a seeded request) — but its images go through the ViT once and its
+    # prompt through the prefill once; the siblings' KV rows are copies of child 0's (kr_kv_fork)
+    n: int = 1
+
+
+def children(pages) -> list:
+    """The sequences a batch of pages starts, page-major with a page's children consecutive: the page itself for n = 1, else n
+    copies with n = 1 and seeds (seed + c) & 0xFFFFFFFF.  This is the row order of every per-sequence list of the engine."""
+    rows = []
+    for p in pages:
+        n = getattr(p, "n", 1)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise KarantaHipError(f"PageRequest.n must be an integer >= 1, not {n!r}")
+        if n == 1:
+            rows.append(p)
+            continue
+        for c in range(int(n)):
+            ch = copy.copy(p)
+            ch.n, ch.seed = 1, (int(getattr(p, "seed", 0) or 0) + c) & 0xFFFFFFFF
+            rows.append(ch)
+    return rows
 
 
 @dataclass
 class GenerateResult:
-    tokens: List[np.ndarray]          # per page: generated ids (EOS included, nothing after it)
+    """Per-sequence lists hold sum(n) entries: page-major, a page's n children consecutive (`children`)."""
+    tokens: List[np.ndarray]          # per sequence: generated ids (EOS included, nothing after it)
     finish_reasons: List[str]         # "stop" | "length"
     prompt_tokens: List[int]
     timings: Dict[str, float]
@@ -334,6 +358,11 @@ class Admission:
     procs: Optional[list] = None       # Engine._control_rows
     adjs: Optional[list] = None        # Engine._adjust_rows
     need: StepFeatures = StepFeatures()
+    # parallel sampling: B / slots / lens / last_rows / cs count SEQUENCES (children); the prefill (M, src, cos, sin, plan) covers
+    # every page once, in child 0's slot, and `forks` names what kr_kv_fork copies afterwards
+    n_pages: int = 0
+    rows: list = field(default_factory=list)    # `children` of the admission's pages, made once per admission
+    forks: list = field(default_factory=list)   # (source slot, prompt length, [sibling slots]) per page with n > 1
 
 
 class Engine:
@@ -556,6 +585,11 @@ class Engine:
         self.d_eos = torch.tensor(list(self.cfg.eos_token_ids), dtype=torch.int32, device=dev)
         self.d_invfreq = torch.from_numpy(POS.rope_inv_freq(t.head_dim, t.rope_theta)).to(dev)
         self.d_last = z(B, dtype=torch.int32)
+        # per slot the hidden row of its prompt's last token (written at every admission) and, on the host, the length of the
+        # prompt whose KV rows the slot holds: what admit_reuse starts a sequence from without ViT or prefill
+        self.d_prompt_x = z(B, t.hidden_size)
+        self._slot_plen = [0] * B
+        self.pages_prefilled = self.sequences_started = self.sequences_forked = self.sequences_reused = 0
         torch.cuda.synchronize(dev)
 
     @staticmethod
@@ -965,28 +999,36 @@ class Engine:
         """Cache rows one sequence may use: prompt + generated tokens (slot mode keeps the last row as the parking row)."""
         return self.s_max - (1 if self._freeze_finished else 0)
 
-    def _prefill_prepare(self, pages: Sequence[PageRequest], n_image_tokens_total: int, slots: Optional[Sequence[int]] = None,
-                         budgets: Optional[Sequence[int]] = None) -> Admission:
+    def _prefill_prepare(self, pages: Sequence[PageRequest], n_image_tokens_total: Optional[int], slots: Optional[Sequence[int]] = None,
+                         budgets: Optional[Sequence[int]] = None, rows: Optional[list] = None) -> Admission:
         """Host side of `prefill` (numpy only: token sources, M-RoPE tables of the prompt and of every decode position,
         the varlen attention plan).  `generate` runs it while the ViT launches are still executing.
         ``budgets``: per page, the number of tokens it may generate (slot mode: its max_tokens + the scheduler's chunk
         overshoot); default: the current request's max_new_tokens.  The bound is each page's OWN prompt + budget — not
-        the engine-wide history size, which only grows."""
+        the engine-wide history size, which only grows.
+        ``slots`` and ``budgets`` hold one entry per SEQUENCE (sum of the pages' n, `children` order); the prompt tables and the
+        attention plan cover every page once, in the slot of its child 0.  ``n_image_tokens_total`` None (admit_reuse): nothing
+        will be prefilled, so neither the image rows nor the prompt-token limit are checked.  ``rows``: `children(pages)` where the
+        caller has made them already."""
         cfg, t = self.cfg, self.cfg.text
-        B = len(pages)
+        rows = children(pages) if rows is None else rows
+        ns = [int(getattr(p, "n", 1)) for p in pages]
+        first = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)     # row of every page's child 0
+        B = len(rows)
         whole_batch = slots is None
         slots = list(range(B)) if whole_batch else [int(j) for j in slots]
         if len(slots) != B or len(set(slots)) != B or min(slots) < 0 or max(slots) >= self.B:
             raise KarantaHipError(f"slots {slots} do not name {B} distinct slots below {self.B}")
-        lens = [int(len(p.input_ids)) for p in pages]
-        M = sum(lens)
-        if M > self.max_tokens:
+        page_lens = [int(len(p.input_ids)) for p in pages]
+        lens = [int(len(p.input_ids)) for p in rows]
+        M = sum(page_lens)
+        if n_image_tokens_total is not None and M > self.max_tokens:
             raise KarantaHipError(f"{M} prompt tokens > max_prompt_tokens {self.max_tokens}")
         if budgets is None:
             budgets = [self._req_max_new] * B
         if len(budgets) != B or max(budgets) > self.max_new:
-            raise KarantaHipError(f"budgets {list(budgets)} do not fit {B} pages / the history of {self.max_new} tokens")
-        self._check_budgets(pages, budgets)
+            raise KarantaHipError(f"budgets {list(budgets)} do not fit {B} sequences / the history of {self.max_new} tokens")
+        self._check_budgets(rows, budgets)
         src = np.empty(M, np.int32)
         cos = np.empty((M, t.head_dim), np.float32)
         sin = np.empty((M, t.head_dim), np.float32)
@@ -1004,14 +1046,14 @@ class Engine:
             pos3, delta = POS.rope_index_one(ids, pg.grids, cfg.image_token_id, cfg.vision.spatial_merge_size)
             c, sn = POS.mrope_tables(pos3, t.head_dim, t.rope_theta, t.mrope_section)
             cos[off:off + len(ids)], sin[off:off + len(ids)] = c, sn
-            deltas[b] = delta
+            deltas[first[b]:first[b + 1]] = delta
             off += len(ids)
             img_off += k
-        if img_off != n_image_tokens_total:
+        if n_image_tokens_total is not None and img_off != n_image_tokens_total:
             raise KarantaHipError(f"Image features and image tokens do not match, tokens: {img_off}, "
                                   f"features: {n_image_tokens_total}")
-        plan = POS.prefill_attn_plan(lens, slots, t.num_kv_heads, self.s_max)
-        last_rows = (np.cumsum(lens) - 1).astype(np.int32)
+        plan = POS.prefill_attn_plan(page_lens, [slots[f] for f in first[:-1]], t.num_kv_heads, self.s_max)
+        last_rows = np.repeat(np.cumsum(page_lens) - 1, ns).astype(np.int32)
         # rotary table of every decode position of every sequence: pos = P + k + delta (all three
         # M-RoPE axes equal for generated text, TF:1124-1136), cos/sin rounded to bf16 (TF:169)
         kk = np.arange(self.max_new, dtype=np.int64)
@@ -1020,15 +1062,17 @@ class Engine:
             p1 = lens[b] + kk + int(deltas[b])
             c_, s_ = POS.mrope_tables(np.stack([p1, p1, p1]), t.head_dim, t.rope_theta, t.mrope_section)
             cs[b, :, : t.head_dim // 2], cs[b, :, t.head_dim // 2:] = c_[:, : t.head_dim // 2], s_[:, : t.head_dim // 2]
-        return Admission(B, slots, whole_batch, lens, M, src, cos, sin, deltas, plan, last_rows, cs, n_image_tokens_total)
+        forks = [(slots[first[i]], page_lens[i], slots[first[i] + 1:first[i + 1]]) for i in range(len(pages)) if ns[i] > 1]
+        return Admission(B, slots, whole_batch, lens, M, src, cos, sin, deltas, plan, last_rows, cs, n_image_tokens_total,
+                         n_pages=len(pages), rows=rows, forks=forks)
 
     def _vit_and_prepare(self, pages: Sequence[PageRequest], pixel_values_device=None, slots: Optional[Sequence[int]] = None,
-                         budgets: Optional[Sequence[int]] = None) -> Admission:
+                         budgets: Optional[Sequence[int]] = None, rows: Optional[list] = None) -> Admission:
         """Front of every admission: the pages' images through the ViT (launches only), then the host tables of the prefill
         while those launches execute."""
         pix = self._pixels_for(pages, pixel_values_device)
         n_img_tok = self.vit_forward(pix, [g for p in pages for g in p.grids]).shape[0] if pix is not None else 0
-        return self._prefill_prepare(pages, n_img_tok, slots, budgets)
+        return self._prefill_prepare(pages, n_img_tok, slots, budgets, rows)
 
     def prefill(self, pages: Sequence[PageRequest], n_image_tokens_total: int, slots: Optional[Sequence[int]] = None,
                 defer_activation: bool = False, adm: Optional[Admission] = None) -> Admission:
@@ -1043,17 +1087,14 @@ class Engine:
         t, L, s, w = self.cfg.text, self.L, self.s, self.w
         if adm is None or adm.n_img != n_image_tokens_total:
             adm = self._prefill_prepare(pages, n_image_tokens_total, slots)
-        adm.need = self._admit_features(pages)
+        rows = adm.rows
+        adm.need = self._admit_features(rows)
         M, d = adm.M, t.hidden_size
         with torch.cuda.stream(self.stream):
             self._h2d(self.p_src, adm.src)
             self._h2d(self.p_cos, adm.cos)
             self._h2d(self.p_sin, adm.sin)
-            adm.temps = np.asarray([temperature(p) for p in pages], np.float32)
-            adm.seeds = np.asarray([int(getattr(p, "seed", 0) or 0) & 0xFFFFFFFF for p in pages], np.uint32).view(np.int32)
-            adm.guides = self._guide_rows(pages)
-            adm.procs = self._control_rows(pages)
-            adm.adjs = self._adjust_rows(pages)
+            self._sampler_rows(adm, rows)
             if not defer_activation:
                 self._write_state(adm)
             self._h2d(self.d_last, adm.last_rows)
@@ -1070,9 +1111,29 @@ class Engine:
                 L.kr_rmsnorm(ptr(self.p_x), d, ptr(w.view(p + "ln2.w")), ptr(self.p_h), M, d, t.rms_norm_eps, s)
                 self._gemm(self.p_h, w.view(p + "gate_up.w"), self.p_act, M, epi=EPI_SILU_MUL8, packed=True, **self._w8kw(p + "gate_up.w"))
                 self._gemm(self.p_act, w.view(p + "down.w"), self.p_x, M, res=self.p_x, packed=True, **self._w8kw(p + "down.w"))
+            self.pages_prefilled += adm.n_pages
             if not defer_activation:
+                self._fork(adm.forks)
                 self._first_tokens(adm)
         return adm
+
+    def _sampler_rows(self, adm: Admission, rows):
+        """What the sampler keeps per sequence, from the admission's sequences (`children` of its pages)."""
+        adm.temps = np.asarray([temperature(p) for p in rows], np.float32)
+        adm.seeds = np.asarray([int(getattr(p, "seed", 0) or 0) & 0xFFFFFFFF for p in rows], np.uint32).view(np.int32)
+        adm.guides = self._guide_rows(rows)
+        adm.procs = self._control_rows(rows)
+        adm.adjs = self._adjust_rows(rows)
+
+    def _fork(self, groups):
+        """kr_kv_fork: the prompt's KV rows of every (source slot, prompt length, [destination slots]), in one launch on the
+        engine's current stream."""
+        if not groups:
+            return
+        t, kc, vc = self.cfg.text, self.kcache, self.vtcache
+        self.L.kr_kv_fork(ptr(kc), ptr(vc), kc.stride(0), kc.stride(1), kc.stride(2), vc.stride(0), vc.stride(1), vc.stride(2),
+                          t.num_layers, t.num_kv_heads, t.head_dim, self.B, self.s_max, fork_plan(groups), self.s)
+        self.sequences_forked += sum(len(g[2]) for g in groups)
 
     def _admit_features(self, pages) -> StepFeatures:
         """What an admission's pages need: raises where the mode does not allow it, else the next steps carry it (from this
@@ -1124,6 +1185,9 @@ class Engine:
         with zeros to max_batch rows.  Slots: one-row copies into the named slots only, the others keep decoding."""
         gt, gm, gs, dgs = zip(*a.guides)
         lens = np.asarray(a.lens, np.int32)
+        for j, n in zip(a.slots, a.lens):
+            self._slot_plen[j] = int(n)
+        self.sequences_started += a.B
         sampler = ((self.d_temp, a.temps), (self.d_seed, a.seeds))
         fields = ((self.d_gtrans, np.asarray(gt, np.int64)), (self.d_gmasks, np.asarray(gm, np.int64)),
                   (self.d_gstate, np.asarray(gs, np.int32)), (self.d_delta, a.deltas),
@@ -1167,10 +1231,12 @@ class Engine:
 
     def _first_tokens(self, a: Admission):
         """Last prompt position of every prefilled sequence (p_x rows d_last) -> its slot's x -> lm_head -> first token: the
-        whole batch in one pass, slots one by one."""
+        whole batch in one pass, slots one by one.  The children of a page read the same row.  The row is also kept per slot
+        (d_prompt_x): what admit_reuse starts a later sequence on the same prompt from."""
         d = self.cfg.text.hidden_size
         for b, j, n in ((0, 0, a.B),) if a.whole_batch else ((b, j, 1) for b, j in enumerate(a.slots)):
             self.L.kr_embed_scatter(ptr(self.d_last[b:]), ptr(self.p_x), 0, ptr(self.d_x[j:]), n, d, self.s)
+            self.L.kr_embed_scatter(ptr(self.d_last[b:]), ptr(self.p_x), 0, ptr(self.d_prompt_x[j:]), n, d, self.s)
             self._lm_head_and_sample(n, slot0=j)
 
     def _lm_head_and_sample(self, B: int, x=None, slot0: int = 0):
@@ -1433,7 +1499,8 @@ class Engine:
         every sampling step the NEXT step's input embedding is replaced by that of the given token, while `tokens` /
         `logits` still report the engine's own argmax and logits.  With a reference's tokens as the forced sequence
         every step can be compared with the reference, also past a near-tie where free-running sequences part."""
-        B = len(pages)
+        rows = children(pages)            # the batch's sequences: a page with n > 1 stands for n of them
+        B = len(rows)
         if not 1 <= B <= self.B:
             raise KarantaHipError(f"batch {B} not in 1..{self.B}")
         if max_new_tokens < 1:
@@ -1442,18 +1509,18 @@ class Engine:
         self._ignore_eos = bool(ignore_eos)
         self._freeze_finished = False
         self._want_logits = bool(return_logits)
-        self._caps = self._step = StepFeatures.of(pages)
-        if force_tokens is not None and any(has_penalties(p) for p in pages):
+        self._caps = self._step = StepFeatures.of(rows)
+        if force_tokens is not None and any(has_penalties(p) for p in rows):
             raise KarantaHipError("force_tokens with repetition / frequency / presence penalties: the output counts would follow "
                                   "the engine's own tokens, not the forced ones")
-        ks = [int(p.logprobs) for p in pages if getattr(p, "logprobs", None) is not None]
+        ks = [int(p.logprobs) for p in rows if getattr(p, "logprobs", None) is not None]
         if ks and not 0 <= max(ks) <= 20:
             raise KarantaHipError("logprobs must be in 0..20")
         self._logprobs = max(ks) if ks else None
         self._last_batch = B
         self._ensure_history(max_new_tokens)
         self._req_max_new = int(max_new_tokens)
-        adm = self._vit_and_prepare(pages, pixel_values_device)
+        adm = self._vit_and_prepare(pages, pixel_values_device, rows=rows)
         self.stream.synchronize()
         t1 = time.perf_counter()
         lens = self.prefill(pages, adm.n_img, adm=adm).lens
@@ -1513,7 +1580,7 @@ class Engine:
             row = hist[b]
             cut, reason = len(row), "length"
             if not ignore_eos:       # a row's own stop ids end it as EOS does (kr_stop_tokens)
-                hit = np.flatnonzero(np.isin(row, list(eos | set(int(x) for x in getattr(pages[b], "stop_token_ids", None) or ()))))
+                hit = np.flatnonzero(np.isin(row, list(eos | set(int(x) for x in getattr(rows[b], "stop_token_ids", None) or ()))))
                 if hit.size:
                     cut, reason = int(hit[0]) + 1, "stop"
             toks.append(row[:cut].astype(np.int64))
@@ -1523,7 +1590,7 @@ class Engine:
             lp = self.d_lp[:steps_done, :B].cpu().numpy()
             li = self.d_lpi[:steps_done, :B].cpu().numpy()
             lps = []
-            for b, p in enumerate(pages):
+            for b, p in enumerate(rows):
                 k = getattr(p, "logprobs", None)
                 n = len(toks[b]) - (1 if reasons[b] == "stop" else 0)   # the EOS step records nothing
                 lps.append(None if k is None else {"token": lp[:n, b, 0].copy(), "top": lp[:n, b, 1:1 + int(k)].copy(),
@@ -1577,9 +1644,47 @@ class Engine:
     def admit(self, pages: Sequence[PageRequest], slots: Sequence[int], budgets: Optional[Sequence[int]] = None) -> List[int]:
         """ViT + prefill of new requests into idle slots; their first token is sampled.  Returns prompt lengths.
         ``budgets``: tokens each page may generate before the host retires it (its max_tokens + the chunk overshoot)."""
-        self._check_budgets(pages, budgets)       # before any launch: an oversized page fails the call, nothing ran
-        adm = self._vit_and_prepare(pages, None, slots, budgets)
+        rows = children(pages)
+        self._check_budgets(rows, budgets)       # before any launch: an oversized page fails the call, nothing ran
+        adm = self._vit_and_prepare(pages, None, slots, budgets, rows)
         return self.prefill(pages, adm.n_img, slots=slots, adm=adm).lens
+
+    def admit_reuse(self, pages: Sequence[PageRequest], srcs: Sequence[int], slots: Sequence[int],
+                    budgets: Optional[Sequence[int]] = None) -> List[int]:
+        """Start sequences from prompts that are already resident: pages[i] from the KV rows and the last-token hidden row that
+        an earlier admission of the SAME prompt left in slot srcs[i] — no ViT, no prefill.  ``slots`` / ``budgets``: one entry per
+        sequence as in `admit` (a page's n children consecutive).  A sequence whose slot is its source is re-activated in place;
+        the others get the prompt's rows by one kr_kv_fork (the source may be decoding: its rows below the prompt length never
+        change).  Runs on the decode stream only.  The caller vouches that srcs[i] holds this page's prompt; what the engine
+        can check is its length.  Returns prompt lengths per sequence."""
+        rows = children(pages)
+        self._check_budgets(rows, budgets)
+        srcs, slots = [int(j) for j in srcs], [int(j) for j in slots]
+        if len(srcs) != len(pages) or any(not 0 <= j < self.B for j in srcs):
+            raise KarantaHipError(f"srcs {srcs} do not name one slot below {self.B} per page")
+        for p, j in zip(pages, srcs):
+            if self._slot_plen[j] < 1 or self._slot_plen[j] != len(p.input_ids):
+                raise KarantaHipError(f"slot {j} holds a prompt of {self._slot_plen[j]} tokens, the page has {len(p.input_ids)}")
+        adm = self._prefill_prepare(pages, None, slots, budgets, rows)
+        src_of = [j for p, j in zip(pages, srcs) for _ in range(int(getattr(p, "n", 1)))]
+        if any(j != sj and j in srcs for j, sj in zip(slots, src_of)):
+            raise KarantaHipError(f"slots {slots}: a destination is another page's source {srcs}")
+        if len(set(srcs)) != len(srcs):
+            raise KarantaHipError(f"srcs {srcs}: one call reuses a slot once (give the page n > 1)")
+        groups = [(sj, len(p.input_ids), [j for j, s2 in zip(slots, src_of) if s2 == sj and j != sj]) for p, sj in zip(pages, srcs)]
+        groups = [g for g in groups if g[2]]
+        adm.need = self._admit_features(rows)
+        with torch.cuda.stream(self.stream):
+            self._sampler_rows(adm, rows)
+            self._fork(groups)
+            self._write_state(adm)
+            for j, sj in zip(slots, src_of):
+                if j != sj:
+                    self.d_prompt_x[j].copy_(self.d_prompt_x[sj])
+                self.d_x[j].copy_(self.d_prompt_x[j])
+                self._lm_head_and_sample(1, slot0=j)
+        self.sequences_reused += len(rows)
+        return adm.lens
 
     def _check_budgets(self, pages, budgets):
         room = self.seq_room()
@@ -1596,7 +1701,8 @@ class Engine:
     # write then cannot land inside the rows the prefill is filling); the slot state and the first sampling step are
     # applied on the decode stream once the admission stream has finished.
     def admit_begin(self, pages: Sequence[PageRequest], slots: Sequence[int], budgets: Optional[Sequence[int]] = None):
-        self._check_budgets(pages, budgets)
+        rows = children(pages)
+        self._check_budgets(rows, budgets)
         slots = [int(j) for j in slots]
         if self._adm_stream is None:
             if self.admission_cus > 0:
@@ -1618,7 +1724,7 @@ class Engine:
         main = (self.stream, self.s)
         self.stream, self.s = self._adm_stream, self._adm_stream.cuda_stream
         try:
-            adm = self._vit_and_prepare(pages, None, slots, budgets)
+            adm = self._vit_and_prepare(pages, None, slots, budgets, rows)
             rec = self.prefill(pages, adm.n_img, slots=slots, defer_activation=True, adm=adm)
             done = torch.cuda.Event()
             done.record(self._adm_stream)
@@ -1638,6 +1744,7 @@ class Engine:
         # the first tokens are sampled with the passes this admission needs, whatever set_step_features did since admit_begin
         self._step |= rec.need
         with torch.cuda.stream(self.stream):
+            self._fork(rec.forks)         # on the decode stream: never beside the decode graph
             self._write_state(rec)
             self._first_tokens(rec)
         return rec.lens

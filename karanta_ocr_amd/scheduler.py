@@ -7,6 +7,11 @@ its slot, and the next waiting request is prefilled into that slot while the oth
 instead of the whole batch waiting for its longest member (`Engine.generate`, static batching).  A request's own
 `stop_token_ids` end it on the device as EOS does; its stop strings (`SlotRequest.stop_check`) are looked for at each harvest.
 
+A request whose page asks for `n` sequences takes n slots at once (one ViT + prefill, the siblings' KV rows forked from child 0's
+slot: `Engine.admit`); its children end one by one, each freeing its slot, and its one result carries them as `choices`.  With
+`prefix_cache=True` a request whose `prompt_key` names a prompt still resident in a slot starts from that slot's rows
+(`Engine.admit_reuse`): no ViT, no prefill.
+
 Only the host logic lives here; it drives `Engine.begin_slots / admit / decode_steps / poll_slots / slot_tokens /
 retire`, and any object with those six methods (the CPU tests use a fake) can stand in for the engine.
 """
@@ -31,6 +36,11 @@ class SlotRequest:
     # stop strings: called at every harvest with the tokens generated so far; returns how many to keep (through the token that
     # completed a match) or None.  Requests without one cause no token reads before they finish.
     stop_check: Optional[Callable[[np.ndarray], Optional[int]]] = None
+    # n > 1: matchers keep state between calls, so such a request carries one per child (child c: stop_checks[c])
+    stop_checks: Optional[Sequence[Callable[[np.ndarray], Optional[int]]]] = None
+    # SlotScheduler(prefix_cache=True): identifies the whole prompt (token ids, grids, image bytes); requests with equal keys
+    # share the prompt's KV rows while a slot still holds them
+    prompt_key: Optional[bytes] = None
 
 
 @dataclass
@@ -43,6 +53,13 @@ class SlotResult:
     request: Optional[SlotRequest] = None   # the request this answers
     status: int = 500                       # HTTP-style class of `error`: 400 = the request itself cannot be served
     logprobs: Optional[Dict[str, np.ndarray]] = None   # when the page asked for them (Engine.slot_logprobs)
+    # page.n > 1: one SlotResult per child, in child order (the fields above are child 0's); None for n == 1
+    choices: Optional[List["SlotResult"]] = None
+
+
+def _n(r: SlotRequest) -> int:
+    """Sequences (slots) a request takes; pages without the attribute (older engines, test fakes) take one."""
+    return int(getattr(r.page, "n", 1) or 1)
 
 
 class SlotScheduler:
@@ -52,7 +69,7 @@ class SlotScheduler:
     def __init__(self, engine, max_tokens_cap: int, chunk: int = 8, eos_token_ids: Optional[Sequence[int]] = None,
                  max_prompt_tokens: Optional[int] = None, max_patches: Optional[int] = None, sampling: bool = False,
                  overlap: bool = False, guided: bool = False, logprobs: Optional[int] = None, admit_min: int = 1,
-                 admit_max_wait: int = 4, launch_ahead: bool = True):
+                 admit_max_wait: int = 4, launch_ahead: bool = True, prefix_cache: bool = False):
         if max_tokens_cap < 1 or chunk < 1:
             raise ValueError("max_tokens_cap and chunk must be >= 1")
         self.engine = engine
@@ -62,8 +79,17 @@ class SlotScheduler:
         self.max_prompt_tokens = max_prompt_tokens if max_prompt_tokens is not None else getattr(engine, "max_tokens", None)
         self.max_patches = max_patches if max_patches is not None else getattr(engine, "max_patches", None)
         self.waiting: Deque[SlotRequest] = collections.deque()
-        self.active: Dict[int, SlotRequest] = {}     # slot -> request
+        self.active: Dict[int, SlotRequest] = {}     # slot -> request (a request with n children is in n slots)
         self.prompt_len: Dict[int, int] = {}
+        self._child: Dict[int, int] = {}             # slot -> which child of its request runs there
+        self._open: Dict[int, list] = {}             # id(request) -> its children's results so far (None: still running)
+        # prompt reuse: per slot (key, prompt length) of the prompt whose rows [0, P) it holds — set when an admission has
+        # completed, kept after the request's end, dropped when the slot is given to another prompt — and when the slot's
+        # last sequence ended (cold admissions evict the resident prompt that finished longest ago)
+        self.prefix_cache = bool(prefix_cache) and hasattr(engine, "admit_reuse")
+        self._resident: Dict[int, tuple] = {}
+        self._freed_at: Dict[int, int] = {}
+        self._tick = 0
         # overlap: ViT + prefill of an admission run on a second stream while the other slots keep decoding
         # (Engine.admit_begin / admit_ready / admit_end); one admission in flight at a time
         self.overlap = bool(overlap) and all(hasattr(engine, m) for m in ("admit_begin", "admit_ready", "admit_end"))
@@ -89,6 +115,9 @@ class SlotScheduler:
         self.phase_s = {"admit": 0.0, "decode_launch": 0.0, "harvest": 0.0}
         self.admissions = 0                          # admission rounds that carried pages
         self.pages_admitted = 0
+        self.sequences_admitted = 0                  # sequences started (children counted one by one)
+        self.sequences_forked = 0                    # ... of which from another slot's KV rows, without their own prefill
+        self.prefix_cache_hits = 0                   # requests started by admit_reuse
         self.slot_steps_busy = 0                     # sum over steps of occupied slots (utilisation numerator)
         # a slot may run up to chunk - 1 steps past its limit before the host looks: size the history for that
         # sampling: pages may carry temperature > 0 (the decode graph then includes the Gumbel-max pass)
@@ -199,10 +228,25 @@ class SlotScheduler:
             lens = self.engine.admit_end(handle)
         except Exception as e:
             return [self._failure(r, f"{type(e).__name__}: {e}") for r in batch]
-        for r, j, n in zip(batch, slots, lens):
-            self.active[j] = r
-            self.prompt_len[j] = int(n)
+        self._activate(batch, slots, lens)
         return []
+
+    def _activate(self, batch, slots, lens, cold: bool = True):
+        """The admitted requests' children are in their slots (slots / lens: one entry per sequence, children consecutive)."""
+        k = 0
+        for r in batch:
+            n = _n(r)
+            self._open[id(r)] = [None] * n
+            for c in range(n):
+                j = slots[k]
+                self.active[j], self._child[j], self.prompt_len[j] = r, c, int(lens[k])
+                self._adm_seq[j] = self._snap_seq    # snapshots taken from now on see this request in the slot
+                if self.prefix_cache and r.prompt_key is not None:
+                    self._resident[j] = (r.prompt_key, int(lens[k]))
+                k += 1
+            self.sequences_admitted += n
+            if cold:
+                self.sequences_forked += n - 1
 
     def run(self, requests: Iterable[SlotRequest]) -> List[SlotResult]:
         """All requests to completion; results in submission order."""
@@ -222,9 +266,11 @@ class SlotScheduler:
 
     # ------------------------------------------------------------------ internals
     def _admit(self, begin_only: bool = False) -> List[SlotResult]:
-        free = [j for j in range(self.n_slots) if j not in self.active]
+        # cold admissions take free slots without a resident prompt first, then the one whose prompt finished longest ago
+        free = sorted((j for j in range(self.n_slots) if j not in self.active),
+                      key=lambda j: (j in self._resident, self._freed_at.get(j, 0) if j in self._resident else 0, j))
         if self.active and self.waiting and free and self.admit_min > 1:
-            ready = min(len(free), len(self.waiting))
+            ready = min(len(free), sum(_n(r) for r in self.waiting))     # in slots
             if ready < min(self.admit_min, self.n_slots) and self._held < self.admit_max_wait:
                 self._held += 1
                 return []
@@ -234,8 +280,14 @@ class SlotScheduler:
         patch_budget = self.max_patches
         failed: List[SlotResult] = []
         room = self.engine.seq_room() if hasattr(self.engine, "seq_room") else None
-        while self.waiting and len(batch) < len(free):
+        slots: List[int] = []                        # of the batch's sequences, children consecutive
+        while self.waiting and free:
             r = self.waiting[0]
+            n_seq = _n(r)
+            if n_seq > self.n_slots:
+                self.waiting.popleft()
+                failed.append(self._failure(r, f"n = {n_seq} exceeds the server's {self.n_slots} slots", status=400))
+                continue
             n_tok = int(len(r.page.input_ids))
             if room is not None and n_tok + self._budget(r) > room:
                 # its own prompt + max_tokens (+ the chunk overshoot) exceed a sequence's cache rows: this request fails
@@ -243,6 +295,18 @@ class SlotScheduler:
                 self.waiting.popleft()
                 failed.append(self._failure(r, f"prompt ({n_tok} tokens) + max_tokens ({min(int(r.max_tokens), self.cap)}) + "
                                                f"{self.over} scheduler steps exceed the sequence capacity {room}", status=400))
+                continue
+            hit = self._resident_slot(r, free)
+            if hit is not None:
+                # resident prompt: no ViT, no prefill.  In place when that slot is free, else forked from it
+                src, in_place = hit
+                if n_seq > len(free):
+                    break
+                self.waiting.popleft()
+                if in_place:
+                    free.remove(src)
+                mine = ([src] if in_place else []) + [free.pop(0) for _ in range(n_seq - (1 if in_place else 0))]
+                failed += self._admit_reuse(r, src, mine)
                 continue
             n_patch = sum(int(np.prod(g)) for g in getattr(r.page, "grids", None) or [])   # from the grids: pages may
             #                                                    carry uint8 images (GPU front end) instead of patches
@@ -257,31 +321,54 @@ class SlotScheduler:
                                                 status=400))
                     continue
                 break  # fits an emptier admission round
+            if n_seq > len(free):
+                break  # FIFO: the head waits for its slots and nothing overtakes it
             self.waiting.popleft()
             batch.append(r)
+            for _ in range(n_seq):
+                j = free.pop(0)
+                self._resident.pop(j, None)          # the slot is given to another prompt
+                slots.append(j)
             if tok_budget is not None:
                 tok_budget -= n_tok
             if patch_budget is not None:
                 patch_budget -= n_patch
         if batch and begin_only:
-            slots = free[:len(batch)]
             try:
                 self._inflight = (self.engine.admit_begin([r.page for r in batch], slots, **self._budget_kw(batch)), batch, slots)
             except Exception as e:
                 return failed + [self._failure(r, f"{type(e).__name__}: {e}") for r in batch]
         elif batch:
-            slots = free[:len(batch)]
             try:
                 lens = self.engine.admit([r.page for r in batch], slots, **self._budget_kw(batch))
             except Exception as e:  # the admission as a whole failed: none of these requests entered a slot
                 return failed + [self._failure(r, f"{type(e).__name__}: {e}") for r in batch]
-            for r, j, n in zip(batch, slots, lens):
-                self.active[j] = r
-                self.prompt_len[j] = int(n)
-                self._adm_seq[j] = self._snap_seq    # snapshots taken from now on see this request in the slot
+            self._activate(batch, slots, lens)
             self.admissions += 1
             self.pages_admitted += len(batch)
         return failed
+
+    def _resident_slot(self, r: SlotRequest, free) -> Optional[tuple]:
+        """(slot that holds the request's prompt, whether the request can run there in place) or None."""
+        if not self.prefix_cache or r.prompt_key is None:
+            return None
+        want = (r.prompt_key, int(len(r.page.input_ids)))
+        held = [j for j, e in self._resident.items() if e == want]
+        idle = [j for j in held if j in free]
+        return (idle[0], True) if idle else (held[0], False) if held else None
+
+    def _admit_reuse(self, r: SlotRequest, src: int, slots: List[int]) -> List[SlotResult]:
+        for j in slots:
+            if j != src:
+                self._resident.pop(j, None)
+        try:
+            lens = self.engine.admit_reuse([r.page], [src], slots, **self._budget_kw([r]))
+        except Exception as e:
+            return [self._failure(r, f"{type(e).__name__}: {e}")]
+        self._activate([r], slots, lens, cold=False)
+        self.prefix_cache_hits += 1
+        self.sequences_forked += sum(1 for j in slots if j != src)
+        return []
 
     def _budget(self, r: SlotRequest) -> int:
         """Cache rows a request may write after its prompt: its token limit plus the steps a slot can run past it
@@ -290,7 +377,7 @@ class SlotScheduler:
 
     def _budget_kw(self, batch) -> dict:
         # engines that check capacity per request take the budgets (test fakes without seq_room do not)
-        return {"budgets": [self._budget(r) for r in batch]} if hasattr(self.engine, "seq_room") else {}
+        return {"budgets": [self._budget(r) for r in batch for _ in range(_n(r))]} if hasattr(self.engine, "seq_room") else {}
 
     def _failure(self, r: SlotRequest, msg: str, status: int = 500) -> SlotResult:
         return SlotResult(r.tag, np.zeros(0, np.int64), "length", 0, error=msg, request=r, status=status)
@@ -303,11 +390,12 @@ class SlotScheduler:
         for j in sorted(self.active):
             if seq is not None and self._adm_seq.get(j, 0) > seq:
                 continue
-            r = self.active[j]
+            r, c = self.active[j], self._child.get(j, 0)
+            check = r.stop_checks[c] if r.stop_checks is not None else r.stop_check
             limit = min(int(r.max_tokens), self.cap)
             n = int(min(gen[j], limit))
             over = bool(fin[j] or gen[j] >= limit)
-            if not over and (r.stop_check is None or n < 1):
+            if not over and (check is None or n < 1):
                 continue
             toks = np.asarray(self.engine.slot_tokens(j, n), np.int64)
             reason, on_token = "length", False
@@ -316,8 +404,8 @@ class SlotScheduler:
                 hit = np.flatnonzero(np.isin(toks, list(stops))) if stops else np.zeros(0, np.int64)
                 if hit.size:
                     toks, reason, on_token = toks[: int(hit[0]) + 1], "stop", True
-            if r.stop_check is not None:
-                keep = r.stop_check(toks)
+            if check is not None:
+                keep = check(toks)
                 if keep is not None and keep <= len(toks):
                     on_token = on_token and keep == len(toks)
                     toks, reason = toks[:int(keep)], "stop"
@@ -330,6 +418,17 @@ class SlotScheduler:
             if k is not None and self.logprobs is not None:
                 n_lp = len(toks) - (1 if on_token else 0)     # the step that finishes on EOS / a stop id records nothing
                 lps = self.engine.slot_logprobs(j, n_lp, int(k))
-            out.append(SlotResult(r.tag, toks, reason, self.prompt_len.pop(j), request=r, logprobs=lps))
-            del self.active[j]
+            res = SlotResult(r.tag, toks, reason, self.prompt_len.pop(j), request=r, logprobs=lps)
+            del self.active[j]                       # the child's slot is free for the next admission
+            self._child.pop(j, None)
+            self._tick += 1
+            self._freed_at[j] = self._tick
+            kids = self._open.get(id(r), [None])
+            kids[c] = res
+            if all(k is not None for k in kids):     # the request's last child: its one result
+                self._open.pop(id(r), None)
+                if len(kids) > 1:
+                    res = SlotResult(r.tag, kids[0].tokens, kids[0].finish_reason, kids[0].prompt_tokens, request=r,
+                                     logprobs=kids[0].logprobs, choices=list(kids))
+                out.append(res)
         return out

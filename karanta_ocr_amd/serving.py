@@ -19,7 +19,15 @@ request: caller skips the attempt), 500 (internal error: caller retries).
 vLLM's semantics and validation (sampling.py; kr_sample_threshold / kr_gumbel_argmax_processed); ``honor_temperature=False``
 (``--greedy``) ignores them with the temperature.  ``logit_bias`` / ``min_tokens`` / ``stop_token_ids`` are applied on the device
 (sampling.parse_adjust_fields; kr_logits_adjust / kr_stop_tokens) and ``stop`` strings (``include_stop_str_in_output``) by the
-scheduler between decode chunks (sampling.StopStrings); ``--greedy`` ignores all of these too.  ``n > 1`` is not served.
+scheduler between decode chunks (sampling.StopStrings); ``--greedy`` ignores all of these too.
+``n`` (an integer >= 1; ``n > 1`` needs ``temperature > 0``, as in vLLM; ``best_of`` must equal it): the response carries
+``choices[0..n-1]``, choice c being exactly what the same request with ``n = 1`` and ``seed + c`` returns (without a ``seed``
+the server draws one base seed) — but the images go through the ViT once and the prompt through the prefill once, and the
+children start from copies of its KV rows (kr_kv_fork).  ``usage.prompt_tokens`` counts the prompt once, ``completion_tokens``
+is the sum over the choices.  ``n`` above the server's decode slots is a 400; ``--greedy`` serves ``n`` as 1.
+``--enable-prefix-caching`` (``LocalServer(prefix_cache=True)``, continuous mode): a request whose whole prompt (token ids,
+grids, image bytes) equals one still resident in a decode slot starts from that slot's rows, without ViT or prefill — the
+reference's retry loop (the same page again at a higher temperature, pipeline.py ``process_page``) becomes decode-only.
 ``guided_regex`` / ``response_format`` / ``logprobs``: guided.py, engine.
 
 Prompt text: the checkpoint's own ``chat_template`` when the model directory ships one (``chat_template.json`` /
@@ -28,6 +36,7 @@ hand-coded Qwen2-VL template otherwise.
 """
 from __future__ import annotations
 
+import hashlib
 import json
 import queue
 import threading
@@ -148,6 +157,8 @@ class ParsedRequest:
     stop_token_ids: Tuple[int, ...] = ()
     stop: Tuple[str, ...] = ()
     include_stop_str_in_output: bool = False
+    n: int = 1                      # choices to return (parallel sampling)
+    prompt_key: Optional[bytes] = None   # ChatFrontend(prompt_keys): 16-byte digest of prompt ids, grids and image bytes
 
 
 ADJUST_FIELDS = ("logit_bias", "min_tokens", "stop_token_ids")
@@ -211,6 +222,7 @@ class ChatFrontend:
         self.device_images = bool(device_images)
         self.max_model_len = max_model_len  # reference --max_model_len default (pipeline.py:1225-1230)
         self._guide_cache: Dict[str, Any] = {}   # regex -> guided.Guide (the pipeline sends one pattern for every page)
+        self.prompt_keys = False     # LocalServer(prefix_cache=True) switches it on: parse() computes ParsedRequest.prompt_key
 
     def _upload(self, u8: np.ndarray):
         """HWC uint8 page -> a tensor resident in HBM (Engine.patches_from_images takes it as it is).  The copy blocks this thread
@@ -296,6 +308,13 @@ class ChatFrontend:
         max_tokens = 100 if mt is None else int(mt)
         if max_tokens < 1:
             raise BadRequest("max_tokens must be >= 1")
+        n = req.get("n")
+        n = 1 if n is None else n
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise BadRequest("n must be an integer >= 1")
+        if req.get("best_of") is not None and (isinstance(req["best_of"], bool) or req["best_of"] != n):
+            raise BadRequest("best_of must equal n (only the n returned candidates are generated)")
+        key = hashlib.blake2b(digest_size=16) if self.prompt_keys else None
         ids: List[int] = []
         pvs, grids, images, n_toks = [], [], [], []
         hand = self._template is None        # the hand-coded Qwen2-VL turns; with the checkpoint's own template only the images are
@@ -321,8 +340,10 @@ class ChatFrontend:
                         img = IP.decode_data_url(url)
                     except Exception as e:  # undecodable image -> 400, like vLLM
                         raise BadRequest(f"cannot decode image: {e}") from e
+                    u8 = np.asarray(img.convert("RGB"), dtype=np.uint8) if self.device_images or key is not None else None
+                    if key is not None:          # the decoded host bytes (about 3 MB per page), before any upload
+                        key.update(repr(u8.shape).encode() + u8.tobytes())
                     if self.device_images:
-                        u8 = np.asarray(img.convert("RGB"), dtype=np.uint8)
                         unit = self.cfg.vision.patch_size * self.cfg.vision.spatial_merge_size
                         try:
                             rh, rw = IP.smart_resize(u8.shape[0], u8.shape[1], unit, self.min_pixels, self.max_pixels)
@@ -354,6 +375,8 @@ class ChatFrontend:
             raise BadRequest(f"temperature / seed: {e}") from e
         if not (0.0 <= temperature <= 100.0):   # NaN fails both comparisons
             raise BadRequest("temperature must be in [0, 100]")
+        if n > 1 and temperature == 0.0:
+            raise BadRequest("n must be 1 when using greedy sampling (temperature 0)")
         logprobs = None
         if req.get("logprobs"):
             try:
@@ -371,9 +394,12 @@ class ChatFrontend:
             raise
         except ValueError as e:
             raise BadRequest(str(e)) from e
-        return ParsedRequest(np.asarray(ids, np.int64), np.concatenate(pvs, 0) if pvs else None, grids, max_tokens,
+        ids_arr = np.asarray(ids, np.int64)
+        if key is not None:
+            key.update(ids_arr.tobytes() + repr([tuple(int(x) for x in g) for g in grids]).encode())
+        return ParsedRequest(ids_arr, np.concatenate(pvs, 0) if pvs else None, grids, max_tokens,
                              str(req.get("model", "karantaocr")), temperature, seed, images or None,
-                             guide, logprobs, **controls)
+                             guide, logprobs, n=n, prompt_key=key.digest() if key is not None else None, **controls)
 
 
 # ----------------------------------------------------------------------------- in-process server
@@ -391,7 +417,8 @@ class LocalServer:
     def __init__(self, engine, frontend: ChatFrontend, served_model_name: str = "karantaocr",
                  batch_wait_s: float = 0.005, log=print, continuous: bool = False, max_tokens_cap: int = 4096,
                  chunk: int = 2, honor_temperature: bool = True, max_logprobs: Optional[int] = None, admit_min: int = 1,
-                 admit_max_wait: int = 16, overlap_admissions: bool = False, launch_ahead: bool = True):
+                 admit_max_wait: int = 16, overlap_admissions: bool = False, launch_ahead: bool = True,
+                 prefix_cache: bool = False):
         self.engine, self.frontend, self.name = engine, frontend, served_model_name
         self.honor_temperature = bool(honor_temperature)   # False: every request is served greedy
         # guided decoding needs the tokenizer's byte strings on the device; engines without set_vocab (test fakes)
@@ -409,6 +436,11 @@ class LocalServer:
         # other slots keep decoding (SlotScheduler(overlap=True))
         self.overlap_admissions = bool(overlap_admissions)
         self.launch_ahead = bool(launch_ahead)
+        # prompt reuse (vLLM's --enable-prefix-caching): continuous mode only, engines with admit_reuse; the front end then keys
+        # every request by its whole prompt
+        self.prefix_cache = bool(prefix_cache) and self.continuous and hasattr(engine, "admit_reuse")
+        if self.prefix_cache:
+            frontend.prompt_keys = True
         self._tok_bytes = None       # the tokenizer's byte strings, fetched once for the stop-string matchers
         self._q: "queue.Queue" = queue.Queue()
         self._running = 0
@@ -442,6 +474,8 @@ class LocalServer:
             return None
         return {"decode_steps": sch.steps, "slot_occupancy": round(sch.slot_steps_busy / max(1, sch.steps * sch.n_slots), 4),
                 "admissions": sch.admissions, "pages_admitted": sch.pages_admitted,
+                "sequences_admitted": sch.sequences_admitted, "sequences_forked": sch.sequences_forked,
+                "prefix_cache_hits": sch.prefix_cache_hits,
                 "host_phase_s": {k: round(v, 3) for k, v in sch.phase_s.items()}}
 
     def models(self) -> Tuple[int, dict]:
@@ -460,6 +494,11 @@ class LocalServer:
         if parsed.logprobs is not None and self.continuous and (self.max_logprobs is None or parsed.logprobs > self.max_logprobs):
             return 400, {"error": {"message": f"logprobs: this server records at most {self.max_logprobs} top_logprobs "
                                               "(start it with --max-logprobs)", "type": "BadRequestError", "code": 400}}
+        if not self.honor_temperature:
+            parsed.n = 1                  # --greedy: one greedy candidate, like the other generation controls
+        if parsed.n > int(self.engine.B):
+            return 400, {"error": {"message": f"n = {parsed.n} exceeds this server's {int(self.engine.B)} decode slots",
+                                   "type": "BadRequestError", "code": 400}}
         room = self.engine.seq_room() if hasattr(self.engine, "seq_room") else None
         over = self.chunk * (2 if self.launch_ahead and not self.overlap_admissions else 1)   # steps past its limit (scheduler.over)
         need = len(parsed.input_ids) + min(int(parsed.max_tokens), self.max_tokens_cap) + (over if self.continuous else 0)
@@ -477,19 +516,23 @@ class LocalServer:
             code = int(slot.get("status", 500))
             kind = "BadRequestError" if code == 400 else "InternalServerError"
             return code, {"error": {"message": slot["error"], "type": kind, "code": code}}
-        toks, reason = slot["tokens"], slot["reason"]
-        text = slot["text"] if slot.get("text") is not None else self.frontend.tok.decode(toks)   # "text": cut at a stop string
         self.latencies.append(time.time() - t0)
         if len(self.latencies) > 20000:          # bounded: /metrics reads the last 10000
             del self.latencies[:10000]
-        n_in, n_out = int(len(parsed.input_ids)), int(len(toks))
-        choice: Dict[str, Any] = {"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": reason}
-        if parsed.logprobs is not None:
-            choice["logprobs"] = self._logprobs_json(toks, slot.get("logprobs"), parsed.logprobs)
+        choices, n_out = [], 0
+        for c, ch in enumerate(slot["choices"]):           # one per child, in child order
+            toks = ch["tokens"]
+            text = ch["text"] if ch.get("text") is not None else self.frontend.tok.decode(toks)   # "text": cut at a stop string
+            choice: Dict[str, Any] = {"index": c, "message": {"role": "assistant", "content": text}, "finish_reason": ch["reason"]}
+            if parsed.logprobs is not None:
+                choice["logprobs"] = self._logprobs_json(toks, ch.get("logprobs"), parsed.logprobs)
+            choices.append(choice)
+            n_out += int(len(toks))
+        n_in = int(len(parsed.input_ids))                  # the prompt counts once
         return 200, {
             "id": "chatcmpl-" + uuid.uuid4().hex, "object": "chat.completion", "created": int(time.time()),
             "model": req.get("model", self.name),
-            "choices": [choice],
+            "choices": choices,
             "usage": {"prompt_tokens": n_in, "completion_tokens": n_out, "total_tokens": n_in + n_out},
         }
 
@@ -514,13 +557,16 @@ class LocalServer:
     def _loop(self):
         from .engine import PageRequest
 
+        carry = None             # a request that did not fit the previous batch's rows
         while not self._stop:
-            first = self._q.get()
+            first = carry if carry is not None else self._q.get()
+            carry = None
             if first is None:
                 break
             batch = [first]
+            rows = first["req"].n            # a batch is packed by sequences: sum(n) <= engine.B
             deadline = time.time() + self.batch_wait_s
-            while len(batch) < self.engine.B:
+            while rows < self.engine.B:
                 try:
                     nxt = self._q.get(timeout=max(0.0, deadline - time.time()))
                 except queue.Empty:
@@ -528,7 +574,11 @@ class LocalServer:
                 if nxt is None:
                     self._stop = True
                     break
+                if rows + nxt["req"].n > self.engine.B:
+                    carry = nxt
+                    break
                 batch.append(nxt)
+                rows += nxt["req"].n
             self._running = len(batch)
             # same shape as vLLM's periodic stats line that the reference scrapes (pipeline.py:782-800)
             self.log(f"Running: {self._running} reqs, Waiting: {self._q.qsize()} reqs")
@@ -536,10 +586,12 @@ class LocalServer:
                 try:
                     pages = [self._page(s["req"]) for s in group]
                     res = self.engine.generate(pages, max(s["req"].max_tokens for s in group))
-                    for i, (s, toks, reason) in enumerate(zip(group, res.tokens, res.finish_reasons)):
-                        if getattr(res, "logprobs", None) is not None:
-                            s["logprobs"] = res.logprobs[i]
-                        self._finish(s, toks, reason)
+                    i = 0                    # the result's rows: a request's children consecutive
+                    for s in group:
+                        for c in range(s["req"].n):
+                            lps = res.logprobs[i] if getattr(res, "logprobs", None) is not None else None
+                            self._finish(s, res.tokens[i], res.finish_reasons[i], c, lps)
+                            i += 1
                 except Exception as e:  # engine failure -> 500 for every request of the group
                     for s in group:
                         s["error"] = f"{type(e).__name__}: {e}"
@@ -547,6 +599,9 @@ class LocalServer:
             self._running = 0
             for s in batch:
                 s["done"].set()
+        if carry is not None:     # stopped with a request held over for the next batch: nobody is left waiting forever
+            carry["error"] = "server shutting down"
+            carry["done"].set()
 
 
     def _static_groups(self, batch):
@@ -589,7 +644,8 @@ class LocalServer:
             page.logprobs = r.logprobs
         if self.honor_temperature and r.temperature > 0:
             page.temperature = r.temperature
-            page.seed = r.seed if r.seed is not None else random.getrandbits(32)
+            page.seed = r.seed if r.seed is not None else random.getrandbits(32)   # the base seed: child c samples with seed + c
+            page.n = int(getattr(r, "n", 1))
         if self.honor_temperature:        # --greedy: the plain greedy path, sampling controls ignored as well
             for name in NEUTRAL:
                 setattr(page, name, getattr(r, name, NEUTRAL[name]))
@@ -598,7 +654,8 @@ class LocalServer:
                     setattr(page, name, getattr(r, name))
         return page
 
-    def _finish(self, s: Dict[str, Any], toks, reason: str):
+    def _finish(self, s: Dict[str, Any], toks, reason: str, c: int = 0, logprobs=None):
+        """Child c of a request is through: its tokens as the response reports them -> s["choices"][c]."""
         mt = s["req"].max_tokens
         if len(toks) > mt:
             toks, reason = toks[:mt], "length"
@@ -609,14 +666,14 @@ class LocalServer:
             toks = toks[:-1]  # the EOS token (or the stop id that ended the sequence) is not part of the message content
         # stop strings: the earliest match cuts the text; usage counts through the token that completed it.  (Continuous mode:
         # the scheduler has already stopped the sequence there with this matcher; static mode: generation ran on.)
-        m = s.get("stop")
-        if m is None:
-            m = self._stop_strings(s["req"])
+        m = s["stops"][c] if s.get("stops") is not None else self._stop_strings(s["req"])   # matchers keep state: one per child
+        text = None
         if m is not None:
             keep = m.check(toks)
             if keep is not None:
-                toks, reason, s["text"] = toks[:keep], "stop", m.text
-        s["tokens"], s["reason"] = toks, reason
+                toks, reason, text = toks[:keep], "stop", m.text
+        n = max(1, int(getattr(s["req"], "n", 1)))
+        s.setdefault("choices", [None] * n)[c] = {"tokens": toks, "reason": reason, "text": text, "logprobs": logprobs}
 
     def _loop_continuous(self):
         from .engine import PageRequest
@@ -626,7 +683,7 @@ class LocalServer:
             sch = SlotScheduler(self.engine, self.max_tokens_cap, self.chunk, sampling=self.honor_temperature,
                                 guided=self.guided, logprobs=self.max_logprobs, admit_min=self.admit_min,
                                 admit_max_wait=self.admit_max_wait, overlap=self.overlap_admissions,
-                                launch_ahead=self.launch_ahead)
+                                launch_ahead=self.launch_ahead, prefix_cache=self.prefix_cache)
         except Exception as e:  # cannot enter slot mode: every request gets a 500
             sch, boot_error = None, f"{type(e).__name__}: {e}"
         self._sch = sch
@@ -651,23 +708,26 @@ class LocalServer:
                     s["done"].set()
                 else:
                     r = s["req"]
-                    s["stop"] = self._stop_strings(r)
-                    sch.submit(SlotRequest(self._page(r), max(1, int(r.max_tokens)), tag=s, stop_check=s["stop"]))
+                    s["stops"] = [self._stop_strings(r) for _ in range(r.n)]
+                    sch.submit(SlotRequest(self._page(r), max(1, int(r.max_tokens)), tag=s, stop_check=s["stops"][0],
+                                           stop_checks=s["stops"] if r.n > 1 else None,
+                                           prompt_key=r.prompt_key if self.prefix_cache else None))
             if self._stop or sch is None:
                 continue
             try:
                 results = sch.step()
             except Exception as e:  # engine failure mid-flight: everything in a slot or waiting fails, slot mode restarts
                 msg = f"{type(e).__name__}: {e}"
-                for r in list(sch.active.values()) + list(sch.waiting):
+                lost = {id(r): r for r in list(sch.active.values()) + list(sch.waiting)}   # a request with n children is in n slots
+                for r in lost.values():
                     r.tag["error"] = msg
                     r.tag["done"].set()
-                self.pages_done += len(sch.active) + len(sch.waiting)
+                self.pages_done += len(lost)
                 try:
                     sch = SlotScheduler(self.engine, self.max_tokens_cap, self.chunk, sampling=self.honor_temperature,
                                         guided=self.guided, logprobs=self.max_logprobs, admit_min=self.admit_min,
                                         admit_max_wait=self.admit_max_wait, overlap=self.overlap_admissions,
-                                launch_ahead=self.launch_ahead)
+                                        launch_ahead=self.launch_ahead, prefix_cache=self.prefix_cache)
                 except Exception as e2:
                     sch, boot_error = None, f"{type(e2).__name__}: {e2}"
                 self._sch = sch
@@ -683,9 +743,8 @@ class LocalServer:
                     s["error"] = res.error
                     s["status"] = getattr(res, "status", 500)
                 else:
-                    if res.logprobs is not None:
-                        s["logprobs"] = res.logprobs
-                    self._finish(s, res.tokens, res.finish_reason)
+                    for c, ch in enumerate(res.choices if getattr(res, "choices", None) else [res]):
+                        self._finish(s, ch.tokens, ch.finish_reason, c, ch.logprobs)
                 self.pages_done += 1
                 s["done"].set()
         # shutting down: nobody is left waiting forever
