@@ -39,7 +39,7 @@ typedef uint16_t kr_bf16;
 /* kr_version() of the library this header describes: major * 100 + minor.  The major changes with every incompatible
  * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family); a caller built
  * against major X must refuse a library whose kr_version() / 100 != X. */
-#define KR_ABI_VERSION 404
+#define KR_ABI_VERSION 405
 
 #define KR_OK 0
 #define KR_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -633,6 +633,68 @@ int kr_sample_greedy(const float* amax_val, const int32_t* amax_idx, int n_part,
                      int hist_stride, const int32_t* prompt_len, int32_t* ctx_len, int32_t* finished,
                      const int32_t* eos, int n_eos, int pad_id, int ignore_eos, kr_bf16* x_next,
                      int batch, kr_stream s);
+
+/* ------------------------------------------------------------------ speculative decode step (prompt-lookup drafts)
+ * `slots` sequences x (k + 1) rows in ONE step of the packed 17..32-row family: row r = j * slots + slot (j = 0..k) processes the
+ * token at position ctx_len[slot] + j of its slot; rows 0..slots-1 are the slots' own rows, so the per-slot state arrays are the
+ * FRONT of the per-row arrays below.  kr_spec_propose fills the draft rows, the layers run over `rows` rows with
+ * kr_linear_decode32_rows / kr_attn_decode_rows, kr_spec_accept replaces kr_sample_greedy.  Every row's numbers are the ones a
+ * one-row step at that context computes, and the sampler's noise is a function of (seed, token index) alone, so a draft is
+ * verified by equality at any temperature: the step emits exactly the tokens `emitted` plain steps would. */
+typedef struct kr_spec {
+    int32_t slots, k, rows;            /* rows >= slots * (k + 1), <= 32 */
+    int32_t ngram_min, ngram_max;      /* 1 <= ngram_min <= ngram_max <= 8 */
+    int32_t s_max;
+    const int32_t* prompt_ids;         /* [slots][prompt_stride]: the prompt's token ids of every slot */
+    int64_t prompt_stride;
+    int32_t* history;                  /* [.][hist_stride]: kr_sample_greedy's token history */
+    int32_t hist_stride;
+    int32_t hist_rows;                 /* rows of `history`: kr_spec_accept never writes at or past it */
+    const uint64_t* script;            /* NULL, or [slots] device addresses (0: none) of a scripted continuation (test hook): */
+    const int32_t* script_len;         /*   draft j = script[generated + j - 1] replaces the lookup; [slots] lengths */
+    int32_t* row_slot;                 /* [rows] per-row state; entries 0..slots-1 belong to the caller (row_slot[r] = r) */
+    int32_t* ctx_len;
+    int32_t* prompt_len;
+    int32_t* finished;
+    float* temperature;
+    uint32_t* seed;
+    int32_t* n_draft;                  /* [slots] */
+    int32_t* draft_tok;                /* [slots][k] */
+    const kr_bf16* embed_table;        /* [vocab][d] */
+    int32_t d, pad_id, vocab;
+    kr_bf16* x;                        /* [rows][ldx] input rows of the step */
+    int64_t ldx;
+    int32_t* proposed;                 /* [slots] counters kr_spec_accept adds to: drafts proposed / accepted */
+    int32_t* accepted;
+} kr_spec;
+
+/* One workgroup per slot.  The slot's sequence s[0..L), L = ctx_len + 1: prompt_ids below prompt_len, then the history.  For n from
+ * ngram_max down to ngram_min (n <= L - 1) the matches are the i with i + n <= L - 1 and s[i..i+n) == s[L-n..L); the first n that
+ * has one decides, and among its matches the one maximising (min(k, L - i - n), i); the drafts are the tokens after it.  Writes
+ * n_draft / draft_tok, and for every row r >= slots: row_slot, ctx_len = min(ctx_len[slot] + j, s_max - 1), prompt_len,
+ * temperature and seed of the slot, finished = 1 where the slot is finished or j > n_draft, and x[r] = the draft's embedding (the
+ * pad token's for an inactive row).  Rows at and past slots * (k + 1) are inactive rows of slot 0 parked at s_max - 1. */
+int kr_spec_propose(const kr_spec* a, kr_stream s);
+
+/* One workgroup per slot, in place of kr_sample_greedy: reduces the ARGMAX partials [rows][n_part] of the slot's k + 1 rows to
+ * t_0..t_k (kr_sample_greedy's order and tie rule) and applies that launch's semantics token by token: t_j is emitted while j = 0, or
+ * j <= n_draft and draft[j - 1] == t_{j-1}; nothing follows an emitted EOS.  Emitted token j -> history[ctx + 1 + j - prompt_len],
+ * ctx_len += emitted, tokens_out / x[slot] take the last one, finished is set on EOS; a finished slot under the freeze bit behaves as
+ * in kr_sample_greedy.  proposed += n_draft; accepted += the drafts that equal the token emitted at their position (emitted - 1, or
+ * `emitted` when the last emitted token is an EOS that was drafted: nothing follows it). */
+int kr_spec_accept(const kr_spec* a, const float* amax_val, const int32_t* amax_idx, int n_part, int32_t* tokens_out,
+                   const int32_t* eos, int n_eos, int ignore_eos, kr_stream s);
+
+/* kr_linear_decode32, KR_DEC_ROPE_KV only, for the rows of a speculative step: the cache base and the cs_table row of row r come
+ * from row_slot[r]; the cache position and the rotary index from the row's own ctx_len / prompt_len entries.  q_out stays per row.
+ * row_slot == NULL: kr_linear_decode32's bits. */
+int kr_linear_decode32_rows(int mode, const kr_dec32* args, const int32_t* row_slot, kr_stream s);
+
+/* kr_attn_decode_slots with q, ctx_len, finished and the workspace records per ROW and the cache base from row_slot[row]: the same
+ * unit partition, accumulation order and records, so row (slot, j) gets the partials of a one-row step at that context. */
+int kr_attn_decode_rows(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
+                        const int32_t* finished, const int32_t* row_slot, float* workspace, int rows, int heads, int kv_heads,
+                        int hd, int s_max, int n_split, float scale, kr_stream s);
 
 /* ------------------------------------------------------------------ multi-GPU: one-time weight broadcast (RCCL)
  * One process per GPU.  Rank 0 calls kr_comm_unique_id and shares the 128 bytes through any host

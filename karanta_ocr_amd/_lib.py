@@ -96,6 +96,10 @@ SIGNATURES = {
     "kr_attn_decode_slots": [c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
     "kr_attn_decode_merge": [c_p, c_p, i32, i32, i32, i32, c_p],
     "kr_sample_greedy": [c_p, c_p, i32, c_p, i32, c_p, c_p, i32, c_p, c_p, c_p, c_p, i32, i32, i32, c_p, i32, c_p],
+    "kr_spec_propose": [c_p, c_p],
+    "kr_spec_accept": [c_p, c_p, c_p, i32, c_p, c_p, i32, i32, c_p],
+    "kr_linear_decode32_rows": [i32, c_p, c_p, c_p],
+    "kr_attn_decode_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
     "kr_comm_unique_id": [c_p],
     "kr_comm_init": [C.POINTER(c_p), i32, i32, c_p],
     "kr_comm_count": [c_p, C.POINTER(i32)],
@@ -141,6 +145,16 @@ class Dec32(C.Structure):
                 ("group_split", C.c_int32), ("reserved0", C.c_int32), ("zero_ptr", c_p), ("zero_bytes", C.c_uint64),
                 ("cs_table", c_p), ("cs_stride", C.c_int32), ("prompt_len", c_p), ("ctx_len", c_p),
                 ("q_out", c_p), ("kcache", c_p), ("vtcache", c_p), ("heads", C.c_int32), ("kv_heads", C.c_int32), ("s_max", C.c_int32)]
+
+
+class Spec(C.Structure):
+    """kr_spec (include/karanta_hip.h): the layout and the buffers of a speculative decode step."""
+    _fields_ = [("slots", C.c_int32), ("k", C.c_int32), ("rows", C.c_int32), ("ngram_min", C.c_int32), ("ngram_max", C.c_int32),
+                ("s_max", C.c_int32), ("prompt_ids", c_p), ("prompt_stride", C.c_int64), ("history", c_p), ("hist_stride", C.c_int32),
+                ("hist_rows", C.c_int32), ("script", c_p), ("script_len", c_p), ("row_slot", c_p), ("ctx_len", c_p),
+                ("prompt_len", c_p), ("finished", c_p), ("temperature", c_p), ("seed", c_p), ("n_draft", c_p), ("draft_tok", c_p),
+                ("embed_table", c_p), ("d", C.c_int32), ("pad_id", C.c_int32), ("vocab", C.c_int32), ("x", c_p), ("ldx", C.c_int64),
+                ("proposed", c_p), ("accepted", c_p)]
 
 
 FORK_MAX_GROUPS = FORK_MAX_SLOTS = 32    # KR_FORK_MAX_GROUPS / KR_FORK_MAX_SLOTS

@@ -124,7 +124,8 @@ def node_main(args) -> int:
     s_len = (2048 + args.t_max + args.chunk + 127) // 64 * 64
     extra = ["--served-model-name", "karantaocr", "--max-num-seqs", str(args.slots), "--max-model-len", str(s_len), "--greedy",
              "--admit-min", str(args.admit_min), "--admit-max-wait", str(args.admit_max_wait), "--max-tokens-cap", str(args.t_max),
-             "--host", "127.0.0.1"] + (["--host-images"] if args.host_images else [])
+             "--host", "127.0.0.1"] + (["--host-images"] if args.host_images else []) + \
+        (["--speculative-config", args.speculative_config] if args.speculative_config else [])
     log_dir = args.log_dir or os.path.join(tmp or tempfile.mkdtemp(prefix="karanta_logs_"), "vllm_logs")
     group = launch.start_servers(model_dir, gpus, ports, extra, log_dir, timeout_s=args.timeout, log=log, preflight=not args.no_preflight,
                                  server_cmd=args.server_cmd.split() if args.server_cmd else None)
@@ -206,7 +207,16 @@ def main(argv=None):
     ap.add_argument("--timeout", type=float, default=600.0, help="--gpus: seconds to wait for the servers' /health")
     ap.add_argument("--no-preflight", action="store_true")
     ap.add_argument("--keep", action="store_true", help="--gpus: keep the written checkpoint / logs")
+    ap.add_argument("--speculative-config", default=None,
+                    help="the server's flag (cli.py), passed through: JSON with method \"ngram\"; --slots x (K + 1) <= 32")
     args = ap.parse_args(argv)
+    spec = None
+    if args.speculative_config:
+        from .cli import speculative_config
+        try:
+            spec = speculative_config(args.speculative_config, args.slots)
+        except ValueError as e:
+            ap.error(str(e))
     if args.gpus is not None:
         return node_main(args)
 
@@ -215,7 +225,7 @@ def main(argv=None):
     from karanta_ocr_amd import serving as S
     from karanta_ocr_amd.clients import VLLMClient
     from karanta_ocr_amd.config import CONFIGS
-    from karanta_ocr_amd.engine import Engine
+    from karanta_ocr_amd.engine import Engine, SpecConfig
     from karanta_ocr_amd.weights import random_weights
 
     cfg = CONFIGS[args.model]
@@ -231,12 +241,16 @@ def main(argv=None):
     P = len(probe.input_ids)
     n_patch = int(np.prod(probe.grids[0]))
     B = args.slots
-    eng = Engine(cfg, max_batch=B, s_max=(P + args.t_max + args.chunk + 64 + 63) // 64 * 64,
-                 max_patches=args.admit * n_patch, max_prompt_tokens=args.admit * P, admission_cus=args.overlap_cus or None)
+    # speculative: the steps a slot runs past its limit emit up to K + 1 tokens each, and the draft rows write K cache rows ahead
+    slack = 2 * args.chunk * (spec[0] + 1) + spec[0] if spec else args.chunk
+    eng = Engine(cfg, max_batch=B, s_max=(P + args.t_max + slack + 64 + 63) // 64 * 64,
+                 max_patches=args.admit * n_patch, max_prompt_tokens=args.admit * P, admission_cus=args.overlap_cus or None,
+                 **({"speculative": SpecConfig(*spec)} if spec else {}))
     eng.load_weights(random_weights(cfg, 0, as_bits=True))
     srv = S.LocalServer(eng, front, log=lambda *_: None, continuous=True, max_tokens_cap=args.t_max, chunk=args.chunk,
                         honor_temperature=False, admit_min=args.admit_min, admit_max_wait=args.admit_max_wait,
-                        overlap_admissions=args.overlap_cus is not None, launch_ahead=not args.no_launch_ahead)
+                        overlap_admissions=args.overlap_cus is not None, launch_ahead=not args.no_launch_ahead,
+                        **({"speculative": True} if spec else {}))
     port = 8791
     S.register_local_server(port, srv)
     guided = GUIDED

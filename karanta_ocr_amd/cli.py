@@ -71,7 +71,38 @@ def build_parser() -> argparse.ArgumentParser:
                          "starts from that slot's KV rows, without ViT or prefill (continuous mode)")
     ap.add_argument("--max-logprobs", type=int, default=None,
                     help="record log-probabilities in the decode graph: the largest top_logprobs a request may ask for (0..20)")
+    ap.add_argument("--speculative-config", default=None,
+                    help="vLLM's flag, as JSON: {\"method\": \"ngram\", \"num_speculative_tokens\": K, \"prompt_lookup_min\": 2, "
+                         "\"prompt_lookup_max\": 4} — prompt-lookup drafts verified K at a time, the same tokens as without it "
+                         "(--max-num-seqs x (K + 1) <= 32; not with --max-logprobs or --static-batching)")
     return ap
+
+
+def speculative_config(text: str, max_num_seqs: int):
+    """(num_tokens, ngram_min, ngram_max) from --speculative-config; ValueError with the reason for what this engine does not do."""
+    import json
+    try:
+        d = json.loads(text)
+    except ValueError as e:
+        raise ValueError(f"--speculative-config is not JSON: {e}") from e
+    if not isinstance(d, dict):
+        raise ValueError("--speculative-config must be a JSON object")
+    method = d.get("method")
+    if method != "ngram":
+        raise ValueError(f"--speculative-config: method {method!r} is not supported (only \"ngram\": prompt-lookup drafts; there is no "
+                         "draft model)")
+    k = d.get("num_speculative_tokens", 3)
+    lo = d.get("prompt_lookup_min", 2)
+    hi = d.get("prompt_lookup_max", max(4, lo) if isinstance(lo, int) else 4)
+    for name, v in (("num_speculative_tokens", k), ("prompt_lookup_min", lo), ("prompt_lookup_max", hi)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"--speculative-config: {name} must be an integer >= 1, not {v!r}")
+    if not lo <= hi <= 8:
+        raise ValueError(f"--speculative-config: prompt_lookup_min {lo} <= prompt_lookup_max {hi} <= 8 does not hold")
+    if max_num_seqs * (k + 1) > 32:
+        raise ValueError(f"--speculative-config: --max-num-seqs {max_num_seqs} x (num_speculative_tokens {k} + 1) = "
+                         f"{max_num_seqs * (k + 1)} rows per decode step, the kernels take 32")
+    return k, lo, hi
 
 
 def parse_args(argv: Optional[List[str]] = None):
@@ -94,6 +125,16 @@ def parse_args(argv: Optional[List[str]] = None):
         ap.error("--max-num-seqs must be in 1..32 (above 16: hidden_size <= 2048 or == 3584)")
     if args.max_num_batched_tokens is not None and args.max_num_batched_tokens < args.max_model_len:
         ap.error("--max-num-batched-tokens must be >= --max-model-len (the longest prompt one request may carry)")
+    args.speculative = None
+    if args.speculative_config is not None:
+        if args.max_logprobs is not None:
+            ap.error("--speculative-config cannot be combined with --max-logprobs: a draft row records no log-probabilities")
+        if args.static_batching:
+            ap.error("--speculative-config needs the slot scheduler: not with --static-batching")
+        try:
+            args.speculative = speculative_config(args.speculative_config, args.max_num_seqs)
+        except ValueError as e:
+            ap.error(str(e))
     args.model_dir = model
     args.served_model_name = args.served_model_name or os.path.basename(os.path.normpath(model))
     args.ignored = unknown
@@ -148,7 +189,7 @@ def admission_budget(args, cfg, max_pixels: int):
 def make_server(args, log=print):
     """Engine + front end + LocalServer from parsed arguments (weights and tokenizer from args.model_dir)."""
     from . import image_processing as IP
-    from .engine import Engine
+    from .engine import Engine, SpecConfig
     from .serving import ChatFrontend, HFTokenizer, LocalServer, load_chat_template
     from .weights import load_checkpoint
 
@@ -171,9 +212,15 @@ def make_server(args, log=print):
         f"{args.max_num_seqs} decode slots of {args.max_model_len} tokens")
     # cache rows per slot: the model length + the steps a slot may run past its limit before the scheduler looks (2 chunks of up to 8
     # with launch-ahead) + the parking row
-    eng = Engine(cfg, device="cuda:0", max_batch=args.max_num_seqs, s_max=(args.max_model_len + 17 + 63) // 64 * 64,
+    spec = getattr(args, "speculative", None)
+    if spec is not None:
+        log(f"speculative decoding: ngram, {spec[0]} draft tokens per step, prompt lookup {spec[1]}..{spec[2]}")
+    # ... speculative: every step past the limit may emit K + 1 tokens, and the draft rows write K cache rows ahead
+    slack = 1 + 16 * (spec[0] + 1 if spec else 1) + (spec[0] if spec else 0)
+    eng = Engine(cfg, device="cuda:0", max_batch=args.max_num_seqs, s_max=(args.max_model_len + slack + 63) // 64 * 64,
                  max_patches=max_patches, max_prompt_tokens=max_prompt_tokens,
-                 weight_dtype=weight_dtype, fp8_activations=bool(getattr(args, "fp8_activations", False)) or None)
+                 weight_dtype=weight_dtype, fp8_activations=bool(getattr(args, "fp8_activations", False)) or None,
+                 **({"speculative": SpecConfig(*spec)} if spec else {}))
     # one server: read the checkpoint.  A launch.py group: rank 0 reads it ONCE, the arena goes to the other GPUs over
     # RCCL / xGMI (north_star: "RCCL broadcast of weights over xGMI"); a failure stops every server of the group
     info = load_or_receive_weights(eng.w, rank, world, lambda: eng.load_weights(load_checkpoint(args.model_dir)[1]),
@@ -190,7 +237,7 @@ def make_server(args, log=print):
     return LocalServer(eng, front, served_model_name=args.served_model_name, log=log, continuous=not args.static_batching,
                        max_tokens_cap=min(args.max_tokens_cap, args.max_model_len), honor_temperature=not args.greedy,
                        max_logprobs=args.max_logprobs, admit_min=args.admit_min, admit_max_wait=args.admit_max_wait,
-                       prefix_cache=bool(getattr(args, "enable_prefix_caching", False)))
+                       prefix_cache=bool(getattr(args, "enable_prefix_caching", False)), **({"speculative": True} if spec else {}))
 
 
 def main(argv: Optional[List[str]] = None, make=make_server, on_ready=None) -> int:

@@ -13,14 +13,17 @@ namespace {
 #ifndef KR_ATTN_DEC_LD        // -DKR_ATTN_DEC_LD=ld8: default-policy K / V^T loads (A/B builds, csrc/tools/build_variant.py)
 #define KR_ATTN_DEC_LD ld8_nt
 #endif
-template <int WAVES>
+// ROWS (kr_attn_decode_rows, the speculative step): blockIdx.z is a ROW — q, ctx_len, finished and the records are the row's, the
+// cache is the one of slot row_slot[row]; the new pointer sits at the tail of the arguments, past the preloaded ones.
+template <int WAVES, bool ROWS = false>
 __global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16* __restrict__ q, const kr_bf16* __restrict__ kcache,
                                                                   const kr_bf16* __restrict__ vtcache,
                                                                   const int32_t* __restrict__ ctx_len,
                                                                   const int32_t* __restrict__ finished, int heads, int kv_heads,
                                                                   int group, int n_split, int s_max, float scale_log2e,
                                                                   kr_bf16* __restrict__ out, float* __restrict__ ws,
-                                                                  int* __restrict__ counters, int ws_bytes) {
+                                                                  int* __restrict__ counters, int ws_bytes,
+                                                                  const int32_t* __restrict__ row_slot) {
     // argument order: everything the first loads need sits in the 16 preloaded dwords (kernarg preload), so the
     // scalar load of ctx_len[b] leaves at once instead of behind a load of the argument tail
     constexpr int HD = 128, DT = HD / 16, REC = HD + 4;
@@ -45,7 +48,7 @@ __global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16*
     bf16x8 qf[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) qf[i] = ld8(qp + i * 32);
-    const int64_t kv_base = (int64_t)b * kv_heads + kvh;
+    const int64_t kv_base = (int64_t)(ROWS ? row_slot[b] : b) * kv_heads + kvh;
     const kr_bf16* kc = kcache + kv_base * s_max * HD;
     const kr_bf16* vc = vtcache + kv_base * (int64_t)(s_max >> 6) * (HD * 64);
 
@@ -304,9 +307,10 @@ __global__ void __launch_bounds__(128) attn_merge_kernel(const float* __restrict
 
 }  // namespace
 
+template <bool ROWS = false>
 static int attn_decode_impl(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
                             const int32_t* finished, kr_bf16* out, float* workspace, int32_t* counters, int batch, int heads,
-                            int kv_heads, int hd, int s_max, int n_split, float scale, kr_stream s) {
+                            int kv_heads, int hd, int s_max, int n_split, float scale, kr_stream s, const int32_t* row_slot = nullptr) {
     KR_CHECK_ARG(q && kcache && vtcache && ctx_len && (out || workspace), "kr_attn_decode_fused: null pointer");
     KR_CHECK_ARG(hd == 128, "kr_attn_decode_fused: hd=%d (only 128)", hd);
     KR_CHECK_ARG(heads % kv_heads == 0 && heads / kv_heads <= 16, "kr_attn_decode_fused: GQA group must be <= 16");
@@ -331,14 +335,14 @@ static int attn_decode_impl(const kr_bf16* q, const kr_bf16* kcache, const kr_bf
     const float sl2 = scale * 1.4426950408889634f;
     const int group = heads / kv_heads;
     if (waves == 8)
-        attn_decode2_kernel<8><<<grid, 512, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
-                                                           workspace, counters, (int)ws_bytes);
+        attn_decode2_kernel<8, ROWS><<<grid, 512, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
+                                                                 workspace, counters, (int)ws_bytes, row_slot);
     else if (waves == 4)
-        attn_decode2_kernel<4><<<grid, 256, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
-                                                           workspace, counters, (int)ws_bytes);
+        attn_decode2_kernel<4, ROWS><<<grid, 256, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
+                                                                 workspace, counters, (int)ws_bytes, row_slot);
     else
-        attn_decode2_kernel<2><<<grid, 128, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
-                                                           workspace, counters, (int)ws_bytes);
+        attn_decode2_kernel<2, ROWS><<<grid, 128, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
+                                                                 workspace, counters, (int)ws_bytes, row_slot);
     KR_CHECK_LAUNCH();
     return KR_OK;
 }
@@ -354,6 +358,14 @@ extern "C" int kr_attn_decode_slots(const kr_bf16* q, const kr_bf16* kcache, con
                                     int n_split, float scale, kr_stream s) {
     KR_CHECK_ARG(finished && workspace, "kr_attn_decode_slots: null pointer");
     return attn_decode_impl(q, kcache, vtcache, ctx_len, finished, nullptr, workspace, nullptr, batch, heads, kv_heads, hd, s_max, n_split, scale, s);
+}
+
+extern "C" int kr_attn_decode_rows(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
+                                   const int32_t* finished, const int32_t* row_slot, float* workspace, int rows, int heads, int kv_heads,
+                                   int hd, int s_max, int n_split, float scale, kr_stream s) {
+    KR_CHECK_ARG(finished && workspace && row_slot, "kr_attn_decode_rows: null pointer");
+    return attn_decode_impl<true>(q, kcache, vtcache, ctx_len, finished, nullptr, workspace, nullptr, rows, heads, kv_heads, hd, s_max, n_split,
+                                  scale, s, row_slot);
 }
 
 static int merge_impl(const float* workspace, kr_bf16* out, int batch, int heads, int hd, int n_split, int xp, kr_stream s) {

@@ -37,15 +37,25 @@ struct D32Args {
     kr_bf16* q_out; kr_bf16* kcache; kr_bf16* vtcache; int heads, kv_heads, s_max;
 };
 
+// ROWS (kr_linear_decode32_rows, ROPE_KV of a speculative step): a row's cache and cs_table row are those of slot row_slot[row];
+// its position and rotary index come from its own ctx_len / prompt_len entries.  The argument struct of that instantiation alone
+// carries the map, so the other instantiations compile as before.
+struct D32RowArgs : D32Args {
+    const int32_t* row_slot;
+};
+template <bool ROWS> struct D32ArgsOf { using type = D32Args; };
+template <> struct D32ArgsOf<true> { using type = D32RowArgs; };
+
 // WAVES physical waves, each owning VW consecutive atoms of the WAVES * VW the reference partition has; U = ring depth in
 // chunks (x fragments and weights of a chunk travel together); NT weight tiles per workgroup.
 // GS ("group split", atomic split-K slabs only): the workgroup owns ONE HALF of a K range's atoms — blockIdx.y = 2 * ks + half —
 // folds them in wave order and adds the half's sum into slab ks, which the other half's workgroup adds into as well: two
 // addends per slab element, so the slab holds (first half) + (second half) = the narrow kernel's fold whichever arrives
 // first.  Half the x bytes per weight byte at the same number of workgroups (NT doubles).
-template <int NT, int EPI, int WAVES, int VW, int U, bool W8, bool GS = false>
+template <int NT, int EPI, int WAVES, int VW, int U, bool W8, bool GS = false, bool ROWS = false>
 __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, const char* hwp, int hM, int hN, int hK, int hcpb,
-                                                           const D32Args a) {
+                                                           const typename D32ArgsOf<ROWS>::type a) {
+    static_assert(!ROWS || EPI == D32_ROPE_KV, "the row map is for ROPE_KV");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using WC = WChunk<W8>;
     constexpr int WLOC = WAVES * VW;                 // atoms of this workgroup
@@ -92,10 +102,11 @@ __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, cons
     constexpr int EW = EPI == D32_ROPE_KV ? MT : MT * NT;     // waves that run an epilogue
     const int emt = wave & 1, et = EPI == D32_ROPE_KV ? 0 : ((wave >> 1) % NT);
     const int eb = fr + 16 * emt, erb = min(eb, M - 1);
-    int pos = 0, plen = 0;
+    int pos = 0, plen = 0, eslot = eb, erslot = erb;   // cache slot of the epilogue row / of the clamped row
     if (EPI == D32_ROPE_KV) {
         pos = a.ctx_len[erb];
         plen = a.prompt_len[erb];
+        if constexpr (ROWS) eslot = erslot = a.row_slot[erb];
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -117,7 +128,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, cons
     const int en = min(tile[et], ntiles - 1) * 16 + fg * 4;
     if (EPI == D32_ROPE_KV) {
         const int i0 = (tile[0] & 7) * 16 + fg * 4;
-        const float* cs = a.cs_table + ((int64_t)erb * a.cs_stride + (pos - plen)) * 128;
+        const float* cs = a.cs_table + ((int64_t)erslot * a.cs_stride + (pos - plen)) * 128;
         const f32x4 cv = *reinterpret_cast<const f32x4*>(cs + i0), sv = *reinterpret_cast<const f32x4*>(cs + 64 + i0);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -253,12 +264,12 @@ __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, cons
                 o1[j] = f2bf(hi[j] * csv[j] + lo[j] * csv[4 + j]);
             }
             kr_bf16* dst = hh < a.heads ? a.q_out + ((int64_t)eb * a.heads + hh) * 128
-                                        : a.kcache + (((int64_t)eb * a.kv_heads + (hh - a.heads)) * a.s_max + pos) * 128;
+                                        : a.kcache + (((int64_t)eslot * a.kv_heads + (hh - a.heads)) * a.s_max + pos) * 128;
             *reinterpret_cast<bf16x4*>(dst + i0) = o0;
             *reinterpret_cast<bf16x4*>(dst + 64 + i0) = o1;
         } else {
             const int kvh = hh - a.heads - a.kv_heads;
-            kr_bf16* vt = a.vtcache + (((int64_t)eb * a.kv_heads + kvh) * (a.s_max >> 6) + (pos >> 6)) * (128 * 64) + kr_vt_off(0, pos & 63, 128);
+            kr_bf16* vt = a.vtcache + (((int64_t)eslot * a.kv_heads + kvh) * (a.s_max >> 6) + (pos >> 6)) * (128 * 64) + kr_vt_off(0, pos & 63, 128);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 vt[(i0 + j) * 32] = __builtin_bit_cast(kr_bf16, f2bf(lo[j]));
@@ -359,6 +370,22 @@ int launch32_q(const kr_dec32& q, const D32Args& a, int groups, kr_stream s) {
     return q.w_scale ? launch32_w<NT, EPI, true>(q, a, groups, s) : launch32_w<NT, EPI, false>(q, a, groups, s);
 }
 
+// the ROPE_KV launch of launch32_q<2, D32_ROPE_KV> with the row map: same geometry, same ring depth
+template <bool W8>
+int launch32_rows(const kr_dec32& q, const D32RowArgs& a, int groups, kr_stream s) {
+    constexpr int NT = 2, WAVES = 8, VW = 1;
+    const int nchunks = q.K >> 6, share = (nchunks + WAVES - 1) / WAVES;
+    const size_t lds = (size_t)MT * WAVES * VW * NT * 1024;
+    auto go = [&](auto fn) {
+        fn<<<dim3(groups, 1), WAVES * 64, lds, kr_hs(s)>>>(reinterpret_cast<const char*>(q.xp), reinterpret_cast<const char*>(q.w_packed), q.M,
+                                                           q.N, q.K, nchunks, a);
+    };
+    if (share <= 3) go(&dec32_kernel<NT, D32_ROPE_KV, WAVES, VW, 3, W8, false, true>);
+    else go(&dec32_kernel<NT, D32_ROPE_KV, WAVES, VW, 5, W8, false, true>);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
 // row-major rows -> XP layout: thread = one 16-byte piece (row b, 8 consecutive k)
 __global__ void __launch_bounds__(256) pack_rows32_kernel(const kr_bf16* __restrict__ x, int64_t ldx, int M, int K, kr_bf16* __restrict__ xp) {
     const int kc = K >> 3, i = blockIdx.x * 256 + threadIdx.x;
@@ -379,7 +406,7 @@ extern "C" int kr_pack_rows32(const kr_bf16* x, int64_t ldx, int M, int K, kr_bf
     return KR_OK;
 }
 
-extern "C" int kr_linear_decode32(int mode, const kr_dec32* qp, kr_stream s) {
+static int linear_decode32_impl(int mode, const kr_dec32* qp, const int32_t* row_slot, kr_stream s) {
     KR_CHECK_ARG(qp, "kr_linear_decode32: null args");
     const kr_dec32& q = *qp;
     KR_CHECK_ARG(q.xp && q.w_packed && ((uintptr_t)q.xp & 15) == 0, "kr_linear_decode32: null / unaligned pointer");
@@ -431,9 +458,24 @@ extern "C" int kr_linear_decode32(int mode, const kr_dec32* qp, kr_stream s) {
                          "kr_linear_decode32: ROPE_KV pointers");
             KR_CHECK_ARG(q.N == (q.heads + 2 * q.kv_heads) * 128 && q.s_max % 64 == 0 && q.ksplit == 1 && q.waves_ref == 8,
                          "kr_linear_decode32: ROPE_KV needs head_dim 128, ksplit 1, waves_ref 8");
+            if (row_slot) {
+                D32RowArgs ra{};
+                static_cast<D32Args&>(ra) = a;
+                ra.row_slot = row_slot;
+                return q.w_scale ? launch32_rows<true>(q, ra, ntiles / 2, s) : launch32_rows<false>(q, ra, ntiles / 2, s);
+            }
             return launch32_q<2, D32_ROPE_KV>(q, a, ntiles / 2, s);
         default:
             kr_set_error("kr_linear_decode32: mode %d not supported (PLAIN, ROPE_KV)", mode);
             return KR_ERR_ARG;
     }
+}
+
+extern "C" int kr_linear_decode32(int mode, const kr_dec32* qp, kr_stream s) {
+    return linear_decode32_impl(mode, qp, nullptr, s);
+}
+
+extern "C" int kr_linear_decode32_rows(int mode, const kr_dec32* qp, const int32_t* row_slot, kr_stream s) {
+    KR_CHECK_ARG(mode == D32_ROPE_KV, "kr_linear_decode32_rows: mode %d (ROPE_KV only)", mode);
+    return linear_decode32_impl(mode, qp, row_slot, s);
 }

@@ -1,0 +1,265 @@
+"""What a speculative decode step costs and what it buys, measured once on the GPU; writes profiles/r05_spec_decode.json (DESIGN.md
+section 5j cites it, scheduler.SPEC_BREAK_EVEN is set from it).
+
+    python karanta_ocr_amd/csrc/tools/spec_bench.py [--parent-tree DIR] [--out profiles/r05_spec_decode.json]
+
+Random weights (timing only), context about 1900, graphs replayed as the engine replays them.
+
+  * plain step: the 8-row and the 32-row plain step of the 2B decoder on this tree — and, with --parent-tree (a checkout of the parent
+    commit with its library built), on the parent, in alternating child processes; the two must agree within the spread of this
+    tree against itself in the same call;
+  * ratio: t_spec / t_plain at the 2B decoder with 8 slots x K = 3 and at the 7B decoder with 4 slots x K = 3;
+  * tokens/s at scripted acceptance of 0 .. 3 drafts per step (the scripts are the plain run's own continuation, made wrong where a
+    run is to stop), against the plain steps' tokens/s;
+  * the attention launches' share of the speculative step (every row of a slot reads the slot's K/V again).
+
+Every measurement is a child process under a time limit of its own; a child that fails ends the run."""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+CTX, STEPS, ROUNDS = 1900, 48, 5
+
+
+def _engine(model, B, spec_k=0):
+    import torch
+    from karanta_ocr_amd.config import CONFIGS
+    from karanta_ocr_amd.engine import Engine
+    kw = {}
+    if spec_k:
+        from karanta_ocr_amd.engine import SpecConfig
+        kw["speculative"] = SpecConfig(spec_k)
+    n_new = STEPS * (ROUNDS + 3) * (spec_k + 1) + 16
+    eng = Engine(CONFIGS[model], max_batch=B, s_max=(CTX + n_new + 128) // 64 * 64, max_patches=64, max_prompt_tokens=64, **kw)
+    eng.w.allocate()
+    n = eng.w.arena.numel() // 2
+    view = eng.w.arena[: 2 * n].view(torch.bfloat16)
+    for i in range(0, n, 1 << 26):
+        m = min(1 << 26, n - i)
+        view[i:i + m] = (torch.randn(m, device=eng.device) * 0.02).to(torch.bfloat16)
+    # the state of a server's decode steps without the chance of an EOS: frozen-slot semantics, EOS ignored
+    eng._ignore_eos, eng._freeze_finished, eng._want_logits = True, True, False
+    eng._ensure_history(n_new)
+    eng._req_max_new = n_new
+    eng._x0 = (torch.randn(B, eng.cfg.text.hidden_size, device=eng.device) * 0.5).to(torch.bfloat16)
+    return eng
+
+
+def _reset(eng):
+    import torch
+    with torch.cuda.stream(eng.stream):
+        eng.d_ctx.fill_(CTX)
+        eng.d_plen.fill_(CTX)
+        eng.d_fin.zero_()
+        eng.d_x[:eng.B].copy_(eng._x0)
+    eng.stream.synchronize()
+
+
+def _time(eng, graph, steps=STEPS, rounds=ROUNDS, before=None):
+    """Per-step milliseconds of `steps` replays, one figure per round (round 0 warms up)."""
+    L = eng.L
+    e0, e1 = C.c_void_p(), C.c_void_p()
+    L.kr_event_create(C.byref(e0)); L.kr_event_create(C.byref(e1))
+    out = []
+    for r in range(rounds + 1):
+        _reset(eng)
+        if before is not None:
+            before()
+        L.kr_event_record(e0, eng.s)
+        for _ in range(steps):
+            L.kr_graph_launch(graph, eng.s)
+        L.kr_event_record(e1, eng.s)
+        L.kr_event_synchronize(e1)
+        ms = C.c_float()
+        L.kr_event_elapsed_ms(e0, e1, C.byref(ms))
+        if r:
+            out.append(ms.value / steps)
+    return out
+
+
+def _plain_graph(eng):
+    import torch
+    _reset(eng)
+    with torch.cuda.stream(eng.stream):
+        eng._decode_step_launches(eng.B)
+        eng.stream.synchronize()
+        return eng._graph_for(eng.B)
+
+
+def child_plain(model):
+    """The plain step at 8 and at 32 rows: uses nothing the parent commit lacks."""
+    import numpy as np
+    out = {}
+    for B in (8, 32):
+        eng = _engine(model, B)
+        ts = _time(eng, _plain_graph(eng))
+        out[str(B)] = {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "rounds_ms": [round(t, 5) for t in ts]}
+        eng.close()
+        del eng
+    return out
+
+
+def child_spec(model, B, K):
+    import numpy as np
+    import torch
+    from karanta_ocr_amd._lib import ptr
+    eng = _engine(model, B, K)
+    L, t = eng.L, eng.cfg.text
+    g_plain = _plain_graph(eng)
+    t_plain = _time(eng, g_plain)
+    # the model's own continuation from the reset state: what a right draft is
+    n_truth = STEPS * (K + 1) + K + 4
+    _reset(eng)
+    for _ in range(n_truth):
+        L.kr_graph_launch(g_plain, eng.s)
+    eng.stream.synchronize()
+    truth = eng.d_hist[:n_truth + 1].cpu().numpy().copy()          # [index, slot]; index 0 is not written from this state
+    _reset(eng)
+    with torch.cuda.stream(eng.stream):
+        eng._spec_step_launches()
+        eng.stream.synchronize()
+        g_spec = eng._graph_for(eng.B, True)
+    out = {"model": model, "slots": B, "K": K, "rows": eng.rows, "ctx": CTX,
+           "plain_ms": float(np.median(t_plain)), "plain_tokens_per_s": B / float(np.median(t_plain)) * 1e3, "accept": {}}
+    for a in range(K + 1):
+        scripts = truth.copy()
+        if a < K:      # step s starts at generated index 1 + s * (a + 1): its draft a + 1 is made wrong
+            for s in range(STEPS + 2):
+                i = 1 + s * (a + 1) + a
+                if i < len(scripts):
+                    scripts[i] = (scripts[i] + 1) % t.vocab_size
+        for b in range(B):
+            eng.set_draft_script(b, scripts[:, b])
+        count0 = [None]
+
+        def before():
+            count0[0] = eng.d_spec_count.cpu().numpy().astype(np.int64).copy()
+        ts = _time(eng, g_spec, before=before)
+        eng.stream.synchronize()
+        d = eng.d_spec_count.cpu().numpy().astype(np.int64) - count0[0]
+        gen = (eng.d_ctx.cpu().numpy() + 1 - eng.d_plen.cpu().numpy()).astype(np.int64)
+        got = eng.d_hist[:int(gen.min()), :B].cpu().numpy()
+        same = bool((got[1:] == truth[1:len(got)]).all())
+        med = float(np.median(ts))
+        out["accept"][str(a)] = {"spec_ms": med, "min_ms": float(min(ts)), "accepted_per_slot_step": float(d[1].sum()) / (B * STEPS),
+                                 "proposed_per_slot_step": float(d[0].sum()) / (B * STEPS),
+                                 "tokens_per_s": float((gen - 1).sum()) / (med * STEPS) * 1e3, "tokens_equal_plain": same}
+    for b in range(B):
+        eng.set_draft_script(b, None)
+    spec_ms = float(np.median([v["spec_ms"] for v in out["accept"].values()]))
+    out["ratio"] = spec_ms / out["plain_ms"]
+    out["break_even_accepted_per_slot_step"] = out["ratio"] - 1
+    # the attention launches alone: rows x (K + 1) reads of a slot's K/V against one
+    H, KVH, hd = t.num_heads, t.num_kv_heads, t.head_dim
+
+    def attn_graph(rows_variant):
+        L.kr_graph_begin_capture(eng.s)
+        for i in range(t.num_layers):
+            kc, vc = ptr(eng.kcache[i]), ptr(eng.vtcache[i])
+            if rows_variant:
+                L.kr_attn_decode_rows(ptr(eng.d_q), kc, vc, ptr(eng.d_ctx), ptr(eng.d_fin), ptr(eng.d_row_slot), ptr(eng.d_ws), eng.rows, H, KVH,
+                                      hd, eng.s_max, eng.n_split, hd ** -0.5, eng.s)
+            else:
+                L.kr_attn_decode_slots(ptr(eng.d_q), kc, vc, ptr(eng.d_ctx), ptr(eng.d_fin), ptr(eng.d_ws), B, H, KVH, hd, eng.s_max,
+                                       eng.n_split, hd ** -0.5, eng.s)
+        g = C.c_void_p()
+        L.kr_graph_end_capture(eng.s, C.byref(g))
+        return g.value
+    # the row state a fully accepted step leaves (all K + 1 rows of every slot live)
+    for b in range(B):
+        eng.set_draft_script(b, truth[:, b])
+    _reset(eng)
+    L.kr_graph_launch(g_spec, eng.s)
+    eng.stream.synchronize()
+    for b in range(B):
+        eng.set_draft_script(b, None)
+
+    def keep_rows():
+        pass
+    for name, rv in (("attn_rows_ms", True), ("attn_slots_ms", False)):
+        g = attn_graph(rv)
+        e0, e1 = C.c_void_p(), C.c_void_p()
+        L.kr_event_create(C.byref(e0)); L.kr_event_create(C.byref(e1))
+        ts = []
+        for r in range(ROUNDS + 1):
+            L.kr_event_record(e0, eng.s)
+            for _ in range(STEPS):
+                L.kr_graph_launch(g, eng.s)
+            L.kr_event_record(e1, eng.s)
+            L.kr_event_synchronize(e1)
+            ms = C.c_float()
+            L.kr_event_elapsed_ms(e0, e1, C.byref(ms))
+            if r:
+                ts.append(ms.value / STEPS)
+        out[name] = float(np.median(ts))
+    out["attn_share_of_spec_step"] = out["attn_rows_ms"] / out["accept"][str(K)]["spec_ms"]
+    out["attn_share_of_plain_step"] = out["attn_slots_ms"] / out["plain_ms"]
+    eng.close()
+    return out
+
+
+def run_child(args, tree, limit):
+    env = dict(os.environ, PYTHONPATH=tree)
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), *args], cwd=tree, env=env, capture_output=True, text=True, timeout=limit)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+        raise SystemExit(f"child {args} in {tree} ended with {r.returncode}: nothing more is started")
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--child", default=None)
+    ap.add_argument("--model", default="Qwen2-VL-2B")
+    ap.add_argument("--slots", type=int, default=8)
+    ap.add_argument("--k", type=int, default=3)
+    ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its library built")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--skip-7b", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r05_spec_decode.json"))
+    a = ap.parse_args()
+    if a.child:
+        sys.path.insert(0, os.getcwd())
+        res = child_plain(a.model) if a.child == "plain" else child_spec(a.model, a.slots, a.k)
+        print(json.dumps(res), flush=True)
+        return 0
+    import numpy as np
+    report = {"context": CTX, "steps_per_round": STEPS, "rounds": ROUNDS, "weights": "random bf16 (timing only)"}
+
+    def save():
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(report, f, indent=1)
+            f.write("\n")
+    # ---- 1. the plain step on this tree and on the parent, alternating
+    runs = {"this": [], "parent": []}
+    for i in range(a.repeats):
+        runs["this"].append(run_child(["--child", "plain"], ROOT, 240))
+        if a.parent_tree:
+            runs["parent"].append(run_child(["--child", "plain"], os.path.abspath(a.parent_tree), 240))
+    plain = {}
+    for B in ("8", "32"):
+        mine = [r[B]["median_ms"] for r in runs["this"]]
+        theirs = [r[B]["median_ms"] for r in runs["parent"]]
+        plain[B] = {"this_tree_ms": mine, "parent_ms": theirs, "aa_spread_ms": max(mine) - min(mine)}
+        if theirs:
+            plain[B]["difference_of_medians_ms"] = float(np.median(mine) - np.median(theirs))
+            plain[B]["within_aa_spread"] = bool(abs(plain[B]["difference_of_medians_ms"]) <= plain[B]["aa_spread_ms"])
+    report["plain_step_2B"] = plain
+    save()
+    # ---- 2.-4. the speculative step
+    report["spec_2B"] = run_child(["--child", "spec", "--model", "Qwen2-VL-2B", "--slots", "8", "--k", "3"], ROOT, 420)
+    save()
+    if not a.skip_7b:
+        report["spec_7B"] = run_child(["--child", "spec", "--model", "Qwen2-VL-7B", "--slots", "4", "--k", "3"], ROOT, 420)
+        save()
+    print(json.dumps(report, indent=1))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

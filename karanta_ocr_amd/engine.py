@@ -25,7 +25,7 @@ import torch
 from . import image_processing as IP
 from . import positions as POS
 from ._lib import (ADJ_CAP, DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_GELU_ERF, EPI_NONE, EPI_QUICK_GELU, EPI_SILU_MUL8,
-                   KarantaHipError, fork_plan, lib, narrow_opts, ptr)
+                   KarantaHipError, Spec, fork_plan, lib, narrow_opts, ptr)
 from .config import ModelConfig
 from .sampling import StepFeatures, adjust_table, has_penalties, needs_processing, sampling_params, temperature
 from .weights import pack_w16x64, to_bf16_bits
@@ -365,10 +365,31 @@ class Admission:
     forks: list = field(default_factory=list)   # (source slot, prompt length, [sibling slots]) per page with n > 1
 
 
+@dataclass(frozen=True)
+class SpecConfig:
+    """Prompt-lookup speculative decoding (vLLM's ngram method): per step and slot up to `num_tokens` draft tokens, copied from
+    behind the latest earlier occurrence of the sequence's last ngram_max .. ngram_min tokens, are verified beside the slot's own
+    row (kr_spec_propose / kr_spec_accept).  The tokens are those of the plain steps, whatever the temperature."""
+    num_tokens: int = 3
+    ngram_min: int = 2
+    ngram_max: int = 4
+
+    def check(self, max_batch: int):
+        k = self.num_tokens
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise KarantaHipError(f"speculative: num_tokens {k!r} must be an integer >= 1")
+        if not 1 <= int(self.ngram_min) <= int(self.ngram_max) <= 8:
+            raise KarantaHipError(f"speculative: 1 <= ngram_min {self.ngram_min} <= ngram_max {self.ngram_max} <= 8")
+        if max_batch * (k + 1) > 32:
+            raise KarantaHipError(f"speculative: max_batch {max_batch} x (num_tokens {k} + 1) = {max_batch * (k + 1)} rows > 32, the most "
+                                  "one decode step takes")
+
+
 class Engine:
     def __init__(self, cfg: ModelConfig, device: str = "cuda:0", max_batch: int = 8, s_max: int = 4096,
                  max_patches: int = 8 * 5476, max_prompt_tokens: int = 8 * 2048, decode_splits: int = 16,
-                 weight_dtype: str = "bf16", fp8_activations: Optional[bool] = None, admission_cus: Optional[int] = None):
+                 weight_dtype: str = "bf16", fp8_activations: Optional[bool] = None, admission_cus: Optional[int] = None,
+                 speculative: Optional[SpecConfig] = None):
         if not torch.cuda.is_available():
             raise KarantaHipError("no HIP device: the karanta MI355X engine has no CPU fallback")
         self.L = lib()
@@ -380,6 +401,15 @@ class Engine:
         self.B = max_batch
         if max_batch > 32:
             raise KarantaHipError("max_batch > 32: the decode kernels take at most two 16-row column tiles")
+        # a speculative step runs max_batch x (K + 1) rows through the packed 17..32-row family (never fewer than 17 rows: its
+        # gate/up launch writes packed activations above 16 rows only); without `speculative` the rows are the slots
+        self.spec = speculative
+        if speculative is not None:
+            speculative.check(max_batch)
+        self.K = int(speculative.num_tokens) if speculative is not None else 0
+        self.rows = max(17, max_batch * (self.K + 1)) if speculative is not None else max_batch
+        self.spec_steps = self.plain_steps = 0
+        self._snap_counts = None
         self.s_max = _align(s_max, 64)
         self.max_patches = max_patches
         self.max_tokens = max_prompt_tokens
@@ -441,7 +471,7 @@ class Engine:
     # ------------------------------------------------------------------ buffers
     def _alloc(self):
         v, t, dev = self.cfg.vision, self.cfg.text, self.device
-        N, M, B = self.max_patches, self.max_tokens, self.B
+        N, M, B, R = self.max_patches, self.max_tokens, self.B, self.rows
         z = lambda *shape, dtype=BF16: torch.zeros(*shape, dtype=dtype, device=dev)
         nvb = N // 64 + 64  # V^T blocks: every image may add one partial block
         if v.variant == "qwen2_5":  # windowed blocks: every window starts a V^T block, edge windows are partial ones
@@ -481,10 +511,10 @@ class Engine:
         self.kcache = z(t.num_layers, B, t.num_kv_heads, self.s_max, t.head_dim)
         self.vtcache = z(t.num_layers, B, t.num_kv_heads, self.s_max // 64, t.head_dim, 64)
         # decode state
-        self.d_x = z(B, t.hidden_size)
-        self.d_x2 = z(B, t.hidden_size)  # the other residual buffer (deferred split-K ping-pong)
+        self.d_x = z(R, t.hidden_size)
+        self.d_x2 = z(R, t.hidden_size)  # the other residual buffer (deferred split-K ping-pong)
         # down_proj slabs of the deferred split: [2][B][hidden]; > 16 rows with the group-split down_proj: two PAIRS (layer parity)
-        self.d_part = z(4 if B > 16 else 2, B, t.hidden_size, dtype=torch.float32)
+        self.d_part = z(4 if R > 16 else 2, R, t.hidden_size, dtype=torch.float32)
         # ONE-slab form of the deferred split: down_proj's two K ranges add into one f32 accumulator with float atomics
         # (a + b onto zero: order-free, reproducible); two accumulators alternate by layer parity, layer L's qkv launch
         # zeroes the one layer L's down_proj adds into.  d_part doubles as the pair.
@@ -495,13 +525,13 @@ class Engine:
         self.d_qkv = z(B, t.qkv_dim)
         # batches above 16 rows keep the inputs of their decode linears in the PACKED layout of kr_linear_decode32 (32 row
         # slots whatever the batch): d_h (normalised rows of kr_decode_resnorm32), d_o (merged heads), d_act (SiLU * up)
-        Bp = 32 if B > 16 else B
+        Bp = 32 if R > 16 else B
         self.d_h = z(Bp, t.hidden_size)
-        self.d_q = z(B, t.num_heads, t.head_dim)
+        self.d_q = z(R, t.num_heads, t.head_dim)
         self.d_o = z(Bp, t.q_dim)
         self.d_act = z(Bp, t.intermediate_size)
-        self.d_logits = z(B, t.vocab_size, dtype=torch.float32)
-        self.d_ws = z(B * t.num_heads * self.n_split * (t.head_dim + 4), dtype=torch.float32)
+        self.d_logits = z(R, t.vocab_size, dtype=torch.float32)
+        self.d_ws = z(R * t.num_heads * self.n_split * (t.head_dim + 4), dtype=torch.float32)
         # waves per workgroup of the narrow decode linears: enough waves that every wave still
         # streams >= 2 K-chunks, no cross-workgroup reduction (each fence/atomic hop costs microseconds)
         self.wv_qkv = self._waves(t.hidden_size // 64)
@@ -520,7 +550,7 @@ class Engine:
         self.wide_blocks = int(os.environ.get("KARANTA_WIDE_BLOCKS", "256"))
         self.wide_waves = int(os.environ.get("KARANTA_WIDE_WAVES", "0"))  # 0: ceil(tiles / blocks), at most 8
         self.wide_spread32 = os.environ.get("KARANTA_WIDE_SPREAD32", "1") == "1"   # > 16 rows: tiles dealt as at <= 16 rows (_wide_geometry)
-        if self.B > 16 and not (self.wide_mode and t.intermediate_size % 64 == 0):
+        if R > 16 and not (self.wide_mode and t.intermediate_size % 64 == 0):
             raise KarantaHipError("max_batch > 16 needs the wide / narrow decode kernels (hidden_size % 512 == 0) and hidden_size <= 2048 or == 3584")
         # Above 16 rows the narrow linears (qkv behind kr_decode_resnorm32, o_proj, down_proj) run as the packed-activation
         # family (kr_linear_decode32) and the wide launches (gate/up, lm_head) hold two 16-row column tiles per weight
@@ -530,7 +560,7 @@ class Engine:
         self.row_split = self.B > 16 and t.hidden_size > 2048
         self.family32, self.resnorm_qkv = self.B > 16, self.row_split     # what bench.py --full counts launches from
         self.group_split_down = int(os.environ.get("KARANTA_DOWN_GS", "1"))   # 0 off, 1 at 16-atom partitions (2B widths), 2 always
-        if self.row_split and t.hidden_size != 3584:
+        if R > 16 and t.hidden_size > 2048 and t.hidden_size != 3584:
             raise KarantaHipError("max_batch > 16: hidden_size <= 2048 or == 3584 (the 7B width) only")
         if self.fp8 and not self.wide_mode:
             raise KarantaHipError("fp8 weights need the wide / narrow decode kernels: hidden_size % 512 == 0 and <= 4096")
@@ -538,17 +568,30 @@ class Engine:
         # 16 rows), so the buffers are sized for the larger one and the sampler is told the launch's own count
         self.n_amax = (max(self._amax_parts(0), self._amax_parts(32)) if self.wide_mode
                        else (t.vocab_size // 16 + 1) // 2)
-        self.d_amax_v = z(B, self.n_amax, dtype=torch.float32)
-        self.d_amax_i = z(B, self.n_amax, dtype=torch.int32)
-        self.d_plen = z(B, dtype=torch.int32)
+        self.d_amax_v = z(R, self.n_amax, dtype=torch.float32)
+        self.d_amax_i = z(R, self.n_amax, dtype=torch.int32)
+        # per-ROW state (prompt length, context, finished, temperature, seed): the slots' entries are in front — what every launch of
+        # a plain step and the host read — and kr_spec_propose writes the entries of a speculative step's draft rows behind them
+        self.d_plen = z(R, dtype=torch.int32)[:B]
         self.d_cs = None  # [B][max_new][128] rotary table of the decode positions, built per request
-        self.d_ctx = z(B, dtype=torch.int32)
+        self.d_ctx = z(R, dtype=torch.int32)[:B]
         self.d_delta = z(B, dtype=torch.int32)
         self.d_tok = z(B, dtype=torch.int32)
-        self.d_fin = z(B, dtype=torch.int32)
+        self.d_fin = z(R, dtype=torch.int32)[:B]
         self._snap_ring, self._snap_next, self._snap_event, self._copy_stream = None, 0, None, None   # snapshot_slots()
-        self.d_temp = z(B, dtype=torch.float32)   # per-slot sampling temperature and seed
-        self.d_seed = z(B, dtype=torch.int32)
+        self.d_temp = z(R, dtype=torch.float32)[:B]   # per-slot sampling temperature and seed
+        self.d_seed = z(R, dtype=torch.int32)[:B]
+        if self.spec is not None:
+            # the slot of every row (a slot's own row: itself), the prompt ids per slot (written at every admission), the drafts
+            # and the counters of proposed / accepted drafts, and the scripted continuations of the test hook (set_draft_script)
+            self.d_row_slot = torch.arange(R, dtype=torch.int32, device=dev) % B
+            self.d_prompt_ids = z(B, self.s_max, dtype=torch.int32)
+            self.d_ndraft = z(B, dtype=torch.int32)
+            self.d_draft = z(B, self.K, dtype=torch.int32)
+            self.d_spec_count = z(2, B, dtype=torch.int32)
+            self.d_script = z(B, dtype=torch.int64)
+            self.d_script_len = z(B, dtype=torch.int32)
+            self._scripts: Dict[int, torch.Tensor] = {}
         # guided decoding: per slot the device addresses of its pattern's tables (0 = unconstrained) + its DFA state
         self.d_gtrans = z(B, dtype=torch.int64)
         self.d_gmasks = z(B, dtype=torch.int64)
@@ -650,7 +693,7 @@ class Engine:
             self.L.kr_linear_decode_narrow(*head, ptr(W), *args)
 
     def _dec32(self, mode, xp, W, M, waves_ref, out=None, out_f32=None, bias=None, res=None, ksplit=1, atomic_out=False, zero=None,
-               kc=0, vc=0, w8=None, w_scale=None, tiles_per_wg=0, group_split=False):
+               kc=0, vc=0, w8=None, w_scale=None, tiles_per_wg=0, group_split=False, row_slot=None):
         """kr_linear_decode32: the decode linears of a 17..32-row batch on PACKED activations (xp: kr_pack_rows32 layout, written
         by kr_decode_resnorm32 / kr_attn_decode_merge32 / the gate/up launch with DEC_OUT_XP), with the K partition of the
         <= 16-row launch of the same layer (waves_ref, ksplit): row for row the bits that launch produces."""
@@ -663,7 +706,10 @@ class Engine:
                   zero.numel() * 4 if zero is not None else 0,
                   ptr(self.d_cs), self.max_new, ptr(self.d_plen), ptr(self.d_ctx), ptr(self.d_q), kc or None, vc or None,
                   t.num_heads, t.num_kv_heads, self.s_max)
-        self.L.kr_linear_decode32(mode, C.byref(a), self.s)
+        if row_slot is not None:    # speculative step: cache and rotary row by the row's slot (kr_linear_decode32_rows)
+            self.L.kr_linear_decode32_rows(mode, C.byref(a), ptr(row_slot), self.s)
+        else:
+            self.L.kr_linear_decode32(mode, C.byref(a), self.s)
 
     # the shipped sequence; ExperimentEngine overrides these per instance; bench.py --full reads resnorm_qkv, family32,
     # resnorm32_qkv (the instance's wide_mode, defer_down, row_split, family32, resnorm_qkv follow from its config: _alloc)
@@ -981,6 +1027,7 @@ class Engine:
     def _ensure_history(self, max_new_tokens: int):
         """Token history, rotary table and (when asked for) log-prob history sized for max_new_tokens; their
         addresses are baked into captured graphs, so a reallocation drops the graphs."""
+        max_new_tokens += self.K      # a speculative step may write K rows past what a plain step reaches
         grow = self.d_hist is None or self.max_new < max_new_tokens
         if grow:
             self.max_new = max_new_tokens
@@ -997,7 +1044,7 @@ class Engine:
 
     def seq_room(self) -> int:
         """Cache rows one sequence may use: prompt + generated tokens (slot mode keeps the last row as the parking row)."""
-        return self.s_max - (1 if self._freeze_finished else 0)
+        return self.s_max - (1 if self._freeze_finished else 0) - self.K     # (the draft rows' K/V land up to K rows ahead)
 
     def _prefill_prepare(self, pages: Sequence[PageRequest], n_image_tokens_total: Optional[int], slots: Optional[Sequence[int]] = None,
                          budgets: Optional[Sequence[int]] = None, rows: Optional[list] = None) -> Admission:
@@ -1026,8 +1073,8 @@ class Engine:
             raise KarantaHipError(f"{M} prompt tokens > max_prompt_tokens {self.max_tokens}")
         if budgets is None:
             budgets = [self._req_max_new] * B
-        if len(budgets) != B or max(budgets) > self.max_new:
-            raise KarantaHipError(f"budgets {list(budgets)} do not fit {B} sequences / the history of {self.max_new} tokens")
+        if len(budgets) != B or max(budgets) > self.max_new - self.K:
+            raise KarantaHipError(f"budgets {list(budgets)} do not fit {B} sequences / the history of {self.max_new - self.K} tokens")
         self._check_budgets(rows, budgets)
         src = np.empty(M, np.int32)
         cos = np.empty((M, t.head_dim), np.float32)
@@ -1211,6 +1258,9 @@ class Engine:
                 self._slot_guides.pop(j, None)
                 if dgs[b] is not None:
                     self._slot_guides[j] = dgs[b]
+        if self.spec is not None:     # kr_spec_propose looks the drafts up in prompt + history
+            for p, j in zip(a.rows, a.slots):
+                self._h2d(self.d_prompt_ids[j], np.asarray(p.input_ids, np.int64).reshape(-1).astype(np.int32))
         # sampling controls: params, prompt bits, output counts cleared
         for (sp, bits, nd), j in zip(a.procs or (), a.slots):
             self._h2d(self.d_sp[j], sp)
@@ -1304,7 +1354,15 @@ class Engine:
 
     # ------------------------------------------------------------------ decode
     def _decode_step_launches(self, B: int):
-        """One decode step = 6 (<= 16 rows) or 7 (17..32 rows) launches per layer + 2 (Qwen2VLDecoderLayer TF:559-624, final norm
+        """One plain decode step over the B slots: the layers, then lm_head and the sampler."""
+        self._lm_head_and_sample(B, self._layer_launches(B))
+
+    def _layer_launches(self, B: int, row_slot=None):
+        """The layers of a decode step over B rows; returns the residual buffer that holds the last layer's output.  row_slot (a
+        speculative step, B = self.rows): row r belongs to slot row_slot[r] — its K/V go to that slot's cache at the row's own
+        position and its attention reads that cache (kr_linear_decode32_rows, kr_attn_decode_rows); the per-row state arrays are
+        the slots' own, continued behind the slots.
+        One decode step = 6 (<= 16 rows) or 7 (17..32 rows) launches per layer + 2 (Qwen2VLDecoderLayer TF:559-624, final norm
         TF:839, lm_head TF:1320-1323).
         <= 16 rows: [(x += down_proj sums) + RMSNorm + QKV + bias + M-RoPE + KV append] (kr_linear_decode_narrow) -> attention
         partials -> merge -> [o_proj + residual] (narrow) -> [RMSNorm + gate/up + SiLU*mul] (kr_linear_decode_wide) ->
@@ -1346,7 +1404,7 @@ class Engine:
                                       x_other.stride(0), ptr(w.view(p + "ln1.w")), t.rms_norm_eps, ptr(self.d_h), B, t.hidden_size,
                                       1 if (gs and pending) else 0, s)
                 self._dec32(DEC_ROPE_KV, self.d_h, w.view(p + "qkv.w"), B, 8, bias=w.view(p + "qkv.b"), kc=kc, vc=vc,
-                            zero=acc, **self._w8kw(p + "qkv.w"))
+                            zero=acc, row_slot=row_slot, **self._w8kw(p + "qkv.w"))
             else:
                 self._dec_narrow(DEC_ROPE_KV, x, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), norm_w=w.view(p + "ln1.w"),
                                  part_in=pin, x_out=x_other if pending else None, kc=kc, vc=vc, zero=acc,
@@ -1354,8 +1412,12 @@ class Engine:
             if pending:
                 x, x_other = x_other, x
             # ---- 2. split-KV attention partials, 3. their merge
-            L.kr_attn_decode_slots(ptr(self.d_q), kc, vc, ptr(self.d_ctx), ptr(self.d_fin), ptr(self.d_ws), B, H, KVH, hd, self.s_max,
-                                   self.n_split, hd ** -0.5, s)
+            if row_slot is not None:
+                L.kr_attn_decode_rows(ptr(self.d_q), kc, vc, ptr(self.d_ctx), ptr(self.d_fin), ptr(row_slot), ptr(self.d_ws), B, H, KVH,
+                                      hd, self.s_max, self.n_split, hd ** -0.5, s)
+            else:
+                L.kr_attn_decode_slots(ptr(self.d_q), kc, vc, ptr(self.d_ctx), ptr(self.d_fin), ptr(self.d_ws), B, H, KVH, hd, self.s_max,
+                                       self.n_split, hd ** -0.5, s)
             (L.kr_attn_decode_merge32 if big else L.kr_attn_decode_merge)(ptr(self.d_ws), ptr(self.d_o), B, H, hd, self.n_split, s)
             # ---- 4. o_proj + residual
             if big:
@@ -1388,7 +1450,100 @@ class Engine:
                 self._dec_narrow(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, waves=self.down_waves_small, **down,
                                  **self._w8kw(p + "down.w"))
             pending = defer
-        self._lm_head_and_sample(B, x)
+        return x
+
+    # ------------------------------------------------------------------ speculative step
+    def _spec_args(self) -> Spec:
+        """kr_spec of this engine's speculative step (read during the call: rebuilt per launch, the history may have grown)."""
+        t, sp = self.cfg.text, self.spec
+        return Spec(self.B, self.K, self.rows, int(sp.ngram_min), int(sp.ngram_max), self.s_max, ptr(self.d_prompt_ids),
+                    self.d_prompt_ids.stride(0), ptr(self.d_hist), self.d_hist.stride(0), self.d_hist.shape[0], ptr(self.d_script),
+                    ptr(self.d_script_len), ptr(self.d_row_slot), ptr(self.d_ctx), ptr(self.d_plen), ptr(self.d_fin), ptr(self.d_temp),
+                    ptr(self.d_seed), ptr(self.d_ndraft), ptr(self.d_draft), ptr(self.w.view("llm.embed")), t.hidden_size,
+                    self.cfg.pad_token_id, t.vocab_size, ptr(self.d_x), self.d_x.stride(0), ptr(self.d_spec_count[0]),
+                    ptr(self.d_spec_count[1]))
+
+    def _spec_refusal(self) -> Optional[str]:
+        """Why the next steps cannot be speculative (None: they can).  A draft row sees the logits of its own position only: the
+        passes that carry state from token to token (a guide's DFA, the penalties' counts, min_tokens) or record per step
+        (log-probabilities) would need that state per draft."""
+        step = self._step
+        if self.spec is None:
+            return "the engine was built without speculative=SpecConfig(...)"
+        if not self._freeze_finished:
+            return "speculative steps run in slot mode (begin_slots)"
+        if step.guided or step.processing or step.adjust:
+            return "the step carries guided decoding, sampling controls or logit adjustments"
+        if self._logprobs is not None:
+            return "log-probabilities are recorded"
+        return None
+
+    def _spec_step_launches(self):
+        """One speculative step: drafts (kr_spec_propose) -> the layers over all rows -> lm_head -> the Gumbel pass when a request
+        samples -> verification and bookkeeping (kr_spec_accept, in kr_sample_greedy's place).  It leaves d_ctx, d_tok, d_x[slot],
+        the history and d_fin in the form a plain step leaves them, so the two kinds alternate freely."""
+        t, L, w, s, R = self.cfg.text, self.L, self.w, self.s, self.rows
+        why = self._spec_refusal()
+        if why is not None:
+            raise KarantaHipError("speculative decode step refused: " + why)
+        a = self._spec_args()
+        L.kr_spec_propose(C.byref(a), s)
+        x = self._layer_launches(R, self.d_row_slot)
+        logits = self.d_logits if self._step.sampling else None
+        self._dec_wide(DEC_ARGMAX, x, w.view("llm.lm_head"), R, norm_w=w.view("llm.norm.w"), out_f32=logits)
+        n_part = self._amax_parts(R)
+        if self._step.sampling:     # the counter of a draft row's noise is its own token index: ctx_len and prompt_len are per row
+            n_part = min(64, n_part)
+            L.kr_gumbel_argmax_guided(ptr(logits), self.d_logits.stride(0), t.vocab_size, ptr(self.d_temp), ptr(self.d_seed),
+                                      ptr(self.d_ctx), ptr(self.d_plen), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, R,
+                                      None, None, 0, 0, s)
+        flags = (1 if self._ignore_eos else 0) | (2 if self._freeze_finished else 0)
+        L.kr_spec_accept(C.byref(a), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(self.d_tok), ptr(self.d_eos),
+                         self.d_eos.numel(), flags, s)
+
+    def set_draft_script(self, slot: int, tokens: Optional[Sequence[int]]):
+        """Test hook: the drafts of `slot` come from a scripted continuation — draft j of a step is tokens[generated + j - 1] —
+        instead of the n-gram lookup, until None is set (an admission does not clear it)."""
+        if self.spec is None:
+            raise KarantaHipError("set_draft_script: the engine was built without speculative=SpecConfig(...)")
+        if not 0 <= int(slot) < self.B:
+            raise KarantaHipError(f"set_draft_script: slot {slot} outside 0..{self.B - 1}")
+        j = int(slot)
+        with torch.cuda.stream(self.stream):
+            if tokens is None:
+                self.d_script[j:j + 1].zero_()
+                self.d_script_len[j:j + 1].zero_()
+                self.stream.synchronize()       # a queued step may still read the tensor this drops
+                self._scripts.pop(j, None)
+                return
+            arr = np.ascontiguousarray(np.asarray(tokens, np.int64).reshape(-1).astype(np.int32))
+            buf = torch.zeros(max(1, arr.size), dtype=torch.int32, device=self.device)
+            self._h2d(buf, arr)
+            self._h2d(self.d_script[j:j + 1], np.asarray([buf.data_ptr()], np.int64))
+            self._h2d(self.d_script_len[j:j + 1], np.asarray([arr.size], np.int32))
+            self.stream.synchronize()
+            self._scripts[j] = buf
+
+    def can_speculate(self) -> bool:
+        """Whether decode_steps(speculative=True) would run with the passes the next steps carry."""
+        return self._spec_refusal() is None
+
+    def spec_counts(self) -> Optional[Tuple[np.ndarray, np.ndarray]]:
+        """(proposed[B], accepted[B]) as of the state the host last read: the snapshot given to read_snapshot(), else (after
+        poll_slots()) the device's counters now."""
+        if self.spec is None:
+            return None
+        if self._snap_counts is not None:
+            return self._snap_counts
+        return self.spec_counters()
+
+    def spec_counters(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(proposed[B], accepted[B]): draft tokens proposed / accepted per slot since begin_slots (synchronises)."""
+        if self.spec is None:
+            raise KarantaHipError("spec_counters: the engine was built without speculative=SpecConfig(...)")
+        self.stream.synchronize()
+        c = self.d_spec_count.cpu().numpy().astype(np.int64)
+        return c[0], c[1]
 
     # ------------------------------------------------------------------ live kernel timing (bench.py roofline)
     def _prof_event_pair(self):
@@ -1465,18 +1620,21 @@ class Engine:
         nbytes = wbytes + 2 * (t.hidden_size + B * t.hidden_size + B * t.intermediate_size)
         return {"launches": n, "avg_us": ms.value * 1e3 / n, "bytes_per_launch": nbytes}
 
-    def _graph_key(self, B: int):
-        return (B, self._ignore_eos, self._freeze_finished, self._logprobs, self._step)
+    def _graph_key(self, B: int, spec: bool = False):
+        return (B, self._ignore_eos, self._freeze_finished, self._logprobs, self._step, "spec" if spec else "plain")
 
-    def _graph_for(self, B: int) -> int:
-        key = self._graph_key(B)
+    def _graph_for(self, B: int, spec: bool = False) -> int:
+        key = self._graph_key(B, spec)
         assert not self._want_logits
         g = self._graphs.get(key)
         if g is None:
             L = self.L
             L.kr_graph_begin_capture(self.s)
             try:
-                self._decode_step_launches(B)
+                if spec:
+                    self._spec_step_launches()
+                else:
+                    self._decode_step_launches(B)
             finally:
                 ge = C.c_void_p()
                 L.kr_graph_end_capture(self.s, C.byref(ge))
@@ -1628,7 +1786,7 @@ class Engine:
         if self._adm_stream is not None:
             self._adm_stream.synchronize()
         self._adm_inflight = 0
-        self._snap_event = None
+        self._snap_event = self._snap_counts = None
         with torch.cuda.stream(self.stream):
             self.d_fin.fill_(1)
             self.d_temp.zero_()
@@ -1639,6 +1797,9 @@ class Engine:
             self.d_ctx.zero_()
             self.d_plen.zero_()
             self.d_x.zero_()
+            if self.spec is not None:
+                self.d_spec_count.zero_()
+        self.spec_steps = self.plain_steps = 0
         self.stream.synchronize()
 
     def admit(self, pages: Sequence[PageRequest], slots: Sequence[int], budgets: Optional[Sequence[int]] = None) -> List[int]:
@@ -1758,11 +1919,21 @@ class Engine:
         adjust: the logit-adjustment launches (logit_bias / min_tokens / stop_token_ids; needs_adjust), same rules."""
         self._step = StepFeatures(bool(sampling), bool(guided), bool(processing), bool(adjust)) & self._caps
 
-    def decode_steps(self, n: int):
-        """n decode steps over all slots (asynchronous on the engine's stream).  While an admission is in flight on a CU-masked
+    def decode_steps(self, n: int, speculative: bool = False):
+        """n decode steps over all slots (asynchronous on the engine's stream).  speculative=True: speculative steps (every slot
+        advances by 1 .. K + 1 tokens per step, the same tokens as plain steps give); raises where the steps carry guided decoding,
+        sampling controls or logit adjustments, or record log-probabilities.  While an admission is in flight on a CU-masked
         stream the captured graph replays on the complementary compute units (same kernels, same grids: the same tokens), ordered
         against the engine's stream by events on both sides."""
-        graph = self._graphs.get(self._graph_key(self.B))
+        spec = bool(speculative)
+        if spec:
+            why = self._spec_refusal()
+            if why is not None:
+                raise KarantaHipError("decode_steps(speculative=True): " + why)
+            self.spec_steps += n
+        else:
+            self.plain_steps += n
+        graph = self._graphs.get(self._graph_key(self.B, spec))
         self.last_decode_disjoint = False      # (observable for tests: which of the two paths the call took)
         if (graph is not None and self._adm_inflight > 0 and self.admission_cus > 0 and self.disjoint_decode
                 and self.admission_cus < self.n_cus):
@@ -1783,17 +1954,17 @@ class Engine:
             return
         with torch.cuda.stream(self.stream):
             for _ in range(n):
-                graph = self._graphs.get(self._graph_key(self.B))
+                graph = self._graphs.get(self._graph_key(self.B, spec))
                 if graph is not None:
                     self.L.kr_graph_launch(graph, self.s)
                 else:  # first step eager (kernel attributes), then captured
-                    self._decode_step_launches(self.B)
-                    self._graph_for(self.B)
+                    self._spec_step_launches() if spec else self._decode_step_launches(self.B)
+                    self._graph_for(self.B, spec)
 
     def poll_slots(self):
         """(finished[B], generated[B]): device EOS flags and tokens generated so far per slot (synchronises)."""
         self.stream.synchronize()
-        self._snap_event = None
+        self._snap_event = self._snap_counts = None
         fin = self.d_fin.cpu().numpy().astype(bool)
         gen = (self.d_ctx.cpu().numpy() + 1 - self.d_plen.cpu().numpy()).astype(np.int64)
         return fin, gen
@@ -1804,13 +1975,16 @@ class Engine:
     def snapshot_slots(self):
         ring = self._snap_ring
         if ring is None:
-            ring = self._snap_ring = [torch.empty(3, self.B, dtype=torch.int32).pin_memory() for _ in range(4)]
+            ring = self._snap_ring = [torch.empty(5 if self.spec is not None else 3, self.B, dtype=torch.int32).pin_memory()
+                                      for _ in range(4)]
         buf = ring[self._snap_next % len(ring)]
         self._snap_next += 1
         with torch.cuda.stream(self.stream):
             buf[0].copy_(self.d_fin, non_blocking=True)
             buf[1].copy_(self.d_ctx, non_blocking=True)
             buf[2].copy_(self.d_plen, non_blocking=True)
+            if self.spec is not None:     # proposed / accepted drafts per slot as of this point: snap["buf"][3], [4]
+                buf[3:5].copy_(self.d_spec_count, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self.stream)
         return {"buf": buf, "event": ev}
@@ -1823,6 +1997,7 @@ class Engine:
         fin = a[0].astype(bool)
         gen = (a[1].astype(np.int64) + 1 - a[2])
         self._snap_event = snap["event"]
+        self._snap_counts = (a[3].astype(np.int64), a[4].astype(np.int64)) if a.shape[0] >= 5 else None
         return fin, gen
 
     def _host_copy(self, t: "torch.Tensor") -> np.ndarray:

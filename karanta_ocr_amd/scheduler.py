@@ -57,6 +57,46 @@ class SlotResult:
     choices: Optional[List["SlotResult"]] = None
 
 
+# Break-even of a speculative chunk: accepted drafts per slot and step below which plain steps emit more tokens per second,
+# t_spec / t_plain - 1 for the step times of the two kinds.  UNMEASURED: this is README's 32-row over 8-row step time of the 2B
+# decoder (1.68 / 1.15 ms), which predates the speculative step and lacks its proposer launch and its repeated K/V reads;
+# csrc/tools/spec_bench.py measures the ratio and writes profiles/r05_spec_decode.json, from which this constant is to be set.
+SPEC_BREAK_EVEN = 1.68 / 1.15 - 1
+
+
+class SpecPolicy:
+    """When speculative chunks pay, as a pure host rule: over the last `window` speculative chunks that had live slots, the accepted
+    drafts per slot and step must reach `break_even`; below it the scheduler runs plain chunks and probes again after `probe_after`
+    of them.  `want()` names the next chunk's kind, `record()` takes what a speculative chunk's counters showed."""
+
+    def __init__(self, break_even: float = SPEC_BREAK_EVEN, window: int = 16, probe_after: int = 64):
+        if window < 1 or probe_after < 1:
+            raise ValueError("window and probe_after must be >= 1")
+        self.break_even, self.window, self.probe_after = float(break_even), int(window), int(probe_after)
+        self._recent: Deque[tuple] = collections.deque(maxlen=self.window)    # (accepted drafts, slot-steps) per speculative chunk
+        self._plain_left = 0
+
+    def want(self) -> bool:
+        """True: the next chunk is speculative.  A plain chunk asked for here counts towards the next probe."""
+        if self._plain_left > 0:
+            self._plain_left -= 1
+            return False
+        return True
+
+    def record(self, accepted: int, slot_steps: int) -> None:
+        if slot_steps <= 0:
+            return
+        self._recent.append((int(accepted), int(slot_steps)))
+        if len(self._recent) == self.window and self.rate() < self.break_even:
+            self._plain_left = self.probe_after
+            self._recent.clear()             # the probe starts a fresh window
+
+    def rate(self) -> float:
+        """Accepted drafts per slot and step over the window (0 before the first record)."""
+        steps = sum(n for _, n in self._recent)
+        return sum(a for a, _ in self._recent) / steps if steps else 0.0
+
+
 def _n(r: SlotRequest) -> int:
     """Sequences (slots) a request takes; pages without the attribute (older engines, test fakes) take one."""
     return int(getattr(r.page, "n", 1) or 1)
@@ -69,7 +109,8 @@ class SlotScheduler:
     def __init__(self, engine, max_tokens_cap: int, chunk: int = 8, eos_token_ids: Optional[Sequence[int]] = None,
                  max_prompt_tokens: Optional[int] = None, max_patches: Optional[int] = None, sampling: bool = False,
                  overlap: bool = False, guided: bool = False, logprobs: Optional[int] = None, admit_min: int = 1,
-                 admit_max_wait: int = 4, launch_ahead: bool = True, prefix_cache: bool = False):
+                 admit_max_wait: int = 4, launch_ahead: bool = True, prefix_cache: bool = False, speculative: bool = False,
+                 spec_policy: Optional[SpecPolicy] = None):
         if max_tokens_cap < 1 or chunk < 1:
             raise ValueError("max_tokens_cap and chunk must be >= 1")
         self.engine = engine
@@ -101,7 +142,21 @@ class SlotScheduler:
         # 0.86 -> 0.84), chunks of 2 gain 2 % (29.6-29.9 against 29.15 pages/s) — the server's defaults.
         self.launch_ahead = (bool(launch_ahead) and not self.overlap
                              and all(hasattr(engine, m) for m in ("snapshot_slots", "read_snapshot")))
-        self.over = (2 if self.launch_ahead else 1) * int(chunk)
+        # speculative: the chunks are speculative steps (Engine(speculative=SpecConfig(...)): up to K + 1 tokens per slot and step, the
+        # same tokens) while no request in a slot needs guided decoding, sampling controls, logit adjustments or log-probabilities
+        # and the policy finds them worth their price; every other chunk is plain
+        self.speculative = bool(speculative)
+        self.spec_k = int(getattr(engine, "K", 0) or 0) if self.speculative else 0
+        if self.speculative and self.spec_k < 1:
+            raise ValueError("speculative=True needs an engine built with speculative=SpecConfig(...)")
+        self.spec_policy = (spec_policy or SpecPolicy()) if self.speculative else None
+        self.spec_steps = self.plain_steps = 0       # decode steps of either kind
+        self.spec_draft_tokens = self.spec_accepted_tokens = 0
+        self._spec_seen = (0, 0)                     # the engine's counters (summed over the slots) at the last look
+        # (snapshot number, slot-steps) of the speculative chunks whose counters the host has not seen yet
+        self._spec_pending: Deque[tuple] = collections.deque()
+        # a step may emit K + 1 tokens: the steps a slot runs past its limit before the host looks count K + 1 tokens each
+        self.over = (2 if self.launch_ahead else 1) * int(chunk) * (self.spec_k + 1)
         self._snap = None                            # (sequence number, handle) of the chunk whose flags are read next
         self._snap_seq = 0                           # snapshots taken so far
         self._adm_seq: Dict[int, int] = {}           # slot -> snapshots taken when its request was admitted
@@ -213,9 +268,43 @@ class SlotScheduler:
                 # (engines older than the adjustment pass take three arguments: it is only named when a request needs it)
                 self.engine.set_step_features(need.sampling, need.guided, need.processing, **({"adjust": True} if need.adjust else {}))
                 self._features_now = need
-        self.engine.decode_steps(self.chunk)
+        if self._spec_chunk():
+            self.engine.decode_steps(self.chunk, speculative=True)
+            self.spec_steps += self.chunk
+            self._spec_pending.append((self._snap_seq, self.chunk * len(self.active)))
+        else:
+            self.engine.decode_steps(self.chunk)
+            self.plain_steps += self.chunk
         self.steps += self.chunk
         self.slot_steps_busy += self.chunk * len(self.active)
+
+    def _spec_chunk(self) -> bool:
+        """Whether the next chunk is speculative: the scheduler's mode, the requests in the slots (and in the admission in flight),
+        the engine's own conditions, then the policy."""
+        if not self.speculative or self.logprobs is not None:
+            return False
+        pending = self._inflight[1] if self._inflight is not None else []
+        need = StepFeatures.of(r.page for r in [*self.active.values(), *pending])
+        if need.guided or need.processing or need.adjust:
+            return False
+        if hasattr(self.engine, "can_speculate") and not self.engine.can_speculate():
+            return False
+        return self.spec_policy.want()
+
+    def _spec_account(self, counts, seq: Optional[int]) -> None:
+        """counts: the engine's (proposed[B], accepted[B]) as of the flags being harvested — snapshot number `seq`, or (None) the
+        device's state now.  What they gained since the last look belongs to the speculative chunks queued up to that point."""
+        if counts is None:
+            return
+        prop, acc = int(np.sum(counts[0])), int(np.sum(counts[1]))
+        d_prop, d_acc = prop - self._spec_seen[0], acc - self._spec_seen[1]
+        self._spec_seen = (prop, acc)
+        self.spec_draft_tokens += d_prop
+        self.spec_accepted_tokens += d_acc
+        slot_steps = 0
+        while self._spec_pending and (seq is None or self._spec_pending[0][0] <= seq):
+            slot_steps += self._spec_pending.popleft()[1]
+        self.spec_policy.record(d_acc, slot_steps)
 
     def _finish_admission(self, block: bool) -> List[SlotResult]:
         if self._inflight is None:
@@ -386,6 +475,8 @@ class SlotScheduler:
         """Requests that finished.  flags / seq: a snapshot's (finished, generated) and its sequence number — slots admitted after it
         was taken still show their previous occupant there and are skipped."""
         fin, gen = flags if flags is not None else self.engine.poll_slots()
+        if self.speculative:
+            self._spec_account(self.engine.spec_counts() if hasattr(self.engine, "spec_counts") else None, seq)
         out: List[SlotResult] = []
         for j in sorted(self.active):
             if seq is not None and self._adm_seq.get(j, 0) > seq:

@@ -418,8 +418,14 @@ class LocalServer:
                  batch_wait_s: float = 0.005, log=print, continuous: bool = False, max_tokens_cap: int = 4096,
                  chunk: int = 2, honor_temperature: bool = True, max_logprobs: Optional[int] = None, admit_min: int = 1,
                  admit_max_wait: int = 16, overlap_admissions: bool = False, launch_ahead: bool = True,
-                 prefix_cache: bool = False):
+                 prefix_cache: bool = False, speculative: bool = False):
         self.engine, self.frontend, self.name = engine, frontend, served_model_name
+        # prompt-lookup speculative decoding (vLLM's --speculative-config, method ngram): continuous mode, an engine built with
+        # speculative=SpecConfig(...), no log-probabilities (SlotScheduler(speculative=True))
+        self.speculative = bool(speculative)
+        if self.speculative and (not continuous or max_logprobs is not None or not getattr(engine, "K", 0)):
+            raise ValueError("speculative=True needs continuous=True, max_logprobs=None and an engine built with "
+                             "speculative=SpecConfig(...)")
         self.honor_temperature = bool(honor_temperature)   # False: every request is served greedy
         # guided decoding needs the tokenizer's byte strings on the device; engines without set_vocab (test fakes)
         # answer guided requests with 400
@@ -476,6 +482,9 @@ class LocalServer:
                 "admissions": sch.admissions, "pages_admitted": sch.pages_admitted,
                 "sequences_admitted": sch.sequences_admitted, "sequences_forked": sch.sequences_forked,
                 "prefix_cache_hits": sch.prefix_cache_hits,
+                # speculative decoding (vLLM's counter names): drafts proposed / accepted, decode steps of either kind
+                "spec_decode_num_draft_tokens": sch.spec_draft_tokens, "spec_decode_num_accepted_tokens": sch.spec_accepted_tokens,
+                "spec_decode_steps": sch.spec_steps, "plain_decode_steps": sch.plain_steps,
                 "host_phase_s": {k: round(v, 3) for k, v in sch.phase_s.items()}}
 
     def models(self) -> Tuple[int, dict]:
@@ -501,6 +510,8 @@ class LocalServer:
                                    "type": "BadRequestError", "code": 400}}
         room = self.engine.seq_room() if hasattr(self.engine, "seq_room") else None
         over = self.chunk * (2 if self.launch_ahead and not self.overlap_admissions else 1)   # steps past its limit (scheduler.over)
+        if self.speculative:
+            over *= int(self.engine.K) + 1        # a speculative step emits up to K + 1 tokens
         need = len(parsed.input_ids) + min(int(parsed.max_tokens), self.max_tokens_cap) + (over if self.continuous else 0)
         if room is not None and need > room:
             # the request's OWN prompt + max_tokens against one sequence's cache rows: a client error for this request
@@ -675,6 +686,9 @@ class LocalServer:
         n = max(1, int(getattr(s["req"], "n", 1)))
         s.setdefault("choices", [None] * n)[c] = {"tokens": toks, "reason": reason, "text": text, "logprobs": logprobs}
 
+    def _spec_kw(self) -> dict:
+        return {"speculative": True} if self.speculative else {}      # (only named when on: test fakes of the scheduler's engine)
+
     def _loop_continuous(self):
         from .engine import PageRequest
         from .scheduler import SlotRequest, SlotScheduler
@@ -683,7 +697,7 @@ class LocalServer:
             sch = SlotScheduler(self.engine, self.max_tokens_cap, self.chunk, sampling=self.honor_temperature,
                                 guided=self.guided, logprobs=self.max_logprobs, admit_min=self.admit_min,
                                 admit_max_wait=self.admit_max_wait, overlap=self.overlap_admissions,
-                                launch_ahead=self.launch_ahead, prefix_cache=self.prefix_cache)
+                                launch_ahead=self.launch_ahead, prefix_cache=self.prefix_cache, **self._spec_kw())
         except Exception as e:  # cannot enter slot mode: every request gets a 500
             sch, boot_error = None, f"{type(e).__name__}: {e}"
         self._sch = sch
@@ -727,7 +741,7 @@ class LocalServer:
                     sch = SlotScheduler(self.engine, self.max_tokens_cap, self.chunk, sampling=self.honor_temperature,
                                         guided=self.guided, logprobs=self.max_logprobs, admit_min=self.admit_min,
                                         admit_max_wait=self.admit_max_wait, overlap=self.overlap_admissions,
-                                        launch_ahead=self.launch_ahead, prefix_cache=self.prefix_cache)
+                                        launch_ahead=self.launch_ahead, prefix_cache=self.prefix_cache, **self._spec_kw())
                 except Exception as e2:
                     sch, boot_error = None, f"{type(e2).__name__}: {e2}"
                 self._sch = sch
