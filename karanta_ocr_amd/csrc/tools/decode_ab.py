@@ -98,9 +98,8 @@ def main():
         for k, v in over.items():
             cur = getattr(eng, k)
             setattr(eng, k, type(cur)(int(v)) if isinstance(cur, (bool, int)) else type(cur)(v))
-        eng._ignore_eos, eng._freeze_finished, eng._want_logits = True, False, False
-        eng._ensure_history(a.steps * (a.rounds + 2) + 8)
-        eng._req_max_new = eng.max_new
+        eng._enter_mode(a.steps * (a.rounds + 2) + 8, ignore_eos=True, freeze_finished=False, want_logits=False, caps=eng._caps,
+                        step=eng._step, logprobs=None)
         engines.append((spec, eng))
 
     def reset(eng):

@@ -42,9 +42,7 @@ def _engine(model, B, spec_k=0):
         m = min(1 << 26, n - i)
         view[i:i + m] = (torch.randn(m, device=eng.device) * 0.02).to(torch.bfloat16)
     # the state of a server's decode steps without the chance of an EOS: frozen-slot semantics, EOS ignored
-    eng._ignore_eos, eng._freeze_finished, eng._want_logits = True, True, False
-    eng._ensure_history(n_new)
-    eng._req_max_new = n_new
+    eng._enter_mode(n_new, ignore_eos=True, freeze_finished=True, want_logits=False, caps=eng._caps, step=eng._step, logprobs=None)
     eng._x0 = (torch.randn(B, eng.cfg.text.hidden_size, device=eng.device) * 0.5).to(torch.bfloat16)
     return eng
 

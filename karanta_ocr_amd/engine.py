@@ -11,24 +11,25 @@ prompt each, any mix of sizes); pages of different requests never interact (SURV
 """
 from __future__ import annotations
 
-import copy
 import ctypes as C
-import math
 import os
 import time
 from dataclasses import dataclass, field
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import image_processing as IP
 from . import positions as POS
-from ._lib import (ADJ_CAP, DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_GELU_ERF, EPI_NONE, EPI_QUICK_GELU, EPI_SILU_MUL8,
-                   KarantaHipError, Spec, fork_plan, lib, narrow_opts, ptr)
+from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_NONE, EPI_SILU_MUL8, KarantaHipError, Spec, fork_plan,
+                   lib, narrow_opts, ptr)
 from .config import ModelConfig
-from .sampling import StepFeatures, adjust_table, has_penalties, needs_processing, sampling_params, temperature
-from .weights import pack_w16x64, to_bf16_bits
+from .device_weights import DeviceWeights, _align
+from .request import GenerateResult, PageRequest, SpecConfig, children
+from .sampler import DeviceGuide, Sampler
+from .sampling import StepFeatures, has_penalties
+from .vision import DevicePlan, VisionTower, device_plan
 
 BF16 = torch.bfloat16
 GEMM_SCRATCH_BYTES = 512 * 65536   # include/karanta_hip.h: KR_GEMM_SCRATCH_BYTES
@@ -36,308 +37,13 @@ FP8_ACT_DEFAULT = False            # fp8 engines: W8A8 prefill on by default? (D
 # default-on switches of csrc/tools/experiment_engine.ExperimentEngine that select a superseded decode launch sequence
 SEQUENCE_SWITCHES = ("KARANTA_NARROW", "KARANTA_NARROW_O", "KARANTA_DEFER_DOWN", "KARANTA_WIDE", "KARANTA_ATOMIC_SLAB", "KARANTA_DEC32")
 
-
-def _bits(w: np.ndarray) -> np.ndarray:
-    return w if w.dtype == np.uint16 else to_bf16_bits(np.asarray(w, dtype=np.float32))
-
-
-def _align(n: int, a: int = 256) -> int:
-    return (n + a - 1) // a * a
-
-
-# =============================================================================
-# weights on the device: one packed arena (this is what kr_bcast_weights sends)
-# =============================================================================
-class DeviceWeights:
-    """All parameters in one contiguous HBM arena, laid out for the kernels:
-
-    * ViT Linears keep their [out, in] row-major layout (K contiguous = MFMA fragment order);
-    * decoder q/k/v are fused into one [q+2kv, d] matrix, gate/up into one [2*ff, d] matrix with
-      rows interleaved in groups of 8 (KR_EPI_SILU_MUL8: one 16-row MFMA tile = 8 gate rows + their 8 up rows);
-    * every decoder Linear and the lm_head are stored PACKED as [N/16][K/64][16][64] tiles
-      (weights.pack_w16x64): decode streams them linearly from HBM, prefill reads the same copy
-      through kr_gemm_bf16(w_packed=1).  A tied lm_head gets its own packed copy (the embedding
-      table itself stays row-major for the gather);
-    * the patch-embed kernel matrix is zero-padded from K=1176 to 1216 (GEMM BK=64).
-    """
-
-    def __init__(self, cfg: ModelConfig, device: torch.device, weight_dtype: str = "bf16"):
-        if weight_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"weight_dtype {weight_dtype!r} (bf16 or fp8)")
-        self.cfg = cfg
-        self.device = device
-        # fp8 (BASELINE.json config 5): the decoder Linears are ALSO kept as e4m3fn codes + one f32 scale per output
-        # row for the decode kernels (half the bytes per step); the bf16 entries then hold the dequantised values
-        # (what the prefill GEMMs read).  lm_head, embeddings, norms, biases and the ViT stay bf16.
-        self.weight_dtype = weight_dtype
-        self.layout: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
-        self.nbytes = 0
-        self.arena: Optional[torch.Tensor] = None
-        self._plan()
-
-    def _add(self, name: str, shape: Tuple[int, ...], itemsize: int = 2):
-        self.layout[name] = (self.nbytes, tuple(shape))
-        self.nbytes = _align(self.nbytes + itemsize * int(np.prod(shape)))
-
-    def _plan(self):
-        v, t = self.cfg.vision, self.cfg.text
-        self._add("vit.patch", (v.embed_dim, v.patch_dim_padded))
-        v25 = v.variant == "qwen2_5"
-        for i in range(v.depth):
-            p = f"vit.{i}."
-            self._add(p + "ln1.w", (v.embed_dim,))
-            self._add(p + "qkv.w", (3 * v.embed_dim, v.embed_dim)); self._add(p + "qkv.b", (3 * v.embed_dim,))
-            self._add(p + "proj.w", (v.embed_dim, v.embed_dim)); self._add(p + "proj.b", (v.embed_dim,))
-            self._add(p + "ln2.w", (v.embed_dim,))
-            if v25:
-                # biased SwiGLU (TF25:85-97): gate / up fused with rows AND biases interleaved in groups of 8
-                # (KR_EPI_SILU_MUL8), width zero-padded to a multiple of 64 (3420 -> 3456)
-                fp = v.mlp_dim_padded
-                self._add(p + "gate_up.w", (2 * fp, v.embed_dim)); self._add(p + "gate_up.b", (2 * fp,))
-                self._add(p + "down.w", (v.embed_dim, fp)); self._add(p + "down.b", (v.embed_dim,))
-            else:
-                self._add(p + "ln1.b", (v.embed_dim,)); self._add(p + "ln2.b", (v.embed_dim,))
-                self._add(p + "fc1.w", (v.mlp_dim, v.embed_dim)); self._add(p + "fc1.b", (v.mlp_dim,))
-                self._add(p + "fc2.w", (v.embed_dim, v.mlp_dim)); self._add(p + "fc2.b", (v.embed_dim,))
-        self._add("vit.merger.ln.w", (v.embed_dim,))
-        if not v25:
-            self._add("vit.merger.ln.b", (v.embed_dim,))
-        self._add("vit.merger.fc1.w", (v.merge_dim, v.merge_dim)); self._add("vit.merger.fc1.b", (v.merge_dim,))
-        self._add("vit.merger.fc2.w", (v.hidden_size, v.merge_dim)); self._add("vit.merger.fc2.b", (v.hidden_size,))
-        self._add("llm.embed", (t.vocab_size, t.hidden_size))
-        for i in range(t.num_layers):
-            p = f"llm.{i}."
-            self._add(p + "ln1.w", (t.hidden_size,))
-            self._add(p + "qkv.w", (t.qkv_dim, t.hidden_size)); self._add(p + "qkv.b", (t.qkv_dim,))
-            self._add(p + "o.w", (t.hidden_size, t.q_dim))
-            self._add(p + "ln2.w", (t.hidden_size,))
-            self._add(p + "gate_up.w", (2 * t.intermediate_size, t.hidden_size))
-            self._add(p + "down.w", (t.hidden_size, t.intermediate_size))
-            if self.weight_dtype == "fp8":
-                for n, shape in (("qkv", (t.qkv_dim, t.hidden_size)), ("o", (t.hidden_size, t.q_dim)),
-                                 ("gate_up", (2 * t.intermediate_size, t.hidden_size)), ("down", (t.hidden_size, t.intermediate_size))):
-                    self._add(p + n + ".w8", shape, itemsize=1)
-                    self._add(p + n + ".s", (shape[0],), itemsize=4)
-        self._add("llm.norm.w", (t.hidden_size,))
-        self._add("llm.lm_head", (t.vocab_size, t.hidden_size))
-
-    def allocate(self):
-        self.arena = torch.zeros(self.nbytes, dtype=torch.uint8, device=self.device)
-
-    def view(self, name: str) -> torch.Tensor:
-        off, shape = self.layout[name]
-        n = int(np.prod(shape))
-        return self.arena[off:off + 2 * n].view(BF16).view(*shape)
-
-    def view_u8(self, name: str) -> torch.Tensor:
-        off, shape = self.layout[name]
-        return self.arena[off:off + int(np.prod(shape))].view(*shape)
-
-    def view_f32(self, name: str) -> torch.Tensor:
-        off, shape = self.layout[name]
-        return self.arena[off:off + 4 * int(np.prod(shape))].view(torch.float32).view(*shape)
-
-    def has(self, name: str) -> bool:
-        return name in self.layout
-
-    def _put(self, name: str, bits: np.ndarray):
-        off, shape = self.layout[name]
-        assert tuple(bits.shape) == shape, (name, bits.shape, shape)
-        src = torch.from_numpy(np.ascontiguousarray(bits).view(np.uint8).reshape(-1))
-        self.arena[off:off + src.numel()].copy_(src, non_blocking=False)
-
-    def load(self, w: Dict[str, np.ndarray]):
-        """Fill the arena from a HF-named state dict (fp32 arrays or bf16 bit patterns)."""
-        if self.arena is None:
-            self.allocate()
-        v, t = self.cfg.vision, self.cfg.text
-        V, Lm = "model.visual.", "model.language_model."
-        pe = _bits(w[V + "patch_embed.proj.weight"]).reshape(v.embed_dim, -1)
-        pad = np.zeros((v.embed_dim, v.patch_dim_padded), np.uint16)
-        pad[:, :pe.shape[1]] = pe
-        self._put("vit.patch", pad)
-        v25 = v.variant == "qwen2_5"
-        for i in range(v.depth):
-            s, d = f"{V}blocks.{i}.", f"vit.{i}."
-            names = [("norm1.weight", "ln1.w"), ("attn.qkv.weight", "qkv.w"), ("attn.qkv.bias", "qkv.b"),
-                     ("attn.proj.weight", "proj.w"), ("attn.proj.bias", "proj.b"), ("norm2.weight", "ln2.w")]
-            if not v25:
-                names += [("norm1.bias", "ln1.b"), ("norm2.bias", "ln2.b"), ("mlp.fc1.weight", "fc1.w"),
-                          ("mlp.fc1.bias", "fc1.b"), ("mlp.fc2.weight", "fc2.w"), ("mlp.fc2.bias", "fc2.b")]
-            for a, b in names:
-                self._put(d + b, _bits(w[s + a]))
-            if v25:
-                ffv, fp, D = v.mlp_dim, v.mlp_dim_padded, v.embed_dim
-                def padded(a, rows):            # zero rows up to the padded width
-                    out = np.zeros((rows,) + a.shape[1:], np.uint16)
-                    out[:a.shape[0]] = a
-                    return out
-                g = padded(_bits(w[s + "mlp.gate_proj.weight"]), fp).reshape(fp // 8, 8, D)
-                u = padded(_bits(w[s + "mlp.up_proj.weight"]), fp).reshape(fp // 8, 8, D)
-                self._put(d + "gate_up.w", np.stack([g, u], 1).reshape(2 * fp, D))
-                gb = padded(_bits(w[s + "mlp.gate_proj.bias"]), fp).reshape(fp // 8, 8)
-                ub = padded(_bits(w[s + "mlp.up_proj.bias"]), fp).reshape(fp // 8, 8)
-                self._put(d + "gate_up.b", np.stack([gb, ub], 1).reshape(2 * fp))
-                dw = np.zeros((D, fp), np.uint16)
-                dw[:, :ffv] = _bits(w[s + "mlp.down_proj.weight"])
-                self._put(d + "down.w", dw)
-                self._put(d + "down.b", _bits(w[s + "mlp.down_proj.bias"]))
-        merger = [("merger.ln_q.weight", "ln.w"), ("merger.mlp.0.weight", "fc1.w"), ("merger.mlp.0.bias", "fc1.b"),
-                  ("merger.mlp.2.weight", "fc2.w"), ("merger.mlp.2.bias", "fc2.b")]
-        if not v25:
-            merger.append(("merger.ln_q.bias", "ln.b"))
-        for a, b in merger:
-            self._put("vit.merger." + b, _bits(w[V + a]))
-        self._put("llm.embed", _bits(w[Lm + "embed_tokens.weight"]))
-        ff = t.intermediate_size
-        if ff % 8:
-            raise KarantaHipError(f"intermediate_size {ff} must be a multiple of 8")
-        fp8 = self.weight_dtype == "fp8"
-        for i in range(t.num_layers):
-            s, d = f"{Lm}layers.{i}.", f"llm.{i}."
-            self._put(d + "ln1.w", _bits(w[s + "input_layernorm.weight"]))
-            self._put(d + "ln2.w", _bits(w[s + "post_attention_layernorm.weight"]))
-            self._put(d + "qkv.b", np.concatenate([_bits(w[s + f"self_attn.{n}_proj.bias"]) for n in "qkv"], 0))
-            if fp8:
-                # quantise every original matrix row-wise (scale = max|row| / 448), then fuse / interleave codes,
-                # scales and the dequantised bf16 copy alike
-                from .weights import as_f32, fp8_e4m3_to_f32, pack_w16x64_fp8, quantize_fp8_rows
-                qs = {n: quantize_fp8_rows(as_f32(w[s + n + ".weight"])) for n in
-                      ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj",
-                       "mlp.up_proj", "mlp.down_proj")}
-                il = lambda a, b: np.stack([a.reshape((ff // 8, 8) + a.shape[1:]), b.reshape((ff // 8, 8) + b.shape[1:])], 1) \
-                    .reshape((2 * ff,) + a.shape[1:])
-                fused = {"qkv": tuple(np.concatenate([qs[f"self_attn.{n}_proj"][k] for n in "qkv"], 0) for k in (0, 1)),
-                         "o": qs["self_attn.o_proj"],
-                         "gate_up": (il(qs["mlp.gate_proj"][0], qs["mlp.up_proj"][0]), il(qs["mlp.gate_proj"][1], qs["mlp.up_proj"][1])),
-                         "down": qs["mlp.down_proj"]}
-                for n, (q, sc) in fused.items():
-                    off8, _ = self.layout[d + n + ".w8"]
-                    src = torch.from_numpy(np.ascontiguousarray(pack_w16x64_fp8(q)).reshape(-1))
-                    self.arena[off8:off8 + src.numel()].copy_(src, non_blocking=False)
-                    offs, _ = self.layout[d + n + ".s"]
-                    srcs = torch.from_numpy(np.ascontiguousarray(sc, np.float32).view(np.uint8).reshape(-1))
-                    self.arena[offs:offs + srcs.numel()].copy_(srcs, non_blocking=False)
-                    self._put(d + n + ".w", pack_w16x64(to_bf16_bits(fp8_e4m3_to_f32(q) * sc[:, None])))
-                continue
-            self._put(d + "qkv.w", pack_w16x64(np.concatenate([_bits(w[s + f"self_attn.{n}_proj.weight"]) for n in "qkv"], 0)))
-            self._put(d + "o.w", pack_w16x64(_bits(w[s + "self_attn.o_proj.weight"])))
-            g = _bits(w[s + "mlp.gate_proj.weight"]).reshape(ff // 8, 8, -1)   # 8-row interleave: KR_EPI_SILU_MUL8
-            u = _bits(w[s + "mlp.up_proj.weight"]).reshape(ff // 8, 8, -1)
-            self._put(d + "gate_up.w", pack_w16x64(np.stack([g, u], 1).reshape(2 * ff, -1)))
-            self._put(d + "down.w", pack_w16x64(_bits(w[s + "mlp.down_proj.weight"])))
-        self._put("llm.norm.w", _bits(w[Lm + "norm.weight"]))
-        head = w[Lm + "embed_tokens.weight"] if (t.tie_word_embeddings or "lm_head.weight" not in w) else w["lm_head.weight"]
-        self._put("llm.lm_head", pack_w16x64(_bits(head)))
-        torch.cuda.synchronize(self.device)
-
-
-# =============================================================================
-# request / result types
-# =============================================================================
-@dataclass
-class PageRequest:
-    """One page = one sequence: prompt token ids (image placeholders included) + its images."""
-    input_ids: np.ndarray                      # int64 [P]
-    pixel_values: Optional[np.ndarray] = None  # fp32 [n_patches, 1176] (all images concatenated)
-    grids: List[Tuple[int, int, int]] = field(default_factory=list)
-    temperature: float = 0.0                   # 0: greedy; > 0: Gumbel-max sampling (kr_gumbel_argmax)
-    seed: int = 0                              # the sampler is counter-based: (seed, token index) fixes every draw
-    images: Optional[List[Any]] = None         # instead of pixel_values: HWC uint8 RGB pages for the GPU front end
-    #                                            (numpy arrays, or torch uint8 tensors already resident in HBM)
-    guide: Any = None                          # guided.Guide / DeviceGuide: the output must match this pattern
-    logprobs: Optional[int] = None             # None: off; k >= 0: log-prob of every token + the k most probable (<= 20)
-    # vLLM's sampling controls (kr_sample_threshold / kr_gumbel_argmax_processed); the defaults are "off"
-    top_k: int = 0                             # 0 or -1: off; k: keep the k largest scores (ties kept)
-    top_p: float = 1.0                         # 1: off; keep the smallest top set whose probability reaches top_p
-    min_p: float = 0.0                         # 0: off; keep p_i >= min_p * p_max
-    repetition_penalty: float = 1.0            # 1: off; tokens of the prompt or the output so far: l > 0 ? l / r : l * r
-    frequency_penalty: float = 0.0             # l -= frequency_penalty * (count in the output so far)
-    presence_penalty: float = 0.0              # l -= presence_penalty * (count > 0)
-    # vLLM's logit adjustments (kr_logits_adjust / kr_stop_tokens), applied before the penalties; the defaults are "off"
-    logit_bias: Optional[Dict[int, float]] = None   # token id -> value added to its logit (fp32)
-    min_tokens: int = 0                        # while fewer tokens are generated, EOS and the stop_token_ids cannot be chosen
-    stop_token_ids: Tuple[int, ...] = ()       # a generated token among these ends the sequence as EOS does
-    # parallel sampling (OpenAI's n): the page starts n sequences, exactly what n copies of it with seeds (seed + c) & 0xFFFFFFFF,
-    # c = 0..n-1, start (vLLM's seeds for the children of a seeded request) — but its images go through the ViT once and its
-    # prompt through the prefill once; the siblings' KV rows are copies of child 0's (kr_kv_fork)
-    n: int = 1
-
-
-def children(pages) -> list:
-    """The sequences a batch of pages starts, page-major with a page's children consecutive: the page itself for n = 1, else n
-    copies with n = 1 and seeds (seed + c) & 0xFFFFFFFF.  This is the row order of every per-sequence list of the engine."""
-    rows = []
-    for p in pages:
-        n = getattr(p, "n", 1)
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
-            raise KarantaHipError(f"PageRequest.n must be an integer >= 1, not {n!r}")
-        if n == 1:
-            rows.append(p)
-            continue
-        for c in range(int(n)):
-            ch = copy.copy(p)
-            ch.n, ch.seed = 1, (int(getattr(p, "seed", 0) or 0) + c) & 0xFFFFFFFF
-            rows.append(ch)
-    return rows
-
-
-@dataclass
-class GenerateResult:
-    """Per-sequence lists hold sum(n) entries: page-major, a page's n children consecutive (`children`)."""
-    tokens: List[np.ndarray]          # per sequence: generated ids (EOS included, nothing after it)
-    finish_reasons: List[str]         # "stop" | "length"
-    prompt_tokens: List[int]
-    timings: Dict[str, float]
-    logits: Optional[np.ndarray] = None  # [B, steps, V] when return_logits
-    logprobs: Optional[List[Optional[Dict[str, np.ndarray]]]] = None   # per page (None where not asked): "token" [n],
-    #                                                                    "top_ids" [n, k], "top" [n, k]
-
-
-class DeviceGuide:
-    """A compiled pattern resident in HBM: DFA transitions [S, 256] uint16 and one allowed-token bit row per state
-    (kr_guide_build_masks).  Built by :meth:`Engine.compile_guide`."""
-
-    def __init__(self, guide, trans: torch.Tensor, masks: torch.Tensor):
-        self.guide, self.trans, self.masks = guide, trans, masks
-        self.start = int(guide.start)
-
-
-@dataclass
-class DevicePlan:
-    """A positions.AttnPlan whose six work lists are resident in HBM (what kr_qkv_prep / kr_attn_varlen_q read)."""
-    host: POS.AttnPlan
-    blk_tok0: torch.Tensor
-    blk_ntok: torch.Tensor
-    blk_kr: torch.Tensor
-    blk_vb: torch.Tensor
-    qblk: torch.Tensor
-    qlen: torch.Tensor
-    n_blk: int
-
-
-def device_plan(plan: POS.AttnPlan, dev: torch.device) -> DevicePlan:
-    t_ = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    return DevicePlan(plan, t_(plan.blk_tok0), t_(plan.blk_ntok), t_(plan.blk_k_row0), t_(plan.blk_vt_blk), t_(plan.qblk),
-                      t_(plan.qblk_len), len(plan.blk_tok0))
-
-
-@dataclass
-class VitTables:
-    """What the vision tower needs per batch geometry (Engine._vit_tables): rotary tables (Qwen2.5-VL: in window order) and the
-    whole-image attention plan; Qwen2.5-VL also the window-order gather / its inverse and the window attention plan."""
-    cos: torch.Tensor
-    sin: torch.Tensor
-    full: DevicePlan
-    perm: Optional[torch.Tensor] = None
-    inv: Optional[torch.Tensor] = None
-    win: Optional[DevicePlan] = None
+__all__ = ["Engine", "PageRequest", "SpecConfig", "DeviceWeights", "GenerateResult", "children", "SEQUENCE_SWITCHES", "DeviceGuide"]
 
 
 @dataclass
 class Admission:
     """One admission — a whole batch (`generate`) or new requests for some slots — from the host tables
-    (Engine._prefill_prepare) over the sampling state (Engine.prefill) to the activation of its sequences."""
+    (Engine._prefill_prepare) over the sampling state (Engine.prefill) to the activation of its sequences (Engine._activate)."""
     B: int
     slots: List[int]
     whole_batch: bool
@@ -354,9 +60,9 @@ class Admission:
     # added by prefill: what the sampler keeps per sequence
     temps: Optional[np.ndarray] = None
     seeds: Optional[np.ndarray] = None
-    guides: Optional[list] = None      # Engine._guide_rows
-    procs: Optional[list] = None       # Engine._control_rows
-    adjs: Optional[list] = None        # Engine._adjust_rows
+    guides: Optional[list] = None      # Sampler._guide_rows
+    procs: Optional[list] = None       # Sampler._control_rows
+    adjs: Optional[list] = None        # Sampler._adjust_rows
     need: StepFeatures = StepFeatures()
     # parallel sampling: B / slots / lens / last_rows / cs count SEQUENCES (children); the prefill (M, src, cos, sin, plan) covers
     # every page once, in child 0's slot, and `forks` names what kr_kv_fork copies afterwards
@@ -364,25 +70,18 @@ class Admission:
     rows: list = field(default_factory=list)    # `children` of the admission's pages, made once per admission
     forks: list = field(default_factory=list)   # (source slot, prompt length, [sibling slots]) per page with n > 1
 
+    def spans(self, width: int):
+        """(first sequence, first slot, slots) of what an activation does per stretch of slots: a whole batch is ONE stretch of
+        `width` slots from slot 0 (its sequences, or max_batch with the idle rows behind them); named slots go one by one, the
+        others keep their state."""
+        return [(0, 0, width)] if self.whole_batch else [(b, j, 1) for b, j in enumerate(self.slots)]
 
-@dataclass(frozen=True)
-class SpecConfig:
-    """Prompt-lookup speculative decoding (vLLM's ngram method): per step and slot up to `num_tokens` draft tokens, copied from
-    behind the latest earlier occurrence of the sequence's last ngram_max .. ngram_min tokens, are verified beside the slot's own
-    row (kr_spec_propose / kr_spec_accept).  The tokens are those of the plain steps, whatever the temperature."""
-    num_tokens: int = 3
-    ngram_min: int = 2
-    ngram_max: int = 4
-
-    def check(self, max_batch: int):
-        k = self.num_tokens
-        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
-            raise KarantaHipError(f"speculative: num_tokens {k!r} must be an integer >= 1")
-        if not 1 <= int(self.ngram_min) <= int(self.ngram_max) <= 8:
-            raise KarantaHipError(f"speculative: 1 <= ngram_min {self.ngram_min} <= ngram_max {self.ngram_max} <= 8")
-        if max_batch * (k + 1) > 32:
-            raise KarantaHipError(f"speculative: max_batch {max_batch} x (num_tokens {k} + 1) = {max_batch * (k + 1)} rows > 32, the most "
-                                  "one decode step takes")
+    def copies(self, rows: np.ndarray, width: int):
+        """(first slot, host rows) of the copies that put one per-sequence field in place: `spans` of the field's `width` rows, a
+        whole batch padded with zeros."""
+        if self.whole_batch:
+            rows = np.concatenate([rows[:self.B], np.zeros(width - self.B, rows.dtype)])
+        return [(j, rows[b:b + n]) for b, j, n in self.spans(width)]
 
 
 class Engine:
@@ -433,21 +132,8 @@ class Engine:
         self.disjoint_decode = os.environ.get("KARANTA_DISJOINT_DECODE", "1") != "0"
         self._dec_stream, self._dec_stream_handle, self._adm_inflight = None, None, 0
         self.n_cus = int(torch.cuda.get_device_properties(self.device).multi_processor_count)
-        self._resample_cache: Dict[tuple, tuple] = {}   # (h, w, rh, rw) -> device tables of the GPU image front end
         self.persist_blocks = int(os.environ.get("KARANTA_PERSIST_BLOCKS", "512"))  # 2 persistent workgroups per CU (swept: 256..1024)
-        if type(self) is Engine and any(os.environ.get(k, "0") not in ("", "0") for k in
-                                        ("KARANTA_PREFETCH", "KARANTA_FAST_RESIDUAL", "KARANTA_ATTN_FUSED", "KARANTA_MERGE_IN_OPROJ")):
-            raise KarantaHipError("KARANTA_PREFETCH / KARANTA_FAST_RESIDUAL / KARANTA_ATTN_FUSED / KARANTA_MERGE_IN_OPROJ are decode "
-                                  "experiments: they run on csrc/tools/experiment_engine.ExperimentEngine with a -DKR_EXPERIMENTS "
-                                  "library (csrc/tools/build_variant.py, KARANTA_HIP_LIB), not on the product engine")
-        # the switches that used to select a superseded launch sequence: refused, not ignored (an A/B of two identical runs)
-        if os.environ.get("KARANTA_RESNORM32_QKV", "1") != "1":
-            raise KarantaHipError("KARANTA_RESNORM32_QKV is retired: the packed family with the fused row-major qkv launch was "
-                                  "measured and dropped (profiles/r04_decode32_chains.txt)")
-        moved = [k for k in SEQUENCE_SWITCHES if os.environ.get(k, "1") != "1"] + [k for k in ("KARANTA_RESNORM_QKV",) if k in os.environ]
-        if type(self) is Engine and moved:
-            raise KarantaHipError(" / ".join(moved) + ": superseded decode launch sequences run on csrc/tools/experiment_engine."
-                                  "ExperimentEngine (csrc/tools/decode_ab.py builds it for such a variant), not on the product engine")
+        self._refuse_retired_switches()
         v, t = cfg.vision, cfg.text
         if v.head_dim not in (80, 128) or t.head_dim != 128:
             raise KarantaHipError(f"unsupported head dims vit={v.head_dim} llm={t.head_dim}")
@@ -468,31 +154,27 @@ class Engine:
         self._last_batch = max_batch
         self._alloc()
 
+    def _refuse_retired_switches(self):
+        if type(self) is Engine and any(os.environ.get(k, "0") not in ("", "0") for k in
+                                        ("KARANTA_PREFETCH", "KARANTA_FAST_RESIDUAL", "KARANTA_ATTN_FUSED", "KARANTA_MERGE_IN_OPROJ")):
+            raise KarantaHipError("KARANTA_PREFETCH / KARANTA_FAST_RESIDUAL / KARANTA_ATTN_FUSED / KARANTA_MERGE_IN_OPROJ are decode "
+                                  "experiments: they run on csrc/tools/experiment_engine.ExperimentEngine with a -DKR_EXPERIMENTS "
+                                  "library (csrc/tools/build_variant.py, KARANTA_HIP_LIB), not on the product engine")
+        # the switches that used to select a superseded launch sequence: refused, not ignored (an A/B of two identical runs)
+        if os.environ.get("KARANTA_RESNORM32_QKV", "1") != "1":
+            raise KarantaHipError("KARANTA_RESNORM32_QKV is retired: the packed family with the fused row-major qkv launch was "
+                                  "measured and dropped (profiles/r04_decode32_chains.txt)")
+        moved = [k for k in SEQUENCE_SWITCHES if os.environ.get(k, "1") != "1"] + [k for k in ("KARANTA_RESNORM_QKV",) if k in os.environ]
+        if type(self) is Engine and moved:
+            raise KarantaHipError(" / ".join(moved) + ": superseded decode launch sequences run on csrc/tools/experiment_engine."
+                                  "ExperimentEngine (csrc/tools/decode_ab.py builds it for such a variant), not on the product engine")
+
     # ------------------------------------------------------------------ buffers
     def _alloc(self):
-        v, t, dev = self.cfg.vision, self.cfg.text, self.device
-        N, M, B, R = self.max_patches, self.max_tokens, self.B, self.rows
+        t, dev = self.cfg.text, self.device
+        M, B, R = self.max_tokens, self.B, self.rows
         z = lambda *shape, dtype=BF16: torch.zeros(*shape, dtype=dtype, device=dev)
-        nvb = N // 64 + 64  # V^T blocks: every image may add one partial block
-        if v.variant == "qwen2_5":  # windowed blocks: every window starts a V^T block, edge windows are partial ones
-            per_win = (v.window_merge_units * v.spatial_merge_size) ** 2
-            nvb = max(nvb, 2 * (N // max(1, min(64, per_win))) + 64)
-        # ViT
-        self.v_pix = z(N, v.patch_dim, dtype=torch.float32)
-        self.v_in = z(N, v.patch_dim_padded)
-        self.v_x = z(N, v.embed_dim)
-        self.v_h = z(N, v.embed_dim)
-        self.v_qkv = z(N, 3 * v.embed_dim)
-        self.v_q = z(v.num_heads, N, v.head_dim)
-        self.v_k = z(v.num_heads, N, v.head_dim)
-        self.v_vt = z(v.num_heads, nvb, v.head_dim, 64)
-        self.v_o = z(N, v.embed_dim)
-        self.v_f = z(N, v.mlp_dim_padded)
-        self.v_perm = None  # Qwen2.5-VL: window-order gather indices live in the per-geometry cache
-        self.v_m1 = z(N // 4 + 1, v.merge_dim)
-        self._vit_cache = {}
-        self._vit_rot_cache = {}   # (t, h, w) -> (cos, sin) of one image, resident in HBM (_vit_tables)
-        self.img_embeds = z(N // 4 + 1, t.hidden_size)
+        self.vision = VisionTower(self)
         # decoder prefill
         self.p_x = z(M, t.hidden_size)
         self.p_h = z(M, t.hidden_size)
@@ -592,36 +274,7 @@ class Engine:
             self.d_script = z(B, dtype=torch.int64)
             self.d_script_len = z(B, dtype=torch.int32)
             self._scripts: Dict[int, torch.Tensor] = {}
-        # guided decoding: per slot the device addresses of its pattern's tables (0 = unconstrained) + its DFA state
-        self.d_gtrans = z(B, dtype=torch.int64)
-        self.d_gmasks = z(B, dtype=torch.int64)
-        self.d_gstate = z(B, dtype=torch.int32)
-        self.mask_words = 2 * ((t.vocab_size + 63) // 64)
-        # sampling controls: per-slot params (sampling_params), output-token counts, prompt-token bit set, the threshold pass's
-        # scratch scores, threshold keys and live flags (kr_sample_threshold / kr_gumbel_argmax_processed / kr_sample_count)
-        self.d_sp = torch.tensor(np.tile(sampling_params(PageRequest(np.zeros(0, np.int64))), (B, 1)), device=dev)
-        self.d_counts = z(B, t.vocab_size, dtype=torch.int32)
-        self.bits_words = (t.vocab_size + 31) // 32
-        self.d_pbits = z(B, self.bits_words, dtype=torch.int32)
-        self.d_work = z(B, t.vocab_size, dtype=torch.float32)
-        self.d_thr = z(B, dtype=torch.int32)
-        self.d_live = z(B, dtype=torch.int32)
-        # logit adjustments: per-slot tables (sampling.adjust_table; a row with n_entries == 0 is left alone) and the values
-        # kr_logits_adjust saves for kr_logits_restore
-        self.d_adj_ids = z(B, ADJ_CAP, dtype=torch.int32)
-        self.d_adj_val = z(B, ADJ_CAP, dtype=torch.float32)
-        self.d_adj_flag = z(B, ADJ_CAP, dtype=torch.int32)
-        self.d_adj_meta = z(B, 4, dtype=torch.int32)
-        self.d_adj_saved = z(B, ADJ_CAP, dtype=torch.float32)
-        self.d_voc_off = self.d_voc_bytes = None   # set_vocab()
-        self._guides: Dict[str, DeviceGuide] = {}
-        self._slot_guides: Dict[int, DeviceGuide] = {}   # keeps the tables of the running requests alive
-        # log-probabilities: [hist][B][1 + 20] / [hist][B][20], allocated with the token history when asked for
-        self.lp_part = max(64 if t.vocab_size > 4096 else 1, -(-t.vocab_size // 4096))   # slices of <= 4096 logits
-        self.d_lp = self.d_lpi = None
-        self.d_lp_pv = z(B, self.lp_part, 20, dtype=torch.float32)
-        self.d_lp_pi = z(B, self.lp_part, 20, dtype=torch.int32)
-        self.d_lp_ms = z(B, self.lp_part, 2, dtype=torch.float32)
+        self.sampler = Sampler(self)
         self.max_new = 0          # size of the token history / rotary tables (only grows: graphs hold their addresses)
         self._req_max_new = 0     # what the current generate() / begin_slots() asked for (capacity checks use this)
         self.d_hist = None
@@ -766,194 +419,18 @@ class Engine:
         src = torch.from_numpy(np.ascontiguousarray(arr))
         dst.view(-1)[:src.numel()].copy_(src.view(-1), non_blocking=False)
 
-    # ------------------------------------------------------------------ vision tower
-    def _vit_tables(self, grids) -> VitTables:
-        """Rotary tables and attention work lists depend only on the image grids: build once per
-        distinct batch geometry and keep them resident in HBM."""
-        key = tuple(tuple(int(x) for x in g) for g in grids)
-        hit = self._vit_cache.get(key)
-        if hit is None:
-            v, dev = self.cfg.vision, self.device
-            t_ = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-            # the rotary tables of an image depend on its own grid only: kept per grid, so that a batch of a new COMPOSITION (every
-            # admission of a corpus with mixed page sizes) costs a concatenation on the device, not ~0.7 ms of numpy per page with the
-            # GPU waiting (the work lists below are a few hundred integers)
-            per_img = []
-            for g in key:
-                hit_i = self._vit_rot_cache.get(g)
-                if hit_i is None:
-                    c_i, s_i = POS.vision_rotary_tables((g,), v.head_dim, v.spatial_merge_size)
-                    hit_i = (t_(c_i), t_(s_i))
-                    if len(self._vit_rot_cache) > 64:
-                        self._vit_rot_cache.clear()
-                    self._vit_rot_cache[g] = hit_i
-                per_img.append(hit_i)
-            cos = per_img[0][0] if len(per_img) == 1 else torch.cat([c for c, _ in per_img])
-            sin = per_img[0][1] if len(per_img) == 1 else torch.cat([s_ for _, s_ in per_img])
-            hit = VitTables(cos, sin, device_plan(POS.vit_attn_plan(key), dev))
-            if v.variant == "qwen2_5":
-                # window order (TF25:430-446): patches move in groups of merge^2; rotary tables move with them;
-                # two attention work lists: windows, and whole images for the fullatt_block_indexes blocks
-                unit = v.spatial_merge_size ** 2
-                order, win_lens = POS.vision_window_order(key, v.spatial_merge_size, v.window_size, v.patch_size)
-                perm = (order[:, None] * unit + np.arange(unit)[None, :]).reshape(-1)      # patch-level gather
-                perm_long = t_(perm.astype(np.int64))
-                hit.cos, hit.sin = cos.index_select(0, perm_long), sin.index_select(0, perm_long)
-                hit.perm, hit.inv = t_(perm.astype(np.int32)), t_(np.argsort(order).astype(np.int32))
-                hit.win = device_plan(POS.segments_attn_plan(win_lens), dev)
-            if len(self._vit_cache) > 16:
-                self._vit_cache.clear()
-            self._vit_cache[key] = hit
-        return hit
-
-    # ------------------------------------------------------------------ GPU image front end
-    def patches_from_images(self, images: Sequence[np.ndarray], min_pixels: int = IP.MIN_PIXELS,
-                            max_pixels: int = IP.MAX_PIXELS_CLASS_DEFAULT,
-                            grids: Optional[Sequence[Sequence[int]]] = None):
-        """HWC uint8 RGB pages -> (pixel_values fp32 [n, 1176] resident in HBM, grids): smart_resize on the host
-        (integers), PIL-identical bicubic resize, normalisation and patch order on the GPU
-        (kr_image_resize_bicubic_u8 / kr_image_normalize_patchify).  Same numbers as
-        image_processing.image_to_patches, bit for bit, without the host resample and with 3 bytes per pixel
-        crossing PCIe instead of 2 x 1176 floats per patch.  ``grids`` (one (1, gh, gw) per image): resize to exactly
-        gh x gw patches — what the prompt's placeholders were counted for — instead of running smart_resize here."""
-        v, L, s, dev = self.cfg.vision, self.L, self.s, self.device
-        unit = v.patch_size * v.spatial_merge_size
-        metas, total = [], 0
-        if grids is not None and len(grids) != len(images):
-            raise KarantaHipError(f"{len(images)} images but {len(grids)} grids")
-        for k, im in enumerate(images):
-            if isinstance(im, torch.Tensor):       # a page already resident in HBM (uint8 HWC): no copy at all
-                if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
-                    raise KarantaHipError("device images must be contiguous HWC uint8 RGB tensors")
-            else:
-                im = np.asarray(im)
-                if im.ndim == 2:
-                    im = np.stack([im] * 3, axis=-1)
-                if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                    raise KarantaHipError("images must be HWC uint8 RGB arrays")
-                im = np.ascontiguousarray(im)
-            h, w = int(im.shape[0]), int(im.shape[1])
-            if grids is not None:
-                g = [int(x) for x in grids[k]]
-                if g[0] != 1 or g[1] % v.spatial_merge_size or g[2] % v.spatial_merge_size or min(g[1:]) < 1:
-                    raise KarantaHipError(f"image grid {tuple(g)} is not (1, even, even)")
-                rh, rw = g[1] * v.patch_size, g[2] * v.patch_size
-            else:
-                rh, rw = IP.smart_resize(h, w, unit, min_pixels, max_pixels)
-            metas.append((im, h, w, rh, rw))
-            total += (rh // v.patch_size) * (rw // v.patch_size)
-        out = torch.empty(total, v.patch_dim, dtype=torch.float32, device=dev)
-        mean = (C.c_float * 3)(*[float(x) for x in IP.CLIP_MEAN])
-        std = (C.c_float * 3)(*[float(x) for x in IP.CLIP_STD])
-        grids, off = [], 0
-        with torch.cuda.stream(self.stream):
-            for im, h, w, rh, rw in metas:
-                if isinstance(im, torch.Tensor):
-                    src = im if im.device == dev else im.to(dev)
-                else:
-                    src = torch.from_numpy(im if im.flags.writeable else im.copy()).to(dev)   # PIL-backed arrays are read-only
-                key = (h, w, rh, rw)
-                tabs = self._resample_cache.get(key)
-                if tabs is None:
-                    t_ = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                    hb, hk = IP.resample_tables(w, rw) if rw != w else (None, None)
-                    vb, vk = IP.resample_tables(h, rh) if rh != h else (None, None)
-                    tabs = tuple(None if a is None else t_(a) for a in (hb, hk, vb, vk))
-                    if len(self._resample_cache) > 64:
-                        self._resample_cache.clear()
-                    self._resample_cache[key] = tabs
-                hb, hk, vb, vk = tabs
-                dst = torch.empty(rh, rw, 3, dtype=torch.uint8, device=dev)
-                tmp = torch.empty(h, rw, 3, dtype=torch.uint8, device=dev) if (rw != w and rh != h) else None
-                L.kr_image_resize_bicubic_u8(ptr(src), h, w, ptr(dst), rh, rw, ptr(tmp), ptr(hb), ptr(hk),
-                                             hk.shape[1] if hk is not None else 0, ptr(vb), ptr(vk),
-                                             vk.shape[1] if vk is not None else 0, s)
-                n = (rh // v.patch_size) * (rw // v.patch_size)
-                L.kr_image_normalize_patchify(ptr(dst), rh, rw, mean, std, v.patch_size, v.spatial_merge_size,
-                                              v.temporal_patch_size, ptr(out[off:]), s)
-                grids.append((1, rh // v.patch_size, rw // v.patch_size))
-                off += n
-        return out, grids
-
-    def _pixels_for(self, pages: Sequence[PageRequest], pixel_values_device):
-        """The pixel source of a batch of pages: caller-resident patches, the GPU front end (pages with `images`),
-        or the pages' host arrays."""
-        if pixel_values_device is not None:
-            return pixel_values_device
-        with_images = [p for p in pages if p.images]
-        if with_images:
-            if any(p.pixel_values is not None and len(p.pixel_values) for p in pages):
-                raise KarantaHipError("a batch mixes pages with `images` and pages with `pixel_values`")
-            for p in pages:
-                if len(p.images or []) != len(p.grids):
-                    raise KarantaHipError(f"a page has {len(p.images or [])} images but {len(p.grids)} grids")
-            pix, _ = self.patches_from_images([im for p in pages for im in (p.images or [])],
-                                              grids=[g for p in pages for g in p.grids])
-            return pix
-        pvs = [p.pixel_values for p in pages if p.pixel_values is not None and len(p.pixel_values)]
-        if not pvs:
-            return None
-        return np.concatenate(pvs, 0) if len(pvs) > 1 else pvs[0]
+    # ------------------------------------------------------------------ vision tower and guides: the components' public entries
+    def patches_from_images(self, images, min_pixels: int = IP.MIN_PIXELS, max_pixels: int = IP.MAX_PIXELS_CLASS_DEFAULT, grids=None):
+        return self.vision.patches_from_images(images, min_pixels, max_pixels, grids)
 
     def vit_forward(self, pixel_values, grids: Sequence[Sequence[int]]) -> torch.Tensor:
-        """Qwen2VisionTransformerPretrainedModel.forward (TF:700-731) or its Qwen2.5-VL successor.  ``pixel_values`` is fp32
-        ``[n, 1176]`` — a numpy array (copied to the device here) or a torch tensor already resident
-        in HBM.  Returns a view of the merged image embeddings ``[T, d]`` (bf16, device)."""
-        v, L, s, w = self.cfg.vision, self.L, self.s, self.w
-        n = int(pixel_values.shape[0])
-        if n == 0:
-            return self.img_embeds[:0]
-        if n > self.max_patches:
-            raise KarantaHipError(f"{n} patches > max_patches {self.max_patches}")
-        with torch.cuda.stream(self.stream):
-            tab = self._vit_tables(grids)
-            assert tab.full.host.n_tokens == n, (tab.full.host.n_tokens, n)
-            if isinstance(pixel_values, torch.Tensor):
-                pix = pixel_values
-                if pix.dtype != torch.float32 or not pix.is_cuda or not pix.is_contiguous():
-                    raise KarantaHipError("device pixel_values must be a contiguous fp32 CUDA tensor")
-            else:
-                self._h2d(self.v_pix, np.asarray(pixel_values, dtype=np.float32))
-                pix = self.v_pix
-            D, H, hd, d_out = v.embed_dim, v.num_heads, v.head_dim, self.cfg.text.hidden_size
-            x, h = self.v_x, self.v_h
-            L.kr_cast_pad_f32_bf16(ptr(pix), ptr(self.v_in), n, v.patch_dim, v.patch_dim_padded, s)
-            self._gemm(self.v_in, w.view("vit.patch"), x, n)
-            if max(pl.host.n_vt_blocks for pl in (tab.full, tab.win) if pl is not None) > self.v_vt.shape[1]:
-                raise KarantaHipError("too many image segments for the V^T buffer")
-            # what the variant decides.  Qwen2-VL (TF:700-731): LayerNorm, fc1 / QuickGELU / fc2, attention over whole images.
-            # Qwen2.5-VL (TF25:430-472): RMSNorm, biased SwiGLU, attention inside the windows except in the
-            # fullatt_block_indexes blocks, tokens gathered into window order for the blocks and scattered back after the merger
-            v25 = v.variant == "qwen2_5"
-            if v25:
-                L.kr_embed_scatter(ptr(tab.perm), ptr(x), 0, ptr(h), n, D, s)   # image order -> window order
-                x, h = h, x
-                norm = lambda name: L.kr_rmsnorm(ptr(x), D, ptr(w.view(name + ".w")), ptr(h), n, D, 1e-6, s)
-                up, down, epi = "gate_up", "down", EPI_SILU_MUL8
-            else:
-                norm = lambda name: L.kr_layernorm(ptr(x), ptr(w.view(name + ".w")), ptr(w.view(name + ".b")), ptr(h), n, D, 1e-6, s)
-                up, down, epi = "fc1", "fc2", EPI_QUICK_GELU
-            for i in range(v.depth):
-                p = f"vit.{i}."
-                norm(p + "ln1")
-                self._gemm(h, w.view(p + "qkv.w"), self.v_qkv, n, bias=w.view(p + "qkv.b"))
-                self._attention(self.v_qkv, D, 2 * D, tab.cos, tab.sin, tab.win if v25 and i not in v.fullatt_block_indexes else tab.full,
-                                self.v_q, self.v_k, self.v_k.stride(0), self.v_vt, self.v_vt.stride(0), self.v_o, H, H, hd, causal=False)
-                self._gemm(self.v_o, w.view(p + "proj.w"), x, n, bias=w.view(p + "proj.b"), res=x)
-                norm(p + "ln2")
-                self._gemm(h, w.view(p + up + ".w"), self.v_f, n, bias=w.view(p + up + ".b"), epi=epi)
-                self._gemm(self.v_f, w.view(p + down + ".w"), x, n, bias=w.view(p + down + ".b"), res=x)
-            # PatchMerger (TF:277-290): norm -> view [n/4, 4D] -> Linear+GELU -> Linear
-            norm("vit.merger.ln")
-            T = n // (v.spatial_merge_size ** 2)
-            merged_in = h.view(-1)[: T * v.merge_dim].view(T, v.merge_dim)
-            self._gemm(merged_in, w.view("vit.merger.fc1.w"), self.v_m1, T, bias=w.view("vit.merger.fc1.b"), epi=EPI_GELU_ERF)
-            # window order: the second GEMM goes to v_o, then back to image order (reverse_indices, TF25:466-468)
-            out = self.v_o.view(-1)[: T * d_out].view(T, d_out) if v25 else self.img_embeds
-            self._gemm(self.v_m1, w.view("vit.merger.fc2.w"), out, T, bias=w.view("vit.merger.fc2.b"))
-            if v25:
-                L.kr_embed_scatter(ptr(tab.inv), ptr(out), 0, ptr(self.img_embeds), T, d_out, s)
-        return self.img_embeds[:T]
+        return self.vision.vit_forward(pixel_values, grids)
+
+    def set_vocab(self, token_bytes: Sequence[bytes]):
+        self.sampler.set_vocab(token_bytes)
+
+    def compile_guide(self, guide) -> DeviceGuide:
+        return self.sampler.compile_guide(guide)
 
     def _attention(self, qkv, k_off, v_off, cos, sin, dp: DevicePlan, q, k, k_stride, vt, vt_stride, out, H, KVH, hd, causal):
         """Varlen attention of a fused [rows, q | k | v] buffer: kr_qkv_prep (rotary on q and k; q head-major, k rows and V^T
@@ -966,63 +443,6 @@ class Engine:
         L.kr_attn_varlen_q(ptr(q), ptr(k), ptr(vt), ptr(out), ptr(dp.qblk), ptr(dp.qlen), dp.host.qblk.shape[0], q.shape[1],
                            H, KVH, hd, k_stride, vt_stride, hd ** -0.5, 1 if causal else 0, dp.host.q_block, s)
 
-    # ------------------------------------------------------------------ guided decoding
-    def set_vocab(self, token_bytes: Sequence[bytes]):
-        """Byte string of every token id (b"" for special tokens) — what a pattern is matched against.  Needed once
-        before any guided request (serving.ChatFrontend hands over its tokenizer's table)."""
-        from .guided import pack_vocab
-        V = self.cfg.text.vocab_size
-        tb = list(token_bytes)[:V] + [b""] * max(0, V - len(token_bytes))
-        off, flat = pack_vocab(tb)
-        self.d_voc_off = torch.from_numpy(off).to(self.device)
-        self.d_voc_bytes = torch.from_numpy(flat).to(self.device)
-        self._guides.clear()
-
-    def compile_guide(self, guide) -> DeviceGuide:
-        """guided.Guide (or a regex string) -> device tables; cached by pattern."""
-        from .guided import Guide, compile_regex
-        if isinstance(guide, DeviceGuide):
-            return guide
-        if isinstance(guide, str):
-            hit = self._guides.get(guide)
-            if hit is not None:
-                return hit
-            guide = compile_regex(guide)
-        if not isinstance(guide, Guide):
-            raise KarantaHipError(f"not a guide: {type(guide).__name__}")
-        if guide.pattern and guide.pattern in self._guides:
-            return self._guides[guide.pattern]
-        if self.d_voc_off is None:
-            raise KarantaHipError("guided decoding needs the vocabulary's byte strings: call Engine.set_vocab() first")
-        S = guide.n_states
-        trans = torch.from_numpy(np.ascontiguousarray(guide.trans).view(np.int16)).to(self.device)
-        accept = torch.from_numpy(np.ascontiguousarray(guide.accept).astype(np.uint8)).to(self.device)
-        masks = torch.empty(S, self.mask_words, dtype=torch.int32, device=self.device)
-        torch.cuda.current_stream(self.device).synchronize()
-        with torch.cuda.stream(self.stream):
-            self.L.kr_guide_build_masks(ptr(trans), ptr(accept), S, ptr(self.d_voc_off), ptr(self.d_voc_bytes),
-                                        self.cfg.text.vocab_size, ptr(self.d_eos), self.d_eos.numel(), ptr(masks),
-                                        self.mask_words, self.s)
-        self.stream.synchronize()
-        dg = DeviceGuide(guide, trans, masks)
-        if guide.pattern:
-            if len(self._guides) >= 64:           # bounded cache: drop the oldest pattern
-                self._guides.pop(next(iter(self._guides)))
-            self._guides[guide.pattern] = dg
-        return dg
-
-    def _guide_rows(self, pages):
-        """Per page: (trans address, masks address, start state, DeviceGuide | None)."""
-        rows = []
-        for p in pages:
-            g = getattr(p, "guide", None)
-            if g is None:
-                rows.append((0, 0, 0, None))
-                continue
-            dg = self.compile_guide(g)
-            rows.append((dg.trans.data_ptr(), dg.masks.data_ptr(), dg.start, dg))
-        return rows
-
     # ------------------------------------------------------------------ admission: host tables, prefill, slot state, first tokens
     def _ensure_history(self, max_new_tokens: int):
         """Token history, rotary table and (when asked for) log-prob history sized for max_new_tokens; their
@@ -1033,14 +453,22 @@ class Engine:
             self.max_new = max_new_tokens
             self.d_hist = torch.zeros(max_new_tokens + 1, self.B, dtype=torch.int32, device=self.device)
             self.d_cs = torch.zeros(self.B, max_new_tokens, self.cfg.text.head_dim, dtype=torch.float32, device=self.device)
-        if self._logprobs is not None and (self.d_lp is None or self.d_lp.shape[0] < self.max_new + 1):
-            self.d_lp = torch.zeros(self.max_new + 1, self.B, 21, dtype=torch.float32, device=self.device)
-            self.d_lpi = torch.zeros(self.max_new + 1, self.B, 20, dtype=torch.int32, device=self.device)
-            grow = True
+        grow = self.sampler.ensure_logprob_history(self.max_new + 1) or grow
         if grow:
             for g in self._graphs.values():
                 self.L.kr_graph_destroy(g)
             self._graphs.clear()
+
+    def _enter_mode(self, max_new_tokens: int, *, ignore_eos: bool, freeze_finished: bool, want_logits: bool, caps: StepFeatures,
+                    step: StepFeatures, logprobs: Optional[int]):
+        """The switches of a mode (generate(), slot mode, a tool's bare decode steps), THEN the history they size (log-probabilities
+        get theirs only when asked for), THEN the budget the capacity checks use: in this order, or the history is smaller than
+        the budget check assumes."""
+        self._ignore_eos, self._freeze_finished, self._want_logits = bool(ignore_eos), bool(freeze_finished), bool(want_logits)
+        self._caps, self._step = caps, step
+        self._logprobs = None if logprobs is None else int(logprobs)
+        self._ensure_history(max_new_tokens)
+        self._req_max_new = int(max_new_tokens)
 
     def seq_room(self) -> int:
         """Cache rows one sequence may use: prompt + generated tokens (slot mode keeps the last row as the parking row)."""
@@ -1117,7 +545,7 @@ class Engine:
                          budgets: Optional[Sequence[int]] = None, rows: Optional[list] = None) -> Admission:
         """Front of every admission: the pages' images through the ViT (launches only), then the host tables of the prefill
         while those launches execute."""
-        pix = self._pixels_for(pages, pixel_values_device)
+        pix = self.vision._pixels_for(pages, pixel_values_device)
         n_img_tok = self.vit_forward(pix, [g for p in pages for g in p.grids]).shape[0] if pix is not None else 0
         return self._prefill_prepare(pages, n_img_tok, slots, budgets, rows)
 
@@ -1129,8 +557,8 @@ class Engine:
         prompt lengths).  ``adm``: what `_prefill_prepare` made of these pages ahead of time.
         ``slots`` (slot scheduler): the cache / state slots the pages go to; only those slots' state is
         touched, the other sequences keep decoding from where they are.  ``defer_activation`` (overlapped
-        admission): only the layers run here (they fill the slots' KV rows); `admit_end` applies the slot state writes and
-        the first sampling step from the returned record on the decode stream."""
+        admission): only the layers run here (they fill the slots' KV rows); `admit_end` activates the sequences (`_activate`) from the
+        returned record on the decode stream."""
         t, L, s, w = self.cfg.text, self.L, self.s, self.w
         if adm is None or adm.n_img != n_image_tokens_total:
             adm = self._prefill_prepare(pages, n_image_tokens_total, slots)
@@ -1141,12 +569,12 @@ class Engine:
             self._h2d(self.p_src, adm.src)
             self._h2d(self.p_cos, adm.cos)
             self._h2d(self.p_sin, adm.sin)
-            self._sampler_rows(adm, rows)
+            self.sampler._sampler_rows(adm, rows)
             if not defer_activation:
-                self._write_state(adm)
+                self._activate(adm, tokens=False)
             self._h2d(self.d_last, adm.last_rows)
             dp = device_plan(adm.plan, self.device)
-            L.kr_embed_scatter(ptr(self.p_src), ptr(w.view("llm.embed")), ptr(self.img_embeds), ptr(self.p_x), M, d, s)
+            L.kr_embed_scatter(ptr(self.p_src), ptr(w.view("llm.embed")), ptr(self.vision.img_embeds), ptr(self.p_x), M, d, s)
             for i in range(t.num_layers):
                 p = f"llm.{i}."
                 L.kr_rmsnorm(ptr(self.p_x), d, ptr(w.view(p + "ln1.w")), ptr(self.p_h), M, d, t.rms_norm_eps, s)
@@ -1161,16 +589,8 @@ class Engine:
             self.pages_prefilled += adm.n_pages
             if not defer_activation:
                 self._fork(adm.forks)
-                self._first_tokens(adm)
+                self._activate(adm, state=False)
         return adm
-
-    def _sampler_rows(self, adm: Admission, rows):
-        """What the sampler keeps per sequence, from the admission's sequences (`children` of its pages)."""
-        adm.temps = np.asarray([temperature(p) for p in rows], np.float32)
-        adm.seeds = np.asarray([int(getattr(p, "seed", 0) or 0) & 0xFFFFFFFF for p in rows], np.uint32).view(np.int32)
-        adm.guides = self._guide_rows(rows)
-        adm.procs = self._control_rows(rows)
-        adm.adjs = self._adjust_rows(rows)
 
     def _fork(self, groups):
         """kr_kv_fork: the prompt's KV rows of every (source slot, prompt length, [destination slots]), in one launch on the
@@ -1185,177 +605,99 @@ class Engine:
     def _admit_features(self, pages) -> StepFeatures:
         """What an admission's pages need: raises where the mode does not allow it, else the next steps carry it (from this
         admission on: its first token included).  Returns the need."""
-        need, caps = StepFeatures.of(pages), self._caps
-        if need.guided and not caps.guided:
-            raise KarantaHipError("a page carries a guide but the engine is not in its guided configuration "
-                                  "(generate() decides from its pages; begin_slots(guided=True) for slot mode)")
-        if need.adjust and not caps.adjust:
-            raise KarantaHipError("a page asks for logit_bias / min_tokens / stop_token_ids but the engine is in its greedy "
-                                  "configuration (generate() decides from its pages; begin_slots(sampling=True) for slot mode)")
-        if need.sampling and not caps.sampling:
-            raise KarantaHipError("a page asks for temperature > 0 but the engine is in its greedy configuration "
-                                  "(generate() decides from its pages; begin_slots(sampling=True) for slot mode)")
-        if need.processing and not caps.processing:
-            raise KarantaHipError("a page asks for top_k / top_p / min_p / penalties but the engine is in its greedy "
-                                  "configuration (generate() decides from its pages; begin_slots(sampling=True) for slot mode)")
+        need = StepFeatures.of(pages)
+        self.sampler.check_features(need)
         self._step |= need
         return need
 
-    def _control_rows(self, pages):
-        """Per page (params row, prompt bit set or None, penalised) when the engine may run the processing launches, else None."""
-        if not self._caps.processing:
-            return None
-        V, rows = self.cfg.text.vocab_size, []
-        for p in pages:
-            sp, nd = sampling_params(p), needs_processing(p)
-            bits = None
-            if nd and sp[3] != 1.0:       # repetition penalty: the prompt's tokens (image placeholders included)
-                ids = np.asarray(p.input_ids, np.int64).reshape(-1)
-                ids = ids[(ids >= 0) & (ids < V)]
-                bits = np.zeros(self.bits_words, np.uint32)
-                np.bitwise_or.at(bits, ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
-            rows.append((sp, bits, nd))
-        return rows
+    def _activate(self, a: Admission, src_of: Optional[Sequence[int]] = None, state: bool = True, tokens: bool = True):
+        """Starts an admission's sequences in their slots, the same way whatever admitted them.
+        `state`: the decode state, field by field from one list of (device field, host rows) — one copy per field for a whole
+        batch, padded with zeros to max_batch rows; one-row copies into named slots, the others keep decoding — then the
+        sampler's own fields (Sampler.write).
+        `tokens`: every sequence's last prompt position -> its slot's x -> lm_head -> first token, the whole batch in one pass,
+        named slots one by one.  The hidden row comes from the prefill just run (row d_last[b] of p_x; the children of a page read
+        the same row), or with `src_of` (admit_reuse: per sequence the slot that holds its prompt) from what that prefill left
+        in d_prompt_x — which every activation keeps per slot for exactly this.
+        A non-deferred prefill writes the state before its layers and samples behind them; every other caller does both at once."""
+        if state:
+            lens = np.asarray(a.lens, np.int32)
+            for j, n in zip(a.slots, a.lens):
+                self._slot_plen[j] = int(n)
+            self.sequences_started += a.B
+            fields = ((self.d_delta, a.deltas), (self.d_ctx, lens - 1), (self.d_plen, lens),   # kr_sample_greedy adds 1 to ctx -> cached tokens
+                      (self.d_temp, a.temps), (self.d_seed, a.seeds))
+            for dst, rows in fields:
+                for j, part in a.copies(rows, self.B):
+                    self._h2d(dst[j:], part)
+            for b, j, n in a.spans(a.B):
+                self._h2d(self.d_cs[j:], a.cs[b:b + n])
+            for _, j, n in a.spans(self.B):
+                self.d_fin[j:j + n].zero_()
+            if self.spec is not None:     # kr_spec_propose looks the drafts up in prompt + history
+                for p, j in zip(a.rows, a.slots):
+                    self._h2d(self.d_prompt_ids[j], np.asarray(p.input_ids, np.int64).reshape(-1).astype(np.int32))
+            self.sampler.write(a)
+        if tokens:
+            d = self.cfg.text.hidden_size
+            for b, j, n in a.spans(a.B):
+                if src_of is None:
+                    self.L.kr_embed_scatter(ptr(self.d_last[b:]), ptr(self.p_x), 0, ptr(self.d_x[j:]), n, d, self.s)
+                    self.L.kr_embed_scatter(ptr(self.d_last[b:]), ptr(self.p_x), 0, ptr(self.d_prompt_x[j:]), n, d, self.s)
+                else:
+                    if j != src_of[b]:
+                        self.d_prompt_x[j].copy_(self.d_prompt_x[src_of[b]])
+                    self.d_x[j].copy_(self.d_prompt_x[j])
+                self._lm_head_and_sample(n, slot0=j)
 
-    def _adjust_rows(self, pages):
-        """Per page its logit-adjustment table (sampling.adjust_table) or None, when the engine may run the adjustment launches,
-        else None."""
-        if not self._caps.adjust:
-            return None
-        try:
-            return [adjust_table(p, self.cfg.eos_token_ids, self.cfg.text.vocab_size) for p in pages]
-        except ValueError as e:
-            raise KarantaHipError(str(e)) from e
+    # ------------------------------------------------------------------ the step's tail: lm_head -> sampler passes -> tokens
+    def _flags(self) -> int:
+        """The flags word of kr_sample_greedy / kr_spec_accept and the sampler's passes."""
+        return (1 if self._ignore_eos else 0) | (2 if self._freeze_finished else 0)
 
-    def _write_state(self, a: Admission):
-        """Decode state of an admission's sequences: the same fields in both modes.  Whole batch: one copy per field, padded
-        with zeros to max_batch rows.  Slots: one-row copies into the named slots only, the others keep decoding."""
-        gt, gm, gs, dgs = zip(*a.guides)
-        lens = np.asarray(a.lens, np.int32)
-        for j, n in zip(a.slots, a.lens):
-            self._slot_plen[j] = int(n)
-        self.sequences_started += a.B
-        sampler = ((self.d_temp, a.temps), (self.d_seed, a.seeds))
-        fields = ((self.d_gtrans, np.asarray(gt, np.int64)), (self.d_gmasks, np.asarray(gm, np.int64)),
-                  (self.d_gstate, np.asarray(gs, np.int32)), (self.d_delta, a.deltas),
-                  (self.d_ctx, lens - 1), (self.d_plen, lens))      # kr_sample_greedy adds 1 to ctx -> number of cached tokens
-        if a.whole_batch:
-            for dst, rows in sampler + fields:
-                padded = np.zeros(self.B, rows.dtype)
-                padded[:a.B] = rows[:a.B]
-                self._h2d(dst, padded)
-            self._h2d(self.d_cs, a.cs)
-            self.d_fin.zero_()
-            self._slot_guides = {b: dg for b, dg in enumerate(dgs) if dg is not None}
-        else:
-            for b, j in enumerate(a.slots):
-                for dst, rows in fields:
-                    self._h2d(dst[j:j + 1], rows[b:b + 1])
-                self._h2d(self.d_cs[j], a.cs[b])
-                for dst, rows in sampler:
-                    self._h2d(dst[j:j + 1], rows[b:b + 1])
-                self.d_fin[j:j + 1].zero_()
-                self._slot_guides.pop(j, None)
-                if dgs[b] is not None:
-                    self._slot_guides[j] = dgs[b]
-        if self.spec is not None:     # kr_spec_propose looks the drafts up in prompt + history
-            for p, j in zip(a.rows, a.slots):
-                self._h2d(self.d_prompt_ids[j], np.asarray(p.input_ids, np.int64).reshape(-1).astype(np.int32))
-        # sampling controls: params, prompt bits, output counts cleared
-        for (sp, bits, nd), j in zip(a.procs or (), a.slots):
-            self._h2d(self.d_sp[j], sp)
-            if bits is not None:
-                self._h2d(self.d_pbits[j], bits.view(np.int32))
-            if nd:
-                self.d_counts[j].zero_()
-        # logit adjustments: the row's table; n_entries = 0 where the page has none, so a slot never keeps its predecessor's
-        if a.adjs is not None and a.whole_batch:
-            self.d_adj_meta.zero_()
-        for tab, j in zip(a.adjs or (), a.slots):
-            if tab is None:
-                if not a.whole_batch:
-                    self.d_adj_meta[j].zero_()
-                continue
-            for dst, rows in zip((self.d_adj_ids, self.d_adj_val, self.d_adj_flag, self.d_adj_meta), tab):
-                self._h2d(dst[j], rows)
-
-    def _first_tokens(self, a: Admission):
-        """Last prompt position of every prefilled sequence (p_x rows d_last) -> its slot's x -> lm_head -> first token: the
-        whole batch in one pass, slots one by one.  The children of a page read the same row.  The row is also kept per slot
-        (d_prompt_x): what admit_reuse starts a later sequence on the same prompt from."""
-        d = self.cfg.text.hidden_size
-        for b, j, n in ((0, 0, a.B),) if a.whole_batch else ((b, j, 1) for b, j in enumerate(a.slots)):
-            self.L.kr_embed_scatter(ptr(self.d_last[b:]), ptr(self.p_x), 0, ptr(self.d_x[j:]), n, d, self.s)
-            self.L.kr_embed_scatter(ptr(self.d_last[b:]), ptr(self.p_x), 0, ptr(self.d_prompt_x[j:]), n, d, self.s)
-            self._lm_head_and_sample(n, slot0=j)
-
-    def _lm_head_and_sample(self, B: int, x=None, slot0: int = 0):
-        """final RMSNorm (fused) -> lm_head with per-workgroup argmax partials -> greedy token,
-        bookkeeping and the next step's rotary table (TF:839, :1320-1323; generate(do_sample=False)).
-        x = the residual buffer holding the last layer's output (d_x unless the decode step ended on the
-        other buffer); the next step's input embedding always goes to d_x."""
-        t, L, w, s = self.cfg.text, self.L, self.w, self.s
-        x = self.d_x if x is None else x
-        j = slot0  # rows j .. j+B-1 of every per-sequence array (the slot scheduler prefills single slots)
-        step = self._step
+    def _lm_head(self, B: int, x, j: int = 0):
+        """final RMSNorm (fused) -> lm_head with per-wave argmax partials over rows j .. j + B - 1 of x (TF:839, :1320-1323).
+        Returns (the f32 logits where a later pass or the caller reads them, else None; the partials per row = the stride the
+        launch wrote d_amax_* with)."""
+        w, step = self.w, self._step
         logits = self.d_logits[j:] if (self._want_logits or step.sampling or step.processing or self._logprobs is not None) else None
         if self.wide_mode:
             self._dec_wide(DEC_ARGMAX, x[j:], w.view("llm.lm_head"), B, norm_w=w.view("llm.norm.w"), out_f32=logits)
         else:
             self._dec(DEC_ARGMAX, x[j:], w.view("llm.lm_head"), B, norm_w=w.view("llm.norm.w"), out_f32=logits,
                       waves=self.wv_wide)
-        n_part = self._amax_parts(B) if self.wide_mode else self.n_amax   # the stride the lm_head launch wrote with
-        flags = (1 if self._ignore_eos else 0) | (2 if self._freeze_finished else 0)
-        gm, gs = (ptr(self.d_gmasks[j:]), ptr(self.d_gstate[j:])) if step.guided else (None, None)
-        if step.adjust:
-            # logit_bias / min_tokens somewhere in the batch: applied in place before the sampler (vLLM's order), undone after it
-            adj = (ptr(self.d_adj_ids[j:]), ptr(self.d_adj_val[j:]), ptr(self.d_adj_flag[j:]), ptr(self.d_adj_meta[j:]))
-            L.kr_logits_adjust(ptr(logits), self.d_logits.stride(0), t.vocab_size, *adj, ptr(self.d_ctx[j:]), ptr(self.d_plen[j:]),
-                               ptr(self.d_adj_saved[j:]), B, s)
-        if step.processing:
-            # sampling controls somewhere in the batch: per-row truncation threshold, then the Gumbel-max argmax over the
-            # penalised scores above it (rows with neutral controls get exactly the partials of the branch below)
-            n_part = min(64, n_part)
-            V, ld = t.vocab_size, self.d_logits.stride(0)
-            L.kr_sample_threshold(ptr(logits), ld, V, ptr(self.d_temp[j:]), ptr(self.d_sp[j:]), ptr(self.d_counts[j:]), V,
-                                  ptr(self.d_pbits[j:]), self.bits_words, gm, gs, self.mask_words, ptr(self.d_fin[j:]), flags,
-                                  ptr(self.d_work[j:]), V, ptr(self.d_thr[j:]), ptr(self.d_live[j:]), B, s)
-            L.kr_gumbel_argmax_processed(ptr(logits), ld, V, ptr(self.d_temp[j:]), ptr(self.d_seed[j:]), ptr(self.d_ctx[j:]),
-                                         ptr(self.d_plen[j:]), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, B, gm, gs,
-                                         self.mask_words, int(self.cfg.eos_token_ids[0]), ptr(self.d_sp[j:]),
-                                         ptr(self.d_counts[j:]), V, ptr(self.d_pbits[j:]), self.bits_words, ptr(self.d_thr[j:]), s)
-        elif step.sampling:
-            # temperature > 0 somewhere in the batch: the partial argmax is redone on logits / T + Gumbel noise
-            # (rows with T = 0 get their plain argmax back); guided slots: only the tokens their DFA state allows take part
-            # (unguided steps: null masks, as kr_gumbel_argmax passes them)
-            n_part = min(64, n_part)
-            mw, fb = (self.mask_words, int(self.cfg.eos_token_ids[0])) if step.guided else (0, 0)
-            L.kr_gumbel_argmax_guided(ptr(logits), self.d_logits.stride(0), t.vocab_size, ptr(self.d_temp[j:]), ptr(self.d_seed[j:]),
-                                      ptr(self.d_ctx[j:]), ptr(self.d_plen[j:]), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, B,
-                                      gm, gs, mw, fb, s)
-        L.kr_sample_greedy(ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(w.view("llm.embed")), t.hidden_size,
-                           ptr(self.d_tok[j:]), ptr(self.d_hist[:, j:]), self.d_hist.stride(0), ptr(self.d_plen[j:]),
-                           ptr(self.d_ctx[j:]), ptr(self.d_fin[j:]), ptr(self.d_eos), self.d_eos.numel(),
-                           self.cfg.pad_token_id, flags, ptr(self.d_x[j:]), B, s)
-        if step.adjust:
-            L.kr_stop_tokens(ptr(self.d_tok[j:]), adj[0], adj[2], adj[3], ptr(self.d_fin[j:]), flags, B, s)
-        if step.processing:
-            L.kr_sample_count(ptr(self.d_tok[j:]), ptr(self.d_live[j:]), ptr(self.d_counts[j:]), t.vocab_size, t.vocab_size, B, s)
-        if step.guided:
-            L.kr_guide_advance(ptr(self.d_tok[j:]), ptr(self.d_fin[j:]), ptr(self.d_gtrans[j:]), ptr(self.d_gstate[j:]),
-                               ptr(self.d_voc_off), ptr(self.d_voc_bytes), t.vocab_size, B, s)
-        if step.adjust:     # log-probabilities and returned logits report what the lm_head wrote
-            L.kr_logits_restore(ptr(logits), self.d_logits.stride(0), t.vocab_size, adj[0], adj[3], ptr(self.d_adj_saved[j:]), B, s)
-        if self._logprobs is not None:
-            L.kr_logprobs_topk(ptr(logits), self.d_logits.stride(0), t.vocab_size, int(self._logprobs), self.lp_part,
-                               ptr(self.d_lp_pv), ptr(self.d_lp_pi), ptr(self.d_lp_ms), ptr(self.d_tok[j:]), ptr(self.d_ctx[j:]),
-                               ptr(self.d_plen[j:]), ptr(self.d_fin[j:]), ptr(self.d_lp[:, j:]), ptr(self.d_lpi[:, j:]),
-                               self.d_lp.shape[0], self.B, 20, B, s)
+        return logits, (self._amax_parts(B) if self.wide_mode else self.n_amax)
+
+    def _lm_head_and_sample(self, B: int, x=None, slot0: int = 0):
+        """lm_head -> the sampler's passes (Sampler.pre_token) -> greedy token over the argmax partials, bookkeeping and the next
+        step's input embedding (generate(do_sample=False)) -> the passes behind the token (Sampler.post_token).
+        x = the residual buffer holding the last layer's output (d_x unless the decode step ended on the
+        other buffer); the next step's input embedding always goes to d_x."""
+        t, w = self.cfg.text, self.w
+        j = slot0  # rows j .. j+B-1 of every per-sequence array (the slot scheduler prefills single slots)
+        logits, n_part = self._lm_head(B, self.d_x if x is None else x, j)
+        flags = self._flags()
+        n_part = self.sampler.pre_token(logits, n_part, B, j, flags)
+        self.L.kr_sample_greedy(ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(w.view("llm.embed")), t.hidden_size,
+                                ptr(self.d_tok[j:]), ptr(self.d_hist[:, j:]), self.d_hist.stride(0), ptr(self.d_plen[j:]),
+                                ptr(self.d_ctx[j:]), ptr(self.d_fin[j:]), ptr(self.d_eos), self.d_eos.numel(),
+                                self.cfg.pad_token_id, flags, ptr(self.d_x[j:]), B, self.s)
+        self.sampler.post_token(logits, B, j, flags)
 
     # ------------------------------------------------------------------ decode
     def _decode_step_launches(self, B: int):
         """One plain decode step over the B slots: the layers, then lm_head and the sampler."""
         self._lm_head_and_sample(B, self._layer_launches(B))
+
+    def _gate_up(self, x, i: int, B: int, out_xp: bool = False):
+        """RMSNorm + gate/up + SiLU*mul of layer i over B rows of x into d_act; out_xp: in the packed layout kr_linear_decode32
+        reads."""
+        w, p = self.w, f"llm.{i}."
+        if self.wide_mode:
+            self._dec_wide(DEC_SILU8 | (DEC_OUT_XP if out_xp else 0), x, w.view(p + "gate_up.w"), B, out=self.d_act,
+                           norm_w=w.view(p + "ln2.w"), **self._w8kw(p + "gate_up.w"))
+        else:
+            self._dec(DEC_SILU8, x, w.view(p + "gate_up.w"), B, out=self.d_act, norm_w=w.view(p + "ln2.w"), waves=self.wv_wide)
 
     def _layer_launches(self, B: int, row_slot=None):
         """The layers of a decode step over B rows; returns the residual buffer that holds the last layer's output.  row_slot (a
@@ -1431,11 +773,7 @@ class Engine:
                 (e0, e1), (e2, _) = self._prof_event_pair(), self._prof_event_pair()
                 L.kr_event_record(e0, s)
                 L.kr_event_record(e1, s)
-            if self.wide_mode:
-                self._dec_wide(DEC_SILU8 | (DEC_OUT_XP if big else 0), x, w.view(p + "gate_up.w"), B, out=self.d_act,
-                               norm_w=w.view(p + "ln2.w"), **self._w8kw(p + "gate_up.w"))
-            else:
-                self._dec(DEC_SILU8, x, w.view(p + "gate_up.w"), B, out=self.d_act, norm_w=w.view(p + "ln2.w"), waves=self.wv_wide)
+            self._gate_up(x, i, B, out_xp=big)
             if self._prof_on:
                 L.kr_event_record(e2, s)
             # ---- 6. down_proj: two K ranges per tile whose sums the next layer's first launch adds to x (deferred split-K),
@@ -1482,22 +820,16 @@ class Engine:
         """One speculative step: drafts (kr_spec_propose) -> the layers over all rows -> lm_head -> the Gumbel pass when a request
         samples -> verification and bookkeeping (kr_spec_accept, in kr_sample_greedy's place).  It leaves d_ctx, d_tok, d_x[slot],
         the history and d_fin in the form a plain step leaves them, so the two kinds alternate freely."""
-        t, L, w, s, R = self.cfg.text, self.L, self.w, self.s, self.rows
+        L, s, R = self.L, self.s, self.rows
         why = self._spec_refusal()
         if why is not None:
             raise KarantaHipError("speculative decode step refused: " + why)
         a = self._spec_args()
         L.kr_spec_propose(C.byref(a), s)
         x = self._layer_launches(R, self.d_row_slot)
-        logits = self.d_logits if self._step.sampling else None
-        self._dec_wide(DEC_ARGMAX, x, w.view("llm.lm_head"), R, norm_w=w.view("llm.norm.w"), out_f32=logits)
-        n_part = self._amax_parts(R)
-        if self._step.sampling:     # the counter of a draft row's noise is its own token index: ctx_len and prompt_len are per row
-            n_part = min(64, n_part)
-            L.kr_gumbel_argmax_guided(ptr(logits), self.d_logits.stride(0), t.vocab_size, ptr(self.d_temp), ptr(self.d_seed),
-                                      ptr(self.d_ctx), ptr(self.d_plen), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, R,
-                                      None, None, 0, 0, s)
-        flags = (1 if self._ignore_eos else 0) | (2 if self._freeze_finished else 0)
+        logits, n_part = self._lm_head(R, x)
+        flags = self._flags()
+        n_part = self.sampler.pre_token(logits, n_part, R, 0, flags)     # (the refusal above leaves it the Gumbel pass alone)
         L.kr_spec_accept(C.byref(a), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(self.d_tok), ptr(self.d_eos),
                          self.d_eos.numel(), flags, s)
 
@@ -1584,19 +916,13 @@ class Engine:
         graph of reps x num_layers back-to-back launches, each on its own layer's weights (so no launch finds its
         weights in a cache: 28 x 55 MB against 32 MB of L2 and 256 MB of Infinity Cache).  The per-launch figure
         includes the dispatch gap between dependent launches, as a rocprofv3 kernel span in a graph replay does."""
-        t, w, L = self.cfg.text, self.w, self.L
+        t, L = self.cfg.text, self.L
         e0, e1 = self._prof_event_pair()
         self._prof_next -= 1
         def chain(n):
             for _ in range(n):
                 for i in range(t.num_layers):
-                    p = f"llm.{i}."
-                    if self.wide_mode:
-                        self._dec_wide(DEC_SILU8, self.d_x, w.view(p + "gate_up.w"), B, out=self.d_act, norm_w=w.view(p + "ln2.w"),
-                                       **self._w8kw(p + "gate_up.w"))
-                    else:
-                        self._dec(DEC_SILU8, self.d_x, w.view(p + "gate_up.w"), B, out=self.d_act, norm_w=w.view(p + "ln2.w"),
-                                  waves=self.wv_wide)
+                    self._gate_up(self.d_x, i, B)
         chain(1)                               # eager once (function attributes), then captured: a replayed
         self.stream.synchronize()              # graph issues the launches at the GPU's pace, not Python's
         g = C.c_void_p()
@@ -1664,20 +990,16 @@ class Engine:
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         t0 = time.perf_counter()
-        self._ignore_eos = bool(ignore_eos)
-        self._freeze_finished = False
-        self._want_logits = bool(return_logits)
-        self._caps = self._step = StepFeatures.of(rows)
         if force_tokens is not None and any(has_penalties(p) for p in rows):
             raise KarantaHipError("force_tokens with repetition / frequency / presence penalties: the output counts would follow "
                                   "the engine's own tokens, not the forced ones")
         ks = [int(p.logprobs) for p in rows if getattr(p, "logprobs", None) is not None]
         if ks and not 0 <= max(ks) <= 20:
             raise KarantaHipError("logprobs must be in 0..20")
-        self._logprobs = max(ks) if ks else None
         self._last_batch = B
-        self._ensure_history(max_new_tokens)
-        self._req_max_new = int(max_new_tokens)
+        need = StepFeatures.of(rows)
+        self._enter_mode(max_new_tokens, ignore_eos=ignore_eos, freeze_finished=False, want_logits=return_logits, caps=need, step=need,
+                         logprobs=max(ks) if ks else None)
         adm = self._vit_and_prepare(pages, pixel_values_device, rows=rows)
         self.stream.synchronize()
         t1 = time.perf_counter()
@@ -1745,8 +1067,8 @@ class Engine:
             reasons.append(reason)
         lps = None
         if self._logprobs is not None:
-            lp = self.d_lp[:steps_done, :B].cpu().numpy()
-            li = self.d_lpi[:steps_done, :B].cpu().numpy()
+            lp = self.sampler.d_lp[:steps_done, :B].cpu().numpy()
+            li = self.sampler.d_lpi[:steps_done, :B].cpu().numpy()
             lps = []
             for b, p in enumerate(rows):
                 k = getattr(p, "logprobs", None)
@@ -1771,16 +1093,13 @@ class Engine:
             raise ValueError("max_new_tokens must be >= 1")
         if logprobs is not None and not 0 <= int(logprobs) <= 20:
             raise KarantaHipError("logprobs must be in 0..20")
-        if guided and self.d_voc_off is None:
+        if guided and self.sampler.d_voc_off is None:
             raise KarantaHipError("guided decoding needs the vocabulary's byte strings: call Engine.set_vocab() first")
-        self._ignore_eos, self._freeze_finished, self._want_logits = False, True, False
         # the sampling controls come with the sampling configuration; the steps carry each pass while a request needs it
         sampled = bool(sampling) or bool(guided)
-        self._caps, self._step = StepFeatures(sampled, bool(guided), sampled, sampled), StepFeatures()
-        self._logprobs = None if logprobs is None else int(logprobs)
         self._last_batch = self.B
-        self._ensure_history(max_new_tokens)
-        self._req_max_new = int(max_new_tokens)
+        self._enter_mode(max_new_tokens, ignore_eos=False, freeze_finished=True, want_logits=False,
+                         caps=StepFeatures(sampled, bool(guided), sampled, sampled), step=StepFeatures(), logprobs=logprobs)
         # a scheduler rebuilt after an exception may have left an overlapped admission in flight: without this the counter stays
         # above zero and every later decode_steps() replays the graph on the complement CU subset
         if self._adm_stream is not None:
@@ -1790,10 +1109,7 @@ class Engine:
         with torch.cuda.stream(self.stream):
             self.d_fin.fill_(1)
             self.d_temp.zero_()
-            self.d_gtrans.zero_()
-            self.d_gmasks.zero_()
-            self.d_adj_meta.zero_()
-            self._slot_guides = {}
+            self.sampler.reset_slots()
             self.d_ctx.zero_()
             self.d_plen.zero_()
             self.d_x.zero_()
@@ -1836,14 +1152,9 @@ class Engine:
         groups = [g for g in groups if g[2]]
         adm.need = self._admit_features(rows)
         with torch.cuda.stream(self.stream):
-            self._sampler_rows(adm, rows)
+            self.sampler._sampler_rows(adm, rows)
             self._fork(groups)
-            self._write_state(adm)
-            for j, sj in zip(slots, src_of):
-                if j != sj:
-                    self.d_prompt_x[j].copy_(self.d_prompt_x[sj])
-                self.d_x[j].copy_(self.d_prompt_x[j])
-                self._lm_head_and_sample(1, slot0=j)
+            self._activate(adm, src_of=src_of)
         self.sequences_reused += len(rows)
         return adm.lens
 
@@ -1906,8 +1217,7 @@ class Engine:
         self._step |= rec.need
         with torch.cuda.stream(self.stream):
             self._fork(rec.forks)         # on the decode stream: never beside the decode graph
-            self._write_state(rec)
-            self._first_tokens(rec)
+            self._activate(rec)
         return rec.lens
 
     def set_step_features(self, sampling: bool, guided: bool, processing: bool = False, adjust: bool = False):
@@ -2016,12 +1326,12 @@ class Engine:
 
     def slot_logprobs(self, slot: int, n: int, k: int) -> Dict[str, np.ndarray]:
         """Log-probabilities of the first n generated tokens of a slot (begin_slots(logprobs=...))."""
-        if self.d_lp is None or self._logprobs is None:
+        if self.sampler.d_lp is None or self._logprobs is None:
             raise KarantaHipError("log-probabilities were not recorded: begin_slots(logprobs=k)")
         k = min(int(k), int(self._logprobs))
-        lp = self._host_copy(self.d_lp[:n, slot])
+        lp = self._host_copy(self.sampler.d_lp[:n, slot])
         return {"token": lp[:, 0].copy(), "top": lp[:, 1:1 + k].copy(),
-                "top_ids": self._host_copy(self.d_lpi[:n, slot, :k]).astype(np.int64)}
+                "top_ids": self._host_copy(self.sampler.d_lpi[:n, slot, :k]).astype(np.int64)}
 
     def retire(self, slot: int):
         """Host-side stop (length limit): the slot idles from the next step on."""

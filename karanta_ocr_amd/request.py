@@ -1,0 +1,89 @@
+"""What a caller hands to the engine and gets back: plain data, importable without torch or the HIP library."""
+from __future__ import annotations
+
+import copy
+from dataclasses import dataclass, field
+from typing import Any, Dict, List, Optional, Tuple
+
+import numpy as np
+
+from ._lib import KarantaHipError
+
+
+@dataclass
+class PageRequest:
+    """One page = one sequence: prompt token ids (image placeholders included) + its images."""
+    input_ids: np.ndarray                      # int64 [P]
+    pixel_values: Optional[np.ndarray] = None  # fp32 [n_patches, 1176] (all images concatenated)
+    grids: List[Tuple[int, int, int]] = field(default_factory=list)
+    temperature: float = 0.0                   # 0: greedy; > 0: Gumbel-max sampling (kr_gumbel_argmax)
+    seed: int = 0                              # the sampler is counter-based: (seed, token index) fixes every draw
+    images: Optional[List[Any]] = None         # instead of pixel_values: HWC uint8 RGB pages for the GPU front end
+    #                                            (numpy arrays, or torch uint8 tensors already resident in HBM)
+    guide: Any = None                          # guided.Guide / DeviceGuide: the output must match this pattern
+    logprobs: Optional[int] = None             # None: off; k >= 0: log-prob of every token + the k most probable (<= 20)
+    # vLLM's sampling controls (kr_sample_threshold / kr_gumbel_argmax_processed); the defaults are "off"
+    top_k: int = 0                             # 0 or -1: off; k: keep the k largest scores (ties kept)
+    top_p: float = 1.0                         # 1: off; keep the smallest top set whose probability reaches top_p
+    min_p: float = 0.0                         # 0: off; keep p_i >= min_p * p_max
+    repetition_penalty: float = 1.0            # 1: off; tokens of the prompt or the output so far: l > 0 ? l / r : l * r
+    frequency_penalty: float = 0.0             # l -= frequency_penalty * (count in the output so far)
+    presence_penalty: float = 0.0              # l -= presence_penalty * (count > 0)
+    # vLLM's logit adjustments (kr_logits_adjust / kr_stop_tokens), applied before the penalties; the defaults are "off"
+    logit_bias: Optional[Dict[int, float]] = None   # token id -> value added to its logit (fp32)
+    min_tokens: int = 0                        # while fewer tokens are generated, EOS and the stop_token_ids cannot be chosen
+    stop_token_ids: Tuple[int, ...] = ()       # a generated token among these ends the sequence as EOS does
+    # parallel sampling (OpenAI's n): the page starts n sequences, exactly what n copies of it with seeds (seed + c) & 0xFFFFFFFF,
+    # c = 0..n-1, start (vLLM's seeds for the children of a seeded request) — but its images go through the ViT once and its
+    # prompt through the prefill once; the siblings' KV rows are copies of child 0's (kr_kv_fork)
+    n: int = 1
+
+
+def children(pages) -> list:
+    """The sequences a batch of pages starts, page-major with a page's children consecutive: the page itself for n = 1, else n
+    copies with n = 1 and seeds (seed + c) & 0xFFFFFFFF.  This is the row order of every per-sequence list of the engine."""
+    rows = []
+    for p in pages:
+        n = getattr(p, "n", 1)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise KarantaHipError(f"PageRequest.n must be an integer >= 1, not {n!r}")
+        if n == 1:
+            rows.append(p)
+            continue
+        for c in range(int(n)):
+            ch = copy.copy(p)
+            ch.n, ch.seed = 1, (int(getattr(p, "seed", 0) or 0) + c) & 0xFFFFFFFF
+            rows.append(ch)
+    return rows
+
+
+@dataclass
+class GenerateResult:
+    """Per-sequence lists hold sum(n) entries: page-major, a page's n children consecutive (`children`)."""
+    tokens: List[np.ndarray]          # per sequence: generated ids (EOS included, nothing after it)
+    finish_reasons: List[str]         # "stop" | "length"
+    prompt_tokens: List[int]
+    timings: Dict[str, float]
+    logits: Optional[np.ndarray] = None  # [B, steps, V] when return_logits
+    logprobs: Optional[List[Optional[Dict[str, np.ndarray]]]] = None   # per page (None where not asked): "token" [n],
+    #                                                                    "top_ids" [n, k], "top" [n, k]
+
+
+@dataclass(frozen=True)
+class SpecConfig:
+    """Prompt-lookup speculative decoding (vLLM's ngram method): per step and slot up to `num_tokens` draft tokens, copied from
+    behind the latest earlier occurrence of the sequence's last ngram_max .. ngram_min tokens, are verified beside the slot's own
+    row (kr_spec_propose / kr_spec_accept).  The tokens are those of the plain steps, whatever the temperature."""
+    num_tokens: int = 3
+    ngram_min: int = 2
+    ngram_max: int = 4
+
+    def check(self, max_batch: int):
+        k = self.num_tokens
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise KarantaHipError(f"speculative: num_tokens {k!r} must be an integer >= 1")
+        if not 1 <= int(self.ngram_min) <= int(self.ngram_max) <= 8:
+            raise KarantaHipError(f"speculative: 1 <= ngram_min {self.ngram_min} <= ngram_max {self.ngram_max} <= 8")
+        if max_batch * (k + 1) > 32:
+            raise KarantaHipError(f"speculative: max_batch {max_batch} x (num_tokens {k} + 1) = {max_batch * (k + 1)} rows > 32, the most "
+                                  "one decode step takes")

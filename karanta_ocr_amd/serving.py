@@ -49,6 +49,7 @@ import numpy as np
 
 from . import image_processing as IP
 from .config import ModelConfig
+from .request import PageRequest
 from .sampling import NEUTRAL, StopStrings, parse_adjust_fields, parse_request_fields
 
 DEFAULT_SYSTEM = "You are a helpful assistant."
@@ -566,8 +567,6 @@ class LocalServer:
 
     # -- scheduler --------------------------------------------------------------
     def _loop(self):
-        from .engine import PageRequest
-
         carry = None             # a request that did not fit the previous batch's rows
         while not self._stop:
             first = carry if carry is not None else self._q.get()
@@ -646,7 +645,6 @@ class LocalServer:
                            None if self._tok_bytes is not None else tok.decode)
 
     def _page(self, r: ParsedRequest):
-        from .engine import PageRequest
         import random
         page = PageRequest(r.input_ids, r.pixel_values, r.grids, images=getattr(r, "images", None))
         if getattr(r, "guide", None) is not None:
@@ -690,7 +688,6 @@ class LocalServer:
         return {"speculative": True} if self.speculative else {}      # (only named when on: test fakes of the scheduler's engine)
 
     def _loop_continuous(self):
-        from .engine import PageRequest
         from .scheduler import SlotRequest, SlotScheduler
 
         try:

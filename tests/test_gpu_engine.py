@@ -481,8 +481,8 @@ def test_guided_generation_and_logprobs_match_oracle(engines, tiny_models, name)
     from karanta_ocr_amd._lib import KarantaHipError
     with pytest.raises(KarantaHipError, match="0..20"):
         eng.generate([PageRequest(ids, pv, [grid], logprobs=21)], 2)
-    eng.d_voc_off = None
-    eng._guides.clear()
+    eng.sampler.d_voc_off = None
+    eng.sampler._guides.clear()
     with pytest.raises(KarantaHipError, match="set_vocab"):
         eng.generate([PageRequest(ids, pv, [grid], guide=r"zz+")], 2)
     eng.set_vocab(voc)

@@ -1,0 +1,151 @@
+"""The engine issues the launches it issued when tests/golden/launch_trace.json was recorded: the same entry points in the same
+order with the same arguments (tests/launch_trace.py), over whole-batch generation with and without sampling controls and a
+guide, slot mode with every kind of admission, the packed 17..32-row family on bf16 and fp8 weights, and speculative steps.
+A change that only moves host code leaves every trace as it is; one that adds, drops, reorders or re-parameterises a launch
+fails here with the first call that differs.
+
+The fixture is recorded by `python -m tests.test_gpu_launch_trace` on a tree whose launches are the wanted ones (it was made
+on the commit before engine.py was split into modules)."""
+import hashlib
+import json
+import os
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+from karanta_ocr_amd.config import CONFIGS  # noqa: E402
+from karanta_ocr_amd.engine import Engine, SpecConfig  # noqa: E402
+from karanta_ocr_amd.weights import random_weights  # noqa: E402
+from tests.launch_trace import canonical, digest, launch_trace, names  # noqa: E402
+from tests.test_gpu_engine import GUIDE_PATTERN  # noqa: E402
+from tests.test_gpu_parallel_sampling import page_of  # noqa: E402
+
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_trace.json")
+LENGTHS = [40, 64, 100]
+_WEIGHTS = {}
+
+
+def _engine(name, **kw):
+    if name not in _WEIGHTS:
+        _WEIGHTS[name] = random_weights(CONFIGS[name], 909)
+    eng = Engine(CONFIGS[name], s_max=512, max_patches=2048, max_prompt_tokens=4096, decode_splits=2, **kw)
+    eng.load_weights(_WEIGHTS[name])
+    return eng
+
+
+def _traced(eng, out, key, fn):
+    with launch_trace(eng) as calls:
+        fn()
+        eng.stream.synchronize()
+    out[key] = calls
+
+
+def group_tiny():
+    """a: whole batches on the tiny model, eager; b: the same engine in slot mode."""
+    from karanta_ocr_amd.serving import ByteTokenizer
+    eng, out = _engine("tiny", max_batch=4), {}
+    cfg = eng.cfg
+    pages = [page_of(cfg, P, variant=b) for b, P in enumerate(LENGTHS)]
+    _traced(eng, out, "a_greedy", lambda: eng.generate(pages, 4, use_graph=False))
+    eng.set_vocab(ByteTokenizer(cfg).token_bytes())
+    mixed = [pages[0],
+             page_of(cfg, 64, variant=1, temperature=0.7, top_k=5, repetition_penalty=1.1, logit_bias={3: 1.0}, logprobs=2, seed=5),
+             page_of(cfg, 100, variant=2, guide=GUIDE_PATTERN)]
+    _traced(eng, out, "a_controls", lambda: eng.generate(mixed, 4, use_graph=False))
+
+    def slots():
+        eng.begin_slots(8, sampling=True)
+        # two pages, three sequences: the page with n = 2 takes slots 0 and 3
+        eng.admit([pages[0], page_of(cfg, 64, variant=1, temperature=0.7, top_k=5, seed=9, n=2)], [2, 0, 3])
+        eng.decode_steps(2)
+        eng.admit_reuse([page_of(cfg, 40, variant=0, logit_bias={3: 1.0})], [2], [1])
+        handle = eng.admit_begin([pages[2]], [3])
+        eng.admit_end(handle)
+        eng.decode_steps(1)
+    _traced(eng, out, "b_slots", slots)
+    eng.close()
+    return out
+
+
+def _group_rows32(dtype):
+    """c: 18 pages at once, the packed 17..32-row decode family."""
+    eng, out = _engine("tiny-w512", max_batch=21, weight_dtype=dtype), {}
+    pages = [page_of(eng.cfg, LENGTHS[b % 3], variant=b) for b in range(18)]
+    _traced(eng, out, "c_" + dtype, lambda: eng.generate(pages, 3))
+    eng.close()
+    return out
+
+
+def group_rows32_bf16():
+    return _group_rows32("bf16")
+
+
+def group_rows32_fp8():
+    return _group_rows32("fp8")
+
+
+def group_spec():
+    """d: four slots with K = 3 are 16 rows, which run as 17."""
+    eng, out = _engine("tiny-w512", max_batch=4, speculative=SpecConfig(3, 2, 4)), {}
+    pages = [page_of(eng.cfg, LENGTHS[b % 3], variant=b) for b in range(4)]
+
+    def steps():
+        eng.begin_slots(16)
+        eng.admit(pages, [0, 1, 2, 3])
+        eng.set_draft_script(1, [7, 8, 9, 10, 11, 12, 13, 14])
+        eng.decode_steps(2, speculative=True)
+        eng.decode_steps(1)
+    _traced(eng, out, "d_spec", steps)
+    eng.close()
+    return out
+
+
+GROUPS = {"tiny": group_tiny, "rows32_bf16": group_rows32_bf16, "rows32_fp8": group_rows32_fp8, "spec": group_spec}
+
+
+def _arg_digests(calls):
+    return [hashlib.sha256(canonical(c).encode()).hexdigest()[:12] for c in calls]
+
+
+def summary(calls):
+    return {"names": names(calls), "sha256": digest(calls), "arg_digests": _arg_digests(calls)}
+
+
+@pytest.mark.parametrize("group", list(GROUPS))
+def test_launches_equal_the_recorded_trace(group, tmp_path):
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    with open(FIXTURE) as f:
+        want = json.load(f)
+    got = GROUPS[group]()
+    assert got, group
+    for key, calls in got.items():
+        ref, mine = want[key], summary(calls)
+        if mine["sha256"] == ref["sha256"]:
+            continue
+        path = tmp_path / f"{key}.json"
+        path.write_text(json.dumps(calls, indent=0))
+        for i, (a, b) in enumerate(zip(mine["names"], ref["names"])):
+            assert a == b, f"{key}: call {i} is {a}, recorded {b} (full trace: {path})"
+        assert len(mine["names"]) == len(ref["names"]), (f"{key}: {len(mine['names'])} calls, recorded {len(ref['names'])}; the "
+                                                         f"first {min(len(mine['names']), len(ref['names']))} have the same names "
+                                                         f"(full trace: {path})")
+        for i, (a, b) in enumerate(zip(mine["arg_digests"], ref["arg_digests"])):
+            assert a == b, f"{key}: call {i} ({mine['names'][i]}) has other arguments than recorded: {calls[i][1]} (full trace: {path})"
+        raise AssertionError(f"{key}: trace digest differs (full trace: {path})")
+
+
+if __name__ == "__main__":
+    import sys
+    recorded = {}
+    for make in GROUPS.values():
+        for key, calls in make().items():
+            recorded[key] = summary(calls)
+            print(f"{key}: {len(calls)} calls, sha256 {recorded[key]['sha256']}")
+    dst = sys.argv[1] if len(sys.argv) > 1 else FIXTURE
+    with open(dst, "w") as f:
+        json.dump(recorded, f, indent=0, sort_keys=True)
+        f.write("\n")

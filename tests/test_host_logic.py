@@ -353,3 +353,16 @@ def test_gpu_busy_tool_on_a_synthetic_trace(tmp_path):
     assert "c  ->  d" in out and "n=    1  avg    300.0 us" in out       # the one long gap, attributed
     out = subprocess.run([sys.executable, tool, str(csv), "--last-s", "0.0000015"], capture_output=True, text=True, check=True).stdout
     assert "kernels 1" in out and "= 100.0 %" in out
+
+
+def test_request_types_and_serving_import_without_torch():
+    """PageRequest and its companions are plain data: importing them, or the serving layer that builds them, loads neither
+    torch nor the HIP library (engine.py re-exports them for its callers)."""
+    import os
+    import subprocess
+    import sys
+    code = ("import sys; import karanta_ocr_amd.request as r, karanta_ocr_amd.serving, karanta_ocr_amd._lib as l; "
+            "assert 'torch' not in sys.modules and l._LIB is None; "
+            "assert [c.seed for c in r.children([r.PageRequest([1, 2], n=3, seed=0xFFFFFFFF)])] == [0xFFFFFFFF, 0, 1]")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    subprocess.run([sys.executable, "-c", code], cwd=root, check=True, timeout=60)
