@@ -39,7 +39,7 @@ typedef uint16_t kr_bf16;
 /* kr_version() of the library this header describes: major * 100 + minor.  The major changes with every incompatible
  * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family); a caller built
  * against major X must refuse a library whose kr_version() / 100 != X. */
-#define KR_ABI_VERSION 405
+#define KR_ABI_VERSION 406
 
 #define KR_OK 0
 #define KR_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -684,6 +684,28 @@ int kr_spec_propose(const kr_spec* a, kr_stream s);
  * `emitted` when the last emitted token is an EOS that was drafted: nothing follows it). */
 int kr_spec_accept(const kr_spec* a, const float* amax_val, const int32_t* amax_idx, int n_part, int32_t* tokens_out,
                    const int32_t* eos, int n_eos, int ignore_eos, kr_stream s);
+
+/* Shared rows: the same step with the rows behind the slots' own as a BUDGET of rows - slots draft rows per step, dealt to the slots
+ * whose lookup found something, instead of k rows owned by every slot: 1 <= slots < rows <= 32 whatever k is.  The three launches
+ * below take kr_spec_propose's and kr_spec_accept's places; kr_spec is read the same way.
+ *
+ * kr_spec_lookup, one workgroup per slot: kr_spec_propose's search (same rule, same script override, same clamps: s_max - 1 -
+ * ctx_len, tokens outside the vocabulary).  Writes n_want[slot] — what kr_spec_propose calls n_draft — and draft_tok; no row state. */
+int kr_spec_lookup(const kr_spec* a, int32_t* n_want, kr_stream s);
+
+/* One workgroup.  Rows slots .. rows - 1 are dealt breadth first: for depth j = 1..k, for the slots in ascending order, a slot that is
+ * not finished and has n_want >= j takes the next free row until none is left; i.e. (slot, j) gets row
+ * slots + sum_{j' < j} #{s : n_want[s] >= j'} + #{s' < slot : n_want[s'] >= j} where that is < rows.  A slot's dealt depths are a
+ * prefix 1..n_draft[slot].  Writes n_draft, draft_row[slot * k + j - 1] (the row, or -1: [slots][k]) and, for every dealt row, what
+ * kr_spec_propose writes for an active draft row: row_slot, ctx_len = min(ctx_len[slot] + j, s_max - 1), prompt_len, temperature,
+ * seed, finished = 0 and x[row] = the draft's embedding.  Every row in slots .. rows - 1 that was not dealt belongs to no slot: it is
+ * parked like a row past kr_spec_propose's layout (slot 0, position s_max - 1, finished = 1, the pad token's embedding). */
+int kr_spec_deal(const kr_spec* a, const int32_t* n_want, int32_t* draft_row, kr_stream s);
+
+/* kr_spec_accept with the ARGMAX partials of a slot's draft j read at row draft_row[slot * k + j - 1] (t_0 at row `slot`); everything
+ * else as there.  proposed += n_draft: the drafts that were dealt a row. */
+int kr_spec_accept_rows(const kr_spec* a, const int32_t* draft_row, const float* amax_val, const int32_t* amax_idx, int n_part,
+                        int32_t* tokens_out, const int32_t* eos, int n_eos, int ignore_eos, kr_stream s);
 
 /* kr_linear_decode32, KR_DEC_ROPE_KV only, for the rows of a speculative step: the cache base and the cs_table row of row r come
  * from row_slot[r]; the cache position and the rotary index from the row's own ctx_len / prompt_len entries.  q_out stays per row.

@@ -98,6 +98,9 @@ SIGNATURES = {
     "kr_sample_greedy": [c_p, c_p, i32, c_p, i32, c_p, c_p, i32, c_p, c_p, c_p, c_p, i32, i32, i32, c_p, i32, c_p],
     "kr_spec_propose": [c_p, c_p],
     "kr_spec_accept": [c_p, c_p, c_p, i32, c_p, c_p, i32, i32, c_p],
+    "kr_spec_lookup": [c_p, c_p, c_p],
+    "kr_spec_deal": [c_p, c_p, c_p, c_p],
+    "kr_spec_accept_rows": [c_p, c_p, c_p, c_p, i32, c_p, c_p, i32, i32, c_p],
     "kr_linear_decode32_rows": [i32, c_p, c_p, c_p],
     "kr_attn_decode_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
     "kr_comm_unique_id": [c_p],

@@ -74,12 +74,18 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--speculative-config", default=None,
                     help="vLLM's flag, as JSON: {\"method\": \"ngram\", \"num_speculative_tokens\": K, \"prompt_lookup_min\": 2, "
                          "\"prompt_lookup_max\": 4} — prompt-lookup drafts verified K at a time, the same tokens as without it "
-                         "(--max-num-seqs x (K + 1) <= 32; not with --max-logprobs or --static-batching)")
+                         "(--max-num-seqs x (K + 1) <= 32, or with \"share_rows\": true any --max-num-seqs up to 31: the rows of a "
+                         "step the sequences leave free are dealt to the drafts; not with --max-logprobs or --static-batching)")
     return ap
 
 
 def speculative_config(text: str, max_num_seqs: int):
     """(num_tokens, ngram_min, ngram_max) from --speculative-config; ValueError with the reason for what this engine does not do."""
+    return speculative_fields(text, max_num_seqs)[:3]
+
+
+def speculative_fields(text: str, max_num_seqs: int):
+    """SpecConfig's fields (num_tokens, ngram_min, ngram_max, share_rows) from --speculative-config; ValueError with the reason."""
     import json
     try:
         d = json.loads(text)
@@ -99,10 +105,19 @@ def speculative_config(text: str, max_num_seqs: int):
             raise ValueError(f"--speculative-config: {name} must be an integer >= 1, not {v!r}")
     if not lo <= hi <= 8:
         raise ValueError(f"--speculative-config: prompt_lookup_min {lo} <= prompt_lookup_max {hi} <= 8 does not hold")
-    if max_num_seqs * (k + 1) > 32:
+    share = d.get("share_rows", False)
+    if not isinstance(share, bool):
+        raise ValueError(f"--speculative-config: share_rows must be true or false, not {share!r}")
+    if share:
+        if k > 31:
+            raise ValueError(f"--speculative-config: num_speculative_tokens {k} > 31, the draft rows a 32-row decode step can hold")
+        if max_num_seqs > 31:
+            raise ValueError(f"--speculative-config: share_rows with --max-num-seqs {max_num_seqs}: every one of the 32 rows of a decode "
+                             "step is a sequence's own, no row is spare for a draft (at most 31)")
+    elif max_num_seqs * (k + 1) > 32:
         raise ValueError(f"--speculative-config: --max-num-seqs {max_num_seqs} x (num_speculative_tokens {k} + 1) = "
                          f"{max_num_seqs * (k + 1)} rows per decode step, the kernels take 32")
-    return k, lo, hi
+    return k, lo, hi, share
 
 
 def parse_args(argv: Optional[List[str]] = None):
@@ -125,14 +140,15 @@ def parse_args(argv: Optional[List[str]] = None):
         ap.error("--max-num-seqs must be in 1..32 (above 16: hidden_size <= 2048 or == 3584)")
     if args.max_num_batched_tokens is not None and args.max_num_batched_tokens < args.max_model_len:
         ap.error("--max-num-batched-tokens must be >= --max-model-len (the longest prompt one request may carry)")
-    args.speculative = None
+    args.speculative, args.speculative_share_rows = None, False
     if args.speculative_config is not None:
         if args.max_logprobs is not None:
             ap.error("--speculative-config cannot be combined with --max-logprobs: a draft row records no log-probabilities")
         if args.static_batching:
             ap.error("--speculative-config needs the slot scheduler: not with --static-batching")
         try:
-            args.speculative = speculative_config(args.speculative_config, args.max_num_seqs)
+            *spec, args.speculative_share_rows = speculative_fields(args.speculative_config, args.max_num_seqs)
+            args.speculative = tuple(spec)
         except ValueError as e:
             ap.error(str(e))
     args.model_dir = model
@@ -212,15 +228,16 @@ def make_server(args, log=print):
         f"{args.max_num_seqs} decode slots of {args.max_model_len} tokens")
     # cache rows per slot: the model length + the steps a slot may run past its limit before the scheduler looks (2 chunks of up to 8
     # with launch-ahead) + the parking row
-    spec = getattr(args, "speculative", None)
+    spec, share = getattr(args, "speculative", None), bool(getattr(args, "speculative_share_rows", False))
     if spec is not None:
-        log(f"speculative decoding: ngram, {spec[0]} draft tokens per step, prompt lookup {spec[1]}..{spec[2]}")
+        log(f"speculative decoding: ngram, {spec[0]} draft tokens per step, prompt lookup {spec[1]}..{spec[2]}"
+            + (", draft rows shared between the sequences" if share else ""))
     # ... speculative: every step past the limit may emit K + 1 tokens, and the draft rows write K cache rows ahead
     slack = 1 + 16 * (spec[0] + 1 if spec else 1) + (spec[0] if spec else 0)
     eng = Engine(cfg, device="cuda:0", max_batch=args.max_num_seqs, s_max=(args.max_model_len + slack + 63) // 64 * 64,
                  max_patches=max_patches, max_prompt_tokens=max_prompt_tokens,
                  weight_dtype=weight_dtype, fp8_activations=bool(getattr(args, "fp8_activations", False)) or None,
-                 **({"speculative": SpecConfig(*spec)} if spec else {}))
+                 **({"speculative": SpecConfig(*spec, share_rows=share)} if spec else {}))
     # one server: read the checkpoint.  A launch.py group: rank 0 reads it ONCE, the arena goes to the other GPUs over
     # RCCL / xGMI (north_star: "RCCL broadcast of weights over xGMI"); a failure stops every server of the group
     info = load_or_receive_weights(eng.w, rank, world, lambda: eng.load_weights(load_checkpoint(args.model_dir)[1]),

@@ -5,17 +5,24 @@
 //   spec_accept_kernel   per slot: final argmax of its k + 1 rows, then kr_sample_greedy's bookkeeping token by token while the
 //                        drafts agree with what the rows before them produced.
 // Between them the rows run through the packed decode family with kr_linear_decode32_rows / kr_attn_decode_rows.
+// Shared rows (kr_spec_lookup -> kr_spec_deal -> ... -> kr_spec_accept_rows): the rows behind the slots' own are a budget dealt per
+// step to the slots whose lookup found something, instead of k rows owned by every slot.
+//   spec_lookup_kernel   per slot: the same search; writes how many drafts the slot wants and their tokens, no row state.
+//   spec_deal_kernel     ONE workgroup: rows slots .. rows - 1 breadth first (depth 1 of every slot in slot order, then depth 2, ...)
+//                        and the row state of each; a row nobody got is parked like a padding row.
+//   spec_accept_kernel   with a map: draft j of a slot is verified on row draft_row[slot * k + j - 1].
 #include "kr_decode_common.h"
+#include "kr_spec_deal.h"
 
 namespace {
 
 constexpr int SPEC_MAX_ROWS = 32, SPEC_MAX_NGRAM = 8;
 
-__global__ void __launch_bounds__(256) spec_propose_kernel(const kr_spec a) {
-    __shared__ unsigned s_key[4];
-    __shared__ int s_nd, s_draft[SPEC_MAX_ROWS];
-    const int slot = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int B = a.slots, K = a.k;
+// The drafts of `slot` (256 threads, all of them call it): thread 0 returns their number and leaves the tokens in s_draft; the other
+// threads return 0.  s_key: 4 words of scratch.
+__device__ __forceinline__ int spec_drafts(const kr_spec& a, int slot, unsigned* s_key, int* s_draft) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int K = a.k;
     const int ctx = a.ctx_len[slot], plen = a.prompt_len[slot], fin = a.finished[slot];
     const int L = ctx + 1;
     const int32_t* prm = a.prompt_ids + (int64_t)slot * a.prompt_stride;
@@ -47,9 +54,9 @@ __global__ void __launch_bounds__(256) spec_propose_kernel(const kr_spec a) {
     }
     if (lane == 0) s_key[wave] = best;
     __syncthreads();
+    int nd = 0;
     if (tid == 0) {
         for (int w = 1; w < 4; ++w) best = s_key[w] > best ? s_key[w] : best;
-        int nd = 0;
         if (!fin) {
             if (script != 0ull) {
                 const int32_t* sc = reinterpret_cast<const int32_t*>(script);
@@ -65,9 +72,21 @@ __global__ void __launch_bounds__(256) spec_propose_kernel(const kr_spec a) {
             for (int j = 0; j < nd; ++j)
                 if (s_draft[j] < 0 || s_draft[j] >= a.vocab) nd = j;   // (a scripted token outside the vocabulary ends the run)
         }
-        s_nd = nd;
-        a.n_draft[slot] = nd;
-        for (int j = 0; j < K; ++j) a.draft_tok[slot * K + j] = j < nd ? s_draft[j] : a.pad_id;
+    }
+    return nd;
+}
+
+__global__ void __launch_bounds__(256) spec_propose_kernel(const kr_spec a) {
+    __shared__ unsigned s_key[4];
+    __shared__ int s_nd, s_draft[SPEC_MAX_ROWS];
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    const int B = a.slots, K = a.k;
+    const int ctx = a.ctx_len[slot], plen = a.prompt_len[slot], fin = a.finished[slot];
+    const int nd0 = spec_drafts(a, slot, s_key, s_draft);
+    if (tid == 0) {
+        s_nd = nd0;
+        a.n_draft[slot] = nd0;
+        for (int j = 0; j < K; ++j) a.draft_tok[slot * K + j] = j < nd0 ? s_draft[j] : a.pad_id;
     }
     __syncthreads();
     const int nd = s_nd;
@@ -95,16 +114,84 @@ __global__ void __launch_bounds__(256) spec_propose_kernel(const kr_spec a) {
     }
 }
 
+// The search alone: how many drafts the slot wants (n_want, kr_spec_propose's n_draft) and their tokens.
+__global__ void __launch_bounds__(256) spec_lookup_kernel(const kr_spec a, int32_t* __restrict__ n_want) {
+    __shared__ unsigned s_key[4];
+    __shared__ int s_draft[SPEC_MAX_ROWS];
+    const int slot = blockIdx.x, K = a.k;
+    const int nd = spec_drafts(a, slot, s_key, s_draft);
+    if (threadIdx.x == 0) {
+        n_want[slot] = nd;
+        for (int j = 0; j < K; ++j) a.draft_tok[slot * K + j] = j < nd ? s_draft[j] : a.pad_id;
+    }
+}
+
+// One workgroup: rows B .. rows - 1 go breadth first to the drafts (slot, j) with j <= n_want[slot] — depth 1 of every slot in slot
+// order, then depth 2, ... — so the row of (slot, j) is B + sum_{j' < j} #{s : want[s] >= j'} + #{s' < slot : want[s'] >= j} where that
+// is below `rows`.  Every global write of row state is indexed by a row r in B .. rows - 1 taken from the loop, never by a computed
+// row: s_owner[r] says whose it is, or that nobody got it (parked: slot 0 at s_max - 1, finished, the pad token).
+__global__ void __launch_bounds__(256) spec_deal_kernel(const kr_spec a, const int32_t* __restrict__ n_want,
+                                                        int32_t* __restrict__ draft_row) {
+    __shared__ int s_want[SPEC_MAX_ROWS], s_cnt[SPEC_MAX_ROWS + 1], s_owner[SPEC_MAX_ROWS];
+    const int tid = threadIdx.x, B = a.slots, K = a.k, R = a.rows;
+    if (tid < SPEC_MAX_ROWS) {
+        s_owner[tid] = -1;
+        s_want[tid] = tid < B ? spec_deal_want(n_want[tid], a.finished[tid], K, a.ctx_len[tid], a.s_max) : 0;
+    }
+    __syncthreads();
+    if (tid >= 1 && tid <= K) s_cnt[tid] = spec_deal_count(s_want, B, tid);      // (s_cnt[0] is not used)
+    __syncthreads();
+    for (int e = tid; e < B * K; e += 256) {
+        const int slot = e / K, j = e - slot * K + 1;
+        const int r = spec_deal_row(s_want, s_cnt, B, R, slot, j);
+        draft_row[e] = r;
+        if (r >= 0) s_owner[r] = e;       // (rows are distinct: one writer per entry)
+    }
+    __syncthreads();
+    if (tid < B) {       // the dealt depths of a slot are a prefix: rows grow with the depth
+        int nd = 0;
+        for (int j = 1; j <= s_want[tid]; ++j)
+            if (spec_deal_row(s_want, s_cnt, B, R, tid, j) >= 0) nd = j;
+        a.n_draft[tid] = nd;
+    }
+    const int n_rows = R - B;
+    if (tid < n_rows) {
+        const int r = B + tid, e = s_owner[r];
+        const bool pad = e < 0;
+        const int slot = pad ? 0 : e / K, j = pad ? 0 : e - slot * K + 1;
+        a.row_slot[r] = slot;
+        a.ctx_len[r] = pad ? a.s_max - 1 : min(a.ctx_len[slot] + j, a.s_max - 1);
+        a.prompt_len[r] = pad ? a.s_max - 1 : a.prompt_len[slot];
+        a.temperature[r] = pad ? 0.f : a.temperature[slot];
+        a.seed[r] = pad ? 0u : a.seed[slot];
+        a.finished[r] = pad ? 1 : 0;
+    }
+    const int d8 = a.d >> 3;
+    for (int i = tid; i < n_rows * d8; i += 256) {
+        const int q = i / d8, c = i - q * d8;
+        const int r = B + q, e = s_owner[r];
+        int t = e < 0 ? a.pad_id : a.draft_tok[e];
+        if (t < 0 || t >= a.vocab) t = a.pad_id;      // (kr_spec_lookup leaves none such below n_want)
+        st8(a.x + (int64_t)r * a.ldx + c * 8, ld8(a.embed_table + (int64_t)t * a.d + c * 8));
+    }
+}
+
+// draft_row == nullptr: the static layout (draft j of a slot on row j * slots + slot); else the map kr_spec_deal wrote.
 __global__ void __launch_bounds__(256) spec_accept_kernel(const kr_spec a, const float* __restrict__ amax_val,
                                                           const int32_t* __restrict__ amax_idx, int n_part,
                                                           int32_t* __restrict__ tokens_out, const int32_t* __restrict__ eos, int n_eos,
-                                                          int flags) {
+                                                          int flags, const int32_t* __restrict__ draft_row) {
     __shared__ int s_t[SPEC_MAX_ROWS], s_last;
     const int slot = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int B = a.slots, K = a.k;
     // t_j: one wave per row, kr_sample_greedy's order (`better`: the larger value, ties to the lowest index)
     for (int j = wave; j <= K; j += 4) {
-        const int64_t r = (int64_t)(j * B + slot) * n_part;
+        const int row = j == 0 ? slot : draft_row == nullptr ? j * B + slot : draft_row[slot * K + j - 1];
+        if (row < 0 || row >= a.rows) {       // draft j was not dealt a row: t_j is never looked at (j > n_draft)
+            if (lane == 0) s_t[j] = -1;
+            continue;
+        }
+        const int64_t r = (int64_t)row * n_part;
         float bv = -INFINITY;
         int bi = 0x7fffffff;
         for (int i0 = lane; i0 < n_part; i0 += 64 * 8) {
@@ -140,7 +227,9 @@ __global__ void __launch_bounds__(256) spec_accept_kernel(const kr_spec a, const
                 a.ctx_len[slot] = ctx + 1;
             }
         } else {
-            const int nd = a.n_draft[slot];
+            int nd = a.n_draft[slot];
+            for (int j = 1; j <= min(nd, K); ++j)
+                if (s_t[j] < 0) nd = j - 1;      // (a map that disagrees with n_draft: no token without a row)
             int e = 0, acc = 0;   // tokens emitted; drafts that turned out to be the token emitted at their position
             for (int j = 0; j <= K; ++j) {
                 if (j > 0 && !(j <= nd && a.draft_tok[slot * K + j - 1] == s_t[j - 1])) break;
@@ -172,10 +261,14 @@ __global__ void __launch_bounds__(256) spec_accept_kernel(const kr_spec a, const
     for (int c = tid; c < (a.d >> 3); c += 256) st8(a.x + (int64_t)slot * a.ldx + c * 8, ld8(a.embed_table + (int64_t)last * a.d + c * 8));
 }
 
-int spec_check(const kr_spec* a, const char* who) {
+int spec_check(const kr_spec* a, const char* who, bool shared_rows = false) {
     KR_CHECK_ARG(a, "%s: null args", who);
-    KR_CHECK_ARG(a->slots >= 1 && a->k >= 1 && a->k < SPEC_MAX_ROWS && a->slots * (a->k + 1) <= a->rows && a->rows <= SPEC_MAX_ROWS,
-                 "%s: slots=%d k=%d rows=%d (slots * (k + 1) <= rows <= 32)", who, a->slots, a->k, a->rows);
+    if (shared_rows)
+        KR_CHECK_ARG(a->slots >= 1 && a->k >= 1 && a->k < SPEC_MAX_ROWS && a->slots < a->rows && a->rows <= SPEC_MAX_ROWS,
+                     "%s: slots=%d k=%d rows=%d (1 <= slots < rows <= 32, 1 <= k < 32)", who, a->slots, a->k, a->rows);
+    else
+        KR_CHECK_ARG(a->slots >= 1 && a->k >= 1 && a->k < SPEC_MAX_ROWS && a->slots * (a->k + 1) <= a->rows && a->rows <= SPEC_MAX_ROWS,
+                     "%s: slots=%d k=%d rows=%d (slots * (k + 1) <= rows <= 32)", who, a->slots, a->k, a->rows);
     KR_CHECK_ARG(a->ngram_min >= 1 && a->ngram_min <= a->ngram_max && a->ngram_max <= SPEC_MAX_NGRAM, "%s: ngram_min=%d ngram_max=%d (1 <= min <= max <= 8)",
                  who, a->ngram_min, a->ngram_max);
     KR_CHECK_ARG(a->s_max >= 2 && a->s_max <= (1 << 20), "%s: s_max=%d", who, a->s_max);
@@ -200,7 +293,32 @@ extern "C" int kr_spec_accept(const kr_spec* a, const float* amax_val, const int
                               const int32_t* eos, int n_eos, int ignore_eos, kr_stream s) {
     if (const int rc = spec_check(a, "kr_spec_accept")) return rc;
     KR_CHECK_ARG(amax_val && amax_idx && tokens_out && n_part > 0 && (n_eos == 0 || eos), "kr_spec_accept: bad args");
-    spec_accept_kernel<<<a->slots, 256, 0, kr_hs(s)>>>(*a, amax_val, amax_idx, n_part, tokens_out, eos, n_eos, ignore_eos);
+    spec_accept_kernel<<<a->slots, 256, 0, kr_hs(s)>>>(*a, amax_val, amax_idx, n_part, tokens_out, eos, n_eos, ignore_eos, nullptr);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_spec_lookup(const kr_spec* a, int32_t* n_want, kr_stream s) {
+    if (const int rc = spec_check(a, "kr_spec_lookup", true)) return rc;
+    KR_CHECK_ARG(n_want, "kr_spec_lookup: null n_want");
+    spec_lookup_kernel<<<a->slots, 256, 0, kr_hs(s)>>>(*a, n_want);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_spec_deal(const kr_spec* a, const int32_t* n_want, int32_t* draft_row, kr_stream s) {
+    if (const int rc = spec_check(a, "kr_spec_deal", true)) return rc;
+    KR_CHECK_ARG(n_want && draft_row, "kr_spec_deal: null n_want / draft_row");
+    spec_deal_kernel<<<1, 256, 0, kr_hs(s)>>>(*a, n_want, draft_row);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_spec_accept_rows(const kr_spec* a, const int32_t* draft_row, const float* amax_val, const int32_t* amax_idx, int n_part,
+                                   int32_t* tokens_out, const int32_t* eos, int n_eos, int ignore_eos, kr_stream s) {
+    if (const int rc = spec_check(a, "kr_spec_accept_rows", true)) return rc;
+    KR_CHECK_ARG(draft_row && amax_val && amax_idx && tokens_out && n_part > 0 && (n_eos == 0 || eos), "kr_spec_accept_rows: bad args");
+    spec_accept_kernel<<<a->slots, 256, 0, kr_hs(s)>>>(*a, amax_val, amax_idx, n_part, tokens_out, eos, n_eos, ignore_eos, draft_row);
     KR_CHECK_LAUNCH();
     return KR_OK;
 }

@@ -13,6 +13,13 @@ Random weights (timing only), context about 1900, graphs replayed as the engine 
     run is to stop), against the plain steps' tokens/s;
   * the attention launches' share of the speculative step (every row of a slot reads the slot's K/V again).
 
+    python karanta_ocr_amd/csrc/tools/spec_bench.py --shared [--parent-tree DIR] [--out profiles/r06_spec_shared_rows.json]
+
+  * --shared: the leg for SpecConfig(share_rows=True) above 16 slots, where the plain step is already the 32-row family: 24 slots x
+    K = 3 (8 spare rows per step) at the 2B decoder against the plain 24-row step of the PARENT commit (--parent-tree; without it
+    this tree's own plain step stands in and the file says so), in alternating child processes; t_spec / t_plain and
+    break_even_accepted_per_slot_step, at full acceptance and with every first draft wrong.
+
 Every measurement is a child process under a time limit of its own; a child that fails ends the run."""
 import argparse
 import ctypes as C
@@ -25,14 +32,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.a
 CTX, STEPS, ROUNDS = 1900, 48, 5
 
 
-def _engine(model, B, spec_k=0):
+def _engine(model, B, spec_k=0, share=False):
     import torch
     from karanta_ocr_amd.config import CONFIGS
     from karanta_ocr_amd.engine import Engine
     kw = {}
     if spec_k:
         from karanta_ocr_amd.engine import SpecConfig
-        kw["speculative"] = SpecConfig(spec_k)
+        kw["speculative"] = SpecConfig(spec_k, share_rows=True) if share else SpecConfig(spec_k)
     n_new = STEPS * (ROUNDS + 3) * (spec_k + 1) + 16
     eng = Engine(CONFIGS[model], max_batch=B, s_max=(CTX + n_new + 128) // 64 * 64, max_patches=64, max_prompt_tokens=64, **kw)
     eng.w.allocate()
@@ -88,11 +95,11 @@ def _plain_graph(eng):
         return eng._graph_for(eng.B)
 
 
-def child_plain(model):
-    """The plain step at 8 and at 32 rows: uses nothing the parent commit lacks."""
+def child_plain(model, sizes=(8, 32)):
+    """The plain step at 8 and at 32 rows (--shared: at 24): uses nothing the parent commit lacks."""
     import numpy as np
     out = {}
-    for B in (8, 32):
+    for B in sizes:
         eng = _engine(model, B)
         ts = _time(eng, _plain_graph(eng))
         out[str(B)] = {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "rounds_ms": [round(t, 5) for t in ts]}
@@ -101,11 +108,13 @@ def child_plain(model):
     return out
 
 
-def child_spec(model, B, K):
+def child_spec(model, B, K, share=False):
+    """share: SpecConfig(share_rows=True) — the drafts compete for the rows - B spare rows, so a slot's progress per step is not the
+    script's choice alone: only the two ends are run, every first draft wrong (0) and every draft right (K)."""
     import numpy as np
     import torch
     from karanta_ocr_amd._lib import ptr
-    eng = _engine(model, B, K)
+    eng = _engine(model, B, K, share)
     L, t = eng.L, eng.cfg.text
     g_plain = _plain_graph(eng)
     t_plain = _time(eng, g_plain)
@@ -121,9 +130,9 @@ def child_spec(model, B, K):
         eng._spec_step_launches()
         eng.stream.synchronize()
         g_spec = eng._graph_for(eng.B, True)
-    out = {"model": model, "slots": B, "K": K, "rows": eng.rows, "ctx": CTX,
+    out = {"model": model, "slots": B, "K": K, "rows": eng.rows, "share_rows": bool(share), "ctx": CTX,
            "plain_ms": float(np.median(t_plain)), "plain_tokens_per_s": B / float(np.median(t_plain)) * 1e3, "accept": {}}
-    for a in range(K + 1):
+    for a in ((0, K) if share else range(K + 1)):
         scripts = truth.copy()
         if a < K:      # step s starts at generated index 1 + s * (a + 1): its draft a + 1 is made wrong
             for s in range(STEPS + 2):
@@ -200,13 +209,49 @@ def child_spec(model, B, K):
     return out
 
 
-def run_child(args, tree, limit):
+def run_child(args, tree, limit, sizes=None):
+    """This file as a child process with `tree`'s package on the path (the child imports karanta_ocr_amd from its working directory).
+    sizes: the plain child's batch sizes, for a tree whose engine this file's --sizes is to drive."""
     env = dict(os.environ, PYTHONPATH=tree)
+    if sizes is not None:
+        args = [*args, "--sizes", ",".join(str(x) for x in sizes)]
     r = subprocess.run([sys.executable, os.path.abspath(__file__), *args], cwd=tree, env=env, capture_output=True, text=True, timeout=limit)
     if r.returncode != 0:
         sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
         raise SystemExit(f"child {args} in {tree} ended with {r.returncode}: nothing more is started")
     return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def main_shared(a):
+    """24 slots x K = 3 with shared rows against the parent commit's plain 24-row step, alternating child processes."""
+    import numpy as np
+    B, K = 24, 3
+    report = {"context": CTX, "steps_per_round": STEPS, "rounds": ROUNDS, "weights": "random bf16 (timing only)", "slots": B, "K": K}
+
+    def save():
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(report, f, indent=1)
+            f.write("\n")
+    runs = {"this": [], "parent": []}
+    for _ in range(a.repeats):
+        runs["this"].append(run_child(["--child", "plain", "--sizes", str(B)], ROOT, 240)[str(B)]["median_ms"])
+        if a.parent_tree:
+            runs["parent"].append(run_child(["--child", "plain"], os.path.abspath(a.parent_tree), 240, sizes=(B,))[str(B)]["median_ms"])
+    base = runs["parent"] or runs["this"]
+    report["plain_step"] = {"this_tree_ms": runs["this"], "parent_ms": runs["parent"], "aa_spread_ms": max(runs["this"]) - min(runs["this"]),
+                            "t_plain_from": "parent commit" if runs["parent"] else "THIS tree (no --parent-tree given)",
+                            "t_plain_ms": float(np.median(base))}
+    save()
+    spec = run_child(["--child", "spec", "--model", "Qwen2-VL-2B", "--slots", str(B), "--k", str(K), "--share"], ROOT, 420)
+    report["spec"] = spec
+    t_spec = float(np.median([v["spec_ms"] for v in spec["accept"].values()]))
+    report["t_spec_ms"] = t_spec
+    report["t_spec_over_t_plain"] = t_spec / report["plain_step"]["t_plain_ms"]
+    report["break_even_accepted_per_slot_step"] = report["t_spec_over_t_plain"] - 1
+    save()
+    print(json.dumps(report, indent=1))
+    return 0
 
 
 def main():
@@ -218,14 +263,21 @@ def main():
     ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its library built")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--skip-7b", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r05_spec_decode.json"))
+    ap.add_argument("--shared", action="store_true", help="the shared-rows leg alone: 24 slots x K = 3 (profiles/r06_spec_shared_rows.json)")
+    ap.add_argument("--share", action="store_true", help="(child) SpecConfig(share_rows=True)")
+    ap.add_argument("--sizes", default="8,32", help="(child plain) the batch sizes")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.child:
         sys.path.insert(0, os.getcwd())
-        res = child_plain(a.model) if a.child == "plain" else child_spec(a.model, a.slots, a.k)
+        res = (child_plain(a.model, [int(x) for x in a.sizes.split(",")]) if a.child == "plain"
+               else child_spec(a.model, a.slots, a.k, a.share))
         print(json.dumps(res), flush=True)
         return 0
     import numpy as np
+    a.out = a.out or os.path.join(ROOT, "profiles", "r06_spec_shared_rows.json" if a.shared else "r05_spec_decode.json")
+    if a.shared:
+        return main_shared(a)
     report = {"context": CTX, "steps_per_round": STEPS, "rounds": ROUNDS, "weights": "random bf16 (timing only)"}
 
     def save():

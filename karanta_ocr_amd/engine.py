@@ -101,12 +101,14 @@ class Engine:
         if max_batch > 32:
             raise KarantaHipError("max_batch > 32: the decode kernels take at most two 16-row column tiles")
         # a speculative step runs max_batch x (K + 1) rows through the packed 17..32-row family (never fewer than 17 rows: its
-        # gate/up launch writes packed activations above 16 rows only); without `speculative` the rows are the slots
+        # gate/up launch writes packed activations above 16 rows only); without `speculative` the rows are the slots.
+        # share_rows: at most 32 of them — the rows behind the slots' own are dealt per step (kr_spec_deal)
         self.spec = speculative
         if speculative is not None:
             speculative.check(max_batch)
         self.K = int(speculative.num_tokens) if speculative is not None else 0
-        self.rows = max(17, max_batch * (self.K + 1)) if speculative is not None else max_batch
+        self.rows = speculative.rows(max_batch) if speculative is not None else max_batch
+        self.share_rows = speculative is not None and bool(speculative.share_rows)
         self.spec_steps = self.plain_steps = 0
         self._snap_counts = None
         self.s_max = _align(s_max, 64)
@@ -270,6 +272,9 @@ class Engine:
             self.d_prompt_ids = z(B, self.s_max, dtype=torch.int32)
             self.d_ndraft = z(B, dtype=torch.int32)
             self.d_draft = z(B, self.K, dtype=torch.int32)
+            if self.share_rows:   # what every slot's lookup found, and the row each draft was dealt (-1: none)
+                self.d_nwant = z(B, dtype=torch.int32)
+                self.d_draft_row = torch.full((B, self.K), -1, dtype=torch.int32, device=dev)
             self.d_spec_count = z(2, B, dtype=torch.int32)
             self.d_script = z(B, dtype=torch.int64)
             self.d_script_len = z(B, dtype=torch.int32)
@@ -819,19 +824,30 @@ class Engine:
     def _spec_step_launches(self):
         """One speculative step: drafts (kr_spec_propose) -> the layers over all rows -> lm_head -> the Gumbel pass when a request
         samples -> verification and bookkeeping (kr_spec_accept, in kr_sample_greedy's place).  It leaves d_ctx, d_tok, d_x[slot],
-        the history and d_fin in the form a plain step leaves them, so the two kinds alternate freely."""
+        the history and d_fin in the form a plain step leaves them, so the two kinds alternate freely.
+        share_rows: the drafts are looked up (kr_spec_lookup), the rows behind the slots dealt to them (kr_spec_deal) and the
+        verification reads each draft at the row it was dealt (kr_spec_accept_rows); everything between is the same launches —
+        they take the row-to-slot map as it comes."""
         L, s, R = self.L, self.s, self.rows
         why = self._spec_refusal()
         if why is not None:
             raise KarantaHipError("speculative decode step refused: " + why)
         a = self._spec_args()
-        L.kr_spec_propose(C.byref(a), s)
+        if self.share_rows:
+            L.kr_spec_lookup(C.byref(a), ptr(self.d_nwant), s)
+            L.kr_spec_deal(C.byref(a), ptr(self.d_nwant), ptr(self.d_draft_row), s)
+        else:
+            L.kr_spec_propose(C.byref(a), s)
         x = self._layer_launches(R, self.d_row_slot)
         logits, n_part = self._lm_head(R, x)
         flags = self._flags()
         n_part = self.sampler.pre_token(logits, n_part, R, 0, flags)     # (the refusal above leaves it the Gumbel pass alone)
-        L.kr_spec_accept(C.byref(a), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(self.d_tok), ptr(self.d_eos),
-                         self.d_eos.numel(), flags, s)
+        if self.share_rows:
+            L.kr_spec_accept_rows(C.byref(a), ptr(self.d_draft_row), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(self.d_tok),
+                                  ptr(self.d_eos), self.d_eos.numel(), flags, s)
+        else:
+            L.kr_spec_accept(C.byref(a), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(self.d_tok), ptr(self.d_eos),
+                             self.d_eos.numel(), flags, s)
 
     def set_draft_script(self, slot: int, tokens: Optional[Sequence[int]]):
         """Test hook: the drafts of `slot` come from a scripted continuation — draft j of a step is tokens[generated + j - 1] —

@@ -73,10 +73,19 @@ class GenerateResult:
 class SpecConfig:
     """Prompt-lookup speculative decoding (vLLM's ngram method): per step and slot up to `num_tokens` draft tokens, copied from
     behind the latest earlier occurrence of the sequence's last ngram_max .. ngram_min tokens, are verified beside the slot's own
-    row (kr_spec_propose / kr_spec_accept).  The tokens are those of the plain steps, whatever the temperature."""
+    row (kr_spec_propose / kr_spec_accept).  The tokens are those of the plain steps, whatever the temperature.
+    share_rows: instead of num_tokens rows owned by every slot (max_batch x (num_tokens + 1) <= 32), the rows of a step that the slots
+    do not take themselves are dealt per step to the slots whose lookup found drafts (kr_spec_lookup / kr_spec_deal /
+    kr_spec_accept_rows): any max_batch up to 31."""
     num_tokens: int = 3
     ngram_min: int = 2
     ngram_max: int = 4
+    share_rows: bool = False
+
+    def rows(self, max_batch: int) -> int:
+        """Rows of a speculative step: never fewer than 17 (the packed 17..32-row family)."""
+        n = max(17, max_batch * (int(self.num_tokens) + 1))
+        return min(32, n) if self.share_rows else n
 
     def check(self, max_batch: int):
         k = self.num_tokens
@@ -84,6 +93,12 @@ class SpecConfig:
             raise KarantaHipError(f"speculative: num_tokens {k!r} must be an integer >= 1")
         if not 1 <= int(self.ngram_min) <= int(self.ngram_max) <= 8:
             raise KarantaHipError(f"speculative: 1 <= ngram_min {self.ngram_min} <= ngram_max {self.ngram_max} <= 8")
-        if max_batch * (k + 1) > 32:
+        if self.share_rows:
+            if k > 31:
+                raise KarantaHipError(f"speculative: num_tokens {k} > 31, the draft rows a 32-row decode step can hold")
+            if not 1 <= max_batch <= 31:
+                raise KarantaHipError(f"speculative: share_rows with max_batch {max_batch}: 1..31 slots — with 32 every row of a decode "
+                                      "step is a slot's own, no row is spare for a draft")
+        elif max_batch * (k + 1) > 32:
             raise KarantaHipError(f"speculative: max_batch {max_batch} x (num_tokens {k} + 1) = {max_batch * (k + 1)} rows > 32, the most "
                                   "one decode step takes")

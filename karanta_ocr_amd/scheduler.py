@@ -61,6 +61,11 @@ class SlotResult:
 # t_spec / t_plain - 1 for the step times of the two kinds.  UNMEASURED: this is README's 32-row over 8-row step time of the 2B
 # decoder (1.68 / 1.15 ms), which predates the speculative step and lacks its proposer launch and its repeated K/V reads;
 # csrc/tools/spec_bench.py measures the ratio and writes profiles/r05_spec_decode.json, from which this constant is to be set.
+# The same constant serves SpecConfig(share_rows=True) above 16 slots, where it is too high: there the plain step is already the
+# 32-row family, so the ratio is only the two extra launches (lookup, deal) and the drafts' repeated K/V reads — measured once,
+# 24 slots x K = 3 at the 2B decoder: t_spec / t_plain = 1.098, break-even 0.098 (spec_bench.py --shared,
+# profiles/r06_spec_shared_rows.json).  One constant is kept until both modes are measured: too high a constant only falls back to
+# plain chunks sooner than it must.
 SPEC_BREAK_EVEN = 1.68 / 1.15 - 1
 
 
