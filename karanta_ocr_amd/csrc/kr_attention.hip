@@ -1,5 +1,5 @@
-// Attention path: rotary + layout prep, flash-style varlen attention (ViT full / decoder causal
-// prefill), decode attention (q_len = 1, GQA, split-KV) — all on v_mfma bf16 with fp32 softmax.
+// Attention path of the ViT and of the decoder prefill: rotary + layout prep, flash-style varlen attention (ViT full /
+// decoder causal) on v_mfma bf16 with fp32 softmax.  Decode attention (q_len = 1) is in kr_attn_decode.hip.
 //
 // Data layout in HBM (chosen for the matrix cores, not inherited from any framework):
 //   Q   : [heads, n, hd]                     rotated, bf16
@@ -149,32 +149,6 @@ __global__ void __launch_bounds__(256) qkv_prep_kernel(const kr_bf16* __restrict
 //   O^T[d][q]   += V^T (A operand, LDS) x P^T (B operand = the S^T accumulators, converted in
 //   place to bf16: no LDS round trip, the MFMA k-order permutation is absorbed by reading V^T
 //   keys in the same order)                                               HD/32 x 4 MFMA
-// Diagnostic build only (-DKR_ATTN_STAMPS, tools/build_variant.py): s_memtime stamps around the segments of one tile
-// iteration, summed per wave and left in a buffer of their own; no shipped build contains a stamp.
-#ifdef KR_ATTN_STAMPS
-__device__ unsigned long long kr_attn_dbg[8 * 8];
-#define KR_STAMP(var)                                                                              \
-    __builtin_amdgcn_sched_barrier(0);                                                             \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory");                    \
-    __builtin_amdgcn_sched_barrier(0)
-extern "C" int kr_attn_debug_read(unsigned long long* out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(kr_attn_dbg), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : 1;
-}
-#else
-#define KR_STAMP(var)
-#endif
-#ifndef KR_ATTN_PRESCALE
-#define KR_ATTN_PRESCALE 1
-#endif
-#ifndef KR_ATTN_ROT
-#define KR_ATTN_ROT 0   // measured slower (see ROT in the kernel): build with -DKR_ATTN_ROT=1 to repeat the experiment
-#endif
-#ifndef KR_ATTN_VPRE
-#define KR_ATTN_VPRE(HD) ((HD) == 80 ? 3 : 0)
-#endif
-#ifndef KR_PIPE_VPRE
-#define KR_PIPE_VPRE 1   // pipelined kernel: V^T fragments read one step ahead of their PV
-#endif
 template <int HD>
 struct AttnCfg {
     static constexpr int KS = HD / 16;               // QK^T k-steps
@@ -182,6 +156,8 @@ struct AttnCfg {
     static constexpr int KCH = HD / 8;               // 16-byte chunks per K row
     static constexpr int KROW = (HD == 128) ? 256 : (KCH + 1) * 16;  // LDS K row bytes (hd=80: 176, conflict-free)
     static constexpr int VROW = 136;                 // LDS V^T row bytes (64 keys + 8 B pad: conflict-free b64 reads)
+    static constexpr bool PRESCALE = HD == 80;       // Q carries scale * log2(e), QK^T starts at -m_ref (see the kernel)
+    static constexpr int VPRE = HD == 80 ? 3 : 0;    // V^T fragment tiles requested ahead of the softmax
 };
 
 // Chunk `vi` of a V^T block in MEMORY order — the block is [2 halves][HD][32 keys] (kr_common.h, kr_vt_off), a chunk is 8 keys of
@@ -204,8 +180,11 @@ __device__ __forceinline__ int k_lds_off(int key, int c) {
 // that — and the loop is bound by vector-ALU ISSUE slots (per 64-key tile and wave: 32 v_exp + 32 v_fma + 16 v_max3 +
 // 16 v_cvt_pk + addresses, about as many cycles as the tile's 22 (hd 80) / 32 (hd 128) MFMAs hold the matrix pipe), so
 // what the r2 work removed were instructions and waits, not bytes: see the comments at the staging lambdas, at ONES
-// and at the permlane swap.  -DKR_ATTN_STAMPS (tools/build_variant.py) builds the per-segment cycle stamps this was
-// read from.
+// and at the permlane swap (per-segment cycle stamps: profiles/r02_attn_stamps.txt).
+// Two other loop structures were built, measured and removed; 4bd05ea is the last tree that contains them.  Software
+// pipelining inside each wave (scores two 32-key sub-tiles ahead of their PV) gained nothing: 1.071 against 1.068 ms
+// (profiles/r03_attn_pipe_ablation.txt).  A 256-query workgroup as 4 waves x 64 queries, one wave per SIMD, was 6 %
+// slower (profiles/r04_attn_q64.txt).
 template <int HD, bool CAUSAL, int NW>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) attn_varlen_kernel(const kr_bf16* __restrict__ q, const kr_bf16* __restrict__ k,
                                                           const kr_bf16* __restrict__ vt, kr_bf16* __restrict__ out,
@@ -217,14 +196,10 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2)
     constexpr int NTHR = NW * 64;
     // staging: the tile's 16-byte chunks, K rows then V^T rows, as ONE list dealt to the threads in whole passes
     constexpr int K_CH = 64 * C::KCH, V_CH = HD * 8, T_CH = K_CH + V_CH, PASSES = (T_CH + NTHR - 1) / NTHR;
-    constexpr int VPRE = KR_ATTN_VPRE(HD);  // V^T tiles prefetched across the softmax
+    constexpr int VPRE = C::VPRE;  // V^T tiles prefetched across the softmax
     // two tile images [K | V^T]: tile t+1 is written while tile t is read, one barrier per tile
     constexpr int K_BYTES = 64 * C::KROW, V_BYTES = C::DT * 32 * C::VROW, IMG = K_BYTES + V_BYTES;
     __shared__ __attribute__((aligned(16))) char img_s[2 * IMG];
-#ifdef KR_ATTN_LDS_PAD
-    __shared__ char lds_pad[KR_ATTN_LDS_PAD];
-    if (nq_total < 0) lds_pad[threadIdx.x] = 1, out[0] = lds_pad[threadIdx.x ^ 1];
-#endif
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lq = lane & 31, lh = lane >> 5;
@@ -268,7 +243,7 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2)
     // held in `cinit`), so that S^T comes out of the matrix pipe as the exp2 argument itself: the 32 v_fma per tile that
     // applied scale and reference were a fifth of the loop's vector-ALU issue slots.  The extra rounding of Q (relative
     // 2^-9 per element) is of the size of the bf16 rounding the HF reference applies to the scores themselves.
-    constexpr bool PRESCALE = (HD == 80) && KR_ATTN_PRESCALE;
+    constexpr bool PRESCALE = C::PRESCALE;
     if (PRESCALE) {
 #pragma unroll
         for (int s = 0; s < C::KS; ++s)
@@ -296,8 +271,8 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2)
     // lane-predicated or tile-count-dependent branch is left around a load or its wait.  With them (r1 / early r2) the
     // compiler had to assume a load into the same registers might still be in flight on the path that skipped the
     // stores, put s_waitcnt vmcnt(0) in front of the LAST load of every tile — i.e. waited for the five loads issued
-    // just before it — and the stamped build (-DKR_ATTN_STAMPS) showed 1500-2400 of the ~4300 cycles per tile in
-    // "load issue".
+    // just before it — and cycle stamps around the loop's segments showed 1500-2400 of the ~4300 cycles per tile in
+    // "load issue" (profiles/r02_attn_stamps.txt).
     bf16x8 treg[PASSES];
     auto load_tile = [&](int t) {
 #pragma unroll
@@ -333,11 +308,7 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     load_tile(n_tiles > 1 ? 1 : 0);
     __syncthreads();
-#ifdef KR_ATTN_STAMPS
-    unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, st4 = 0, st5 = 0, st6 = 0;
-    unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
-#endif
-    // P (bf16) and the V^T fragments of a tile; with ROT they live across the barrier (see below)
+    // P (bf16) and the V^T fragments of a tile
     bf16x8 vf[C::DT][4], pf[2][2];
     auto load_v = [&](const char* v_s, int dt) {
         const char* vrow = v_s + (dt * 32 + lq) * C::VROW;
@@ -361,25 +332,12 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2)
                     o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[dt][sub * 2 + ss], pf[sub][ss], o[dt], 0, 0, 0);
         }
     };
-    // ROT (8-wave workgroups with every V^T fragment prefetched): the two waves a SIMD holds come from the same workgroup and
-    // march in step — both in QK^T (matrix pipe contended, vector ALU idle), then both in the softmax (the reverse).  The
-    // second half of the waves therefore runs its PV one barrier LATE, from registers: tile t's P and V^T fragments are kept
-    // across the barrier and multiplied at the top of the next iteration, so one wave's PV / QK^T MFMAs sit beside the other's
-    // softmax.  Nothing else changes: PV(t) still completes before tile t + 1's rescale decision, in program order.
-    // MEASURED (r2, same box, bit-identical outputs): 8 x 4900 tokens 1.196-1.200 ms per block against 1.135-1.152 without,
-    // 19 276 tokens 2.21 against 2.11 — the late PV is 12 bare MFMAs that no longer hide this wave's exponentials, and that
-    // costs more than the staggering gains.  OFF by default (KR_ATTN_ROT).
-    constexpr bool ROT = (NW == 8) && (VPRE == C::DT) && KR_ATTN_ROT;
-    const bool rot = ROT && __builtin_amdgcn_readfirstlane(wave) >= NW / 2;
-    bool pend = false;
+    // Not here: running the second half of an 8-wave workgroup's PV one barrier late, from registers, so that a SIMD's two
+    // waves are out of phase, measured 1.196-1.200 ms against 1.135-1.152 per ViT block (ViT attention r2 table;
+    // 4bd05ea is the last tree with the code).
     for (int t = 0; t < n_tiles; ++t) {
-        KR_STAMP(st0);
         const char* k_s = img_s + (t & 1) * IMG;
         const char* v_s = k_s + K_BYTES;
-        if (ROT && rot && pend) {
-            do_pv(nullptr);
-            pend = false;
-        }
 
         // ---- S^T = K Q^T.  All K fragments of the tile are requested before the first MFMA.
         // (r2: requesting one 32-key half at a time does not lower the register peak, and forcing 3 waves per SIMD
@@ -411,10 +369,6 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2)
                     kf[sub][ks] = *reinterpret_cast<const bf16x8*>(k_s + k_lds_off<HD>(sub * 32 + lq, 2 * ks + lh));
         }
         __builtin_amdgcn_sched_barrier(0);
-        KR_STAMP(st1);
-#ifdef KR_ATTN_PRIO
-        __builtin_amdgcn_s_setprio(1);
-#endif
         f32x16 s[2];
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
@@ -429,9 +383,6 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2)
             for (int ks = 1; ks < C::KS; ++ks)
                 s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[sub][ks], qf[ks], s[sub], 0, 0, 0);
         }
-#ifdef KR_ATTN_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
         // V^T fragments of the first VPRE 32-row tiles of O^T are requested here, behind the QK^T MFMAs: their LDS
         // round trips run under the softmax instead of in front of each PV MFMA (the register file has the room since
         // the accumulators stopped being copied: 186 -> ~230 of the 256 two waves per SIMD allow)
@@ -460,20 +411,12 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2)
         for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
             for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[sub][r]);
-#ifdef KR_ATTN_SHFL
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-#else
         {   // the other half-wave's maximum: one v_permlane32_swap (vector ALU) instead of an LDS round trip
             const unsigned mb = __builtin_bit_cast(unsigned, mx);
             const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
             mx = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
         }
-#endif
         if (!PRESCALE) mx *= scale_log2e;  // scale > 0: max commutes with it
-#ifdef KR_ATTN_STAMPS
-        asm volatile("" : "+v"(mx));
-#endif
-        KR_STAMP(st2);
         if (PRESCALE) {
             // the scores ARE s - m_run already: mx is this tile's maximum relative to the reference.  The first tile moves
             // the reference onto its own maximum (o and l are still zero: nothing to scale), later tiles move it only
@@ -524,34 +467,14 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2)
                 pf[sub][h8] = __builtin_convertvector(pv, bf16x8);
             }
         l_run += psum;
-        if (ROT && rot) pend = true;
-        else do_pv(v_s);
+        do_pv(v_s);
         }
-#ifdef KR_ATTN_STAMPS
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) asm volatile("" : "+v"(o[dt]));
-#endif
-        KR_STAMP(st3);
         // tile t+1 (in registers since the previous barrier) -> the other image; it was last read during tile
         // t-1, which every wave left at the previous barrier
         store_tile(img_s + ((t + 1) & 1) * IMG);
-        KR_STAMP(st4);
         __syncthreads();
-        KR_STAMP(st5);
         load_tile(t + 2 < n_tiles ? t + 2 : n_tiles - 1);
-        KR_STAMP(st6);
-#ifdef KR_ATTN_STAMPS
-        acc[0] += st1 - st0; acc[1] += st2 - st1; acc[2] += st3 - st2; acc[3] += st4 - st3; acc[4] += st5 - st4; acc[5] += st6 - st5;
-#endif
     }
-    if (ROT && rot && pend) do_pv(nullptr);
-#ifdef KR_ATTN_STAMPS
-    if (blockIdx.x == gridDim.x / 2 && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) kr_attn_dbg[wave * 8 + i] = acc[i];
-        kr_attn_dbg[wave * 8 + 6] = (unsigned long long)n_tiles;
-    }
-#endif
     }  // n_tiles > 0
 
     // ---- normalise and store: lane = query, 4 consecutive d per register quad
@@ -577,829 +500,6 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2)
                 *reinterpret_cast<bf16x4*>(op + d) = ov;
             }
         }
-}
-
-// =====================================================================================
-// 4 waves x 64 queries: ONE wave per SIMD with the whole register file (VERDICT r3 next #4b; the guide's "4-wave, one-wave-per-SIMD"
-// attention structure, cdna_hip_programming.md)
-// =====================================================================================
-// A workgroup is still 256 queries of one head over the same two-image K / V^T ring, but its 4 waves own 64 queries each (two
-// 32-query blocks): the K and V^T fragments a wave reads from LDS feed TWO MFMA chains (half the fragment reads per MFMA), and the
-// overlap of softmax and matrix work has to come from inside the wave — QK^T of block 1 and PV of block 0 are independent of
-// block 0's / block 1's exponentials, in one basic block for the scheduler to interleave — instead of from a second wave on the
-// SIMD.  Same arithmetic per query as attn_varlen_kernel (PRESCALE, ONES row, lazy reference): bit-identical outputs.
-template <int HD, bool CAUSAL>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) attn_varlen_q64_kernel(
-    const kr_bf16* __restrict__ q, const kr_bf16* __restrict__ k, const kr_bf16* __restrict__ vt, kr_bf16* __restrict__ out,
-    const int32_t* __restrict__ qblk, const int32_t* __restrict__ qblk_len, int64_t nq_total, int q_heads, int group,
-    int64_t k_head_stride, int64_t vt_head_stride, float scale_log2e) {
-    using C = AttnCfg<HD>;
-    constexpr int NTHR = 256, QB = 2;
-    constexpr int K_CH = 64 * C::KCH, V_CH = HD * 8, T_CH = K_CH + V_CH, PASSES = (T_CH + NTHR - 1) / NTHR;
-    constexpr int K_BYTES = 64 * C::KROW, V_BYTES = C::DT * 32 * C::VROW, IMG = K_BYTES + V_BYTES;
-    __shared__ __attribute__((aligned(16))) char img_s[2 * IMG];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lq = lane & 31, lh = lane >> 5;
-    const int bi = blockIdx.x / q_heads, head = blockIdx.x - bi * q_heads, kvh = head / group;
-    const int64_t q_row0 = qblk[4 * bi + 0];
-    const int n_q = qblk[4 * bi + 1];
-    const int64_t k_row0 = (int64_t)qblk[4 * bi + 2];
-    const int64_t vt_blk0 = (int64_t)qblk[4 * bi + 3];
-    const int kv_len_seg = qblk_len[2 * bi + 0];
-    const int q_pos0 = qblk_len[2 * bi + 1];
-    int kv_len = kv_len_seg;
-    if (CAUSAL) kv_len = min(kv_len, q_pos0 + n_q);
-    const int n_tiles = (kv_len + 63) >> 6;
-    constexpr bool ONES = C::DT * 32 > HD;
-    if (ONES) {
-        for (int e = tid; e < (C::DT * 32 - HD) * C::VROW / 8; e += NTHR) {
-            const unsigned v = e < 16 ? 0x3F803F80u : 0u;
-            reinterpret_cast<u32x2*>(img_s + K_BYTES + HD * C::VROW)[e] = (u32x2){v, v};
-            reinterpret_cast<u32x2*>(img_s + IMG + K_BYTES + HD * C::VROW)[e] = (u32x2){v, v};
-        }
-    }
-    constexpr bool PRESCALE = (HD == 80) && KR_ATTN_PRESCALE;
-    int ql[QB];
-    bool q_valid[QB];
-    bf16x8 qf[QB][C::KS];
-#pragma unroll
-    for (int b = 0; b < QB; ++b) {
-        ql[b] = wave * 64 + b * 32 + lq;
-        q_valid[b] = ql[b] < n_q;
-        if (!q_valid[b]) ql[b] = n_q - 1;
-        const kr_bf16* qp = q + ((int64_t)head * nq_total + q_row0 + ql[b]) * HD + lh * 8;
-#pragma unroll
-        for (int s = 0; s < C::KS; ++s) qf[b][s] = ld8(qp + s * 16);
-        if (PRESCALE) {
-#pragma unroll
-            for (int s = 0; s < C::KS; ++s)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) qf[b][s][j] = f2bf(bf2f(qf[b][s][j]) * scale_log2e);
-        }
-    }
-    float m_run[QB], l_run[QB];
-    f32x16 o[QB][C::DT], cinit[QB];   // cinit: -m_ref of the block's queries in every register (zero without PRESCALE)
-#pragma unroll
-    for (int b = 0; b < QB; ++b) {
-        m_run[b] = PRESCALE ? 0.f : -1e30f;
-        l_run[b] = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) cinit[b][r] = 0.f;
-#pragma unroll
-        for (int t = 0; t < C::DT; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[b][t][r] = 0.f;
-    }
-    const kr_bf16* kbase = k + (int64_t)kvh * k_head_stride + k_row0 * HD;
-    const kr_bf16* vbase = vt + (int64_t)kvh * vt_head_stride + vt_blk0 * (int64_t)(HD * 64);
-    bf16x8 treg[PASSES];
-    auto load_tile = [&](int t) {
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            int idx = p * NTHR + tid;
-            idx = idx < T_CH ? idx : T_CH - 1;
-            const int key = idx / C::KCH, c = idx - key * C::KCH;
-            int kg = t * 64 + key;
-            kg = kg < kv_len_seg ? kg : kv_len_seg - 1;
-            const kr_bf16* kp = kbase + (int64_t)kg * HD + c * 8;
-            const kr_bf16* vp = vbase + (int64_t)t * (HD * 64) + (idx - K_CH) * 8;
-            treg[p] = ld8(idx < K_CH ? kp : vp);
-        }
-    };
-    auto store_tile = [&](char* img) {
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            int idx = p * NTHR + tid;
-            idx = idx < T_CH ? idx : T_CH - 1;
-            const int key = idx / C::KCH, c = idx - key * C::KCH;
-            const int off = idx < K_CH ? k_lds_off<HD>(key, c) : K_BYTES + vt_lds_piece<HD>(idx - K_CH, C::VROW);
-            const u32x4 w = __builtin_bit_cast(u32x4, treg[p]);
-            u32x2* dstp = reinterpret_cast<u32x2*>(img + off);
-            dstp[0] = (u32x2){w[0], w[1]};
-            dstp[1] = (u32x2){w[2], w[3]};
-        }
-    };
-    if (n_tiles > 0) {
-        load_tile(0);
-        store_tile(img_s);
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-        load_tile(n_tiles > 1 ? 1 : 0);
-        __syncthreads();
-        for (int t = 0; t < n_tiles; ++t) {
-            const char* k_s = img_s + (t & 1) * IMG;
-            const char* v_s = k_s + K_BYTES;
-            if (!CAUSAL || t * 64 <= q_pos0 + wave * 64 + 63) {
-                bf16x8 kf[2][C::KS];
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                    for (int ks = 0; ks < C::KS; ++ks)
-                        kf[sub][ks] = *reinterpret_cast<const bf16x8*>(k_s + k_lds_off<HD>(sub * 32 + lq, 2 * ks + lh));
-                f32x16 s[QB][2];
-#pragma unroll
-                for (int b = 0; b < QB; ++b)
-#pragma unroll
-                    for (int sub = 0; sub < 2; ++sub) {
-                        // the chain starts from the block's persistent -m_ref tuple (PRESCALE) / from zero: no per-tile register fill
-                        s[b][sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[sub][0], qf[b][0], cinit[b], 0, 0, 0);
-#pragma unroll
-                        for (int ks = 1; ks < C::KS; ++ks)
-                            s[b][sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[sub][ks], qf[b][ks], s[b][sub], 0, 0, 0);
-                    }
-                // V^T fragments: read once, used by both query blocks
-                bf16x8 vf[C::DT][4];
-#pragma unroll
-                for (int dt = 0; dt < C::DT; ++dt) {
-                    const char* vrow = v_s + (dt * 32 + lq) * C::VROW;
-#pragma unroll
-                    for (int f = 0; f < 4; ++f) {
-                        const int kb = f * 16 + 4 * lh;
-                        const u32x2 lo = *reinterpret_cast<const u32x2*>(vrow + kb * 2);
-                        const u32x2 hi = *reinterpret_cast<const u32x2*>(vrow + (kb + 8) * 2);
-                        vf[dt][f] = __builtin_bit_cast(bf16x8, (u32x4){lo[0], lo[1], hi[0], hi[1]});
-                    }
-                }
-                bf16x8 pf[QB][2][2];
-#pragma unroll
-                for (int b = 0; b < QB; ++b) {
-                    const int qpos = q_pos0 + wave * 64 + b * 32 + lq;
-                    bool need_mask = t * 64 + 64 > kv_len_seg;
-                    if (CAUSAL) need_mask |= t * 64 + 63 > q_pos0 + wave * 64 + b * 32;
-                    if (need_mask) {
-#pragma unroll
-                        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) {
-                                const int key = t * 64 + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                                const bool ok = key < kv_len_seg && (!CAUSAL || key <= qpos);
-                                s[b][sub][r] = ok ? s[b][sub][r] : -INFINITY;
-                            }
-                    }
-                    float mx = -INFINITY;
-#pragma unroll
-                    for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[b][sub][r]);
-                    {
-                        const unsigned mb = __builtin_bit_cast(unsigned, mx);
-                        const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-                        mx = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
-                    }
-                    if (!PRESCALE) mx *= scale_log2e;
-                    if (PRESCALE) {
-                        const bool first = t == 0;
-                        if (first || __any(mx > 8.0f)) {
-                            const float d = first ? (mx > -INFINITY ? mx : 0.f) : fmaxf(mx, 0.f);
-                            m_run[b] += d;
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) cinit[b][r] = -m_run[b];
-#pragma unroll
-                            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                                for (int r = 0; r < 16; ++r) s[b][sub][r] -= d;
-                            if (!first) {
-                                const float alpha = __builtin_amdgcn_exp2f(-d);
-                                l_run[b] *= alpha;
-#pragma unroll
-                                for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-                                    for (int r = 0; r < 16; ++r) o[b][dt][r] *= alpha;
-                            }
-                        }
-                    } else {
-                        const float m_new = fmaxf(m_run[b], mx);
-                        if (__any(m_new - m_run[b] > 8.0f)) {
-                            const float alpha = __builtin_amdgcn_exp2f(m_run[b] - m_new);
-                            m_run[b] = m_new;
-                            l_run[b] *= alpha;
-#pragma unroll
-                            for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-                                for (int r = 0; r < 16; ++r) o[b][dt][r] *= alpha;
-                        }
-                    }
-                    float psum = 0.f;
-#pragma unroll
-                    for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                        for (int h8 = 0; h8 < 2; ++h8) {
-                            f32x8 pv;
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) {
-                                pv[j] = PRESCALE ? __builtin_amdgcn_exp2f(s[b][sub][h8 * 8 + j])
-                                                 : __builtin_amdgcn_exp2f(__builtin_fmaf(s[b][sub][h8 * 8 + j], scale_log2e, -m_run[b]));
-                                if (!ONES) psum += pv[j];
-                            }
-                            pf[b][sub][h8] = __builtin_convertvector(pv, bf16x8);
-                        }
-                    l_run[b] += psum;
-                }
-#pragma unroll
-                for (int b = 0; b < QB; ++b)
-#pragma unroll
-                    for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-                        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                            for (int ss = 0; ss < 2; ++ss)
-                                o[b][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[dt][sub * 2 + ss], pf[b][sub][ss], o[b][dt], 0, 0, 0);
-            }
-            store_tile(img_s + ((t + 1) & 1) * IMG);
-            __syncthreads();
-            load_tile(t + 2 < n_tiles ? t + 2 : n_tiles - 1);
-        }
-    }
-#pragma unroll
-    for (int b = 0; b < QB; ++b) {
-        float l_tot;
-        if (ONES) {
-            l_tot = __shfl(o[b][HD / 32][8], lq, 64);
-        } else {
-            l_tot = l_run[b] + __shfl_xor(l_run[b], 32, 64);
-        }
-        const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-        if (q_valid[b]) {
-            kr_bf16* op = out + (q_row0 + ql[b]) * ((int64_t)q_heads * HD) + (int64_t)head * HD;
-#pragma unroll
-            for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int d = dt * 32 + 8 * i + 4 * lh;
-                    if (d < HD) {
-                        bf16x4 ov;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) ov[j] = f2bf(o[b][dt][4 * i + j] * inv);
-                        *reinterpret_cast<bf16x4*>(op + d) = ov;
-                    }
-                }
-        }
-    }
-}
-
-#ifdef KR_ATTN_PIPE_EXPERIMENT
-// =====================================================================================
-// EXPERIMENT (r3, measured, NOT adopted; built only with -DKR_ATTN_PIPE_EXPERIMENT via tools/build_variant.py):
-// the same attention, software-pipelined INSIDE each wave
-// =====================================================================================
-// attn_varlen_kernel runs a tile as a dependent chain per wave — K reads -> QK^T -> max -> exp -> PV — so a wave's own
-// MFMAs never sit beside its own exponentials, and its MFMA chains are dependent back to back.  Here the unit is a
-// 32-key SUB-tile j and one step of a wave's stream is
-//     matrix pipe : PV(j) and QK^T(j + 2), alternating (adjacent MFMAs are independent; PV leads by two while the
-//                   K fragments land)
-//     vector ALU  : P(j + 1) = bf16(exp2(S(j + 1))) in the MFMA gaps (sched_group_barrier), then mask and maximum of the
-//                   S(j + 2) just finished
-//     rare branch : the lazy reference moves by d for S(j + 2): O (PV(j) is in it) and l are scaled by 2^-d, the one P
-//                   already formed from the old reference whose PV is still to come (P(j + 1)) is scaled with them, d is
-//                   taken from S(j + 2) and from the QK^T start tuple
-// i.e. scores are produced two sub-tiles ahead of their PV.  Tiles are staged TWO ahead (three LDS images: during
-// iteration t the waves read K of tile t + 1 and V^T of tiles t / t + 1 and write tile t + 2), one barrier per tile;
-// Q / K / V^T / P layouts, the ones row, PRESCALE and the branch-free staging are attn_varlen_kernel's.  The ISA is what
-// was asked for (hd 80: 211 registers, no spill; MFMAs alternating with 4-8 v_exp / v_cvt between them).
-// MEASURED (profiles/r03_attn_pipe_ablation.txt; same box, same operands, outputs within the kernel tests' tolerance):
-// 8 x 4900 tokens 1.071 ms against 1.068 for attn_varlen_kernel, 19 276 tokens 1.971 against 1.970 — NO gain, and two
-// earlier forms (QK^T one sub-tile ahead; the decision taken beside the next step's leading MFMAs) the same.  The
-// ablation switches below say why: without exponentials -5 %, without staging and barrier -15 %, without the K / V^T
-// fragment reads -10 %, all three -32 % (0.72 ms = the 22 MFMAs per tile alone, 1.5 PFLOP/s of matrix work), and the
-// parts ADD whatever their order in the stream, at 0.49 MFMA-busy and a clock that moves little (1.97 - 2.26 GHz over the
-// variants: not a DVFS effect).  The loop is not bound by a dependency chain, by issue order or by the two waves of a SIMD
-// marching in step: a tile's vector-ALU, LDS and staging work does not run beside its MFMAs on this SIMD in any order
-// tried, so only doing less per tile would help: fragment reads shared by 64 queries per wave (one wave per SIMD on 512
-// registers) and LDS-DMA staging are the two levers left, ~5 % and ~8 % of this kernel.
-// the order of a step's MFMAs: entry i is PV number idx[i] (is_pv) or QK^T k-step idx[i]
-template <int NPV, int KS>
-struct PipeOrder {
-    bool is_pv[NPV + KS] = {};
-    int idx[NPV + KS] = {};
-    constexpr PipeOrder() {
-        int np = 0, nq = 0;
-        for (int i = 0; i < NPV + KS; ++i) {
-            const bool take_pv = (np < NPV) && (np < 2 || nq >= KS || ((i & 1) == 0));
-            is_pv[i] = take_pv;
-            idx[i] = take_pv ? np++ : nq++;
-        }
-    }
-};
-template <int HD, bool CAUSAL, int NW>
-__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2))) attn_varlen_pipe_kernel(
-    const kr_bf16* __restrict__ q, const kr_bf16* __restrict__ k, const kr_bf16* __restrict__ vt, kr_bf16* __restrict__ out,
-    const int32_t* __restrict__ qblk, const int32_t* __restrict__ qblk_len, int64_t nq_total, int q_heads, int group,
-    int64_t k_head_stride, int64_t vt_head_stride, float scale_log2e) {
-    using C = AttnCfg<HD>;
-    constexpr int NTHR = NW * 64;
-    constexpr int K_CH = 64 * C::KCH, V_CH = HD * 8, T_CH = K_CH + V_CH, PASSES = (T_CH + NTHR - 1) / NTHR;
-    constexpr int K_BYTES = 64 * C::KROW, V_BYTES = C::DT * 32 * C::VROW, IMG = K_BYTES + V_BYTES;
-    __shared__ __attribute__((aligned(16))) char img_s[3 * IMG];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lq = lane & 31, lh = lane >> 5;
-    const int bi = blockIdx.x / q_heads, head = blockIdx.x - bi * q_heads, kvh = head / group;
-    const int64_t q_row0 = qblk[4 * bi + 0];
-    const int n_q = qblk[4 * bi + 1];
-    const int64_t k_row0 = (int64_t)qblk[4 * bi + 2];
-    const int64_t vt_blk0 = (int64_t)qblk[4 * bi + 3];
-    const int kv_len_seg = qblk_len[2 * bi + 0];
-    const int q_pos0 = qblk_len[2 * bi + 1];
-    int kv_len = kv_len_seg;
-    if (CAUSAL) kv_len = min(kv_len, q_pos0 + n_q);
-    const int n_tiles = (kv_len + 63) >> 6;
-
-    constexpr bool ONES = C::DT * 32 > HD;
-    if (ONES) {
-        for (int e = tid; e < (C::DT * 32 - HD) * C::VROW / 8; e += NTHR) {
-            const unsigned v = e < 16 ? 0x3F803F80u : 0u;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) reinterpret_cast<u32x2*>(img_s + i * IMG + K_BYTES + HD * C::VROW)[e] = (u32x2){v, v};
-        }
-    }
-
-    int ql = wave * 32 + lq;
-    const bool q_valid = ql < n_q;
-    if (!q_valid) ql = n_q - 1;
-    const kr_bf16* qp = q + ((int64_t)head * nq_total + q_row0 + ql) * HD + lh * 8;
-    bf16x8 qf[C::KS];
-#pragma unroll
-    for (int s = 0; s < C::KS; ++s) qf[s] = ld8(qp + s * 16);
-    constexpr bool PRESCALE = (HD == 80) && KR_ATTN_PRESCALE;
-    if (PRESCALE) {
-#pragma unroll
-        for (int s = 0; s < C::KS; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) qf[s][j] = f2bf(bf2f(qf[s][j]) * scale_log2e);
-    }
-    f32x16 cinit;   // PRESCALE: -reference in every register (lane = query); else zero
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cinit[r] = 0.f;
-    const int qpos = q_pos0 + wave * 32 + lq;
-
-    const kr_bf16* kbase = k + (int64_t)kvh * k_head_stride + k_row0 * HD;
-    const kr_bf16* vbase = vt + (int64_t)kvh * vt_head_stride + vt_blk0 * (int64_t)(HD * 64);
-
-    f32x16 o[C::DT];
-#pragma unroll
-    for (int t = 0; t < C::DT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
-    float m_run = -1e30f, l_run = 0.f;   // m_run: the non-PRESCALE reference
-
-    bf16x8 treg[PASSES];
-    auto load_tile = [&](int t) __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            int idx = p * NTHR + tid;
-            idx = idx < T_CH ? idx : T_CH - 1;
-            const int key = idx / C::KCH, c = idx - key * C::KCH;
-            int kg = t * 64 + key;
-            kg = kg < kv_len_seg ? kg : kv_len_seg - 1;
-            const kr_bf16* kp = kbase + (int64_t)kg * HD + c * 8;
-            const kr_bf16* vp = vbase + (int64_t)t * (HD * 64) + (idx - K_CH) * 8;   // the block in MEMORY order (see vt_lds_piece)
-            treg[p] = ld8(idx < K_CH ? kp : vp);
-        }
-    };
-    auto store_tile = [&](char* img) __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            int idx = p * NTHR + tid;
-            idx = idx < T_CH ? idx : T_CH - 1;
-            const int key = idx / C::KCH, c = idx - key * C::KCH;
-            const int off = idx < K_CH ? k_lds_off<HD>(key, c) : K_BYTES + vt_lds_piece<HD>(idx - K_CH, C::VROW);
-            const u32x4 w = __builtin_bit_cast(u32x4, treg[p]);
-            u32x2* dstp = reinterpret_cast<u32x2*>(img + off);
-            dstp[0] = (u32x2){w[0], w[1]};
-            dstp[1] = (u32x2){w[2], w[3]};
-        }
-    };
-    auto read_k = [&](const char* k_s, int sub, bf16x8 (&kf)[C::KS]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int ks = 0; ks < C::KS; ++ks)
-            kf[ks] = *reinterpret_cast<const bf16x8*>(k_s + k_lds_off<HD>(sub * 32 + lq, 2 * ks + lh));
-    };
-    auto read_v = [&](const char* v_s, int sub, bf16x8 (&vf)[C::DT][2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) {
-            const char* vrow = v_s + (dt * 32 + lq) * C::VROW;
-#pragma unroll
-            for (int ss = 0; ss < 2; ++ss) {
-                const int kb = (sub * 2 + ss) * 16 + 4 * lh;  // keys kb..kb+3 and kb+8..kb+11
-                const u32x2 lo = *reinterpret_cast<const u32x2*>(vrow + kb * 2);
-                const u32x2 hi = *reinterpret_cast<const u32x2*>(vrow + (kb + 8) * 2);
-                vf[dt][ss] = __builtin_bit_cast(bf16x8, (u32x4){lo[0], lo[1], hi[0], hi[1]});
-            }
-        }
-    };
-    f32x16 zero16;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
-    auto mask_scores = [&](f32x16& s, int t, int sub) __attribute__((always_inline)) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = t * 64 + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const bool ok = key < kv_len_seg && (!CAUSAL || key <= qpos);
-            s[r] = ok ? s[r] : -INFINITY;
-        }
-    };
-    auto max_scores = [&](const f32x16& s) __attribute__((always_inline)) {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[r]);
-        const unsigned mb = __builtin_bit_cast(unsigned, mx);
-        const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-        return fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
-    };
-    auto exp_scores = [&](const f32x16& s, bf16x8 (&pf)[2]) __attribute__((always_inline)) {
-        float psum = 0.f;
-#pragma unroll
-        for (int h8 = 0; h8 < 2; ++h8) {
-            f32x8 pv8;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-#ifdef KR_PIPE_NO_EXP
-                pv8[j] = s[h8 * 8 + j];
-#else
-                pv8[j] = PRESCALE ? __builtin_amdgcn_exp2f(s[h8 * 8 + j])
-                                  : __builtin_amdgcn_exp2f(__builtin_fmaf(s[h8 * 8 + j], scale_log2e, -m_run));
-#endif
-                if (!ONES) psum += pv8[j];
-            }
-            pf[h8] = __builtin_convertvector(pv8, bf16x8);
-        }
-        l_run += psum;
-    };
-    // One step j: PV(j) (P = pf_in, V^T fragments vf read one step earlier) and QK^T(j + 2) (sub-tile (tk, subk), into
-    // s_acc) on the matrix pipe, alternating; beside them P(j + 1) = exp2(s_prev) into pf_out; then mask and maximum of the
-    // finished s_acc and, rarely, the reference move for it: O (PV(j) is in it) and l are scaled by 2^-d, the one P already
-    // formed from the old reference whose PV is still to come (pf_out) is scaled with them, and d is taken from s_acc and
-    // from the QK^T start tuple.
-    constexpr int NPV = 2 * C::DT, N_MFMA = NPV + C::KS;
-    auto step = [&](auto MASKC, f32x16& s_prev, f32x16& s_acc, int tk, int subk, bf16x8 (&pf_out)[2], const bf16x8 (&pf_in)[2],
-                    const char* k_s, const bf16x8 (&vf)[C::DT][2], const char* v_next, int sub_next,
-                    bf16x8 (&vf_next)[C::DT][2]) __attribute__((always_inline)) {
-        constexpr bool MASK = decltype(MASKC)::value;
-        asm volatile("" : "+v"(s_prev));   // the step's vector work stays inside the step
-        bf16x8 kf[C::KS];
-#ifdef KR_PIPE_NO_KREAD
-#pragma unroll
-        for (int ks = 0; ks < C::KS; ++ks) kf[ks] = qf[ks];
-#else
-        read_k(k_s, subk, kf);
-#endif
-#ifdef KR_PIPE_NO_VREAD
-#pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-            for (int ss = 0; ss < 2; ++ss) vf_next[dt][ss] = vf[dt][ss];
-#else
-        read_v(v_next, sub_next, vf_next);
-#endif
-        f32x16 acc = PRESCALE ? cinit : zero16;
-        // MFMA i of the step (PipeOrder): PV leads by two (its operands are in registers, K fragments are landing), then
-        // the chains alternate: adjacent MFMAs never depend on each other
-        constexpr PipeOrder<NPV, C::KS> ORD{};
-#pragma unroll
-        for (int i = 0; i < N_MFMA; ++i) {
-            const int n = ORD.idx[i];
-            if (ORD.is_pv[i]) {
-#ifndef KR_PIPE_NO_PV
-                o[n % C::DT] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[n % C::DT][n / C::DT], pf_in[n / C::DT], o[n % C::DT], 0, 0, 0);
-#endif
-            } else {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[n], qf[n], acc, 0, 0, 0);
-            }
-        }
-        exp_scores(s_prev, pf_out);
-        s_acc = acc;
-        if (MASK) mask_scores(s_acc, tk, subk);
-        float mx = max_scores(s_acc);
-#pragma unroll
-        for (int i = 0; i < N_MFMA; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, ONES ? 3 : 5, 0);
-        }
-        if (!PRESCALE) mx *= scale_log2e;
-        const float grow = PRESCALE ? mx : fmaxf(m_run, mx) - m_run;
-        if (__any(grow > 8.0f)) {
-            const float d = fmaxf(grow, 0.f);
-            const float alpha = __builtin_amdgcn_exp2f(-d);
-            l_run *= alpha;
-#pragma unroll
-            for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-#pragma unroll
-            for (int h8 = 0; h8 < 2; ++h8)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) pf_out[h8][j] = f2bf(bf2f(pf_out[h8][j]) * alpha);
-            if (PRESCALE) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    cinit[r] -= d;
-                    s_acc[r] -= d;
-                }
-            } else {
-                m_run += d;
-            }
-        }
-    };
-
-    if (n_tiles > 0) {
-        load_tile(0);
-        store_tile(img_s);
-        load_tile(n_tiles > 1 ? 1 : 0);
-        store_tile(img_s + IMG);
-        load_tile(n_tiles > 2 ? 2 : n_tiles - 1);
-        __syncthreads();
-        bf16x8 vfa[C::DT][2], vfb[C::DT][2], pfa[2], pfb[2];
-        f32x16 s0, s1;
-        // ---- prologue: S(0, 0) with the first reference = its own maximum, P(0, 0), S(0, 1) (not yet looked at), V^T(0, 0)
-        {
-            bf16x8 kf[C::KS];
-            read_k(img_s, 0, kf);
-            s0 = zero16;
-#pragma unroll
-            for (int ks = 0; ks < C::KS; ++ks) s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], s0, 0, 0, 0);
-            mask_scores(s0, 0, 0);
-            const float mx = max_scores(s0);
-            if (PRESCALE) {
-                const float d = mx > -INFINITY ? mx : 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    cinit[r] = -d;
-                    s0[r] -= d;
-                }
-            } else {
-                m_run = mx > -INFINITY ? mx * scale_log2e : 0.f;
-            }
-            read_k(img_s, 1, kf);
-            s1 = PRESCALE ? cinit : zero16;
-#pragma unroll
-            for (int ks = 0; ks < C::KS; ++ks) s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], s1, 0, 0, 0);
-            exp_scores(s0, pfa);
-            mask_scores(s1, 0, 1);
-            float mx1 = max_scores(s1);   // the decision for (0, 1): O is still zero, P(0, 0) waits for its PV
-            if (!PRESCALE) mx1 *= scale_log2e;
-            const float grow = PRESCALE ? mx1 : fmaxf(m_run, mx1) - m_run;
-            if (__any(grow > 8.0f)) {
-                const float d = fmaxf(grow, 0.f);
-                const float alpha = __builtin_amdgcn_exp2f(-d);
-                l_run *= alpha;
-#pragma unroll
-                for (int h8 = 0; h8 < 2; ++h8)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) pfa[h8][j] = f2bf(bf2f(pfa[h8][j]) * alpha);
-                if (PRESCALE) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        cinit[r] -= d;
-                        s1[r] -= d;
-                    }
-                } else {
-                    m_run += d;
-                }
-            }
-            read_v(img_s + K_BYTES, 0, vfa);
-        }
-        auto tile_body = [&](auto MASKC, int t) __attribute__((always_inline)) {
-            const int cur = t % 3, nx = (t + 1) % 3, nn = (t + 2) % 3;
-            const char* v_s = img_s + cur * IMG + K_BYTES;
-            const char* k_s = img_s + nx * IMG;
-            // PV(t, 0) with QK^T(t + 1, 0); P of (t, 1); V^T(t, 1) for the next step
-            step(MASKC, s1, s0, t + 1, 0, pfb, pfa, k_s, vfa, v_s, 1, vfb);
-            // PV(t, 1) with QK^T(t + 1, 1); P of (t + 1, 0); V^T(t + 1, 0).  Past the last tile the image
-            // holds that tile again: those scores are never used, and no tile-count branch sits in the loop
-            step(MASKC, s0, s1, t + 1, 1, pfa, pfb, k_s, vfb, k_s + K_BYTES, 0, vfa);
-            // tile t + 2 (in registers since the previous barrier) -> the third image, last read (V^T of tile t - 1)
-            // before the previous barrier
-#ifndef KR_PIPE_NO_STAGE
-            store_tile(img_s + nn * IMG);
-#endif
-#ifndef KR_PIPE_NO_BARRIER
-            __syncthreads();
-#endif
-#ifndef KR_PIPE_NO_STAGE
-            load_tile(t + 3 < n_tiles ? t + 3 : n_tiles - 1);
-#endif
-        };
-        // iteration t forms the scores of tile t + 1: plain while every key of it is visible to every query of the block
-        int t_plain = kv_len_seg >> 6;
-        if (CAUSAL) t_plain = min(t_plain, (q_pos0 + 1) >> 6);
-        t_plain = min(t_plain - 1, n_tiles);
-        int t = 0;
-        for (; t < t_plain; ++t) tile_body(std::false_type{}, t);
-        for (; t < n_tiles; ++t) tile_body(std::true_type{}, t);
-    }
-
-    float l_tot;
-    if (ONES) {
-        static_assert(!ONES || HD % 32 == 16, "ones row register");
-        l_tot = __shfl(o[HD / 32][8], lq, 64);
-    } else {
-        l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    }
-    const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-    if (!q_valid) return;
-    kr_bf16* op = out + (q_row0 + ql) * ((int64_t)q_heads * HD) + (int64_t)head * HD;
-#pragma unroll
-    for (int dt = 0; dt < C::DT; ++dt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int d = dt * 32 + 8 * i + 4 * lh;
-            if (d < HD) {
-                bf16x4 ov;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) ov[j] = f2bf(o[dt][4 * i + j] * inv);
-                *reinterpret_cast<bf16x4*>(op + d) = ov;
-            }
-        }
-}
-#endif  // KR_ATTN_PIPE_EXPERIMENT
-
-// =====================================================================================
-// decode: rotary + KV append for one new token per sequence
-// =====================================================================================
-__global__ void __launch_bounds__(256) decode_qkv_prep_kernel(const kr_bf16* __restrict__ qkv,
-                                                              const float* __restrict__ inv_freq,
-                                                              const int32_t* __restrict__ ctx_len,
-                                                              const int32_t* __restrict__ rope_delta,
-                                                              kr_bf16* __restrict__ q_out, kr_bf16* __restrict__ kcache,
-                                                              kr_bf16* __restrict__ vtcache, int heads, int kv_heads,
-                                                              int hd, int layer, int batch, int s_max) {
-    const int b = blockIdx.x;
-    const int pos = ctx_len[b];
-    const float rp = (float)(pos + rope_delta[b]);
-    const int half = hd >> 1;
-    const int qkv_dim = (heads + 2 * kv_heads) * hd;
-    const kr_bf16* row = qkv + (int64_t)b * qkv_dim;
-    const int64_t kv_base = ((int64_t)layer * batch + b) * kv_heads;
-    // rotary on q heads and k heads: one thread per (head, i < hd/2)
-    for (int e = threadIdx.x; e < (heads + kv_heads) * half; e += blockDim.x) {
-        const int h = e / half, i = e - h * half;
-        const float ang = rp * inv_freq[i];
-        // HF casts cos/sin to the activation dtype (TF:modeling_qwen2_vl.py:169)
-        const float c = bfround(cosf(ang)), s = bfround(sinf(ang));
-        const float x0 = bfbits2f(row[h * hd + i]), x1 = bfbits2f(row[h * hd + i + half]);
-        const __bf16 y0 = f2bf(x0 * c - x1 * s), y1 = f2bf(x1 * c + x0 * s);
-        kr_bf16* dst;
-        if (h < heads) {
-            dst = q_out + ((int64_t)b * heads + h) * hd;
-        } else {
-            dst = kcache + ((kv_base + (h - heads)) * s_max + pos) * hd;
-        }
-        dst[i] = __builtin_bit_cast(kr_bf16, y0);
-        dst[i + half] = __builtin_bit_cast(kr_bf16, y1);
-    }
-    // V -> transposed cache column
-    const kr_bf16* vrow = row + (heads + kv_heads) * hd;
-    for (int e = threadIdx.x; e < kv_heads * hd; e += blockDim.x) {
-        const int h = e / hd, d = e - h * hd;
-        vtcache[((kv_base + h) * (s_max >> 6) + (pos >> 6)) * (hd * 64) + kr_vt_off(d, pos & 63, hd)] = vrow[e];
-    }
-}
-
-// =====================================================================================
-// decode attention, v_mfma_f32_16x16x32_bf16, K and V^T straight from HBM to registers
-// =====================================================================================
-// grid = (n_split, kv_heads, batch), 4 waves per block; wave `part` = split*4 + wave walks the
-// 64-key blocks part, part + n_part, ...  Heads of the GQA group sit on the 16 MFMA columns.
-//   S[key][g]   : A = K rows (keys permuted so that lane group fg ends up with keys 8fg..8fg+7)
-//                 B = Q^T
-//   O^T[d][g]  += A = V^T (16 B = 8 consecutive keys per lane), B = P^T (the S accumulators)
-// Partials (m, l, O) go to the fp32 workspace; attn_decode_combine_kernel merges them.
-template <int HD>
-__global__ void __launch_bounds__(256) attn_decode_kernel(const kr_bf16* __restrict__ q, const kr_bf16* __restrict__ kcache,
-                                                          const kr_bf16* __restrict__ vtcache,
-                                                          const int32_t* __restrict__ ctx_len, float* __restrict__ ws,
-                                                          int heads, int kv_heads, int layer, int batch, int s_max,
-                                                          float scale_log2e) {
-    constexpr int DT = HD / 16;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int fr = lane & 15, fg = lane >> 4;
-    const int kvh = blockIdx.y, b = blockIdx.z;
-    const int group = heads / kv_heads;
-    const int n_part = gridDim.x * 4;
-    const int part = blockIdx.x * 4 + wave;
-    const int ctx = ctx_len[b] + 1;
-    const int nb = (ctx + 63) >> 6;
-
-    const int g = fr < group ? fr : 0;
-    const kr_bf16* qp = q + ((int64_t)b * heads + kvh * group + g) * HD + fg * 32;
-    bf16x8 qf[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) qf[i] = ld8(qp + i * 8);
-
-    const int64_t kv_base = ((int64_t)layer * batch + b) * kv_heads + kvh;
-    const kr_bf16* kc = kcache + kv_base * s_max * HD;
-    const kr_bf16* vc = vtcache + kv_base * (int64_t)(s_max >> 6) * (HD * 64);
-
-    f32x4 o[DT];
-#pragma unroll
-    for (int t = 0; t < DT; ++t) o[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float m_run = -1e30f, l_run = 0.f;
-
-    for (int blk = part; blk < nb; blk += n_part) {
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-            const int key0 = blk * 64 + hf * 32;
-            if (key0 >= ctx) break;  // wave-uniform
-            // K fragments: tile kt, row r holds key 8(r>>2) + 4kt + (r&3)
-            bf16x8 kf[2][4];
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-                const kr_bf16* kp = kc + (int64_t)(key0 + 8 * (fr >> 2) + 4 * kt + (fr & 3)) * HD + fg * 32;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) kf[kt][i] = ld8_nt(kp + i * 8);
-            }
-            // V^T fragments: row d = dt*16 + fr, keys key0 + 8fg .. +7
-            bf16x8 vf[DT];
-            const kr_bf16* vp = vc + (int64_t)blk * (HD * 64) + hf * (HD * 32) + fg * 8;
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) vf[dt] = ld8_nt(vp + (dt * 16 + fr) * 32);
-
-            f32x4 s[2];
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-                s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][i], qf[i], s[kt], 0, 0, 0);
-            }
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key = key0 + 8 * fg + 4 * kt + r;
-                    const float v = key < ctx ? s[kt][r] * scale_log2e : -INFINITY;
-                    s[kt][r] = v;
-                    mx = fmaxf(mx, v);
-                }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-            m_run = m_new;
-            bf16x8 pf;
-            float psum = 0.f;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const __bf16 pb = f2bf(__builtin_amdgcn_exp2f(s[kt][r] - m_new));
-                    psum += bf2f(pb);
-                    pf[kt * 4 + r] = pb;
-                }
-            l_run = l_run * alpha + psum;
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt], pf, o[dt], 0, 0, 0);
-            }
-        }
-    }
-    // l: sum the four key groups of each head column
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
-    if (fr < group) {
-        float* w = ws + (((int64_t)b * heads + kvh * group + fr) * n_part + part) * (HD + 2);
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4*>(w + dt * 16 + fg * 4) = o[dt];
-        if (fg == 0) {
-            w[HD] = m_run;
-            w[HD + 1] = l_run;
-        }
-    }
-}
-
-// grid = batch*heads blocks of HD threads
-__global__ void attn_decode_combine_kernel(const float* __restrict__ ws, kr_bf16* __restrict__ out, int n_part, int hd) {
-    const int bh = blockIdx.x, d = threadIdx.x;
-    const float* w = ws + (int64_t)bh * n_part * (hd + 2);
-    float mx = -1e30f;
-    for (int p = 0; p < n_part; ++p) mx = fmaxf(mx, w[p * (hd + 2) + hd]);
-    float acc = 0.f, l = 0.f;
-    for (int p = 0; p < n_part; ++p) {
-        const float sc = __builtin_amdgcn_exp2f(w[p * (hd + 2) + hd] - mx);
-        l += w[p * (hd + 2) + hd + 1] * sc;
-        acc += w[p * (hd + 2) + d] * sc;
-    }
-    out[(int64_t)bh * hd + d] = __builtin_bit_cast(kr_bf16, f2bf(l > 0.f ? acc / l : 0.f));
-}
-
-// scattered K / V^T append (standalone operator; the engine uses the blocked prep kernels)
-__global__ void __launch_bounds__(256) kv_append_kernel(const kr_bf16* __restrict__ k, const kr_bf16* __restrict__ v,
-                                                        int64_t row_stride, const int32_t* __restrict__ tok_seq,
-                                                        const int32_t* __restrict__ tok_pos, kr_bf16* __restrict__ kcache,
-                                                        kr_bf16* __restrict__ vtcache, int64_t n, int kv_heads, int hd,
-                                                        int layer, int batch, int s_max) {
-    const int64_t total = n * kv_heads * hd;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int d = (int)(i % hd);
-        const int64_t t = i / hd;
-        const int h = (int)(t % kv_heads);
-        const int64_t tok = t / kv_heads;
-        const int sq = tok_seq[tok], pos = tok_pos[tok];
-        const int64_t base = ((int64_t)layer * batch + sq) * kv_heads + h;
-        kcache[(base * s_max + pos) * hd + d] = k[tok * row_stride + h * hd + d];
-        vtcache[(base * (s_max >> 6) + (pos >> 6)) * (hd * 64) + kr_vt_off(d, pos & 63, hd)] = v[tok * row_stride + h * hd + d];
-    }
 }
 
 }  // namespace
@@ -1467,34 +567,12 @@ static int attn_varlen_impl(const kr_bf16* q, const kr_bf16* k, const kr_bf16* v
     dim3 grid((unsigned)(n_qblk * q_heads));
     const float sl = scale * 1.4426950408889634f;
     const int group = q_heads / kv_heads;
-#ifdef KR_ATTN_PIPE_EXPERIMENT
-    const char* penv = getenv("KARANTA_ATTN_PIPE");   // experiment build: 0 = the product loop (same-library A/B)
-    const int pipe = penv ? atoi(penv) : 1;
-#define KR_LAUNCH_ATTN(HD_, C_, NW_)                                                                                       \
-    do {                                                                                                                   \
-        if (pipe)                                                                                                          \
-            attn_varlen_pipe_kernel<HD_, C_, NW_><<<grid, NW_ * 64, 0, kr_hs(s)>>>(q, k, vt, out, qblk, qblk_len, nq_total,     \
-                                                                                   q_heads, group, k_head_stride,          \
-                                                                                   vt_head_stride, sl);                    \
-        else                                                                                                               \
-            attn_varlen_kernel<HD_, C_, NW_><<<grid, NW_ * 64, 0, kr_hs(s)>>>(q, k, vt, out, qblk, qblk_len, nq_total,          \
-                                                                              q_heads, group, k_head_stride,               \
-                                                                              vt_head_stride, sl);                         \
-    } while (0)
-#else
 #define KR_LAUNCH_ATTN(HD_, C_, NW_)                                                                                       \
     attn_varlen_kernel<HD_, C_, NW_><<<grid, NW_ * 64, 0, kr_hs(s)>>>(q, k, vt, out, qblk, qblk_len, nq_total, q_heads, group, \
                                                                       k_head_stride, vt_head_stride, sl)
-#endif
-    static const int q64_default = [] { const char* e = getenv("KARANTA_ATTN_Q64"); return e ? atoi(e) : 0; }();
-    const char* q64e = getenv("KARANTA_ATTN_Q64_NOW");   // tools/attn_microbench.py: same-process A/B
-    const bool q64 = q_block == 256 && (q64e ? atoi(q64e) != 0 : q64_default != 0);
 #define KR_LAUNCH_ATTN_Q(HD_, C_)                                                                                          \
     do {                                                                                                                   \
-        if (q64 && HD_ == 80) /* hd 128: two query blocks' accumulators do not fit 512 registers (spills) */               \
-            attn_varlen_q64_kernel<80, C_><<<grid, 256, 0, kr_hs(s)>>>(q, k, vt, out, qblk, qblk_len, nq_total, q_heads, group,  \
-                                                                       k_head_stride, vt_head_stride, sl);                 \
-        else if (q_block == 256) KR_LAUNCH_ATTN(HD_, C_, 8);                                                               \
+        if (q_block == 256) KR_LAUNCH_ATTN(HD_, C_, 8);                                                                    \
         else KR_LAUNCH_ATTN(HD_, C_, 4);                                                                                   \
     } while (0)
     if (hd == 80) {
@@ -1520,45 +598,4 @@ extern "C" int kr_attn_varlen_q(const kr_bf16* q, const kr_bf16* k, const kr_bf1
                                 int64_t k_head_stride, int64_t vt_head_stride, float scale, int causal, int q_block, kr_stream s) {
     return attn_varlen_impl(q, k, vt, out, qblk, qblk_len, n_qblk, nq_total, q_heads, kv_heads, hd, k_head_stride, vt_head_stride,
                             scale, causal, q_block, s);
-}
-
-extern "C" int kr_kv_append(const kr_bf16* k, const kr_bf16* v, int64_t row_stride, const int32_t* tok_seq,
-                            const int32_t* tok_pos, kr_bf16* kcache, kr_bf16* vtcache, int64_t n, int kv_heads, int hd,
-                            int layer, int batch, int s_max, kr_stream s) {
-    KR_CHECK_ARG(k && v && tok_seq && tok_pos && kcache && vtcache && s_max % 64 == 0, "kr_kv_append: bad args");
-    if (n == 0) return KR_OK;
-    const int64_t total = n * kv_heads * hd;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 8192) grid = 8192;
-    kv_append_kernel<<<grid, 256, 0, kr_hs(s)>>>(k, v, row_stride, tok_seq, tok_pos, kcache, vtcache, n, kv_heads, hd,
-                                                 layer, batch, s_max);
-    KR_CHECK_LAUNCH();
-    return KR_OK;
-}
-
-extern "C" int kr_decode_qkv_prep(const kr_bf16* qkv, const float* inv_freq, const int32_t* ctx_len,
-                                  const int32_t* rope_delta, kr_bf16* q_out, kr_bf16* kcache, kr_bf16* vtcache, int batch,
-                                  int heads, int kv_heads, int hd, int layer, int s_max, kr_stream s) {
-    KR_CHECK_ARG(qkv && inv_freq && ctx_len && rope_delta && q_out && kcache && vtcache, "kr_decode_qkv_prep: null");
-    KR_CHECK_ARG(batch > 0 && s_max % 64 == 0 && hd % 2 == 0, "kr_decode_qkv_prep: bad sizes");
-    decode_qkv_prep_kernel<<<batch, 256, 0, kr_hs(s)>>>(qkv, inv_freq, ctx_len, rope_delta, q_out, kcache, vtcache, heads,
-                                                        kv_heads, hd, layer, batch, s_max);
-    KR_CHECK_LAUNCH();
-    return KR_OK;
-}
-
-extern "C" int kr_attn_decode_gqa(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
-                                  kr_bf16* out, float* workspace, int batch, int heads, int kv_heads, int hd, int layer,
-                                  int s_max, int n_split, float scale, kr_stream s) {
-    KR_CHECK_ARG(q && kcache && vtcache && ctx_len && out && workspace, "kr_attn_decode_gqa: null pointer");
-    KR_CHECK_ARG(hd == 128, "kr_attn_decode_gqa: hd=%d (only 128)", hd);
-    KR_CHECK_ARG(heads % kv_heads == 0 && heads / kv_heads <= 16, "kr_attn_decode_gqa: GQA group must be <= 16");
-    KR_CHECK_ARG(batch > 0 && n_split > 0 && s_max % 64 == 0, "kr_attn_decode_gqa: bad sizes");
-    dim3 grid(n_split, kv_heads, batch);
-    attn_decode_kernel<128><<<grid, 256, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, workspace, heads, kv_heads, layer,
-                                                        batch, s_max, scale * 1.4426950408889634f);
-    KR_CHECK_LAUNCH();
-    attn_decode_combine_kernel<<<batch * heads, hd, 0, kr_hs(s)>>>(workspace, out, n_split * 4, hd);
-    KR_CHECK_LAUNCH();
-    return KR_OK;
 }

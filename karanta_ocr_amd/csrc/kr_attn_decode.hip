@@ -4,6 +4,7 @@
 //                        workgroup of each (sequence, kv head) is an experiment build (-DKR_EXPERIMENTS).
 //   attn_merge_kernel    the merge launch: row-major rows (kr_attn_decode_merge) or the packed XP layout of 17..32-row
 //                        batches (kr_attn_decode_merge32).
+// The closing section holds the first-generation decode operators, which the engine does not launch.
 #include "kr_decode_common.h"
 
 namespace {
@@ -392,4 +393,244 @@ extern "C" int kr_attn_decode_merge(const float* workspace, kr_bf16* out, int ba
 extern "C" int kr_attn_decode_merge32(const float* workspace, kr_bf16* out_xp, int batch, int heads, int hd, int n_split,
                                       kr_stream s) {
     return merge_impl(workspace, out_xp, batch, heads, hd, n_split, 1, s);
+}
+
+// =====================================================================================
+// First-generation decode operators: kr_decode_qkv_prep, kr_attn_decode_gqa, kr_kv_append
+// =====================================================================================
+// The engine does not launch any of these: its decode step rotates and appends in the qkv linear's epilogue (kr_decode.hip)
+// and attends with attn_decode2_kernel above.  They stay exported and tested as standalone operators.
+namespace {
+
+// =====================================================================================
+// decode: rotary + KV append for one new token per sequence
+// =====================================================================================
+__global__ void __launch_bounds__(256) decode_qkv_prep_kernel(const kr_bf16* __restrict__ qkv,
+                                                              const float* __restrict__ inv_freq,
+                                                              const int32_t* __restrict__ ctx_len,
+                                                              const int32_t* __restrict__ rope_delta,
+                                                              kr_bf16* __restrict__ q_out, kr_bf16* __restrict__ kcache,
+                                                              kr_bf16* __restrict__ vtcache, int heads, int kv_heads,
+                                                              int hd, int layer, int batch, int s_max) {
+    const int b = blockIdx.x;
+    const int pos = ctx_len[b];
+    const float rp = (float)(pos + rope_delta[b]);
+    const int half = hd >> 1;
+    const int qkv_dim = (heads + 2 * kv_heads) * hd;
+    const kr_bf16* row = qkv + (int64_t)b * qkv_dim;
+    const int64_t kv_base = ((int64_t)layer * batch + b) * kv_heads;
+    // rotary on q heads and k heads: one thread per (head, i < hd/2)
+    for (int e = threadIdx.x; e < (heads + kv_heads) * half; e += blockDim.x) {
+        const int h = e / half, i = e - h * half;
+        const float ang = rp * inv_freq[i];
+        // HF casts cos/sin to the activation dtype (TF:modeling_qwen2_vl.py:169)
+        const float c = bfround(cosf(ang)), s = bfround(sinf(ang));
+        const float x0 = bfbits2f(row[h * hd + i]), x1 = bfbits2f(row[h * hd + i + half]);
+        const __bf16 y0 = f2bf(x0 * c - x1 * s), y1 = f2bf(x1 * c + x0 * s);
+        kr_bf16* dst;
+        if (h < heads) {
+            dst = q_out + ((int64_t)b * heads + h) * hd;
+        } else {
+            dst = kcache + ((kv_base + (h - heads)) * s_max + pos) * hd;
+        }
+        dst[i] = __builtin_bit_cast(kr_bf16, y0);
+        dst[i + half] = __builtin_bit_cast(kr_bf16, y1);
+    }
+    // V -> transposed cache column
+    const kr_bf16* vrow = row + (heads + kv_heads) * hd;
+    for (int e = threadIdx.x; e < kv_heads * hd; e += blockDim.x) {
+        const int h = e / hd, d = e - h * hd;
+        vtcache[((kv_base + h) * (s_max >> 6) + (pos >> 6)) * (hd * 64) + kr_vt_off(d, pos & 63, hd)] = vrow[e];
+    }
+}
+
+// =====================================================================================
+// decode attention, v_mfma_f32_16x16x32_bf16, K and V^T straight from HBM to registers
+// =====================================================================================
+// grid = (n_split, kv_heads, batch), 4 waves per block; wave `part` = split*4 + wave walks the
+// 64-key blocks part, part + n_part, ...  Heads of the GQA group sit on the 16 MFMA columns.
+//   S[key][g]   : A = K rows (keys permuted so that lane group fg ends up with keys 8fg..8fg+7)
+//                 B = Q^T
+//   O^T[d][g]  += A = V^T (16 B = 8 consecutive keys per lane), B = P^T (the S accumulators)
+// Partials (m, l, O) go to the fp32 workspace; attn_decode_combine_kernel merges them.
+template <int HD>
+__global__ void __launch_bounds__(256) attn_decode_kernel(const kr_bf16* __restrict__ q, const kr_bf16* __restrict__ kcache,
+                                                          const kr_bf16* __restrict__ vtcache,
+                                                          const int32_t* __restrict__ ctx_len, float* __restrict__ ws,
+                                                          int heads, int kv_heads, int layer, int batch, int s_max,
+                                                          float scale_log2e) {
+    constexpr int DT = HD / 16;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fr = lane & 15, fg = lane >> 4;
+    const int kvh = blockIdx.y, b = blockIdx.z;
+    const int group = heads / kv_heads;
+    const int n_part = gridDim.x * 4;
+    const int part = blockIdx.x * 4 + wave;
+    const int ctx = ctx_len[b] + 1;
+    const int nb = (ctx + 63) >> 6;
+
+    const int g = fr < group ? fr : 0;
+    const kr_bf16* qp = q + ((int64_t)b * heads + kvh * group + g) * HD + fg * 32;
+    bf16x8 qf[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) qf[i] = ld8(qp + i * 8);
+
+    const int64_t kv_base = ((int64_t)layer * batch + b) * kv_heads + kvh;
+    const kr_bf16* kc = kcache + kv_base * s_max * HD;
+    const kr_bf16* vc = vtcache + kv_base * (int64_t)(s_max >> 6) * (HD * 64);
+
+    f32x4 o[DT];
+#pragma unroll
+    for (int t = 0; t < DT; ++t) o[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float m_run = -1e30f, l_run = 0.f;
+
+    for (int blk = part; blk < nb; blk += n_part) {
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+            const int key0 = blk * 64 + hf * 32;
+            if (key0 >= ctx) break;  // wave-uniform
+            // K fragments: tile kt, row r holds key 8(r>>2) + 4kt + (r&3)
+            bf16x8 kf[2][4];
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+                const kr_bf16* kp = kc + (int64_t)(key0 + 8 * (fr >> 2) + 4 * kt + (fr & 3)) * HD + fg * 32;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) kf[kt][i] = ld8_nt(kp + i * 8);
+            }
+            // V^T fragments: row d = dt*16 + fr, keys key0 + 8fg .. +7
+            bf16x8 vf[DT];
+            const kr_bf16* vp = vc + (int64_t)blk * (HD * 64) + hf * (HD * 32) + fg * 8;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) vf[dt] = ld8_nt(vp + (dt * 16 + fr) * 32);
+
+            f32x4 s[2];
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+                s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][i], qf[i], s[kt], 0, 0, 0);
+            }
+            float mx = -INFINITY;
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int key = key0 + 8 * fg + 4 * kt + r;
+                    const float v = key < ctx ? s[kt][r] * scale_log2e : -INFINITY;
+                    s[kt][r] = v;
+                    mx = fmaxf(mx, v);
+                }
+            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float m_new = fmaxf(m_run, mx);
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+            m_run = m_new;
+            bf16x8 pf;
+            float psum = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const __bf16 pb = f2bf(__builtin_amdgcn_exp2f(s[kt][r] - m_new));
+                    psum += bf2f(pb);
+                    pf[kt * 4 + r] = pb;
+                }
+            l_run = l_run * alpha + psum;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt], pf, o[dt], 0, 0, 0);
+            }
+        }
+    }
+    // l: sum the four key groups of each head column
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
+    if (fr < group) {
+        float* w = ws + (((int64_t)b * heads + kvh * group + fr) * n_part + part) * (HD + 2);
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4*>(w + dt * 16 + fg * 4) = o[dt];
+        if (fg == 0) {
+            w[HD] = m_run;
+            w[HD + 1] = l_run;
+        }
+    }
+}
+
+// grid = batch*heads blocks of HD threads
+__global__ void attn_decode_combine_kernel(const float* __restrict__ ws, kr_bf16* __restrict__ out, int n_part, int hd) {
+    const int bh = blockIdx.x, d = threadIdx.x;
+    const float* w = ws + (int64_t)bh * n_part * (hd + 2);
+    float mx = -1e30f;
+    for (int p = 0; p < n_part; ++p) mx = fmaxf(mx, w[p * (hd + 2) + hd]);
+    float acc = 0.f, l = 0.f;
+    for (int p = 0; p < n_part; ++p) {
+        const float sc = __builtin_amdgcn_exp2f(w[p * (hd + 2) + hd] - mx);
+        l += w[p * (hd + 2) + hd + 1] * sc;
+        acc += w[p * (hd + 2) + d] * sc;
+    }
+    out[(int64_t)bh * hd + d] = __builtin_bit_cast(kr_bf16, f2bf(l > 0.f ? acc / l : 0.f));
+}
+
+// scattered K / V^T append (standalone operator; the engine uses the blocked prep kernels)
+__global__ void __launch_bounds__(256) kv_append_kernel(const kr_bf16* __restrict__ k, const kr_bf16* __restrict__ v,
+                                                        int64_t row_stride, const int32_t* __restrict__ tok_seq,
+                                                        const int32_t* __restrict__ tok_pos, kr_bf16* __restrict__ kcache,
+                                                        kr_bf16* __restrict__ vtcache, int64_t n, int kv_heads, int hd,
+                                                        int layer, int batch, int s_max) {
+    const int64_t total = n * kv_heads * hd;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int d = (int)(i % hd);
+        const int64_t t = i / hd;
+        const int h = (int)(t % kv_heads);
+        const int64_t tok = t / kv_heads;
+        const int sq = tok_seq[tok], pos = tok_pos[tok];
+        const int64_t base = ((int64_t)layer * batch + sq) * kv_heads + h;
+        kcache[(base * s_max + pos) * hd + d] = k[tok * row_stride + h * hd + d];
+        vtcache[(base * (s_max >> 6) + (pos >> 6)) * (hd * 64) + kr_vt_off(d, pos & 63, hd)] = v[tok * row_stride + h * hd + d];
+    }
+}
+
+}  // namespace
+
+extern "C" int kr_kv_append(const kr_bf16* k, const kr_bf16* v, int64_t row_stride, const int32_t* tok_seq,
+                            const int32_t* tok_pos, kr_bf16* kcache, kr_bf16* vtcache, int64_t n, int kv_heads, int hd,
+                            int layer, int batch, int s_max, kr_stream s) {
+    KR_CHECK_ARG(k && v && tok_seq && tok_pos && kcache && vtcache && s_max % 64 == 0, "kr_kv_append: bad args");
+    if (n == 0) return KR_OK;
+    const int64_t total = n * kv_heads * hd;
+    int grid = (int)((total + 255) / 256);
+    if (grid > 8192) grid = 8192;
+    kv_append_kernel<<<grid, 256, 0, kr_hs(s)>>>(k, v, row_stride, tok_seq, tok_pos, kcache, vtcache, n, kv_heads, hd,
+                                                 layer, batch, s_max);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_decode_qkv_prep(const kr_bf16* qkv, const float* inv_freq, const int32_t* ctx_len,
+                                  const int32_t* rope_delta, kr_bf16* q_out, kr_bf16* kcache, kr_bf16* vtcache, int batch,
+                                  int heads, int kv_heads, int hd, int layer, int s_max, kr_stream s) {
+    KR_CHECK_ARG(qkv && inv_freq && ctx_len && rope_delta && q_out && kcache && vtcache, "kr_decode_qkv_prep: null");
+    KR_CHECK_ARG(batch > 0 && s_max % 64 == 0 && hd % 2 == 0, "kr_decode_qkv_prep: bad sizes");
+    decode_qkv_prep_kernel<<<batch, 256, 0, kr_hs(s)>>>(qkv, inv_freq, ctx_len, rope_delta, q_out, kcache, vtcache, heads,
+                                                        kv_heads, hd, layer, batch, s_max);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_attn_decode_gqa(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
+                                  kr_bf16* out, float* workspace, int batch, int heads, int kv_heads, int hd, int layer,
+                                  int s_max, int n_split, float scale, kr_stream s) {
+    KR_CHECK_ARG(q && kcache && vtcache && ctx_len && out && workspace, "kr_attn_decode_gqa: null pointer");
+    KR_CHECK_ARG(hd == 128, "kr_attn_decode_gqa: hd=%d (only 128)", hd);
+    KR_CHECK_ARG(heads % kv_heads == 0 && heads / kv_heads <= 16, "kr_attn_decode_gqa: GQA group must be <= 16");
+    KR_CHECK_ARG(batch > 0 && n_split > 0 && s_max % 64 == 0, "kr_attn_decode_gqa: bad sizes");
+    dim3 grid(n_split, kv_heads, batch);
+    attn_decode_kernel<128><<<grid, 256, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, workspace, heads, kv_heads, layer,
+                                                        batch, s_max, scale * 1.4426950408889634f);
+    KR_CHECK_LAUNCH();
+    attn_decode_combine_kernel<<<batch * heads, hd, 0, kr_hs(s)>>>(workspace, out, n_split * 4, hd);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
 }

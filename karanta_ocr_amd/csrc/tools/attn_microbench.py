@@ -43,28 +43,7 @@ def run(lens, H, KVH, hd, causal, q_block, reps=10):
         ms = C.c_float(); L.kr_event_elapsed_ms(e0, e1, C.byref(ms))
         best = min(best, ms.value / reps)
     flops = sum(4.0 * x * x * hd * H * (0.5 if causal else 1.0) for x in lens)
-    stamps(q_block)
     return best, flops / best / 1e9, o
-
-
-SEGMENTS = ("K reads", "QK^T + max", "exp + PV", "tile -> LDS", "barrier", "load issue")
-
-
-def stamps(q_block):
-    """Diagnostic builds only (tools/build_variant.py ... -DKR_ATTN_STAMPS, KARANTA_HIP_LIB=...): cycles per tile and per
-    segment of the middle workgroup's waves.  SHARES are what to read, not totals: the stamps fence overlaps."""
-    try:
-        fn = C.CDLL(os.environ["KARANTA_HIP_LIB"]).kr_attn_debug_read
-    except (KeyError, AttributeError, OSError):
-        return
-    buf = (C.c_ulonglong * 64)()
-    if fn(buf) != 0:
-        return
-    for w in range(q_block // 32):
-        nt = max(1, buf[w * 8 + 6])
-        seg = [buf[w * 8 + i] / nt for i in range(6)]
-        print(f"      wave {w}: {nt} tiles, s_memtime ticks / tile  " + "  ".join(f"{n} {v:.0f}" for n, v in zip(SEGMENTS, seg))
-              + f"  sum {sum(seg):.0f}", flush=True)
 
 
 def run_prep(lens, H, KVH, hd, reps=10):
@@ -109,13 +88,8 @@ if __name__ == "__main__":
                                               "prefill 8 x 1394, 12/2 heads x 128 causal": ([1394] * 8, 12, 2, 128, True),
                                               "vit 1 x 19276": ([19276], 16, 16, 80, False)}.items():
         outs = {}
-        for qb in (128, 256, "256 (4 waves x 64 queries)"):
-            # r4: the one-wave-per-SIMD form of the 256-query workgroup (hd 80 only; KARANTA_ATTN_Q64_NOW is read per call)
-            os.environ["KARANTA_ATTN_Q64_NOW"] = "1" if isinstance(qb, str) else "0"
-            if isinstance(qb, str) and hd != 80:
-                continue
-            ms, tf, o = run(lens, H, KVH, hd, causal, 256 if isinstance(qb, str) else qb)
+        for qb in (128, 256):
+            ms, tf, o = run(lens, H, KVH, hd, causal, qb)
             outs[qb] = o
             print(f"{name:45s} q_block {qb}: {ms:8.3f} ms  {tf:7.1f} TFLOP/s", flush=True)
-        os.environ["KARANTA_ATTN_Q64_NOW"] = "0"
         print("    max |diff| between the block sizes:", max(float((outs[128].float() - o.float()).abs().max()) for o in outs.values()), flush=True)

@@ -1,6 +1,6 @@
 """Build a VARIANT of libkaranta_hip.so with extra -D switches on one or more sources, for same-box A/B measurements.
 
-    python karanta_ocr_amd/csrc/tools/build_variant.py NAME kr_attention.hip '-DKR_ATTN_VPRE(HD)=0' ...
+    python karanta_ocr_amd/csrc/tools/build_variant.py NAME kr_attn_decode.hip -DKR_ATTN_DEC_LD=ld8 ...
     python karanta_ocr_amd/csrc/tools/build_variant.py exp kr_decode.hip,kr_attn_decode.hip,kr_selftest.hip -DKR_EXPERIMENTS
         (the decode experiments of rounds 1-2 and their entry points, include/karanta_hip_experiments.h; every source that
         reads KR_EXP, csrc/kr_decode_common.h, has to be named)

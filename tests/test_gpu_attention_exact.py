@@ -65,43 +65,40 @@ def run_varlen(L, case, plan, causal, k_hs, vt_hs, what):
     AP.check_output(host(o), case, what)
 
 
-def run_vit(L, lens, pattern, q_block, monkeypatch):
-    """"4x64": the 256-query workgroup as 4 waves x 64 queries (attn_varlen_q64_kernel)."""
-    monkeypatch.setenv("KARANTA_ATTN_Q64_NOW", "1" if q_block == "4x64" else "0")
+def run_vit(L, lens, pattern, q_block):
     case = cached(("vit", tuple(lens), pattern), lambda: AP.vit_case(lens, pattern))
     k_row0 = np.concatenate([[0], np.cumsum(lens)[:-1]])
     vt_blk0 = np.concatenate([[0], np.cumsum([(x + 63) // 64 for x in lens])[:-1]])
-    plan = POS.make_attn_plan(lens, k_row0, vt_blk0, False, q_block=256 if q_block == "4x64" else q_block)
+    plan = POS.make_attn_plan(lens, k_row0, vt_blk0, False, q_block=q_block)
     n = sum(lens)
     assert case.k.shape == (4, n, 80) and case.vt.shape == (4, plan.n_vt_blocks, 80, 64)
     run_varlen(L, case, plan, False, n * 80, plan.n_vt_blocks * 80 * 64, f"vit {lens} {pattern} q_block={q_block}")
 
 
-@pytest.mark.parametrize("q_block", [128, 256, "4x64"])
+@pytest.mark.parametrize("q_block", [128, 256])
 @pytest.mark.parametrize("pattern", AP.vit_patterns(AP.VIT_LENS["ragged"]))
-def test_vit_hd80_ragged_segments_return_the_winning_key(L, pattern, q_block, monkeypatch):
+def test_vit_hd80_ragged_segments_return_the_winning_key(L, pattern, q_block):
     """Segments of 1 .. 300 keys stored back to back: with `up` the first K row of the next segment outranks a segment's
     last key, with `down` the previous segment's last row outranks its first; the tents put the winner on and beside
     every 32- and 64-key border."""
-    run_vit(L, AP.VIT_LENS["ragged"], pattern, q_block, monkeypatch)
+    run_vit(L, AP.VIT_LENS["ragged"], pattern, q_block)
 
 
-@pytest.mark.parametrize("q_block", [128, 256, "4x64"])
+@pytest.mark.parametrize("q_block", [128, 256])
 @pytest.mark.parametrize("pattern", AP.vit_patterns(AP.VIT_LENS["windows"]))
-def test_vit_hd80_window_segments_return_the_winning_key(L, pattern, q_block, monkeypatch):
+def test_vit_hd80_window_segments_return_the_winning_key(L, pattern, q_block):
     """The segment lengths of Qwen2.5-VL's windows (64 and the ragged ones at the right / bottom edge)."""
-    run_vit(L, AP.VIT_LENS["windows"], pattern, q_block, monkeypatch)
+    run_vit(L, AP.VIT_LENS["windows"], pattern, q_block)
 
 
-@pytest.mark.parametrize("q_block", [128, 256, "4x64"])
+@pytest.mark.parametrize("q_block", [128, 256])
 @pytest.mark.parametrize("pattern", ["up", "down"])
-def test_vit_hd80_long_segment(L, pattern, q_block, monkeypatch):
+def test_vit_hd80_long_segment(L, pattern, q_block):
     """22 KV tiles: `up` moves the lazy reference maximum in every tile, `down` never after the first."""
-    run_vit(L, AP.VIT_LONG, pattern, q_block, monkeypatch)
+    run_vit(L, AP.VIT_LONG, pattern, q_block)
 
 
-def run_prefill(L, lens, H, KVH, s_max, q_block, monkeypatch):
-    monkeypatch.setenv("KARANTA_ATTN_Q64_NOW", "0")
+def run_prefill(L, lens, H, KVH, s_max, q_block):
     case = cached(("prefill", tuple(lens), H, KVH, s_max), lambda: AP.prefill_case(lens, H, KVH, s_max))
     B = len(lens)
     plan = POS.prefill_attn_plan(lens, list(range(B)), KVH, s_max)
@@ -114,17 +111,17 @@ def run_prefill(L, lens, H, KVH, s_max, q_block, monkeypatch):
 
 @pytest.mark.parametrize("q_block", [128, 256])
 @pytest.mark.parametrize("H,KVH", AP.PREFILL_HEADS)
-def test_prefill_hd128_every_query_checks_its_own_mask_edge(L, H, KVH, q_block, monkeypatch):
+def test_prefill_hd128_every_query_checks_its_own_mask_edge(L, H, KVH, q_block):
     """Even kv heads: each of the 723 queries must return its own diagonal key although the next key (masked only by
     causality) and the stale cache rows past the prompt outrank it — across tile (64), wave (32) and query-block borders.
     Odd kv heads: key 0 wins for every query."""
-    run_prefill(L, AP.PREFILL_LENS, H, KVH, AP.PREFILL_S_MAX, q_block, monkeypatch)
+    run_prefill(L, AP.PREFILL_LENS, H, KVH, AP.PREFILL_S_MAX, q_block)
 
 
 @pytest.mark.parametrize("q_block", [128, 256])
-def test_prefill_hd128_long_prompt(L, q_block, monkeypatch):
+def test_prefill_hd128_long_prompt(L, q_block):
     H, KVH = AP.PREFILL_LONG_HEADS
-    run_prefill(L, AP.PREFILL_LONG, H, KVH, AP.PREFILL_LONG_S_MAX, q_block, monkeypatch)
+    run_prefill(L, AP.PREFILL_LONG, H, KVH, AP.PREFILL_LONG_S_MAX, q_block)
 
 
 # ----------------------------------------------------------------------------- decode: split-KV partials and their merges

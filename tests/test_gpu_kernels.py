@@ -656,12 +656,10 @@ def run_prep_attn(L, lens, H, KVH, hd, causal, seed, as_cache=False, s_max=256, 
     assert_close_bf16(host(o), ref, rel=2 ** -6, abs_=2e-2, what="attention out")
 
 
-@pytest.mark.parametrize("q_block", [128, 256, "4x64"])
+@pytest.mark.parametrize("q_block", [128, 256])
 @pytest.mark.parametrize("lens", [[24], [64], [130, 5, 200], [129], [1, 63, 65], [257, 300], [4900]])
-def test_vit_attention_hd80(L, lens, q_block, monkeypatch):
-    """"4x64": the 256-query workgroup as 4 waves x 64 queries (attn_varlen_q64_kernel, one wave per SIMD)."""
-    monkeypatch.setenv("KARANTA_ATTN_Q64_NOW", "1" if q_block == "4x64" else "0")
-    run_prep_attn(L, lens, H=4, KVH=4, hd=80, causal=False, seed=sum(lens), q_block=256 if q_block == "4x64" else q_block)
+def test_vit_attention_hd80(L, lens, q_block):
+    run_prep_attn(L, lens, H=4, KVH=4, hd=80, causal=False, seed=sum(lens), q_block=q_block)
 
 
 @pytest.mark.parametrize("lens", [[4900], [4920, 1408]])
