@@ -39,7 +39,7 @@ typedef uint16_t kr_bf16;
 /* kr_version() of the library this header describes: major * 100 + minor.  The major changes with every incompatible
  * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family); a caller built
  * against major X must refuse a library whose kr_version() / 100 != X. */
-#define KR_ABI_VERSION 406
+#define KR_ABI_VERSION 407
 
 #define KR_OK 0
 #define KR_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -706,6 +706,42 @@ int kr_spec_deal(const kr_spec* a, const int32_t* n_want, int32_t* draft_row, kr
  * else as there.  proposed += n_draft: the drafts that were dealt a row. */
 int kr_spec_accept_rows(const kr_spec* a, const int32_t* draft_row, const float* amax_val, const int32_t* amax_idx, int n_part,
                         int32_t* tokens_out, const int32_t* eos, int n_eos, int ignore_eos, kr_stream s);
+
+/* Guided slots in a speculative step.  A draft row needs the DFA state its token is chosen under; the state at draft depth j is the
+ * slot's state walked over drafts 1..j.  Three launches of integer work (one workgroup or less per slot) around the step; the
+ * launches between them are unchanged, and kr_gumbel_argmax_guided reads the per-row entries written here.  The per-row arrays hold
+ * `rows` entries; entries 0..slots-1 are the caller's (the slots' own guides and states) and only kr_spec_guide_advance writes them. */
+typedef struct kr_spec_guide {
+    uint64_t* guide_trans;             /* [rows] device address of the row's DFA table [S][256] uint16 (0: unconstrained) */
+    uint64_t* guide_masks;             /* [rows] address of the pattern's mask table (kr_guide_build_masks) */
+    int32_t* guide_state;              /* [rows] DFA state the row's token is chosen under */
+    int32_t mask_words;                /* even, mask_words * 32 >= kr_spec.vocab */
+    const int32_t* vocab_off;          /* as kr_guide_advance: [vocab + 1] */
+    const uint8_t* vocab_bytes;
+    int32_t* draft_state;              /* [slots][k] scratch: the state after drafts 1..j */
+    int32_t* ctx_before;               /* [slots] scratch: ctx_len at the start of the step */
+} kr_spec_guide;
+
+/* Before any row is spent on a draft.  n_count: kr_spec_propose's n_draft (static layout: after kr_spec_propose) or kr_spec_lookup's
+ * n_want (shared rows: between kr_spec_lookup and kr_spec_deal, so a forbidden draft is not dealt a row another slot could use).
+ * Per slot: ctx_before = ctx_len, always.  A finished slot, or one with guide_trans == 0, keeps its count and its drafts.  Otherwise,
+ * from st = guide_state[slot], for j = 1..n_count: draft j is kept iff its bit is set in mask row st (the bit
+ * kr_gumbel_argmax_guided tests); the first draft that is not cuts the count to j - 1; a kept draft moves st = walk(st, bytes(draft))
+ * and draft_state[slot][j - 1] = st; a kept draft without bytes (an EOS id in an accepting state) cuts the count to j: nothing follows
+ * an EOS.  draft_tok at and beyond the new count becomes pad_id. */
+int kr_spec_guide_trim(const kr_spec* a, const kr_spec_guide* g, int32_t* n_count, kr_stream s);
+
+/* After the trim (static layout, draft_row == NULL: draft j of a slot on row j * slots + slot) or after kr_spec_deal (draft_row: its
+ * map, -1 entries belong to nobody).  Every row r >= slots: the row of draft (slot, j) with j <= n_draft[slot] of a guided slot gets
+ * the slot's guide_trans and guide_masks and guide_state = draft_state[slot][j - 1]; every other row (inactive, parked, padding, of an
+ * unguided slot) gets zeros in all three.  Static layout only: a row (slot, j) with j > n_draft[slot] also gets finished = 1, because
+ * kr_spec_propose ran before the trim. */
+int kr_spec_guide_rows(const kr_spec* a, const kr_spec_guide* g, const int32_t* draft_row, kr_stream s);
+
+/* After kr_spec_accept / kr_spec_accept_rows.  Per slot with guide_trans != 0: guide_state is walked over the e = ctx_len - ctx_before
+ * tokens the step emitted (read from `history`), except the last one where the step set finished (kr_guide_advance skips the rows
+ * kr_sample_greedy has just finished): the state e plain guided steps leave. */
+int kr_spec_guide_advance(const kr_spec* a, const kr_spec_guide* g, kr_stream s);
 
 /* kr_linear_decode32, KR_DEC_ROPE_KV only, for the rows of a speculative step: the cache base and the cs_table row of row r come
  * from row_slot[r]; the cache position and the rotary index from the row's own ctx_len / prompt_len entries.  q_out stays per row.

@@ -101,6 +101,9 @@ SIGNATURES = {
     "kr_spec_lookup": [c_p, c_p, c_p],
     "kr_spec_deal": [c_p, c_p, c_p, c_p],
     "kr_spec_accept_rows": [c_p, c_p, c_p, c_p, i32, c_p, c_p, i32, i32, c_p],
+    "kr_spec_guide_trim": [c_p, c_p, c_p, c_p],
+    "kr_spec_guide_rows": [c_p, c_p, c_p, c_p],
+    "kr_spec_guide_advance": [c_p, c_p, c_p],
     "kr_linear_decode32_rows": [i32, c_p, c_p, c_p],
     "kr_attn_decode_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
     "kr_comm_unique_id": [c_p],
@@ -160,7 +163,13 @@ class Spec(C.Structure):
                 ("proposed", c_p), ("accepted", c_p)]
 
 
-FORK_MAX_GROUPS = FORK_MAX_SLOTS = 32    # KR_FORK_MAX_GROUPS / KR_FORK_MAX_SLOTS
+class SpecGuide(C.Structure):
+    """kr_spec_guide (include/karanta_hip.h): the guides of a speculative step's rows and the scratch of its three launches."""
+    _fields_ = [("guide_trans", c_p), ("guide_masks", c_p), ("guide_state", c_p), ("mask_words", C.c_int32), ("vocab_off", c_p),
+                ("vocab_bytes", c_p), ("draft_state", c_p), ("ctx_before", c_p)]
+
+
+FORK_MAX_GROUPS = FORK_MAX_SLOTS = 32   # KR_FORK_MAX_GROUPS / KR_FORK_MAX_SLOTS
 
 
 class ForkGroup(C.Structure):

@@ -209,13 +209,14 @@ def main(argv=None):
     ap.add_argument("--keep", action="store_true", help="--gpus: keep the written checkpoint / logs")
     ap.add_argument("--speculative-config", default=None,
                     help="the server's flag (cli.py), passed through: JSON with method \"ngram\"; --slots x (K + 1) <= 32, or "
-                         "\"share_rows\": true and up to 31 slots")
+                         "\"share_rows\": true and up to 31 slots; \"guided\": true lets the guided requests speculate")
     args = ap.parse_args(argv)
     spec = None
     if args.speculative_config:
-        from .cli import speculative_fields
+        from .cli import speculative_fields, speculative_guided
         try:
-            spec = speculative_fields(args.speculative_config, args.slots)      # SpecConfig's fields, share_rows among them
+            # SpecConfig's fields, share_rows and guided among them
+            spec = (*speculative_fields(args.speculative_config, args.slots), speculative_guided(args.speculative_config))
         except ValueError as e:
             ap.error(str(e))
     if args.gpus is not None:

@@ -75,7 +75,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="vLLM's flag, as JSON: {\"method\": \"ngram\", \"num_speculative_tokens\": K, \"prompt_lookup_min\": 2, "
                          "\"prompt_lookup_max\": 4} — prompt-lookup drafts verified K at a time, the same tokens as without it "
                          "(--max-num-seqs x (K + 1) <= 32, or with \"share_rows\": true any --max-num-seqs up to 31: the rows of a "
-                         "step the sequences leave free are dealt to the drafts; not with --max-logprobs or --static-batching)")
+                         "step the sequences leave free are dealt to the drafts; with \"guided\": true requests with guided_regex / "
+                         "response_format speculate too, their drafts checked against the pattern; not with --max-logprobs or "
+                         "--static-batching)")
     return ap
 
 
@@ -120,6 +122,21 @@ def speculative_fields(text: str, max_num_seqs: int):
     return k, lo, hi, share
 
 
+def speculative_guided(text: str) -> bool:
+    """SpecConfig.guided from --speculative-config: the key "guided", true or false (absent: false); ValueError with the reason."""
+    import json
+    try:
+        d = json.loads(text)
+    except ValueError as e:
+        raise ValueError(f"--speculative-config is not JSON: {e}") from e
+    if not isinstance(d, dict):
+        raise ValueError("--speculative-config must be a JSON object")
+    guided = d.get("guided", False)
+    if not isinstance(guided, bool):
+        raise ValueError(f"--speculative-config: guided must be true or false, not {guided!r}")
+    return guided
+
+
 def parse_args(argv: Optional[List[str]] = None):
     ap = build_parser()
     args, unknown = ap.parse_known_args(argv)
@@ -140,7 +157,7 @@ def parse_args(argv: Optional[List[str]] = None):
         ap.error("--max-num-seqs must be in 1..32 (above 16: hidden_size <= 2048 or == 3584)")
     if args.max_num_batched_tokens is not None and args.max_num_batched_tokens < args.max_model_len:
         ap.error("--max-num-batched-tokens must be >= --max-model-len (the longest prompt one request may carry)")
-    args.speculative, args.speculative_share_rows = None, False
+    args.speculative, args.speculative_share_rows, args.speculative_guided = None, False, False
     if args.speculative_config is not None:
         if args.max_logprobs is not None:
             ap.error("--speculative-config cannot be combined with --max-logprobs: a draft row records no log-probabilities")
@@ -149,6 +166,7 @@ def parse_args(argv: Optional[List[str]] = None):
         try:
             *spec, args.speculative_share_rows = speculative_fields(args.speculative_config, args.max_num_seqs)
             args.speculative = tuple(spec)
+            args.speculative_guided = speculative_guided(args.speculative_config)
         except ValueError as e:
             ap.error(str(e))
     args.model_dir = model
@@ -229,15 +247,17 @@ def make_server(args, log=print):
     # cache rows per slot: the model length + the steps a slot may run past its limit before the scheduler looks (2 chunks of up to 8
     # with launch-ahead) + the parking row
     spec, share = getattr(args, "speculative", None), bool(getattr(args, "speculative_share_rows", False))
+    spec_guided = bool(getattr(args, "speculative_guided", False))
     if spec is not None:
         log(f"speculative decoding: ngram, {spec[0]} draft tokens per step, prompt lookup {spec[1]}..{spec[2]}"
-            + (", draft rows shared between the sequences" if share else ""))
+            + (", draft rows shared between the sequences" if share else "")
+            + (", guided requests included" if spec_guided else ""))
     # ... speculative: every step past the limit may emit K + 1 tokens, and the draft rows write K cache rows ahead
     slack = 1 + 16 * (spec[0] + 1 if spec else 1) + (spec[0] if spec else 0)
     eng = Engine(cfg, device="cuda:0", max_batch=args.max_num_seqs, s_max=(args.max_model_len + slack + 63) // 64 * 64,
                  max_patches=max_patches, max_prompt_tokens=max_prompt_tokens,
                  weight_dtype=weight_dtype, fp8_activations=bool(getattr(args, "fp8_activations", False)) or None,
-                 **({"speculative": SpecConfig(*spec, share_rows=share)} if spec else {}))
+                 **({"speculative": SpecConfig(*spec, share_rows=share, guided=spec_guided)} if spec else {}))
     # one server: read the checkpoint.  A launch.py group: rank 0 reads it ONCE, the arena goes to the other GPUs over
     # RCCL / xGMI (north_star: "RCCL broadcast of weights over xGMI"); a failure stops every server of the group
     info = load_or_receive_weights(eng.w, rank, world, lambda: eng.load_weights(load_checkpoint(args.model_dir)[1]),

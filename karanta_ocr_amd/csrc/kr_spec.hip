@@ -11,6 +11,8 @@
 //   spec_deal_kernel     ONE workgroup: rows slots .. rows - 1 breadth first (depth 1 of every slot in slot order, then depth 2, ...)
 //                        and the row state of each; a row nobody got is parked like a padding row.
 //   spec_accept_kernel   with a map: draft j of a slot is verified on row draft_row[slot * k + j - 1].
+// Guided slots (kr_spec_guide_trim -> kr_spec_guide_rows -> ... -> kr_spec_guide_advance, around either layout): the drafts a slot's
+// guide forbids are dropped, every draft row gets the DFA state behind its drafts, the slot's state follows the emitted tokens.
 #include "kr_decode_common.h"
 #include "kr_spec_deal.h"
 
@@ -280,7 +282,160 @@ int spec_check(const kr_spec* a, const char* who, bool shared_rows = false) {
     return KR_OK;
 }
 
+// ---------------------------------------------------------------- guided slots in a speculative step (kr_spec_guide)
+// A guide's DFA state per draft: the state at depth j is the slot's state walked over drafts 1..j.  Integer work only.
+//   spec_guide_trim_kernel     per slot, before any row is spent: the drafts are kept while the guide allows them (the bit
+//                              kr_gumbel_argmax_guided tests); the state behind every kept draft goes to draft_state.
+//   spec_guide_rows_kernel     ONE workgroup: the guide entries of every row behind the slots' own.
+//   spec_guide_advance_kernel  per slot, after the verification: the slot's state walked over the tokens the step emitted.
+constexpr int GUIDE_STAGE = 32;     // bytes of a token held in LDS; a longer token's tail is read from the table
+
+// The tokens of one slot's walk, staged by the lanes: their byte ranges and first bytes (len -1: a token outside the vocabulary).
+struct GuideStage {
+    int tok[SPEC_MAX_ROWS], off[SPEC_MAX_ROWS], len[SPEC_MAX_ROWS];
+    uint8_t bytes[SPEC_MAX_ROWS][GUIDE_STAGE];
+};
+
+__device__ __forceinline__ void guide_stage(GuideStage& s, int q, int t, int vocab, const int32_t* __restrict__ vocab_off,
+                                            const uint8_t* __restrict__ vocab_bytes) {
+    s.tok[q] = t;
+    if (t < 0 || t >= vocab) {
+        s.off[q] = 0;
+        s.len[q] = -1;
+        return;
+    }
+    const int o0 = vocab_off[t], n = max(0, vocab_off[t + 1] - o0);
+    s.off[q] = o0;
+    s.len[q] = n;
+    for (int i = 0; i < min(n, GUIDE_STAGE); ++i) s.bytes[q][i] = vocab_bytes[o0 + i];
+}
+
+// walk(st, bytes(token q)): kr_guide_advance's loop
+__device__ __forceinline__ unsigned guide_walk(const GuideStage& s, int q, unsigned st, const uint16_t* __restrict__ trans,
+                                               const uint8_t* __restrict__ vocab_bytes) {
+    for (int i = 0; i < s.len[q] && st != 0; ++i) {
+        const unsigned byte = i < GUIDE_STAGE ? s.bytes[q][i] : vocab_bytes[s.off[q] + i];
+        st = trans[st * 256u + byte];
+    }
+    return st;
+}
+
+__global__ void __launch_bounds__(64) spec_guide_trim_kernel(const kr_spec a, const kr_spec_guide g, int32_t* __restrict__ n_count) {
+    __shared__ GuideStage s;
+    const int slot = blockIdx.x, tid = threadIdx.x, K = a.k;
+    if (tid == 0) g.ctx_before[slot] = a.ctx_len[slot];
+    const uint64_t tp = g.guide_trans[slot];
+    if (tp == 0 || a.finished[slot]) return;          // (uniform per workgroup) the slot keeps its count and its drafts
+    const int n = max(0, min(K, n_count[slot]));
+    if (tid < n) guide_stage(s, tid, a.draft_tok[slot * K + tid], a.vocab, g.vocab_off, g.vocab_bytes);
+    __syncthreads();
+    if (tid != 0) return;
+    const uint16_t* trans = reinterpret_cast<const uint16_t*>(tp);
+    const uint32_t* masks = reinterpret_cast<const uint32_t*>(g.guide_masks[slot]);
+    unsigned st = (unsigned)g.guide_state[slot];
+    int keep = n;
+    for (int j = 0; j < n; ++j) {
+        const int t = s.tok[j];
+        const bool ok = s.len[j] >= 0 && masks != nullptr && ((masks[(int64_t)st * g.mask_words + (t >> 5)] >> (t & 31)) & 1u) != 0;
+        if (!ok) {          // the guide forbids draft j + 1 in the state behind draft j
+            keep = j;
+            break;
+        }
+        st = guide_walk(s, j, st, trans, g.vocab_bytes);
+        g.draft_state[slot * K + j] = (int)st;
+        if (s.len[j] == 0) {      // allowed without bytes: an EOS in an accepting state, and nothing follows an EOS
+            keep = j + 1;
+            break;
+        }
+    }
+    n_count[slot] = keep;
+    for (int j = keep; j < K; ++j) a.draft_tok[slot * K + j] = a.pad_id;
+}
+
+// draft_row == nullptr: the static layout (draft j of a slot on row j * slots + slot); else the map kr_spec_deal wrote.  As in
+// spec_deal_kernel every global write is indexed by a row taken from the loop: s_owner[r] says whose row r is, or nobody's.
+__global__ void __launch_bounds__(64) spec_guide_rows_kernel(const kr_spec a, const kr_spec_guide g, const int32_t* __restrict__ draft_row) {
+    __shared__ int s_owner[SPEC_MAX_ROWS];
+    const int tid = threadIdx.x, B = a.slots, K = a.k, R = a.rows;
+    if (tid < SPEC_MAX_ROWS) {
+        int e = -1;
+        if (draft_row == nullptr && tid >= B && tid < B * (K + 1)) e = (tid % B) * K + tid / B - 1;
+        s_owner[tid] = e;
+    }
+    __syncthreads();
+    if (draft_row != nullptr)
+        for (int e = tid; e < B * K; e += 64) {
+            const int r = draft_row[e];
+            if (r >= B && r < R) s_owner[r] = e;       // (rows are distinct: one writer per entry)
+        }
+    __syncthreads();
+    const int r = B + tid;
+    if (r >= R) return;
+    const int e = s_owner[r];
+    const int slot = e < 0 ? 0 : e / K, j = e < 0 ? 0 : e - slot * K + 1;
+    const bool live = e >= 0 && j <= a.n_draft[slot];
+    const uint64_t tp = live ? g.guide_trans[slot] : 0ull;
+    g.guide_trans[r] = tp;
+    g.guide_masks[r] = tp != 0 ? g.guide_masks[slot] : 0ull;
+    g.guide_state[r] = tp != 0 ? g.draft_state[slot * K + j - 1] : 0;
+    if (draft_row == nullptr && e >= 0 && !live) a.finished[r] = 1;     // kr_spec_propose ran before the trim
+}
+
+__global__ void __launch_bounds__(64) spec_guide_advance_kernel(const kr_spec a, const kr_spec_guide g) {
+    __shared__ GuideStage s;
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    const uint64_t tp = g.guide_trans[slot];
+    if (tp == 0) return;                              // (uniform per workgroup)
+    const int before = g.ctx_before[slot], plen = a.prompt_len[slot];
+    const int e = max(0, min(a.k + 1, a.ctx_len[slot] - before));
+    // a step that finished the slot: its last token is not walked (kr_guide_advance skips the rows kr_sample_greedy has just finished)
+    const int n = e > 0 && a.finished[slot] ? e - 1 : e;
+    if (tid < n) {
+        const int h = before + 1 - plen + tid;
+        guide_stage(s, tid, h >= 0 && h < a.hist_rows ? a.history[(int64_t)h * a.hist_stride + slot] : -1, a.vocab, g.vocab_off,
+                    g.vocab_bytes);
+    }
+    __syncthreads();
+    if (tid != 0 || n == 0) return;
+    const uint16_t* trans = reinterpret_cast<const uint16_t*>(tp);
+    unsigned st = (unsigned)g.guide_state[slot];
+    for (int i = 0; i < n; ++i) st = guide_walk(s, i, st, trans, g.vocab_bytes);      // (len -1: the state stays, as in kr_guide_advance)
+    g.guide_state[slot] = (int)st;
+}
+
+int spec_guide_check(const kr_spec* a, const kr_spec_guide* g, const char* who, bool shared_rows) {
+    if (const int rc = spec_check(a, who, shared_rows)) return rc;
+    KR_CHECK_ARG(g, "%s: null guide args", who);
+    KR_CHECK_ARG(g->guide_trans && g->guide_masks && g->guide_state && g->vocab_off && g->vocab_bytes && g->draft_state && g->ctx_before,
+                 "%s: null pointer in kr_spec_guide", who);
+    KR_CHECK_ARG(g->mask_words > 0 && g->mask_words % 2 == 0 && (int64_t)g->mask_words * 32 >= a->vocab,
+                 "%s: mask_words=%d must be even and cover the vocabulary", who, g->mask_words);
+    return KR_OK;
+}
+
 }  // namespace
+
+extern "C" int kr_spec_guide_trim(const kr_spec* a, const kr_spec_guide* g, int32_t* n_count, kr_stream s) {
+    if (const int rc = spec_guide_check(a, g, "kr_spec_guide_trim", true)) return rc;
+    KR_CHECK_ARG(n_count, "kr_spec_guide_trim: null n_count");
+    spec_guide_trim_kernel<<<a->slots, 64, 0, kr_hs(s)>>>(*a, *g, n_count);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_spec_guide_rows(const kr_spec* a, const kr_spec_guide* g, const int32_t* draft_row, kr_stream s) {
+    if (const int rc = spec_guide_check(a, g, "kr_spec_guide_rows", draft_row != nullptr)) return rc;
+    spec_guide_rows_kernel<<<1, 64, 0, kr_hs(s)>>>(*a, *g, draft_row);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_spec_guide_advance(const kr_spec* a, const kr_spec_guide* g, kr_stream s) {
+    if (const int rc = spec_guide_check(a, g, "kr_spec_guide_advance", true)) return rc;
+    spec_guide_advance_kernel<<<a->slots, 64, 0, kr_hs(s)>>>(*a, *g);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
 
 extern "C" int kr_spec_propose(const kr_spec* a, kr_stream s) {
     if (const int rc = spec_check(a, "kr_spec_propose")) return rc;

@@ -20,6 +20,13 @@ Random weights (timing only), context about 1900, graphs replayed as the engine 
     this tree's own plain step stands in and the file says so), in alternating child processes; t_spec / t_plain and
     break_even_accepted_per_slot_step, at full acceptance and with every first draft wrong.
 
+    python karanta_ocr_amd/csrc/tools/spec_bench.py --guided [--parent-tree DIR] [--out profiles/r07_spec_guided.json]
+
+  * --guided: the leg for SpecConfig(guided=True): 8 slots x K = 3 at the 2B decoder, every slot under a guide that forbids half of the
+    vocabulary, scripted full-acceptance drafts; the guided speculative step (three launches more: kr_spec_guide_trim / _rows /
+    _advance) over the guided plain step of the PARENT commit (--parent-tree; without it this tree's own guided plain step stands in
+    and the file says so), in alternating child processes, and the same engine's unguided pair beside it.
+
 Every measurement is a child process under a time limit of its own; a child that fails ends the run."""
 import argparse
 import ctypes as C
@@ -32,14 +39,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.a
 CTX, STEPS, ROUNDS = 1900, 48, 5
 
 
-def _engine(model, B, spec_k=0, share=False):
+GUIDE = r"[a-z]+"
+
+
+def _token_bytes(i: int) -> bytes:
+    """A synthetic token table for the guided leg: even ids spell lower-case letters (GUIDE allows them in every state), odd ids
+    digits (it never does) — the mask is half set."""
+    base = 97 if i % 2 == 0 else 48
+    return bytes(base + (i // 10 ** p) % 10 for p in range(3))
+
+
+def _engine(model, B, spec_k=0, share=False, guided=False):
     import torch
     from karanta_ocr_amd.config import CONFIGS
     from karanta_ocr_amd.engine import Engine
     kw = {}
     if spec_k:
         from karanta_ocr_amd.engine import SpecConfig
-        kw["speculative"] = SpecConfig(spec_k, share_rows=True) if share else SpecConfig(spec_k)
+        kw["speculative"] = (SpecConfig(spec_k, share_rows=share, guided=True) if guided
+                             else SpecConfig(spec_k, share_rows=True) if share else SpecConfig(spec_k))
     n_new = STEPS * (ROUNDS + 3) * (spec_k + 1) + 16
     eng = Engine(CONFIGS[model], max_batch=B, s_max=(CTX + n_new + 128) // 64 * 64, max_patches=64, max_prompt_tokens=64, **kw)
     eng.w.allocate()
@@ -51,7 +69,26 @@ def _engine(model, B, spec_k=0, share=False):
     # the state of a server's decode steps without the chance of an EOS: frozen-slot semantics, EOS ignored
     eng._enter_mode(n_new, ignore_eos=True, freeze_finished=True, want_logits=False, caps=eng._caps, step=eng._step, logprobs=None)
     eng._x0 = (torch.randn(B, eng.cfg.text.hidden_size, device=eng.device) * 0.5).to(torch.bfloat16)
+    eng._guide = None
     return eng
+
+
+def _guide_slots(eng, on=True):
+    """Every slot under GUIDE (compiled once), or none: the steps carry the masked Gumbel pass and the DFA advance, or neither."""
+    from karanta_ocr_amd.sampling import StepFeatures
+    B, sm = eng.B, eng.sampler
+    if on and eng._guide is None:
+        V = eng.cfg.text.vocab_size
+        table = [_token_bytes(i) for i in range(V)]
+        for e in eng.cfg.eos_token_ids:
+            table[int(e)] = b""
+        eng.set_vocab(table)
+        eng._guide = eng.compile_guide(GUIDE)
+    eng.stream.synchronize()
+    eng._caps = eng._step = StepFeatures(True, True, False, False) if on else StepFeatures()
+    sm.d_gtrans[:B].fill_(eng._guide.trans.data_ptr() if on else 0)
+    sm.d_gmasks[:B].fill_(eng._guide.masks.data_ptr() if on else 0)
+    _reset(eng)
 
 
 def _reset(eng):
@@ -61,6 +98,8 @@ def _reset(eng):
         eng.d_plen.fill_(CTX)
         eng.d_fin.zero_()
         eng.d_x[:eng.B].copy_(eng._x0)
+        if getattr(eng, "_guide", None) is not None:
+            eng.sampler.d_gstate[:eng.B].fill_(eng._guide.start)
     eng.stream.synchronize()
 
 
@@ -209,6 +248,78 @@ def child_spec(model, B, K, share=False):
     return out
 
 
+def _all_allowed(eng, toks) -> bool:
+    """Every generated token is one GUIDE allows: an even id, or an EOS id (allowed once the pattern matches; the steps ignore it)."""
+    import numpy as np
+    return bool(((toks % 2 == 0) | np.isin(toks, list(eng.cfg.eos_token_ids))).all())
+
+
+def child_guided_plain(model, B):
+    """The guided plain step (every slot under GUIDE): uses nothing the parent commit lacks."""
+    import numpy as np
+    eng = _engine(model, B)
+    _guide_slots(eng)
+    ts = _time(eng, _plain_graph(eng))
+    eng.stream.synchronize()
+    gen = eng.d_hist[1:STEPS, :B].cpu().numpy()
+    out = {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "rounds_ms": [round(t, 5) for t in ts],
+           "tokens_all_allowed": _all_allowed(eng, gen)}
+    eng.close()
+    return out
+
+
+def _full_acceptance_pair(eng, K):
+    """The plain step and the speculative step at scripted full acceptance, with the passes the engine's steps carry now."""
+    import numpy as np
+    import torch
+    L, B = eng.L, eng.B
+    g_plain = _plain_graph(eng)
+    t_plain = _time(eng, g_plain)
+    n_truth = STEPS * (K + 1) + K + 4
+    _reset(eng)
+    for _ in range(n_truth):
+        L.kr_graph_launch(g_plain, eng.s)
+    eng.stream.synchronize()
+    truth = eng.d_hist[:n_truth + 1].cpu().numpy().copy()
+    _reset(eng)
+    with torch.cuda.stream(eng.stream):
+        eng._spec_step_launches()
+        eng.stream.synchronize()
+        g_spec = eng._graph_for(B, True)
+    for b in range(B):
+        eng.set_draft_script(b, truth[:, b])
+    count0 = [None]
+
+    def before():
+        count0[0] = eng.d_spec_count.cpu().numpy().astype(np.int64).copy()
+    ts = _time(eng, g_spec, before=before)
+    eng.stream.synchronize()
+    d = eng.d_spec_count.cpu().numpy().astype(np.int64) - count0[0]
+    gen = (eng.d_ctx.cpu().numpy() + 1 - eng.d_plen.cpu().numpy()).astype(np.int64)
+    got = eng.d_hist[:int(gen.min()), :B].cpu().numpy()
+    for b in range(B):
+        eng.set_draft_script(b, None)
+    return {"plain_ms": float(np.median(t_plain)), "spec_ms": float(np.median(ts)), "spec_min_ms": float(min(ts)),
+            "ratio": float(np.median(ts)) / float(np.median(t_plain)),
+            "accepted_per_slot_step": float(d[1].sum()) / (B * STEPS), "proposed_per_slot_step": float(d[0].sum()) / (B * STEPS),
+            "tokens_equal_plain": bool((got[1:] == truth[1:len(got)]).all()), "tokens": truth[1:STEPS]}
+
+
+def child_guided(model, B, K):
+    """SpecConfig(guided=True): the same engine's unguided pair (plain step, speculative step), then the guided pair."""
+    eng = _engine(model, B, K, guided=True)
+    out = {"model": model, "slots": B, "K": K, "rows": eng.rows, "ctx": CTX, "guide": GUIDE}
+    for name, on in (("unguided", False), ("guided", True)):
+        _guide_slots(eng, on)
+        r = _full_acceptance_pair(eng, K)
+        toks = r.pop("tokens")
+        if on:
+            r["tokens_all_allowed"] = _all_allowed(eng, toks)
+        out[name] = r
+    eng.close()
+    return out
+
+
 def run_child(args, tree, limit, sizes=None):
     """This file as a child process with `tree`'s package on the path (the child imports karanta_ocr_amd from its working directory).
     sizes: the plain child's batch sizes, for a tree whose engine this file's --sizes is to drive."""
@@ -254,6 +365,43 @@ def main_shared(a):
     return 0
 
 
+def main_guided(a):
+    """8 slots x K = 3, every slot guided, against the parent commit's guided plain step, alternating child processes."""
+    import numpy as np
+    B, K = 8, 3
+    report = {"context": CTX, "steps_per_round": STEPS, "rounds": ROUNDS, "weights": "random bf16 (timing only)", "slots": B, "K": K,
+              "guide": GUIDE}
+
+    def save():
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(report, f, indent=1)
+            f.write("\n")
+    child = ["--child", "guided-plain", "--slots", str(B)]
+    runs = {"this": [], "parent": []}
+    for _ in range(a.repeats):
+        runs["this"].append(run_child(child, ROOT, 240))
+        if a.parent_tree:
+            runs["parent"].append(run_child(child, os.path.abspath(a.parent_tree), 240))
+    mine, theirs = [r["median_ms"] for r in runs["this"]], [r["median_ms"] for r in runs["parent"]]
+    report["guided_plain_step"] = {"this_tree_ms": mine, "parent_ms": theirs, "aa_spread_ms": max(mine) - min(mine),
+                                   "t_plain_from": "parent commit" if theirs else "THIS tree (no --parent-tree given)",
+                                   "t_plain_ms": float(np.median(theirs or mine)),
+                                   "tokens_all_allowed": all(r["tokens_all_allowed"] for r in runs["this"] + runs["parent"])}
+    save()
+    spec = run_child(["--child", "guided", "--model", "Qwen2-VL-2B", "--slots", str(B), "--k", str(K)], ROOT, 420)
+    report["spec"] = spec
+    report["t_spec_guided_ms"] = spec["guided"]["spec_ms"]
+    report["t_spec_over_t_plain_guided"] = spec["guided"]["spec_ms"] / report["guided_plain_step"]["t_plain_ms"]
+    report["break_even_accepted_per_slot_step"] = report["t_spec_over_t_plain_guided"] - 1
+    report["t_spec_over_t_plain_unguided_same_engine"] = spec["unguided"]["ratio"]
+    report["guided_spec_step_minus_unguided_spec_step_ms"] = spec["guided"]["spec_ms"] - spec["unguided"]["spec_ms"]
+    report["guided_plain_step_minus_unguided_plain_step_ms"] = spec["guided"]["plain_ms"] - spec["unguided"]["plain_ms"]
+    save()
+    print(json.dumps(report, indent=1))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", default=None)
@@ -264,6 +412,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--skip-7b", action="store_true")
     ap.add_argument("--shared", action="store_true", help="the shared-rows leg alone: 24 slots x K = 3 (profiles/r06_spec_shared_rows.json)")
+    ap.add_argument("--guided", action="store_true", help="the guided leg alone: 8 slots x K = 3, every slot under a guide "
+                                                          "(profiles/r07_spec_guided.json)")
     ap.add_argument("--share", action="store_true", help="(child) SpecConfig(share_rows=True)")
     ap.add_argument("--sizes", default="8,32", help="(child plain) the batch sizes")
     ap.add_argument("--out", default=None)
@@ -271,11 +421,16 @@ def main():
     if a.child:
         sys.path.insert(0, os.getcwd())
         res = (child_plain(a.model, [int(x) for x in a.sizes.split(",")]) if a.child == "plain"
+               else child_guided_plain(a.model, a.slots) if a.child == "guided-plain"
+               else child_guided(a.model, a.slots, a.k) if a.child == "guided"
                else child_spec(a.model, a.slots, a.k, a.share))
         print(json.dumps(res), flush=True)
         return 0
     import numpy as np
-    a.out = a.out or os.path.join(ROOT, "profiles", "r06_spec_shared_rows.json" if a.shared else "r05_spec_decode.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r07_spec_guided.json" if a.guided else
+                                  "r06_spec_shared_rows.json" if a.shared else "r05_spec_decode.json")
+    if a.guided:
+        return main_guided(a)
     if a.shared:
         return main_shared(a)
     report = {"context": CTX, "steps_per_round": STEPS, "rounds": ROUNDS, "weights": "random bf16 (timing only)"}

@@ -109,6 +109,8 @@ class Engine:
         self.K = int(speculative.num_tokens) if speculative is not None else 0
         self.rows = speculative.rows(max_batch) if speculative is not None else max_batch
         self.share_rows = speculative is not None and bool(speculative.share_rows)
+        # guided steps speculate too (SpecConfig.guided); the slot scheduler reads this before it asks for a speculative chunk
+        self.spec_guided = speculative is not None and bool(speculative.guided)
         self.spec_steps = self.plain_steps = 0
         self._snap_counts = None
         self.s_max = _align(s_max, 64)
@@ -808,15 +810,20 @@ class Engine:
 
     def _spec_refusal(self) -> Optional[str]:
         """Why the next steps cannot be speculative (None: they can).  A draft row sees the logits of its own position only: the
-        passes that carry state from token to token (a guide's DFA, the penalties' counts, min_tokens) or record per step
-        (log-probabilities) would need that state per draft."""
+        passes that carry state from token to token (the penalties' counts, min_tokens) or record per step (log-probabilities)
+        would need that state per draft.  A guide's DFA state is had per draft (kr_spec_guide_*) where the engine was built with
+        SpecConfig(guided=True)."""
         step = self._step
         if self.spec is None:
             return "the engine was built without speculative=SpecConfig(...)"
         if not self._freeze_finished:
             return "speculative steps run in slot mode (begin_slots)"
-        if step.guided or step.processing or step.adjust:
-            return "the step carries guided decoding, sampling controls or logit adjustments"
+        if self.spec_guided:
+            if step.processing or step.adjust:
+                return "the step carries sampling controls or logit adjustments"
+        elif step.guided or step.processing or step.adjust:
+            return ("the step carries guided decoding, sampling controls or logit adjustments"
+                    + (" (guided requests speculate on an engine built with SpecConfig(guided=True))" if step.guided else ""))
         if self._logprobs is not None:
             return "log-probabilities are recorded"
         return None
@@ -827,17 +834,30 @@ class Engine:
         the history and d_fin in the form a plain step leaves them, so the two kinds alternate freely.
         share_rows: the drafts are looked up (kr_spec_lookup), the rows behind the slots dealt to them (kr_spec_deal) and the
         verification reads each draft at the row it was dealt (kr_spec_accept_rows); everything between is the same launches —
-        they take the row-to-slot map as it comes."""
+        they take the row-to-slot map as it comes.
+        A step that carries guided requests (SpecConfig(guided=True)) has three launches more: the drafts a slot's guide forbids are
+        dropped before any row is spent on them (kr_spec_guide_trim: behind kr_spec_propose, or between kr_spec_lookup and
+        kr_spec_deal), every draft row gets the guide and the DFA state behind its drafts (kr_spec_guide_rows) for the masked Gumbel
+        pass, and the slots' states follow the tokens the verification emitted (kr_spec_guide_advance).  An unguided step issues
+        none of them."""
         L, s, R = self.L, self.s, self.rows
         why = self._spec_refusal()
         if why is not None:
             raise KarantaHipError("speculative decode step refused: " + why)
         a = self._spec_args()
+        g = self.sampler.spec_guide_args() if self._step.guided else None
         if self.share_rows:
             L.kr_spec_lookup(C.byref(a), ptr(self.d_nwant), s)
+            if g is not None:
+                L.kr_spec_guide_trim(C.byref(a), C.byref(g), ptr(self.d_nwant), s)
             L.kr_spec_deal(C.byref(a), ptr(self.d_nwant), ptr(self.d_draft_row), s)
+            if g is not None:
+                L.kr_spec_guide_rows(C.byref(a), C.byref(g), ptr(self.d_draft_row), s)
         else:
             L.kr_spec_propose(C.byref(a), s)
+            if g is not None:
+                L.kr_spec_guide_trim(C.byref(a), C.byref(g), ptr(self.d_ndraft), s)
+                L.kr_spec_guide_rows(C.byref(a), C.byref(g), None, s)
         x = self._layer_launches(R, self.d_row_slot)
         logits, n_part = self._lm_head(R, x)
         flags = self._flags()
@@ -848,6 +868,8 @@ class Engine:
         else:
             L.kr_spec_accept(C.byref(a), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(self.d_tok), ptr(self.d_eos),
                              self.d_eos.numel(), flags, s)
+        if g is not None:
+            L.kr_spec_guide_advance(C.byref(a), C.byref(g), s)
 
     def set_draft_script(self, slot: int, tokens: Optional[Sequence[int]]):
         """Test hook: the drafts of `slot` come from a scripted continuation — draft j of a step is tokens[generated + j - 1] —
@@ -1247,9 +1269,9 @@ class Engine:
 
     def decode_steps(self, n: int, speculative: bool = False):
         """n decode steps over all slots (asynchronous on the engine's stream).  speculative=True: speculative steps (every slot
-        advances by 1 .. K + 1 tokens per step, the same tokens as plain steps give); raises where the steps carry guided decoding,
-        sampling controls or logit adjustments, or record log-probabilities.  While an admission is in flight on a CU-masked
-        stream the captured graph replays on the complementary compute units (same kernels, same grids: the same tokens), ordered
+        advances by 1 .. K + 1 tokens per step, the same tokens as plain steps give); raises where the steps carry guided decoding
+        (without SpecConfig(guided=True)), sampling controls or logit adjustments, or record log-probabilities.  While an admission
+        is in flight on a CU-masked stream the captured graph replays on the complementary compute units (same kernels, same grids: the same tokens), ordered
         against the engine's stream by events on both sides."""
         spec = bool(speculative)
         if spec:

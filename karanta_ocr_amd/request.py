@@ -76,11 +76,15 @@ class SpecConfig:
     row (kr_spec_propose / kr_spec_accept).  The tokens are those of the plain steps, whatever the temperature.
     share_rows: instead of num_tokens rows owned by every slot (max_batch x (num_tokens + 1) <= 32), the rows of a step that the slots
     do not take themselves are dealt per step to the slots whose lookup found drafts (kr_spec_lookup / kr_spec_deal /
-    kr_spec_accept_rows): any max_batch up to 31."""
+    kr_spec_accept_rows): any max_batch up to 31.
+    guided: steps that carry guided requests speculate too — the drafts of a guided slot are kept while its guide allows them and
+    every draft row is masked with the DFA state behind its drafts (kr_spec_guide_trim / kr_spec_guide_rows /
+    kr_spec_guide_advance).  Off, such steps are plain steps, as before the option existed."""
     num_tokens: int = 3
     ngram_min: int = 2
     ngram_max: int = 4
     share_rows: bool = False
+    guided: bool = False
 
     def rows(self, max_batch: int) -> int:
         """Rows of a speculative step: never fewer than 17 (the packed 17..32-row family)."""
@@ -93,6 +97,8 @@ class SpecConfig:
             raise KarantaHipError(f"speculative: num_tokens {k!r} must be an integer >= 1")
         if not 1 <= int(self.ngram_min) <= int(self.ngram_max) <= 8:
             raise KarantaHipError(f"speculative: 1 <= ngram_min {self.ngram_min} <= ngram_max {self.ngram_max} <= 8")
+        if not isinstance(self.guided, (bool, np.bool_)):
+            raise KarantaHipError(f"speculative: guided {self.guided!r} must be True or False")
         if self.share_rows:
             if k > 31:
                 raise KarantaHipError(f"speculative: num_tokens {k} > 31, the draft rows a 32-row decode step can hold")

@@ -11,7 +11,7 @@ from typing import Dict, Sequence
 import numpy as np
 import torch
 
-from ._lib import ADJ_CAP, KarantaHipError, ptr
+from ._lib import ADJ_CAP, KarantaHipError, SpecGuide, ptr
 from .request import PageRequest
 from .sampling import StepFeatures, adjust_table, needs_processing, sampling_params, temperature
 
@@ -30,10 +30,18 @@ class Sampler:
         self.eng, self.cfg, self.device, self.L = eng, eng.cfg, eng.device, eng.L
         t, dev, B = self.cfg.text, self.device, eng.B
         z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
-        # guided decoding: per slot the device addresses of its pattern's tables (0 = unconstrained) + its DFA state
-        self.d_gtrans = z(B, dtype=torch.int64)
-        self.d_gmasks = z(B, dtype=torch.int64)
-        self.d_gstate = z(B, dtype=torch.int32)
+        # guided decoding: per slot the device addresses of its pattern's tables (0 = unconstrained) + its DFA state.  An engine that
+        # speculates on guided steps (SpecConfig(guided=True)) keeps them per ROW, the slots' entries in front: kr_spec_guide_rows
+        # writes those of a speculative step's draft rows behind them, and admissions, reset_slots and plain steps stay per slot
+        spec = getattr(eng, "spec", None)
+        self.spec_guided = spec is not None and bool(spec.guided)
+        G = max(B, eng.rows) if self.spec_guided else B
+        self.d_gtrans = z(G, dtype=torch.int64)
+        self.d_gmasks = z(G, dtype=torch.int64)
+        self.d_gstate = z(G, dtype=torch.int32)
+        if self.spec_guided:    # kr_spec_guide's scratch: the state behind every draft, ctx_len at the start of the step
+            self.d_draft_state = z(B, eng.K, dtype=torch.int32)
+            self.d_ctx_before = z(B, dtype=torch.int32)
         self.mask_words = 2 * ((t.vocab_size + 63) // 64)
         # sampling controls: per-slot params (sampling_params), output-token counts, prompt-token bit set, the threshold pass's
         # scratch scores, threshold keys and live flags (kr_sample_threshold / kr_gumbel_argmax_processed / kr_sample_count)
@@ -216,6 +224,11 @@ class Sampler:
                 continue
             for dst, rows in zip((self.d_adj_ids, self.d_adj_val, self.d_adj_flag, self.d_adj_meta), tab):
                 h2d(dst[j], rows)
+
+    def spec_guide_args(self) -> SpecGuide:
+        """kr_spec_guide of the engine's guided speculative step (read during the call)."""
+        return SpecGuide(ptr(self.d_gtrans), ptr(self.d_gmasks), ptr(self.d_gstate), self.mask_words, ptr(self.d_voc_off),
+                         ptr(self.d_voc_bytes), ptr(self.d_draft_state), ptr(self.d_ctx_before))
 
     # ------------------------------------------------------------------ the step's tail around the token choice
     def _adj(self, j):
