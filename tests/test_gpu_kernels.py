@@ -1,9 +1,11 @@
 """Parity of every HIP kernel against numpy restatements, through the C-ABI (ctypes), on a real
 MI355X.  Integer-valued inputs make the MFMA paths bit-exact (any layout slip fails exactly);
 random inputs use a stated bf16 tolerance.  The attention tests here run N(0,1) q, k, v — a flat softmax, where one key
-among thousands moves the output by less than the tolerance: they check the arithmetic (and, in the decode tests, that
-finite stale cache rows past the context change nothing); masks, row offsets and trip counts are checked to the key by
-test_gpu_attention_exact.py."""
+among thousands moves the output by less than the tolerance, and the outputs themselves are of the size of its absolute
+term: they check the arithmetic coarsely (and, in the decode tests, that finite stale cache rows past the context change
+nothing); masks, row offsets and trip counts are checked to the key by test_gpu_attention_exact.py, and the softmax
+arithmetic — denominator, lazy rescale, accumulation over tiles, merges — is bounded per element, from the kernels' rounding
+points, by test_gpu_attention_arith.py."""
 import ctypes as C
 import math
 
