@@ -588,7 +588,7 @@ int kr_guide_advance(const int32_t* tokens, const int32_t* finished, const uint6
  * probable token (ties: lowest id), j < k <= 20, rows strided by hist_batch * (1 + k_stride) / hist_batch * k_stride;
  * h = ctx_len[b] - prompt_len[b] as left by kr_sample_greedy (the token-history index); rows with finished[b] != 0
  * record nothing.  part_val / part_idx [batch][n_part][k] and part_ms [batch][n_part][2] are scratch;
- * ceil(vocab / n_part) <= 4096. */
+ * ceil(vocab / n_part) <= 4096, n_part <= 1024 and n_part * max(k, 1) * 8 <= 159 KiB (the merge's candidate table in LDS). */
 int kr_logprobs_topk(const float* logits, int64_t ld_logits, int vocab, int k, int n_part, float* part_val,
                      int32_t* part_idx, float* part_ms, const int32_t* tokens, const int32_t* ctx_len,
                      const int32_t* prompt_len, const int32_t* finished, float* out_lp, int32_t* out_idx, int hist_len,

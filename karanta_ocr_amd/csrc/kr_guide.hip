@@ -65,6 +65,7 @@ __global__ void __launch_bounds__(64) guide_advance_kernel(const int32_t* __rest
 // ---------------------------------------------------------------- log-probabilities
 constexpr int LP_MAX_K = 20;       // OpenAI's top_logprobs bound
 constexpr int LP_SLICE = 4096;     // floats of one vocabulary slice held in LDS
+constexpr size_t LP_MERGE_LDS = 160 * 1024 - 1024;   // largest candidate table of the merge (bytes of dynamic LDS)
 
 __device__ __forceinline__ void block_argmax(float& bv, int& bi, float* s_v, int* s_i) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -216,10 +217,17 @@ extern "C" int kr_logprobs_topk(const float* logits, int64_t ld_logits, int voca
     KR_CHECK_ARG(k >= 0 && k <= LP_MAX_K && k <= k_stride, "kr_logprobs_topk: k must be in 0..%d and <= k_stride", LP_MAX_K);
     KR_CHECK_ARG(n_part > 0 && n_part <= 1024 && (vocab + n_part - 1) / n_part <= LP_SLICE,
                  "kr_logprobs_topk: a vocabulary slice (vocab / n_part) must fit %d floats", LP_SLICE);
+    // the merge's candidate table (n_part * k values and ids) next to its 48 static bytes: checked before anything is launched,
+    // and the kernel's dynamic-LDS limit (64 KiB by default) raised to what the check accepts
+    const size_t lds = (size_t)n_part * (k > 0 ? k : 1) * 8;
+    KR_CHECK_ARG(lds <= LP_MERGE_LDS, "kr_logprobs_topk: n_part * k candidates exceed the LDS");
+    static KrPerDeviceOnce attr;
+    if (attr.need()) {
+        KR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&logprob_merge_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)LP_MERGE_LDS));
+    }
     logprob_partial_kernel<<<dim3(n_part, batch), 256, 0, kr_hs(s)>>>(logits, ld_logits, vocab, k, part_val, part_idx, part_ms);
     KR_CHECK_LAUNCH();
-    const size_t lds = (size_t)n_part * (k > 0 ? k : 1) * 8;
-    KR_CHECK_ARG(lds <= 160 * 1024 - 1024, "kr_logprobs_topk: n_part * k candidates exceed the LDS");
     logprob_merge_kernel<<<batch, 256, lds, kr_hs(s)>>>(part_val, part_idx, part_ms, n_part, k, logits, ld_logits, vocab, tokens, ctx_len,
                                                         prompt_len, finished, out_lp, out_idx, hist_len, hist_batch, k_stride);
     KR_CHECK_LAUNCH();

@@ -24,7 +24,8 @@ def penalise(logits, prompt_ids, out_tokens, vocab, rep=1.0, freq=0.0, pres=0.0)
     if len(prompt_ids):
         hit[np.asarray(prompt_ids, np.int64)] = True
     r = np.float32(rep)
-    l = np.where(hit, np.where(l > 0, l / r, l * r), l).astype(np.float32)
+    with np.errstate(over="ignore"):      # np.where computes both branches: l * r may overflow where it is not taken
+        l = np.where(hit, np.where(l > 0, l / r, l * r), l).astype(np.float32)
     sub = (np.float32(freq) * c.astype(np.float32)).astype(np.float32) + \
           (np.float32(pres) * (c > 0).astype(np.float32)).astype(np.float32)
     return (l - sub.astype(np.float32)).astype(np.float32)
@@ -35,7 +36,9 @@ def tempered(lp, T):
 
 
 def kept_set(v, allowed, top_k=0, top_p=1.0, min_p=0.0, rel=1e-4):
-    """(kept, excused) boolean arrays over the vocabulary for the scores v (fp32) of the allowed tokens."""
+    """(kept, excused) boolean arrays over the vocabulary for the scores v (fp32) of the allowed tokens.
+    The `>=` here compares VALUES, so -0 and +0 are one score; the device compares keys (fkey / kr_fkey), in which -0
+    ranks below +0: a cut at +0 drops the tokens at -0 there.  tests/select_cases.py pins that case to the key."""
     v = np.asarray(v, np.float32)
     keep = np.asarray(allowed, bool).copy()
     exc = np.zeros_like(keep)
