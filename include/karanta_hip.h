@@ -39,7 +39,7 @@ typedef uint16_t kr_bf16;
 /* kr_version() of the library this header describes: major * 100 + minor.  The major changes with every incompatible
  * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family); a caller built
  * against major X must refuse a library whose kr_version() / 100 != X. */
-#define KR_ABI_VERSION 407
+#define KR_ABI_VERSION 408
 
 #define KR_OK 0
 #define KR_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -329,12 +329,17 @@ int kr_linear_decode_wide(int mode, const kr_bf16* x, int64_t ldx, const kr_bf16
  *                     lets layer L's qkv launch zero the slab layer L's down_proj will add into.
  *   part_rows       : the part_in slabs have `part_rows` rows each ([n_part_in][part_rows][K]) instead of M — the launch
  *                     covers a row range of a larger batch whose down_proj wrote the slabs (decode batches above 16 rows
- *                     at the 7B width run the norm-prologue launches once per 16-row range).  0: = M. */
+ *                     at the 7B width run the norm-prologue launches once per 16-row range).  0: = M.
+ *   w_resident != 0 : the launch loads its weights with the default cache policy instead of nontemporal loads, so their
+ *                     lines stay in the 256 MiB Infinity Cache for the next call on the same weights (the other launches'
+ *                     nontemporal streams do not displace them: profiles/r05_ic_residency.txt).  The caller keeps the sum of
+ *                     the weights it marks below the cache size.  Same bytes loaded, same output bits. */
 typedef struct kr_narrow_opts {
     float* zero_ptr;
     uint64_t zero_bytes;
     int32_t atomic_out;
     int32_t part_rows;
+    int32_t w_resident;
 } kr_narrow_opts;
 
 /* Narrow decode linears (qkv, o_proj, down_proj): one workgroup per 16-row tile (ROPE_KV: per rotary tile

@@ -133,15 +133,16 @@ EXPERIMENT_SIGNATURES = {
 
 class NarrowOpts(C.Structure):
     """kr_narrow_opts (include/karanta_hip.h): the explicit per-launch options of kr_linear_decode_narrow*."""
-    _fields_ = [("zero_ptr", c_p), ("zero_bytes", C.c_uint64), ("atomic_out", C.c_int32), ("part_rows", C.c_int32)]
+    _fields_ = [("zero_ptr", c_p), ("zero_bytes", C.c_uint64), ("atomic_out", C.c_int32), ("part_rows", C.c_int32),
+                ("w_resident", C.c_int32)]
 
 
-def narrow_opts(zero_ptr: int = 0, zero_bytes: int = 0, atomic_out: bool = False, part_rows: int = 0):
+def narrow_opts(zero_ptr: int = 0, zero_bytes: int = 0, atomic_out: bool = False, part_rows: int = 0, w_resident: bool = False):
     """A kr_narrow_opts* for one launch (0 = NULL when every field is at its default).  The struct is read during the
     call only, so the temporary may die right after it."""
-    if not (zero_bytes or atomic_out or part_rows):
+    if not (zero_bytes or atomic_out or part_rows or w_resident):
         return None
-    return C.byref(NarrowOpts(zero_ptr or None, int(zero_bytes), 1 if atomic_out else 0, int(part_rows)))
+    return C.byref(NarrowOpts(zero_ptr or None, int(zero_bytes), 1 if atomic_out else 0, int(part_rows), 1 if w_resident else 0))
 
 class Dec32(C.Structure):
     """kr_dec32 (include/karanta_hip.h): the arguments of kr_linear_decode32."""

@@ -70,6 +70,8 @@ struct DecLinArgs {
     // carry a zeroing job for the accumulator the NEXT down_proj will add into
     int part_atomic;
     float* zero_ptr; int zero_n16;
+    // narrow kernel: weight loads with the default cache policy (kr_narrow_opts.w_resident), picked on the host
+    int w_resident;
     // SILU8 output in the XP layout of 17..32-row batches (kr_common.h, kr_xp_byte_offset): the down_proj launch of such a
     // batch (kr_linear_decode32) reads its x fragments as whole cache lines
     int out_xp;
@@ -1061,7 +1063,8 @@ template <> struct NarrowCfg<56> { static constexpr int RL = 7; };
 
 // U = ring depth in 64-wide K chunks: the host picks the smallest instantiated U that covers a wave's share of K
 // (then every chunk is requested up front and at most one request per wave is redundant), else the deepest ring.
-template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8, int MT>
+// RES: the weight loads use the default cache policy instead of the nontemporal one (WChunk::load); nothing else differs.
+template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8, int MT, bool RES>
 __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* hx, const kr_bf16* hwp, const kr_bf16* hnorm_w, const float* hpart_in,
                                                                 int64_t hldx, int hM, int hN, int hK, int hcpb, float hnorm_eps,
                                                                 int hprows, const DecLinArgs a) {
@@ -1170,7 +1173,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
     for (int u = 0; u < U; ++u) {
         const int c = min(max(min(c0 + u, c1 - 1), cb0), nchunks - 1);
 #pragma unroll
-        for (int t = 0; t < NT; ++t) wbuf[u][t].load(wp[t], c);
+        for (int t = 0; t < NT; ++t) wbuf[u][t].template load<RES>(wp[t], c);
     }
     __builtin_amdgcn_sched_barrier(0);
     if (a.zero_ptr) {   // zero the other split-K accumulator (behind this launch's own requests: plain 16-byte stores)
@@ -1350,7 +1353,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
                         }
                     }
 #pragma unroll
-                    for (int t = 0; t < NT; ++t) wbuf[u][t].load(wp[t], cn);
+                    for (int t = 0; t < NT; ++t) wbuf[u][t].template load<RES>(wp[t], cn);
                 }
             }
         }
@@ -1464,13 +1467,13 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
     }
 }
 
-template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8, int MT>
+template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8, int MT, bool RES>
 int launch_narrow_m(DecLinArgs& a, int groups, kr_stream s) {
     const int nchunks = a.K >> 6, cpb = (nchunks + a.ksplit - 1) / a.ksplit;
     const size_t xbytes = NORM ? (((size_t)a.M * (cpb * 128 + 16) + 127) & ~(size_t)127) : 0;
     const size_t lds = xbytes + (size_t)WAVES * NT * 256 * 4;
     KR_CHECK_ARG(lds <= 160 * 1024, "kr_linear_decode_narrow: M=%d K=%d needs %zu bytes of LDS", a.M, a.K, lds);
-    auto fn = &dec_narrow_kernel<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, MT>;
+    auto fn = &dec_narrow_kernel<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, MT, RES>;
     static KrPerDeviceOnce attr;
     if (attr.need()) {
         KR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1484,23 +1487,26 @@ int launch_narrow_m(DecLinArgs& a, int groups, kr_stream s) {
 
 // M > 16: two batch column tiles.  Only on 8-wave workgroups (the x fragments of the direct path double) and not
 // with the K = 3584 row registers; the engine sizes its batches accordingly.
-template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8>
+template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8, bool RES>
 int launch_narrow_w(DecLinArgs& a, int groups, kr_stream s) {
     if (a.M > 16) {
         if constexpr (WAVES == 8 && NCH != 56) {
-            return launch_narrow_m<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, 2>(a, groups, s);
+            return launch_narrow_m<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, 2, RES>(a, groups, s);
         } else {
             kr_set_error("kr_linear_decode_narrow: M=%d > 16 needs 8-wave workgroups and K != 3584", a.M);
             return KR_ERR_ARG;
         }
     }
-    return launch_narrow_m<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, 1>(a, groups, s);
+    return launch_narrow_m<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, 1, RES>(a, groups, s);
 }
 
 template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U>
 int launch_narrow_u(DecLinArgs& a, int groups, kr_stream s) {
-    return a.w_scale ? launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, true>(a, groups, s)
-                     : launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, false>(a, groups, s);
+    if (a.w_resident)
+        return a.w_scale ? launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, true, true>(a, groups, s)
+                         : launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, false, true>(a, groups, s);
+    return a.w_scale ? launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, true, false>(a, groups, s)
+                     : launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, false, false>(a, groups, s);
 }
 
 // chunks of K the busiest wave of a workgroup owns
@@ -1889,6 +1895,7 @@ static int narrow_impl(int mode, const kr_bf16* x, int64_t ldx, const float* par
     a.part_rows = o.part_rows;
     a.n_part = part_in ? n_part_in : 0;
     a.zero_ptr = o.zero_bytes ? o.zero_ptr : nullptr; a.zero_n16 = (int)(o.zero_bytes >> 4); a.part_atomic = o.atomic_out ? 1 : 0;
+    a.w_resident = o.w_resident ? 1 : 0;
     KR_CHECK_ARG(!a.part_atomic || (ksplit == 2 && mode == DEPI_PLAIN), "kr_linear_decode_narrow: atomic_out is for ksplit 2 (order-free sum)");
     KR_CHECK_ARG(a.part_rows == 0 || (part_in && a.part_rows >= M), "kr_linear_decode_narrow: part rows %d < M %d", a.part_rows, M);
     if (KR_EXP && pf_blocks > 0) {   // experiment builds: prefetch workgroups ride on this launch

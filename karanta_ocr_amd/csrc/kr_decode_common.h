@@ -26,13 +26,17 @@ constexpr int DEPI_PARTIAL = 16;  // internal: PLAIN with deferred split-K slabs
 //         (v_cvt_scalef32_pk_bf16_fp8: every e4m3 value is exact in bf16; the per-row scale is applied in the epilogue)
 // x_byte: the operand inside the chunk's 128 B of a row-major x row (<= 16-row kernels); xp_off: inside a column tile's
 // 2 KiB of a packed chunk (XP layout of 17..32-row batches, kr_decode32.hip).
+// load<RES>: the cache policy of the weight loads.  false (every launch but the ones the engine picks): nontemporal, the line is
+// not kept behind the wave that read it; true: default policy, the line stays in the Infinity Cache for the next decode step
+// (the narrow kernel's w_resident launches: DESIGN section 5-r5).  The bytes loaded are the same.
 template <bool W8> struct WChunk;
 template <> struct WChunk<false> {
     static constexpr int BYTES = 2048;
     bf16x8 v[2];
-    __device__ __forceinline__ void load(const char* p, int64_t c) {
-        v[0] = ld8_nt(reinterpret_cast<const kr_bf16*>(p + c * BYTES));
-        v[1] = ld8_nt(reinterpret_cast<const kr_bf16*>(p + c * BYTES + 1024));
+    template <bool RES = false> __device__ __forceinline__ void load(const char* p, int64_t c) {
+        const kr_bf16* q = reinterpret_cast<const kr_bf16*>(p + c * BYTES);
+        v[0] = RES ? ld8(q) : ld8_nt(q);
+        v[1] = RES ? ld8(q + 512) : ld8_nt(q + 512);
     }
     __device__ __forceinline__ bf16x8 frag(int h) const { return v[h]; }
     static __device__ __forceinline__ int x_byte(int h, int fg) { return h * 64 + fg * 16; }
@@ -42,8 +46,9 @@ template <> struct WChunk<false> {
 template <> struct WChunk<true> {
     static constexpr int BYTES = 1024;
     u32x4 q;
-    __device__ __forceinline__ void load(const char* p, int64_t c) {
-        q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + c * BYTES));
+    template <bool RES = false> __device__ __forceinline__ void load(const char* p, int64_t c) {
+        const u32x4* w = reinterpret_cast<const u32x4*>(p + c * BYTES);
+        q = RES ? *w : __builtin_nontemporal_load(w);
     }
     __device__ __forceinline__ bf16x8 frag(int h) const {
         // each conversion yields two bf16 packed in one register; they are moved as 32-bit words (element-wise

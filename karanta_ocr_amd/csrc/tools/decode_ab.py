@@ -4,7 +4,9 @@
         [--rounds 5] variant [variant ...]
 
 A variant is a comma-separated list of Engine attribute overrides, e.g. `base`, `attn_fused_merge=1`,
-`attn_fused_merge=1,n_split=4`.  The weight arena is filled with random bf16 values ON THE DEVICE (timing does not depend
+`attn_fused_merge=1,n_split=4`; `resident=<MB>[:kind@gain+kind@gain]` sets the Infinity-Cache residency budget of the narrow
+launches' weights (Engine.set_resident_budget; kinds qkv, o, down; without kinds: the engine's measured gains), e.g.
+`resident=177:qkv` = qkv alone, `resident=240:qkv@0.07+o@0.02` = the planner on those gains.  The weight arena is filled with random bf16 values ON THE DEVICE (timing does not depend
 on the values), the decode state is set up directly (every sequence at context `ctx`), and each variant's decode step
 is captured in a hipGraph and replayed `steps` times between two HIP events; rounds alternate between the variants.
 Prints per variant: median and min ms/step, and the HBM-roofline fraction of the step."""
@@ -84,6 +86,12 @@ def main():
         eng = cls(cfg, max_batch=B, s_max=s_max, max_patches=64, max_prompt_tokens=64,
                   decode_splits=int(over.pop("n_split", 16)), weight_dtype=a.weights)
         over.pop("steps_per_graph", None)     # handled where the graph is captured
+        if "resident" in over:                # resident=<MB>[:kind@gain+kind@gain]: Infinity-Cache budget (and the planner's gains)
+            mb, _, kinds = over.pop("resident").partition(":")
+            gains = [(k.split("@")[0], float(k.split("@")[1]) if "@" in k else 1.0) for k in kinds.split("+")] if kinds else None
+            eng.set_resident_budget(int(mb), gains)
+            print(f"{spec}: {len(eng.resident)} resident launches "
+                  f"({', '.join(f'{k} x {sum(1 for _, kk in eng.resident if kk == k)}' for k in sorted({k for _, k in eng.resident}))})", flush=True)
         for k, v in old.items():
             if v is None:
                 os.environ.pop(k, None)
@@ -193,7 +201,7 @@ def main():
     roof_ms = (cfg.decoder_weight_bytes(a.weights) + B * (a.ctx + a.steps / 2) * kvb) / 8e12 * 1e3
     for spec, _ in engines:
         t = np.asarray(times[spec])
-        print(f"{spec:50s} median {np.median(t):.4f} ms/step  min {t.min():.4f}  ({roof_ms / np.median(t) * 100:.1f} % of the 8 TB/s step roofline)",
+        print(f"{spec:50s} median {np.median(t):.4f} ms/step  min {t.min():.4f}  max {t.max():.4f}  ({roof_ms / np.median(t) * 100:.1f} % of the 8 TB/s step roofline)",
               flush=True)
 
 

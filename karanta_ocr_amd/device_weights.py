@@ -1,7 +1,7 @@
 """The model's parameters on the device: one packed arena, laid out for the kernels."""
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Dict, FrozenSet, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -19,6 +19,35 @@ def _bits(w: np.ndarray) -> np.ndarray:
 
 def _align(n: int, a: int = 256) -> int:
     return (n + a - 1) // a * a
+
+
+def narrow_weight_bytes(cfg: ModelConfig, weight_dtype: str = "bf16") -> List[Dict[str, int]]:
+    """Per decoder layer, the bytes a <= 16-row decode step streams for each narrow launch: {"qkv", "o", "down"} -> bytes.
+    bf16: the packed matrix; fp8: its e4m3 codes + one f32 scale per output row (what kr_linear_decode_narrow_fp8 reads)."""
+    t = cfg.text
+    shapes = {"qkv": (t.qkv_dim, t.hidden_size), "o": (t.hidden_size, t.q_dim), "down": (t.hidden_size, t.intermediate_size)}
+    per = (lambda n, k: n * k + 4 * n) if weight_dtype == "fp8" else (lambda n, k: 2 * n * k)
+    return [{kind: per(*shape) for kind, shape in shapes.items()} for _ in range(t.num_layers)]
+
+
+def plan_resident(layer_bytes: Sequence[Dict[str, int]], gains: Sequence[Tuple[str, float]], budget_bytes: int,
+                  min_us: float = 0.0) -> FrozenSet[Tuple[int, str]]:
+    """Which (layer, launch kind) weights a decode step loads with the default cache policy, so that they stay in the
+    Infinity Cache from step to step (kr_narrow_opts.w_resident), under a byte budget.
+    layer_bytes: per layer {kind: bytes} (narrow_weight_bytes); gains: (kind, measured us saved per MB resident), kinds with no
+    gain left out or <= 0.  Greedy by gain per byte: kinds in falling gain (ties: by name), layers in rising order; a weight that
+    no longer fits is passed over, smaller ones behind it may still fit.  Never more than budget_bytes in all.
+    min_us: a launch whose expected saving (gain x its MB) is below this is not planned: the per-MB figures were measured on
+    matrices of several MB read from HBM and say nothing about one that is a fraction of that."""
+    order = sorted(((g, kind) for kind, g in gains if g > 0), key=lambda e: (-e[0], e[1]))
+    left, chosen = int(budget_bytes), set()
+    for g, kind in order:
+        for layer, sizes in enumerate(layer_bytes):
+            n = sizes.get(kind, 0)
+            if 0 < n <= left and g * n / 1e6 >= min_us and (layer, kind) not in chosen:
+                chosen.add((layer, kind))
+                left -= n
+    return frozenset(chosen)
 
 
 class DeviceWeights:

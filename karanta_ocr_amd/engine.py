@@ -25,7 +25,7 @@ from . import positions as POS
 from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_NONE, EPI_SILU_MUL8, KarantaHipError, Spec, fork_plan,
                    lib, narrow_opts, ptr)
 from .config import ModelConfig
-from .device_weights import DeviceWeights, _align
+from .device_weights import DeviceWeights, _align, narrow_weight_bytes, plan_resident
 from .request import GenerateResult, PageRequest, SpecConfig, children
 from .sampler import DeviceGuide, Sampler
 from .sampling import StepFeatures, has_penalties
@@ -35,6 +35,15 @@ BF16 = torch.bfloat16
 GEMM_SCRATCH_BYTES = 512 * 65536   # include/karanta_hip.h: KR_GEMM_SCRATCH_BYTES
 FP8_ACT_DEFAULT = False            # fp8 engines: W8A8 prefill on by default? (measured error and speed)
 # default-on switches of csrc/tools/experiment_engine.ExperimentEngine that select a superseded decode launch sequence
+# Infinity-Cache residency of the <= 16-row narrow launches' weights (kr_narrow_opts.w_resident):
+# (launch kind, us saved per MB of its weights kept resident, measured inside a replayed 2B / 8-row step), and the default budget.
+# qkv: 12.3 us per step for 176 MB; o_proj (2.8 us for 132 MB) and down_proj (none) stayed inside the spread of three repeats
+# and are left out (profiles/r05_ic_residency.txt).  192 MB: the smallest swept budget that holds qkv in all 28 layers of the 2B model.
+IC_RESIDENT_GAINS: Tuple[Tuple[str, float], ...] = (("qkv", 0.07),)
+IC_RESIDENT_MB = 192
+# a launch is planned only if its expected saving reaches what two identical graphs differ by per launch in that sweep (3-4 us per
+# step over 28 launches): the sub-MB matrices of the test-sized models keep their nontemporal loads
+IC_RESIDENT_MIN_US = 0.1
 SEQUENCE_SWITCHES = ("KARANTA_NARROW", "KARANTA_NARROW_O", "KARANTA_DEFER_DOWN", "KARANTA_WIDE", "KARANTA_ATOMIC_SLAB", "KARANTA_DEC32")
 
 __all__ = ["Engine", "PageRequest", "SpecConfig", "DeviceWeights", "GenerateResult", "children", "SEQUENCE_SWITCHES", "DeviceGuide"]
@@ -88,7 +97,7 @@ class Engine:
     def __init__(self, cfg: ModelConfig, device: str = "cuda:0", max_batch: int = 8, s_max: int = 4096,
                  max_patches: int = 8 * 5476, max_prompt_tokens: int = 8 * 2048, decode_splits: int = 16,
                  weight_dtype: str = "bf16", fp8_activations: Optional[bool] = None, admission_cus: Optional[int] = None,
-                 speculative: Optional[SpecConfig] = None):
+                 speculative: Optional[SpecConfig] = None, ic_resident_mb: Optional[int] = None):
         if not torch.cuda.is_available():
             raise KarantaHipError("no HIP device: the karanta MI355X engine has no CPU fallback")
         self.L = lib()
@@ -143,6 +152,7 @@ class Engine:
             raise KarantaHipError(f"unsupported head dims vit={v.head_dim} llm={t.head_dim}")
         self.w = DeviceWeights(cfg, self.device, weight_dtype)
         self.fp8 = weight_dtype == "fp8"
+        self.set_resident_budget(IC_RESIDENT_MB if ic_resident_mb is None else ic_resident_mb)
         # fp8 engine: prefill GEMMs read the fp8 codes (kr_gemm_fp8); KARANTA_FP8_PREFILL=0: their dequantised bf16 copy
         self.fp8_prefill_gemm = os.environ.get("KARANTA_FP8_PREFILL", "1") == "1"
         # W8A8 prefill (fp8 engine): the activations entering the decoder's prefill GEMMs are quantised per token to e4m3
@@ -157,6 +167,19 @@ class Engine:
         self._prof_next = 0
         self._last_batch = max_batch
         self._alloc()
+
+    def set_resident_budget(self, mb: int, gains: Optional[Sequence[Tuple[str, float]]] = None):
+        """The (layer, kind) whose <= 16-row narrow launches load their weights with the default cache policy: up to `mb` MB of
+        them stay in the Infinity Cache from one decode step to the next (device_weights.plan_resident).  gains: the planner's
+        (kind, us per MB) list when it is not the measured one (tools, tests).  The policy is baked into captured decode
+        graphs, so a call after construction drops them."""
+        for g in getattr(self, "_graphs", {}).values():
+            self.L.kr_graph_destroy(g)
+        getattr(self, "_graphs", {}).clear()
+        self.ic_resident_mb = int(mb)
+        self.resident = plan_resident(narrow_weight_bytes(self.cfg, self.w.weight_dtype),
+                                      IC_RESIDENT_GAINS if gains is None else gains, self.ic_resident_mb * 10 ** 6,
+                                      IC_RESIDENT_MIN_US)
 
     def _refuse_retired_switches(self):
         if type(self) is Engine and any(os.environ.get(k, "0") not in ("", "0") for k in
@@ -334,10 +357,11 @@ class Engine:
                                 ptr(self.d_amax_v), ptr(self.d_amax_i), self.s)
 
     def _dec_narrow(self, mode, x, W, M, out=None, out_f32=None, bias=None, norm_w=None, res=None, waves=8, ksplit=1,
-                    part_in=None, x_out=None, kc=0, vc=0, w8=None, w_scale=None, zero=None, atomic_out=False):
+                    part_in=None, x_out=None, kc=0, vc=0, w8=None, w_scale=None, zero=None, atomic_out=False,
+                    resident=False):
         """kr_linear_decode_narrow: one workgroup per tile (pair); ksplit > 1 = deferred split-K sums in out_f32.
         w8 / w_scale: the fp8 copy of W and its row scales (kr_linear_decode_narrow_fp8).  zero (an f32 tensor the launch
-        also zeroes), atomic_out: the launch's kr_narrow_opts."""
+        also zeroes), atomic_out, resident (w_resident: the weights stay in the Infinity Cache): the launch's kr_narrow_opts."""
         t = self.cfg.text
         N, K = W.shape
         o = out if out is not None else out_f32
@@ -346,7 +370,7 @@ class Engine:
         args = (ptr(bias), ptr(norm_w), t.rms_norm_eps, ptr(res), res.stride(0) if res is not None else 0, ptr(out),
                 ptr(out_f32), o.stride(-2) if o is not None else 0, M, N, K, waves, ksplit, ptr(self.d_cs), self.max_new,
                 ptr(self.d_plen), ptr(self.d_ctx), ptr(self.d_q), kc, vc, t.num_heads, t.num_kv_heads, self.s_max,
-                narrow_opts(ptr(zero), zero.numel() * 4 if zero is not None else 0, atomic_out), self.s)
+                narrow_opts(ptr(zero), zero.numel() * 4 if zero is not None else 0, atomic_out, w_resident=resident), self.s)
         if w8 is not None:
             self.L.kr_linear_decode_narrow_fp8(*head, ptr(w8), ptr(w_scale), *args)
         else:
@@ -757,7 +781,7 @@ class Engine:
             else:
                 self._dec_narrow(DEC_ROPE_KV, x, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), norm_w=w.view(p + "ln1.w"),
                                  part_in=pin, x_out=x_other if pending else None, kc=kc, vc=vc, zero=acc,
-                                 **self._w8kw(p + "qkv.w"))
+                                 resident=(i, "qkv") in self.resident, **self._w8kw(p + "qkv.w"))
             if pending:
                 x, x_other = x_other, x
             # ---- 2. split-KV attention partials, 3. their merge
@@ -772,7 +796,8 @@ class Engine:
             if big:
                 self._dec32(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, self.o_waves, out=x, res=x, **self._w8kw(p + "o.w"))
             else:
-                self._dec_narrow(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, out=x, res=x, waves=self.o_waves, **self._w8kw(p + "o.w"))
+                self._dec_narrow(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, out=x, res=x, waves=self.o_waves,
+                                 resident=(i, "o") in self.resident, **self._w8kw(p + "o.w"))
             # ---- 5. RMSNorm + gate/up + SiLU*mul (the kernel bench.py's roofline object is measured on)
             if self._prof_on:
                 # [e0][e1] gate/up [e2]: the empty bracket e0..e1 measures what two back-to-back event
@@ -793,7 +818,7 @@ class Engine:
                 self._dec32(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, self.down_waves_small, **down, **self._w8kw(p + "down.w"))
             else:
                 self._dec_narrow(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, waves=self.down_waves_small, **down,
-                                 **self._w8kw(p + "down.w"))
+                                 resident=(i, "down") in self.resident, **self._w8kw(p + "down.w"))
             pending = defer
         return x
 
