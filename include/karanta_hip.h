@@ -39,7 +39,7 @@ typedef uint16_t kr_bf16;
 /* kr_version() of the library this header describes: major * 100 + minor.  The major changes with every incompatible
  * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family); a caller built
  * against major X must refuse a library whose kr_version() / 100 != X. */
-#define KR_ABI_VERSION 408
+#define KR_ABI_VERSION 409
 
 #define KR_OK 0
 #define KR_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -626,6 +626,60 @@ typedef struct kr_fork_plan {
 int kr_kv_fork(kr_bf16* kcache, kr_bf16* vtcache, int64_t k_layer_stride, int64_t k_slot_stride, int64_t k_head_stride,
                int64_t vt_layer_stride, int64_t vt_slot_stride, int64_t vt_head_stride, int layers, int kv_heads, int hd,
                int slots, int s_max, const kr_fork_plan* plan, kr_stream s);
+
+/* ------------------------------------------------------------------ fp8 (e4m3fn) KV cache
+ * The same logical layout as the bf16 cache with one byte per element: K [slots, kv_heads, s_max, 128] and V^T
+ * [slots, kv_heads, s_max / 64, 2, 128, 32] per layer (element index = byte index), and one f32 scale per (K or V, kv head):
+ * `scale` = [2][kv_heads] of this layer, a code stands for code * scale.  ONE quantisation rule, wherever a value enters the cache:
+ * the bf16 value the bf16 cache would have held, divided by the scale in f32, clamped to +-448 (v_med3_f32, not the conversion's
+ * saturation), converted with v_cvt_pk_fp8_f32 (round to nearest even).  Code 0 is 0.0 and no NaN code is ever written.  Only
+ * head_dim 128.  The entry points below are the fp8-cache forms of existing ones: same launches, same records, plus a kr_kv8. */
+typedef struct kr_kv8 {
+    uint8_t* k;                        /* this layer's K codes */
+    uint8_t* vt;                       /* this layer's V^T codes */
+    const float* scale;                /* device, [2][kv_heads]: K scales, then V scales */
+} kr_kv8;
+
+/* Prefill side: the rows an admission wrote into a ONE-LAYER bf16 scratch (k_src [slots, kv_heads, s_max, 128], vt_src the V^T
+ * blocks, contiguous, the strides of a layer of the bf16 cache) are converted into `dst`, a layer of the fp8 cache.  Per (slot, len)
+ * of the plan and per kv head: K rows [0, len) and whole V^T blocks [0, ceil(len / 64)).  K rows at or beyond len, the other slots
+ * and the scratch keep their bytes.  Elementwise, 16-byte loads and 8-byte stores, one launch, the grid capped and strided; the
+ * plan is HOST memory carried in the kernel arguments (as kr_kv_fork).  n_clamped (device, optional): += the number of converted
+ * elements whose |value / scale| exceeded 448 — at most one atomic add per workgroup, and only by a workgroup that clamped.
+ * KR_ERR_ARG: hd != 128, a slot outside [0, slots) or listed twice, len outside [1, s_max], n outside [1, 32]. */
+#define KR_KVQ_MAX_ROWS 32
+typedef struct kr_kvq_plan {
+    int32_t n;                         /* 1 .. KR_KVQ_MAX_ROWS */
+    int32_t slot[KR_KVQ_MAX_ROWS];
+    int32_t len[KR_KVQ_MAX_ROWS];      /* prompt length: rows [0, len) */
+} kr_kvq_plan;
+int kr_kv_quantize(const kr_bf16* k_src, const kr_bf16* vt_src, const kr_kv8* dst, int kv_heads, int hd, int slots, int s_max,
+                   const kr_kvq_plan* plan, int32_t* n_clamped, kr_stream s);
+
+/* kr_kv_fork for a cache of one-byte elements (a piece is hd x 64 bytes): strides in elements = bytes, multiples of 16; hd % 16. */
+int kr_kv_fork8(uint8_t* kcache, uint8_t* vtcache, int64_t k_layer_stride, int64_t k_slot_stride, int64_t k_head_stride,
+                int64_t vt_layer_stride, int64_t vt_slot_stride, int64_t vt_head_stride, int layers, int kv_heads, int hd,
+                int slots, int s_max, const kr_fork_plan* plan, kr_stream s);
+
+/* kr_attn_decode_slots / kr_attn_decode_rows on an fp8 cache: the same unit partition, split and wave geometry, early return and
+ * records, so kr_attn_decode_merge / _merge32 run unchanged.  The codes are converted to bf16 in registers (exact) and multiplied
+ * with the bf16 matrix instruction as there; scale[kvh] of K is folded into the score scale, the wave's O is multiplied by
+ * scale[kv_heads + kvh] once. */
+int kr_attn_decode_slots_kv8(const kr_bf16* q, const kr_kv8* kv, const int32_t* ctx_len, const int32_t* finished, float* workspace,
+                             int batch, int heads, int kv_heads, int hd, int s_max, int n_split, float scale, kr_stream s);
+int kr_attn_decode_rows_kv8(const kr_bf16* q, const kr_kv8* kv, const int32_t* ctx_len, const int32_t* finished,
+                            const int32_t* row_slot, float* workspace, int rows, int heads, int kv_heads, int hd, int s_max,
+                            int n_split, float scale, kr_stream s);
+
+/* The KV append of a decode step into an fp8 cache: kr_linear_decode_narrow / _narrow_fp8 (w_scale NULL: bf16 weights) and
+ * kr_linear_decode32 / _rows (row_slot NULL: the slots' own rows) in mode KR_DEC_ROPE_KV with the epilogue ROPE_KV8 — q is written
+ * as there, K goes out as two packed 4-byte stores of codes, V^T as byte stores; kcache / vtcache of the record are ignored. */
+int kr_linear_decode_narrow_kv8(const kr_bf16* x, int64_t ldx, const float* part_in, int n_part_in, kr_bf16* x_out, int64_t ldxo,
+                                const void* w_packed, const float* w_scale, const kr_bf16* bias, const kr_bf16* norm_w,
+                                float norm_eps, int M, int N, int K, int waves, const float* cs_table, int cs_stride,
+                                const int32_t* prompt_len, const int32_t* ctx_len, kr_bf16* q_out, const kr_kv8* kv, int heads,
+                                int kv_heads, int s_max, const kr_narrow_opts* opts, kr_stream s);
+int kr_linear_decode32_kv8(const kr_dec32* args, const kr_kv8* kv, const int32_t* row_slot, kr_stream s);
 
 /* Greedy sampling from the ARGMAX partials + per-step bookkeeping: token -> tokens_out[b] and
  * history[(ctx_len[b] + 1 - prompt_len[b]) * hist_stride + b] (= this sequence's generated-token

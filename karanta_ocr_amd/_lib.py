@@ -106,6 +106,13 @@ SIGNATURES = {
     "kr_spec_guide_advance": [c_p, c_p, c_p],
     "kr_linear_decode32_rows": [i32, c_p, c_p, c_p],
     "kr_attn_decode_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
+    "kr_kv_quantize": [c_p, c_p, c_p, i32, i32, i32, i32, c_p, c_p, c_p],
+    "kr_kv_fork8": [c_p, c_p, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, c_p, c_p],
+    "kr_attn_decode_slots_kv8": [c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
+    "kr_attn_decode_rows_kv8": [c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
+    "kr_linear_decode_narrow_kv8": [c_p, i64, c_p, i32, c_p, i64, c_p, c_p, c_p, c_p, f32, i32, i32, i32, i32, c_p, i32, c_p, c_p,
+                                    c_p, c_p, i32, i32, i32, c_p, c_p],
+    "kr_linear_decode32_kv8": [c_p, c_p, c_p, c_p],
     "kr_comm_unique_id": [c_p],
     "kr_comm_init": [C.POINTER(c_p), i32, i32, c_p],
     "kr_comm_count": [c_p, C.POINTER(i32)],
@@ -168,6 +175,33 @@ class SpecGuide(C.Structure):
     """kr_spec_guide (include/karanta_hip.h): the guides of a speculative step's rows and the scratch of its three launches."""
     _fields_ = [("guide_trans", c_p), ("guide_masks", c_p), ("guide_state", c_p), ("mask_words", C.c_int32), ("vocab_off", c_p),
                 ("vocab_bytes", c_p), ("draft_state", c_p), ("ctx_before", c_p)]
+
+
+class Kv8(C.Structure):
+    """kr_kv8 (include/karanta_hip.h): one layer of the fp8 KV cache and its [2][kv_heads] scales."""
+    _fields_ = [("k", c_p), ("vt", c_p), ("scale", c_p)]
+
+
+def kv8(k: int, vt: int, scale: int):
+    """A kr_kv8* from three device addresses; read during the call only."""
+    return C.byref(Kv8(k, vt, scale))
+
+
+KVQ_MAX_ROWS = 32                       # KR_KVQ_MAX_ROWS
+
+
+class KvqPlan(C.Structure):
+    """kr_kvq_plan (include/karanta_hip.h): the (slot, prompt length) rows kr_kv_quantize converts."""
+    _fields_ = [("n", C.c_int32), ("slot", C.c_int32 * KVQ_MAX_ROWS), ("len", C.c_int32 * KVQ_MAX_ROWS)]
+
+
+def kvq_plan(rows):
+    """A kr_kvq_plan* from [(slot, prompt length), ...]; too many rows are passed on as a count the library rejects."""
+    p = KvqPlan()
+    p.n = len(rows) if len(rows) <= KVQ_MAX_ROWS else -1
+    for i, (slot, n) in enumerate(list(rows)[:KVQ_MAX_ROWS]):
+        p.slot[i], p.len[i] = int(slot), int(n)
+    return C.byref(p)
 
 
 FORK_MAX_GROUPS = FORK_MAX_SLOTS = 32   # KR_FORK_MAX_GROUPS / KR_FORK_MAX_SLOTS

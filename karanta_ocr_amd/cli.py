@@ -66,6 +66,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--admit-max-wait", type=int, default=48, help="... but at most this many scheduler steps of 2 decode steps")
     ap.add_argument("--quantization", default=None, choices=("fp8",),
                     help="decoder Linears as fp8 codes + row scales (vLLM's flag; implied by a checkpoint with a quantization_config)")
+    ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "bfloat16", "fp8", "fp8_e4m3"),
+                    help="vLLM's flag: auto = bfloat16; fp8 = fp8_e4m3: the KV cache as e4m3 codes with one scale per (layer, K or V, "
+                         "kv head) — half the cache's bytes and half the decode attention's traffic; scales from the checkpoint's "
+                         "k_scale / v_scale tensors where it ships them, else 1.0 (the server logs what an admission had to clamp)")
     ap.add_argument("--enable-prefix-caching", action="store_true",
                     help="vLLM's flag: a request whose whole prompt (ids, grids, image bytes) is still resident in a decode slot "
                          "starts from that slot's KV rows, without ViT or prefill (continuous mode)")
@@ -257,11 +261,20 @@ def make_server(args, log=print):
     eng = Engine(cfg, device="cuda:0", max_batch=args.max_num_seqs, s_max=(args.max_model_len + slack + 63) // 64 * 64,
                  max_patches=max_patches, max_prompt_tokens=max_prompt_tokens,
                  weight_dtype=weight_dtype, fp8_activations=bool(getattr(args, "fp8_activations", False)) or None,
+                 kv_cache_dtype=getattr(args, "kv_cache_dtype", "auto"),
                  **({"speculative": SpecConfig(*spec, share_rows=share, guided=spec_guided)} if spec else {}))
     # one server: read the checkpoint.  A launch.py group: rank 0 reads it ONCE, the arena goes to the other GPUs over
     # RCCL / xGMI (north_star: "RCCL broadcast of weights over xGMI"); a failure stops every server of the group
     info = load_or_receive_weights(eng.w, rank, world, lambda: eng.load_weights(load_checkpoint(args.model_dir)[1]),
                                    stream=eng.s, log=log)
+    kv_bytes = eng.kv_cache_bytes()
+    log(f"KV cache: {eng.kv_cache_dtype}, {kv_bytes / 2 ** 20:.0f} MiB for {args.max_num_seqs} slots of {eng.s_max} rows")
+    if eng.kv8:      # every server of a group reads the (tiny) scale tensors itself: only rank 0 reads the weights
+        from .weights import load_kv_scales
+        sc = load_kv_scales(args.model_dir, cfg)
+        if sc is not None:
+            eng.set_kv_scales(*sc, source="checkpoint (self_attn.k_scale / v_scale)")
+        log(f"fp8 KV cache scales: {eng.kv_scale_source}")
     if world > 1:
         log(f"weight broadcast: {info['bytes'] / 1e9:.2f} GB in {info['bcast_s']:.3f}s over {info['rccl_ranks']} RCCL ranks")
     template = load_chat_template(args.model_dir)

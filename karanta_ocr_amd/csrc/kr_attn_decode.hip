@@ -16,15 +16,32 @@ namespace {
 #endif
 // ROWS (kr_attn_decode_rows, the speculative step): blockIdx.z is a ROW — q, ctx_len, finished and the records are the row's, the
 // cache is the one of slot row_slot[row]; the new pointer sits at the tail of the arguments, past the preloaded ones.
-template <int WAVES, bool ROWS = false>
-__global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16* __restrict__ q, const kr_bf16* __restrict__ kcache,
-                                                                  const kr_bf16* __restrict__ vtcache,
+// KV8 (kr_attn_decode_slots_kv8 / _rows_kv8): the cache holds e4m3 codes, one byte per element, same layout; kv_scale = [2][kv_heads]
+// sits at the tail of the arguments too.  A unit is 4 KiB of K rows + 4 KiB of V^T, every load 16 bytes per lane:
+//   K    load j of key tile kt: lane (fr, fg) reads channels 64j + 16fg .. +15 of its key row — the four lane groups cover 64
+//        contiguous bytes of each of 16 rows, the two loads of a tile a whole 128-byte row.  The 16 bytes are TWO k-steps: k-step
+//        2j + h pairs K[key][64j + 16fg + 8h + e] with Q[g][the same channel], e = 0..7 — the Q fragments are loaded in that
+//        permutation (a dot product does not care).
+//   V^T  load i: lane (fr, fg) reads keys 16 (fg & 1) .. +15 of channel 32i + 16 (fg >> 1) + fr: one instruction = 1 KiB of
+//        contiguous memory.  Its low 8 bytes belong to channel tile 2i in lane groups 0, 1 and to tile 2i + 1 in groups 2, 3; one
+//        v_permlane32_swap per register (low halves of the upper 32 lanes <-> high halves of the lower 32) leaves tile 2i in the
+//        low and tile 2i + 1 in the high registers of every lane, lane group fg holding keys 8 pi(fg) .. +7 with pi = (0, 2, 1, 3).
+//        K row fr of tile kt is therefore key 8 pi(fr >> 2) + 4kt + (fr & 3): P comes out of the S accumulators in V's key order.
+//   The codes are converted to bf16 in registers (exact) right before their matrix instruction; K's scale is folded into
+//   scale_log2e, V's multiplies the wave's O once.
+template <bool KV8> struct KvElem { using T = kr_bf16; };
+template <> struct KvElem<true> { using T = uint8_t; };
+
+template <int WAVES, bool ROWS = false, bool KV8 = false>
+__global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16* __restrict__ q, const typename KvElem<KV8>::T* __restrict__ kcache,
+                                                                  const typename KvElem<KV8>::T* __restrict__ vtcache,
                                                                   const int32_t* __restrict__ ctx_len,
                                                                   const int32_t* __restrict__ finished, int heads, int kv_heads,
                                                                   int group, int n_split, int s_max, float scale_log2e,
                                                                   kr_bf16* __restrict__ out, float* __restrict__ ws,
                                                                   int* __restrict__ counters, int ws_bytes,
-                                                                  const int32_t* __restrict__ row_slot) {
+                                                                  const int32_t* __restrict__ row_slot,
+                                                                  const float* __restrict__ kv_scale) {
     // argument order: everything the first loads need sits in the 16 preloaded dwords (kernarg preload), so the
     // scalar load of ctx_len[b] leaves at once instead of behind a load of the argument tail
     constexpr int HD = 128, DT = HD / 16, REC = HD + 4;
@@ -45,13 +62,17 @@ __global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16*
     const int g = fr < group ? fr : 0;
     // MFMA k-step i pairs K[key][32i + 8fg + j] with Q[g][32i + 8fg + j]: per load instruction the
     // four lane groups cover 64 contiguous bytes of each of 16 key rows
-    const kr_bf16* qp = q + ((int64_t)b * heads + kvh * group + g) * HD + fg * 8;
+    const kr_bf16* qp = q + ((int64_t)b * heads + kvh * group + g) * HD + fg * (KV8 ? 16 : 8);
     bf16x8 qf[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) qf[i] = ld8(qp + i * 32);
+    for (int i = 0; i < 4; ++i) qf[i] = ld8(qp + (KV8 ? (i >> 1) * 64 + (i & 1) * 8 : i * 32));
     const int64_t kv_base = (int64_t)(ROWS ? row_slot[b] : b) * kv_heads + kvh;
-    const kr_bf16* kc = kcache + kv_base * s_max * HD;
-    const kr_bf16* vc = vtcache + kv_base * (int64_t)(s_max >> 6) * (HD * 64);
+    const typename KvElem<KV8>::T* kc = kcache + kv_base * s_max * HD;
+    const typename KvElem<KV8>::T* vc = vtcache + kv_base * (int64_t)(s_max >> 6) * (HD * 64);
+    // KV8: lane group fg of a key tile / of P stands for keys 8 pi(fg) .. +7
+    const int pfg = KV8 ? ((fg & 1) << 1) | (fg >> 1) : fg;
+    float sl2 = scale_log2e;
+    if constexpr (KV8) sl2 *= kv_scale[kvh];
 
     f32x4 o[DT];
 #pragma unroll
@@ -61,9 +82,24 @@ __global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16*
     // (1.4k .. 2.4k keys = 44 .. 76 units) 64 parts leave one unit — one memory round trip — per wave; a wave with
     // more requests unit u + n_part before it computes unit u
     const int nu = (ctx + 31) >> 5;
-    bf16x8 kf[2][4], vf[DT], kf2[2][4], vf2[DT];
-    auto load_unit = [&](int u, bf16x8 (&kk)[2][4], bf16x8 (&vv)[DT]) {
+    // KV8: a unit is half the registers — K [kt][j] and V^T [i] of 16 bytes each
+    constexpr int KI = KV8 ? 2 : 4, VI = KV8 ? 4 : DT;
+    bf16x8 kf[2][KI], vf[VI], kf2[2][KI], vf2[VI];
+    auto load_unit = [&](int u, bf16x8 (&kk)[2][KI], bf16x8 (&vv)[VI]) {
         const int key0 = u * 32;
+        if constexpr (KV8) {
+            const char* kb = reinterpret_cast<const char*>(kc);
+            const char* vb = reinterpret_cast<const char*>(vc);
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+                const char* kp = kb + (int64_t)(key0 + 8 * ((((fr >> 2) & 1) << 1) | (fr >> 3)) + 4 * kt + (fr & 3)) * HD + fg * 16;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) kk[kt][j] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kp + j * 64));
+            }
+            const char* vp = vb + (int64_t)(u >> 1) * (HD * 64) + (u & 1) * (HD * 32) + ((fg >> 1) * 16 + fr) * 32 + (fg & 1) * 16;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) vv[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(vp + i * (32 * 32)));
+        } else {
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
             const kr_bf16* kp = kc + (int64_t)(key0 + 8 * (fr >> 2) + 4 * kt + (fr & 3)) * HD + fg * 8;
@@ -75,6 +111,7 @@ __global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16*
         const kr_bf16* vp = vc + (int64_t)(u >> 1) * (HD * 64) + (u & 1) * (HD * 32) + fg * 8;
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) vv[dt] = KR_ATTN_DEC_LD(vp + (dt * 16 + fr) * 32);
+        }
     };
     int u = part;
     if (u < nu) load_unit(u, kf, vf);
@@ -88,15 +125,24 @@ __global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16*
             for (int kt = 0; kt < 2; ++kt) {
                 s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int i = 0; i < 4; ++i) s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kt][i], qf[i], s[kt], 0, 0, 0);
+                for (int i = 0; i < 4; ++i) {
+                    bf16x8 ka;
+                    if constexpr (KV8) {
+                        const u32x4 w = __builtin_bit_cast(u32x4, kf[kt][i >> 1]);
+                        ka = kv8_to_bf16x8(w[2 * (i & 1)], w[2 * (i & 1) + 1]);
+                    } else {
+                        ka = kf[kt][i];
+                    }
+                    s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[i], s[kt], 0, 0, 0);
+                }
             }
             float mx = -INFINITY;
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int key = key0 + 8 * fg + 4 * kt + r;
-                    const float v = key < ctx ? s[kt][r] * scale_log2e : -INFINITY;
+                    const int key = key0 + 8 * pfg + 4 * kt + r;
+                    const float v = key < ctx ? s[kt][r] * sl2 : -INFINITY;
                     s[kt][r] = v;
                     mx = fmaxf(mx, v);
                 }
@@ -120,22 +166,41 @@ __global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16*
             for (int dt = 0; dt < DT; ++dt) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt], pf, o[dt], 0, 0, 0);
+                if constexpr (!KV8) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt], pf, o[dt], 0, 0, 0);
+            }
+            if constexpr (KV8) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    // load i after the swap of the halves: channel tile 2i in the low registers, 2i + 1 in the high ones
+                    const u32x4 w = __builtin_bit_cast(u32x4, vf[i]);
+                    const auto s0 = __builtin_amdgcn_permlane32_swap(w[0], w[2], false, false);
+                    const auto s1 = __builtin_amdgcn_permlane32_swap(w[1], w[3], false, false);
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)
+                        o[2 * i + h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kv8_to_bf16x8(s0[h], s1[h]), pf, o[2 * i + h], 0, 0, 0);
+                }
             }
         }
         if (un < nu) {
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) kf[kt][i] = kf2[kt][i];
+                for (int i = 0; i < KI; ++i) kf[kt][i] = kf2[kt][i];
 #pragma unroll
-            for (int dt = 0; dt < DT; ++dt) vf[dt] = vf2[dt];
+            for (int dt = 0; dt < VI; ++dt) vf[dt] = vf2[dt];
         }
         u = un;
     }
     l_run += __shfl_xor(l_run, 16, 64);
     l_run += __shfl_xor(l_run, 32, 64);
     // ---- merge the waves through LDS
+    if constexpr (KV8) {
+        const float vs = kv_scale[kv_heads + kvh];
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[dt][r] *= vs;
+    }
     if (fr < group) {
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4*>(&o_s[wave][fr][dt * 16 + fg * 4]) = o[dt];
@@ -308,10 +373,11 @@ __global__ void __launch_bounds__(128) attn_merge_kernel(const float* __restrict
 
 }  // namespace
 
-template <bool ROWS = false>
-static int attn_decode_impl(const kr_bf16* q, const kr_bf16* kcache, const kr_bf16* vtcache, const int32_t* ctx_len,
-                            const int32_t* finished, kr_bf16* out, float* workspace, int32_t* counters, int batch, int heads,
-                            int kv_heads, int hd, int s_max, int n_split, float scale, kr_stream s, const int32_t* row_slot = nullptr) {
+template <bool ROWS = false, bool KV8 = false>
+static int attn_decode_impl(const kr_bf16* q, const typename KvElem<KV8>::T* kcache, const typename KvElem<KV8>::T* vtcache,
+                            const int32_t* ctx_len, const int32_t* finished, kr_bf16* out, float* workspace, int32_t* counters,
+                            int batch, int heads, int kv_heads, int hd, int s_max, int n_split, float scale, kr_stream s,
+                            const int32_t* row_slot = nullptr, const float* kv_scale = nullptr) {
     KR_CHECK_ARG(q && kcache && vtcache && ctx_len && (out || workspace), "kr_attn_decode_fused: null pointer");
     KR_CHECK_ARG(hd == 128, "kr_attn_decode_fused: hd=%d (only 128)", hd);
     KR_CHECK_ARG(heads % kv_heads == 0 && heads / kv_heads <= 16, "kr_attn_decode_fused: GQA group must be <= 16");
@@ -336,14 +402,14 @@ static int attn_decode_impl(const kr_bf16* q, const kr_bf16* kcache, const kr_bf
     const float sl2 = scale * 1.4426950408889634f;
     const int group = heads / kv_heads;
     if (waves == 8)
-        attn_decode2_kernel<8, ROWS><<<grid, 512, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
-                                                                 workspace, counters, (int)ws_bytes, row_slot);
+        attn_decode2_kernel<8, ROWS, KV8><<<grid, 512, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max,
+                                                                      sl2, out, workspace, counters, (int)ws_bytes, row_slot, kv_scale);
     else if (waves == 4)
-        attn_decode2_kernel<4, ROWS><<<grid, 256, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
-                                                                 workspace, counters, (int)ws_bytes, row_slot);
+        attn_decode2_kernel<4, ROWS, KV8><<<grid, 256, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max,
+                                                                      sl2, out, workspace, counters, (int)ws_bytes, row_slot, kv_scale);
     else
-        attn_decode2_kernel<2, ROWS><<<grid, 128, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max, sl2, out,
-                                                                 workspace, counters, (int)ws_bytes, row_slot);
+        attn_decode2_kernel<2, ROWS, KV8><<<grid, 128, 0, kr_hs(s)>>>(q, kcache, vtcache, ctx_len, finished, heads, kv_heads, group, n_split, s_max,
+                                                                      sl2, out, workspace, counters, (int)ws_bytes, row_slot, kv_scale);
     KR_CHECK_LAUNCH();
     return KR_OK;
 }
@@ -367,6 +433,24 @@ extern "C" int kr_attn_decode_rows(const kr_bf16* q, const kr_bf16* kcache, cons
     KR_CHECK_ARG(finished && workspace && row_slot, "kr_attn_decode_rows: null pointer");
     return attn_decode_impl<true>(q, kcache, vtcache, ctx_len, finished, nullptr, workspace, nullptr, rows, heads, kv_heads, hd, s_max, n_split,
                                   scale, s, row_slot);
+}
+
+extern "C" int kr_attn_decode_slots_kv8(const kr_bf16* q, const kr_kv8* kv, const int32_t* ctx_len, const int32_t* finished,
+                                        float* workspace, int batch, int heads, int kv_heads, int hd, int s_max, int n_split,
+                                        float scale, kr_stream s) {
+    KR_CHECK_ARG(finished && workspace && kv && kv->k && kv->vt && kv->scale, "kr_attn_decode_slots_kv8: null pointer");
+    KR_CHECK_ARG((((uintptr_t)kv->k | (uintptr_t)kv->vt) & 15) == 0, "kr_attn_decode_slots_kv8: the cache must be 16-byte aligned");
+    return attn_decode_impl<false, true>(q, kv->k, kv->vt, ctx_len, finished, nullptr, workspace, nullptr, batch, heads, kv_heads, hd,
+                                         s_max, n_split, scale, s, nullptr, kv->scale);
+}
+
+extern "C" int kr_attn_decode_rows_kv8(const kr_bf16* q, const kr_kv8* kv, const int32_t* ctx_len, const int32_t* finished,
+                                       const int32_t* row_slot, float* workspace, int rows, int heads, int kv_heads, int hd,
+                                       int s_max, int n_split, float scale, kr_stream s) {
+    KR_CHECK_ARG(finished && workspace && row_slot && kv && kv->k && kv->vt && kv->scale, "kr_attn_decode_rows_kv8: null pointer");
+    KR_CHECK_ARG((((uintptr_t)kv->k | (uintptr_t)kv->vt) & 15) == 0, "kr_attn_decode_rows_kv8: the cache must be 16-byte aligned");
+    return attn_decode_impl<true, true>(q, kv->k, kv->vt, ctx_len, finished, nullptr, workspace, nullptr, rows, heads, kv_heads, hd,
+                                        s_max, n_split, scale, s, row_slot, kv->scale);
 }
 
 static int merge_impl(const float* workspace, kr_bf16* out, int batch, int heads, int hd, int n_split, int xp, kr_stream s) {

@@ -75,6 +75,8 @@ struct DecLinArgs {
     // SILU8 output in the XP layout of 17..32-row batches (kr_common.h, kr_xp_byte_offset): the down_proj launch of such a
     // batch (kr_linear_decode32) reads its x fragments as whole cache lines
     int out_xp;
+    // ROPE_KV8: the fp8 cache of this layer (kcache / vtcache unused)
+    Kv8 kv8;
 };
 
 template <int NT, int EPI, int WAVES>
@@ -1107,7 +1109,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
     float* red = reinterpret_cast<float*>(smem + (NORM ? ((M * xrow + 127) & ~127) : 0));
 
     int tile[NT];
-    if (EPI == DEPI_ROPE_KV) {
+    if (depi_rope(EPI)) {
         tile[0] = (g >> 2) * 8 + (g & 3);
         tile[NT - 1] = tile[0] + 4;
     } else {
@@ -1162,7 +1164,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         pos[mt] = plen[mt] = 0;
-        if (EPI == DEPI_ROPE_KV) {
+        if (depi_rope(EPI)) {
             pos[mt] = a.ctx_len[rb[mt]];
             plen[mt] = a.prompt_len[rb[mt]];
         }
@@ -1278,7 +1280,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int j = 0; j < 8; ++j) csv[mt][j] = 0.f;
-    if (EPI == DEPI_ROPE_KV) {
+    if (depi_rope(EPI)) {
         const int i0 = (tile[0] & 7) * 16 + fg * 4;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
@@ -1364,7 +1366,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
         if (b >= M) return;
 #pragma unroll
         for (int t = 0; t < NT; ++t) apply_w_scale(a.w_scale, min(tile[t], ntiles - 1) * 16 + fg * 4, sum[t]);
-        if (EPI == DEPI_ROPE_KV) {
+        if (depi_rope(EPI)) {
             const int hh = tile[0] >> 3;                   // global head index in [q heads | k heads | v heads]
             const int i0 = (tile[0] & 7) * 16 + fg * 4;    // channel in [0, 64)
             float lo[4], hi[4];
@@ -1380,6 +1382,11 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
                     o0[j] = f2bf(lo[j] * csv[mt][j] - hi[j] * csv[mt][4 + j]);
                     o1[j] = f2bf(hi[j] * csv[mt][j] + lo[j] * csv[mt][4 + j]);
                 }
+                if (EPI == DEPI_ROPE_KV8 && hh >= a.heads) {   // the codes of the bf16 values the bf16 cache would hold
+                    const int kh = hh - a.heads;
+                    kv8_append_k(a.kv8.k + ((int64_t)b * a.kv_heads + kh) * a.s_max * 128, pos[mt], i0, o0, o1, a.kv8.scale[kh]);
+                    return;
+                }
                 kr_bf16* dst = hh < a.heads
                                    ? a.q_out + ((int64_t)b * a.heads + hh) * 128
                                    : a.kcache + (((int64_t)b * a.kv_heads + (hh - a.heads)) * a.s_max + pos[mt]) * 128;
@@ -1387,6 +1394,10 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
                 *reinterpret_cast<bf16x4*>(dst + 64 + i0) = o1;
             } else {
                 const int kvh = hh - a.heads - a.kv_heads;
+                if (EPI == DEPI_ROPE_KV8) {
+                    kv8_append_v(a.kv8.vt + ((int64_t)b * a.kv_heads + kvh) * a.s_max * 128, pos[mt], i0, lo, hi, a.kv8.scale[a.kv_heads + kvh]);
+                    return;
+                }
                 kr_bf16* vt = a.vtcache + (((int64_t)b * a.kv_heads + kvh) * (a.s_max >> 6) + (pos[mt] >> 6)) * (128 * 64) + kr_vt_off(0, pos[mt] & 63, 128);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -1871,7 +1882,8 @@ static int narrow_impl(int mode, const kr_bf16* x, int64_t ldx, const float* par
                                        const float* cs_table, int cs_stride, const int32_t* prompt_len, const int32_t* ctx_len,
                                        kr_bf16* q_out, kr_bf16* kcache, kr_bf16* vtcache, int heads, int kv_heads, int s_max,
                                        const kr_narrow_opts* opts, kr_stream s, float* x_out_f32 = nullptr, int64_t ldxf = 0,
-                                       const void* pf_ptr = nullptr, size_t pf_bytes = 0, int pf_blocks = 0) {
+                                       const void* pf_ptr = nullptr, size_t pf_bytes = 0, int pf_blocks = 0,
+                                       const kr_kv8* kv8 = nullptr) {
     KR_CHECK_ARG(x && w_packed, "kr_linear_decode_narrow: null pointer");
     const kr_narrow_opts o = opts ? *opts : kr_narrow_opts{};
     KR_CHECK_ARG((o.zero_ptr || o.zero_bytes == 0) && ((uintptr_t)o.zero_ptr & 15) == 0 && (o.zero_bytes & 15) == 0 && o.zero_bytes < (1u << 30),
@@ -1920,6 +1932,14 @@ static int narrow_impl(int mode, const kr_bf16* x, int64_t ldx, const float* par
             return waves == 16 ? launch_narrow_direct<DEPI_PLAIN, 16>(a, ntiles, s)
                                : launch_narrow_direct<DEPI_PLAIN, 8>(a, ntiles, s);
         case DEPI_ROPE_KV:
+            if (kv8) {   // kr_linear_decode_narrow_kv8: the fp8 cache, the fused norm prologue only (the engine's <= 16-row qkv launch)
+                KR_CHECK_ARG(bias && cs_table && prompt_len && ctx_len && q_out && kv8->k && kv8->vt && kv8->scale && cs_stride > 0 && norm_w,
+                             "kr_linear_decode_narrow_kv8: ROPE_KV8 pointers (norm_w included)");
+                KR_CHECK_ARG(N == (heads + 2 * kv_heads) * 128 && s_max % 64 == 0 && ksplit == 1 && (((uintptr_t)kv8->k | (uintptr_t)kv8->vt) & 3) == 0,
+                             "kr_linear_decode_narrow_kv8: ROPE_KV8 needs head_dim 128, ksplit 1, a 4-byte aligned cache");
+                a.kv8 = Kv8{kv8->k, kv8->vt, kv8->scale};
+                return launch_narrow_norm<2, DEPI_ROPE_KV8>(a, ntiles / 2, s);
+            }
             KR_CHECK_ARG(bias && cs_table && prompt_len && ctx_len && q_out && kcache && vtcache && cs_stride > 0,
                          "kr_linear_decode_narrow: ROPE_KV pointers");
             KR_CHECK_ARG(N == (heads + 2 * kv_heads) * 128 && s_max % 64 == 0 && ksplit == 1,
@@ -1962,6 +1982,19 @@ extern "C" int kr_linear_decode_narrow_fp8(int mode, const kr_bf16* x, int64_t l
     return narrow_impl(mode, x, ldx, part_in, n_part_in, x_out, ldxo, w_packed_fp8, w_scale, bias, norm_w, norm_eps, residual, ldr,
                        out, out_f32, ldc, M, N, K, waves, ksplit, cs_table, cs_stride, prompt_len, ctx_len, q_out, kcache, vtcache,
                        heads, kv_heads, s_max, opts, s);
+}
+
+// The qkv launch of a <= 16-row step into an fp8 cache (EPI ROPE_KV8): bf16 weights (w_scale NULL) or fp8 weights.
+extern "C" int kr_linear_decode_narrow_kv8(const kr_bf16* x, int64_t ldx, const float* part_in, int n_part_in, kr_bf16* x_out,
+                                           int64_t ldxo, const void* w_packed, const float* w_scale, const kr_bf16* bias,
+                                           const kr_bf16* norm_w, float norm_eps, int M, int N, int K, int waves,
+                                           const float* cs_table, int cs_stride, const int32_t* prompt_len, const int32_t* ctx_len,
+                                           kr_bf16* q_out, const kr_kv8* kv, int heads, int kv_heads, int s_max,
+                                           const kr_narrow_opts* opts, kr_stream s) {
+    KR_CHECK_ARG(kv, "kr_linear_decode_narrow_kv8: kv is NULL");
+    return narrow_impl(DEPI_ROPE_KV, x, ldx, part_in, n_part_in, x_out, ldxo, w_packed, w_scale, bias, norm_w, norm_eps, nullptr, 0,
+                       nullptr, nullptr, 0, M, N, K, waves, 1, cs_table, cs_stride, prompt_len, ctx_len, q_out, nullptr, nullptr,
+                       heads, kv_heads, s_max, opts, s, nullptr, 0, nullptr, 0, 0, kv);
 }
 
 // ---- residual sum + RMSNorm ONCE per batch (decode batches above 16 rows)

@@ -43,8 +43,13 @@ struct D32Args {
 struct D32RowArgs : D32Args {
     const int32_t* row_slot;
 };
-template <bool ROWS> struct D32ArgsOf { using type = D32Args; };
-template <> struct D32ArgsOf<true> { using type = D32RowArgs; };
+// ROPE_KV8 (kr_linear_decode32_kv8): the fp8 cache of this layer; with or without the row map, in a struct of its own as well.
+struct D32Kv8Args : D32RowArgs {
+    Kv8 kv8;
+};
+template <bool ROWS, bool KV8 = false> struct D32ArgsOf { using type = D32Args; };
+template <> struct D32ArgsOf<true, false> { using type = D32RowArgs; };
+template <bool ROWS> struct D32ArgsOf<ROWS, true> { using type = D32Kv8Args; };
 
 // WAVES physical waves, each owning VW consecutive atoms of the WAVES * VW the reference partition has; U = ring depth in
 // chunks (x fragments and weights of a chunk travel together); NT weight tiles per workgroup.
@@ -54,8 +59,8 @@ template <> struct D32ArgsOf<true> { using type = D32RowArgs; };
 // first.  Half the x bytes per weight byte at the same number of workgroups (NT doubles).
 template <int NT, int EPI, int WAVES, int VW, int U, bool W8, bool GS = false, bool ROWS = false>
 __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, const char* hwp, int hM, int hN, int hK, int hcpb,
-                                                           const typename D32ArgsOf<ROWS>::type a) {
-    static_assert(!ROWS || EPI == D32_ROPE_KV, "the row map is for ROPE_KV");
+                                                           const typename D32ArgsOf<ROWS, EPI == DEPI_ROPE_KV8>::type a) {
+    static_assert(!ROWS || depi_rope(EPI), "the row map is for ROPE_KV");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using WC = WChunk<W8>;
     constexpr int WLOC = WAVES * VW;                 // atoms of this workgroup
@@ -73,7 +78,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, cons
     const int c0 = ab[0], c1 = ab[VW];
 
     int tile[NT];
-    if (EPI == D32_ROPE_KV) {   // rotary tile pair: channels i and i + 64 of one head
+    if (depi_rope(EPI)) {   // rotary tile pair: channels i and i + 64 of one head
         tile[0] = (g >> 2) * 8 + (g & 3);
         tile[NT - 1] = tile[0] + 4;
     } else {
@@ -99,11 +104,11 @@ __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, cons
             for (int h = 0; h < 2; ++h) xf[u][mt][h] = *reinterpret_cast<const bf16x8*>(xq[h] + (int64_t)c * 4096 + mt * 2048);
     }
     // epilogue role of this wave: column tile emt, weight tile et (ROPE_KV: the pair)
-    constexpr int EW = EPI == D32_ROPE_KV ? MT : MT * NT;     // waves that run an epilogue
-    const int emt = wave & 1, et = EPI == D32_ROPE_KV ? 0 : ((wave >> 1) % NT);
+    constexpr int EW = depi_rope(EPI) ? MT : MT * NT;     // waves that run an epilogue
+    const int emt = wave & 1, et = depi_rope(EPI) ? 0 : ((wave >> 1) % NT);
     const int eb = fr + 16 * emt, erb = min(eb, M - 1);
     int pos = 0, plen = 0, eslot = eb, erslot = erb;   // cache slot of the epilogue row / of the clamped row
-    if (EPI == D32_ROPE_KV) {
+    if (depi_rope(EPI)) {
         pos = a.ctx_len[erb];
         plen = a.prompt_len[erb];
         if constexpr (ROWS) eslot = erslot = a.row_slot[erb];
@@ -126,7 +131,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, cons
 #pragma unroll
     for (int j = 0; j < 8; ++j) csv[j] = 0.f;
     const int en = min(tile[et], ntiles - 1) * 16 + fg * 4;
-    if (EPI == D32_ROPE_KV) {
+    if (depi_rope(EPI)) {
         const int i0 = (tile[0] & 7) * 16 + fg * 4;
         const float* cs = a.cs_table + ((int64_t)erslot * a.cs_stride + (pos - plen)) * 128;
         const f32x4 cv = *reinterpret_cast<const f32x4*>(cs + i0), sv = *reinterpret_cast<const f32x4*>(cs + 64 + i0);
@@ -217,13 +222,13 @@ __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, cons
         }
         return;
     }
-    static_assert(GS || (EPI == D32_ROPE_KV ? MT : MT * NT) <= WAVES, "one epilogue role per wave");
+    static_assert(GS || (depi_rope(EPI) ? MT : MT * NT) <= WAVES, "one epilogue role per wave");
     if (wave >= EW) return;
-    constexpr int ET = EPI == D32_ROPE_KV ? NT : 1;   // tiles this epilogue wave folds
+    constexpr int ET = depi_rope(EPI) ? NT : 1;   // tiles this epilogue wave folds
     f32x4 sum[ET];
 #pragma unroll
     for (int e = 0; e < ET; ++e) {
-        const int t = EPI == D32_ROPE_KV ? e : et;
+        const int t = depi_rope(EPI) ? e : et;
         // the narrow kernel's fold: wave order inside each half of the atoms, then the two halves added (GS: this workgroup's
         // atoms ARE one half; the slab add is the second level)
         constexpr int NH = GS ? 1 : 2;
@@ -247,7 +252,7 @@ __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, cons
         }
     }
     if (eb >= M) return;
-    if constexpr (EPI == D32_ROPE_KV) {
+    if constexpr (depi_rope(EPI)) {
         const int hh = tile[0] >> 3;                   // head index in [q heads | k heads | v heads]
         const int i0 = (tile[0] & 7) * 16 + fg * 4;    // channel in [0, 64)
         float lo[4], hi[4];
@@ -263,12 +268,23 @@ __global__ void __launch_bounds__(WAVES * 64) dec32_kernel(const char* hxp, cons
                 o0[j] = f2bf(lo[j] * csv[j] - hi[j] * csv[4 + j]);
                 o1[j] = f2bf(hi[j] * csv[j] + lo[j] * csv[4 + j]);
             }
+            if constexpr (EPI == DEPI_ROPE_KV8) {   // the codes of the bf16 values the bf16 cache would hold
+                if (hh >= a.heads) {
+                    const int kh = hh - a.heads;
+                    kv8_append_k(a.kv8.k + ((int64_t)eslot * a.kv_heads + kh) * a.s_max * 128, pos, i0, o0, o1, a.kv8.scale[kh]);
+                    return;
+                }
+            }
             kr_bf16* dst = hh < a.heads ? a.q_out + ((int64_t)eb * a.heads + hh) * 128
                                         : a.kcache + (((int64_t)eslot * a.kv_heads + (hh - a.heads)) * a.s_max + pos) * 128;
             *reinterpret_cast<bf16x4*>(dst + i0) = o0;
             *reinterpret_cast<bf16x4*>(dst + 64 + i0) = o1;
         } else {
             const int kvh = hh - a.heads - a.kv_heads;
+            if constexpr (EPI == DEPI_ROPE_KV8) {
+                kv8_append_v(a.kv8.vt + ((int64_t)eslot * a.kv_heads + kvh) * a.s_max * 128, pos, i0, lo, hi, a.kv8.scale[a.kv_heads + kvh]);
+                return;
+            }
             kr_bf16* vt = a.vtcache + (((int64_t)eslot * a.kv_heads + kvh) * (a.s_max >> 6) + (pos >> 6)) * (128 * 64) + kr_vt_off(0, pos & 63, 128);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -386,6 +402,22 @@ int launch32_rows(const kr_dec32& q, const D32RowArgs& a, int groups, kr_stream 
     return KR_OK;
 }
 
+// launch32_rows for the fp8 cache (ROPE_KV8), with the row map or without
+template <bool W8, bool ROWS>
+int launch32_kv8(const kr_dec32& q, const D32Kv8Args& a, int groups, kr_stream s) {
+    constexpr int NT = 2, WAVES = 8, VW = 1;
+    const int nchunks = q.K >> 6, share = (nchunks + WAVES - 1) / WAVES;
+    const size_t lds = (size_t)MT * WAVES * VW * NT * 1024;
+    auto go = [&](auto fn) {
+        fn<<<dim3(groups, 1), WAVES * 64, lds, kr_hs(s)>>>(reinterpret_cast<const char*>(q.xp), reinterpret_cast<const char*>(q.w_packed), q.M,
+                                                           q.N, q.K, nchunks, a);
+    };
+    if (share <= 3) go(&dec32_kernel<NT, DEPI_ROPE_KV8, WAVES, VW, 3, W8, false, ROWS>);
+    else go(&dec32_kernel<NT, DEPI_ROPE_KV8, WAVES, VW, 5, W8, false, ROWS>);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
 // row-major rows -> XP layout: thread = one 16-byte piece (row b, 8 consecutive k)
 __global__ void __launch_bounds__(256) pack_rows32_kernel(const kr_bf16* __restrict__ x, int64_t ldx, int M, int K, kr_bf16* __restrict__ xp) {
     const int kc = K >> 3, i = blockIdx.x * 256 + threadIdx.x;
@@ -406,7 +438,7 @@ extern "C" int kr_pack_rows32(const kr_bf16* x, int64_t ldx, int M, int K, kr_bf
     return KR_OK;
 }
 
-static int linear_decode32_impl(int mode, const kr_dec32* qp, const int32_t* row_slot, kr_stream s) {
+static int linear_decode32_impl(int mode, const kr_dec32* qp, const int32_t* row_slot, kr_stream s, const kr_kv8* kv8 = nullptr) {
     KR_CHECK_ARG(qp, "kr_linear_decode32: null args");
     const kr_dec32& q = *qp;
     KR_CHECK_ARG(q.xp && q.w_packed && ((uintptr_t)q.xp & 15) == 0, "kr_linear_decode32: null / unaligned pointer");
@@ -454,10 +486,20 @@ static int linear_decode32_impl(int mode, const kr_dec32* qp, const int32_t* row
             return nt2 ? launch32_q<2, D32_PLAIN>(q, a, (ntiles + 1) / 2, s) : launch32_q<1, D32_PLAIN>(q, a, ntiles, s);
         }
         case D32_ROPE_KV:
-            KR_CHECK_ARG(q.bias && q.cs_table && q.prompt_len && q.ctx_len && q.q_out && q.kcache && q.vtcache && q.cs_stride > 0,
+            KR_CHECK_ARG(q.bias && q.cs_table && q.prompt_len && q.ctx_len && q.q_out && (kv8 || (q.kcache && q.vtcache)) && q.cs_stride > 0,
                          "kr_linear_decode32: ROPE_KV pointers");
             KR_CHECK_ARG(q.N == (q.heads + 2 * q.kv_heads) * 128 && q.s_max % 64 == 0 && q.ksplit == 1 && q.waves_ref == 8,
                          "kr_linear_decode32: ROPE_KV needs head_dim 128, ksplit 1, waves_ref 8");
+            if (kv8) {
+                KR_CHECK_ARG(kv8->k && kv8->vt && kv8->scale && (((uintptr_t)kv8->k | (uintptr_t)kv8->vt) & 3) == 0,
+                             "kr_linear_decode32_kv8: null / unaligned cache");
+                D32Kv8Args ka{};
+                static_cast<D32Args&>(ka) = a;
+                ka.row_slot = row_slot;
+                ka.kv8 = Kv8{kv8->k, kv8->vt, kv8->scale};
+                if (row_slot) return q.w_scale ? launch32_kv8<true, true>(q, ka, ntiles / 2, s) : launch32_kv8<false, true>(q, ka, ntiles / 2, s);
+                return q.w_scale ? launch32_kv8<true, false>(q, ka, ntiles / 2, s) : launch32_kv8<false, false>(q, ka, ntiles / 2, s);
+            }
             if (row_slot) {
                 D32RowArgs ra{};
                 static_cast<D32Args&>(ra) = a;
@@ -478,4 +520,9 @@ extern "C" int kr_linear_decode32(int mode, const kr_dec32* qp, kr_stream s) {
 extern "C" int kr_linear_decode32_rows(int mode, const kr_dec32* qp, const int32_t* row_slot, kr_stream s) {
     KR_CHECK_ARG(mode == D32_ROPE_KV, "kr_linear_decode32_rows: mode %d (ROPE_KV only)", mode);
     return linear_decode32_impl(mode, qp, row_slot, s);
+}
+
+extern "C" int kr_linear_decode32_kv8(const kr_dec32* qp, const kr_kv8* kv, const int32_t* row_slot, kr_stream s) {
+    KR_CHECK_ARG(kv, "kr_linear_decode32_kv8: kv is NULL");
+    return linear_decode32_impl(D32_ROPE_KV, qp, row_slot, s, kv);
 }

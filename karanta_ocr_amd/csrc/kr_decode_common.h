@@ -75,6 +75,66 @@ __device__ __forceinline__ void apply_w_scale(const float* w_scale, int n, f32x4
     }
 }
 
+// ---------------------------------------------------------------- fp8 (e4m3fn) KV cache (include/karanta_hip.h, kr_kv8)
+// DEPI_ROPE_KV8: ROPE_KV whose K / V go to an fp8 cache.  A value of the EPI template parameter only (the fp8-cache entry points
+// pick it); the public mode stays KR_DEC_ROPE_KV.
+constexpr int DEPI_ROPE_KV8 = 5;
+constexpr bool depi_rope(int epi) { return epi == DEPI_ROPE_KV || epi == DEPI_ROPE_KV8; }
+
+// The cache pointers of an fp8-cache launch as they travel in kernel arguments (kr_kv8 by value).
+struct Kv8 {
+    uint8_t* k; uint8_t* vt; const float* scale;
+};
+
+// THE quantisation rule: a bf16-rounded value x, divided by the scale in f32 (a correctly rounded division: tests/kv_fp8_ref.py
+// restates it in numpy), clamped to +-448 explicitly, converted with v_cvt_pk_fp8_f32 (RNE).  `clamped` counts the values the
+// clamp changed.  v_med3_f32 returns the minimum of the two bounds for a NaN input: -448, a finite code.
+__device__ __forceinline__ float kv8_clamp(float x, float sc, int& clamped) {
+    const float y = x / sc;
+    const float c = __builtin_amdgcn_fmed3f(y, -448.f, 448.f);
+    clamped += (c != y) ? 1 : 0;
+    return c;
+}
+// four values -> four codes in one register, byte j = value j
+__device__ __forceinline__ unsigned kv8_pack4(float x0, float x1, float x2, float x3, float sc, int& clamped) {
+    int w = 0;
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(x0, sc, clamped), kv8_clamp(x1, sc, clamped), w, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(x2, sc, clamped), kv8_clamp(x3, sc, clamped), w, true);
+    return (unsigned)w;
+}
+__device__ __forceinline__ uint8_t kv8_code(float x, float sc, int& clamped) {
+    return (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(x, sc, clamped), 0.f, 0, false) & 0xff);
+}
+// eight codes (two registers, ascending bytes) -> eight bf16, exactly (moved as 32-bit words: see WChunk<true>::frag)
+__device__ __forceinline__ bf16x8 kv8_to_bf16x8(unsigned w0, unsigned w1) {
+    u32x4 o;
+    o[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w0, 1.0f, false));
+    o[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w0, 1.0f, true));
+    o[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w1, 1.0f, false));
+    o[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w1, 1.0f, true));
+    return __builtin_bit_cast(bf16x8, o);
+}
+
+// The ROPE_KV8 append of one lane: channels i0 .. i0+3 and 64+i0 .. 64+i0+3 of row `pos` of a (slot, kv head) whose K rows start
+// at `krow0` and whose V^T blocks at `vt0`.  K: two packed 4-byte stores; V^T: byte stores at stride 32 (kr_vt_off).
+__device__ __forceinline__ void kv8_append_k(uint8_t* krow0, int pos, int i0, const bf16x4& o0, const bf16x4& o1, float sc) {
+    int n = 0;
+    uint8_t* dst = krow0 + (int64_t)pos * 128;
+    *reinterpret_cast<unsigned*>(dst + i0) = kv8_pack4(bf2f(o0[0]), bf2f(o0[1]), bf2f(o0[2]), bf2f(o0[3]), sc, n);
+    *reinterpret_cast<unsigned*>(dst + 64 + i0) = kv8_pack4(bf2f(o1[0]), bf2f(o1[1]), bf2f(o1[2]), bf2f(o1[3]), sc, n);
+}
+__device__ __forceinline__ void kv8_append_v(uint8_t* vt0, int pos, int i0, const float (&lo)[4], const float (&hi)[4], float sc) {
+    int n = 0;
+    uint8_t* vt = vt0 + (int64_t)(pos >> 6) * (128 * 64) + kr_vt_off(0, pos & 63, 128);
+    // lo / hi are bf16-rounded already (the projection output is a bf16 tensor)
+    const unsigned a = kv8_pack4(lo[0], lo[1], lo[2], lo[3], sc, n), b = kv8_pack4(hi[0], hi[1], hi[2], hi[3], sc, n);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        vt[(i0 + j) * 32] = (uint8_t)(a >> (8 * j));
+        vt[(64 + i0 + j) * 32] = (uint8_t)(b >> (8 * j));
+    }
+}
+
 __device__ __forceinline__ void better(float& bv, int& bi, float v, int i) {
     if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
 }

@@ -5,6 +5,7 @@
 //                    way, 16 KB at hd 128.  A workgroup takes whole pieces: 16 B per lane, up to four loads per lane in flight
 //                    before the first store, and what it loaded is stored to EVERY destination of the group, so the source is
 //                    read once however many children there are.  The grid is capped and strides over the pieces.
+//                    kr_kv_fork8 (the fp8 cache): the same kernel over one-byte elements, a piece is hd x 64 bytes.
 // The plan (kr_fork_plan, host memory) is validated and flattened on the host into the kernel's arguments: no device table,
 // no copy, no allocation.  All offsets are 64-bit: a layer of the 2B cache at 32 slots x 16384 rows is 268 M elements.
 #include "kr_common.h"
@@ -91,16 +92,18 @@ __global__ void __launch_bounds__(FORK_THREADS) kv_fork_kernel(const ForkArgs a)
 
 }  // namespace
 
-extern "C" int kr_kv_fork(kr_bf16* kcache, kr_bf16* vtcache, int64_t k_layer_stride, int64_t k_slot_stride, int64_t k_head_stride,
-                          int64_t vt_layer_stride, int64_t vt_slot_stride, int64_t vt_head_stride, int layers, int kv_heads,
-                          int hd, int slots, int s_max, const kr_fork_plan* plan, kr_stream s) {
+// EPV = elements per 16-byte vector: 8 (kr_kv_fork, bf16) or 16 (kr_kv_fork8, the fp8 cache's bytes).  The kernel moves vectors and
+// does not know the difference.
+static int fork_impl(void* kcache, void* vtcache, int64_t k_layer_stride, int64_t k_slot_stride, int64_t k_head_stride,
+                     int64_t vt_layer_stride, int64_t vt_slot_stride, int64_t vt_head_stride, int layers, int kv_heads,
+                     int hd, int slots, int s_max, const kr_fork_plan* plan, const int EPV, kr_stream s) {
     KR_CHECK_ARG(kcache && vtcache && plan, "kr_kv_fork: null pointer");
-    KR_CHECK_ARG(layers > 0 && kv_heads > 0 && hd > 0 && hd % 8 == 0 && slots > 0 && slots <= KR_FORK_MAX_SLOTS && s_max > 0
-                 && s_max % 64 == 0, "kr_kv_fork: bad geometry (hd %% 8, 1 <= slots <= %d, s_max %% 64)", KR_FORK_MAX_SLOTS);
+    KR_CHECK_ARG(layers > 0 && kv_heads > 0 && hd > 0 && hd % EPV == 0 && slots > 0 && slots <= KR_FORK_MAX_SLOTS && s_max > 0
+                 && s_max % 64 == 0, "kr_kv_fork: bad geometry (hd %% %d, 1 <= slots <= %d, s_max %% 64)", EPV, KR_FORK_MAX_SLOTS);
     KR_CHECK_ARG(((uintptr_t)kcache | (uintptr_t)vtcache) % 16 == 0, "kr_kv_fork: caches must be 16-byte aligned");
     const int64_t span = (int64_t)s_max * hd;     // elements of one (layer, slot, head) in either cache
     const int64_t strides[6] = {k_layer_stride, k_slot_stride, k_head_stride, vt_layer_stride, vt_slot_stride, vt_head_stride};
-    for (int i = 0; i < 6; ++i) KR_CHECK_ARG(strides[i] > 0 && strides[i] % 8 == 0, "kr_kv_fork: strides must be multiples of 8 elements");
+    for (int i = 0; i < 6; ++i) KR_CHECK_ARG(strides[i] > 0 && strides[i] % EPV == 0, "kr_kv_fork: strides must be multiples of %d elements", EPV);
     KR_CHECK_ARG(k_head_stride >= span && vt_head_stride >= span, "kr_kv_fork: head stride below s_max x hd");
     KR_CHECK_ARG(k_slot_stride >= (int64_t)kv_heads * k_head_stride && vt_slot_stride >= (int64_t)kv_heads * vt_head_stride,
                  "kr_kv_fork: slot stride below kv_heads x head stride");
@@ -140,15 +143,29 @@ extern "C" int kr_kv_fork(kr_bf16* kcache, kr_bf16* vtcache, int64_t k_layer_str
     a.dst0[plan->n_groups] = nd;
     a.kc = reinterpret_cast<uint4*>(kcache);
     a.vc = reinterpret_cast<uint4*>(vtcache);
-    a.k_sl = k_layer_stride / 8, a.k_ss = k_slot_stride / 8, a.k_sh = k_head_stride / 8;
-    a.v_sl = vt_layer_stride / 8, a.v_ss = vt_slot_stride / 8, a.v_sh = vt_head_stride / 8;
+    a.k_sl = k_layer_stride / EPV, a.k_ss = k_slot_stride / EPV, a.k_sh = k_head_stride / EPV;
+    a.v_sl = vt_layer_stride / EPV, a.v_ss = vt_slot_stride / EPV, a.v_sh = vt_head_stride / EPV;
     a.kv_heads = kv_heads;
-    a.piece_vecs = hd * 8;                // 64 tokens x hd bf16 / 16 B
-    a.row_vecs = hd / 8;
+    a.piece_vecs = hd * 64 / EPV;         // 64 tokens x hd elements / 16 B
+    a.row_vecs = hd / EPV;
     a.n_groups = plan->n_groups;
     a.total = (int32_t)total;
     const int grid = (int)(total < FORK_MAX_BLOCKS ? total : FORK_MAX_BLOCKS);
     kv_fork_kernel<<<grid, FORK_THREADS, 0, kr_hs(s)>>>(a);
     KR_CHECK_LAUNCH();
     return KR_OK;
+}
+
+extern "C" int kr_kv_fork(kr_bf16* kcache, kr_bf16* vtcache, int64_t k_layer_stride, int64_t k_slot_stride, int64_t k_head_stride,
+                          int64_t vt_layer_stride, int64_t vt_slot_stride, int64_t vt_head_stride, int layers, int kv_heads,
+                          int hd, int slots, int s_max, const kr_fork_plan* plan, kr_stream s) {
+    return fork_impl(kcache, vtcache, k_layer_stride, k_slot_stride, k_head_stride, vt_layer_stride, vt_slot_stride, vt_head_stride,
+                     layers, kv_heads, hd, slots, s_max, plan, 8, s);
+}
+
+extern "C" int kr_kv_fork8(uint8_t* kcache, uint8_t* vtcache, int64_t k_layer_stride, int64_t k_slot_stride, int64_t k_head_stride,
+                           int64_t vt_layer_stride, int64_t vt_slot_stride, int64_t vt_head_stride, int layers, int kv_heads,
+                           int hd, int slots, int s_max, const kr_fork_plan* plan, kr_stream s) {
+    return fork_impl(kcache, vtcache, k_layer_stride, k_slot_stride, k_head_stride, vt_layer_stride, vt_slot_stride, vt_head_stride,
+                     layers, kv_heads, hd, slots, s_max, plan, 16, s);
 }

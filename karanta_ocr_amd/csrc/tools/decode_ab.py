@@ -6,7 +6,9 @@
 A variant is a comma-separated list of Engine attribute overrides, e.g. `base`, `attn_fused_merge=1`,
 `attn_fused_merge=1,n_split=4`; `resident=<MB>[:kind@gain+kind@gain]` sets the Infinity-Cache residency budget of the narrow
 launches' weights (Engine.set_resident_budget; kinds qkv, o, down; without kinds: the engine's measured gains), e.g.
-`resident=177:qkv` = qkv alone, `resident=240:qkv@0.07+o@0.02` = the planner on those gains.  The weight arena is filled with random bf16 values ON THE DEVICE (timing does not depend
+`resident=177:qkv` = qkv alone, `resident=240:qkv@0.07+o@0.02` = the planner on those gains; `kv_cache_dtype=fp8` builds that variant's
+engine with the fp8 KV cache (`--kv-dtype fp8`: every variant that does not say otherwise), e.g. `base kv_cache_dtype=fp8` = bf16
+against fp8 cache in interleaved rounds.  The weight arena is filled with random bf16 values ON THE DEVICE (timing does not depend
 on the values), the decode state is set up directly (every sequence at context `ctx`), and each variant's decode step
 is captured in a hipGraph and replayed `steps` times between two HIP events; rounds alternate between the variants.
 Prints per variant: median and min ms/step, and the HBM-roofline fraction of the step."""
@@ -49,6 +51,7 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--weights", default="bf16")
+    ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"), help="KV cache of the variants without a kv_cache_dtype= of their own")
     ap.add_argument("--chain", default=None,
                     help="instead of whole steps: time ONE kind of launch as a chain over the layers' weights (graph of reps x "
                          "layers launches; the per-launch figure includes the dependent-launch gap): comma-separated list of "
@@ -84,7 +87,11 @@ def main():
         cls = ExperimentEngine if (EXPERIMENT_KEYS & set(over) or EXPERIMENT_ENV & set(env)) else Engine
         over.pop("experiment", None)
         eng = cls(cfg, max_batch=B, s_max=s_max, max_patches=64, max_prompt_tokens=64,
-                  decode_splits=int(over.pop("n_split", 16)), weight_dtype=a.weights)
+                  decode_splits=int(over.pop("n_split", 16)), weight_dtype=a.weights,
+                  **({"kv_cache_dtype": "fp8"} if over.pop("kv_cache_dtype", a.kv_dtype).startswith("fp8") else {}))
+        if eng.kv8:     # codes below the NaN encodings, every value finite (timing does not depend on them)
+            eng.kcache.copy_(torch.randint(0, 0x78, eng.kcache.shape, dtype=torch.uint8, device=eng.device))
+            eng.vtcache.copy_(torch.randint(0, 0x78, eng.vtcache.shape, dtype=torch.uint8, device=eng.device))
         over.pop("steps_per_graph", None)     # handled where the graph is captured
         if "resident" in over:                # resident=<MB>[:kind@gain+kind@gain]: Infinity-Cache budget (and the planner's gains)
             mb, _, kinds = over.pop("resident").partition(":")
@@ -197,9 +204,9 @@ def main():
             L.kr_event_elapsed_ms(e0, e1, C.byref(ms))
             if r:                                  # round 0 warms up
                 times[spec].append(ms.value / a.steps)
-    kvb = cfg.text.kv_bytes_per_token
-    roof_ms = (cfg.decoder_weight_bytes(a.weights) + B * (a.ctx + a.steps / 2) * kvb) / 8e12 * 1e3
-    for spec, _ in engines:
+    for spec, eng in engines:
+        kvb = cfg.text.kv_bytes_per_token // (2 if eng.kv8 else 1)       # the bytes THIS variant's step streams
+        roof_ms = (cfg.decoder_weight_bytes(a.weights) + B * (a.ctx + a.steps / 2) * kvb) / 8e12 * 1e3
         t = np.asarray(times[spec])
         print(f"{spec:50s} median {np.median(t):.4f} ms/step  min {t.min():.4f}  max {t.max():.4f}  ({roof_ms / np.median(t) * 100:.1f} % of the 8 TB/s step roofline)",
               flush=True)
@@ -216,15 +223,16 @@ def chains(a, engines, reset):
         t, w = eng.cfg.text, eng.w
         H, KVH, hd = t.num_heads, t.num_kv_heads, t.head_dim
 
-        def one(kind, i):
+        def one(kind, i, eng=eng, t=t, w=w, H=H, KVH=KVH, hd=hd):      # bound now: called after the loop has moved on
             p = f"llm.{i}."
             kc, vc = ptr(eng.kcache[i]), ptr(eng.vtcache[i])
+            k8 = {"kv8_layer": i} if eng.kv8 else {}
             if kind == "qkv":
                 eng._dec_narrow(DEC_ROPE_KV, eng.d_x, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), norm_w=w.view(p + "ln1.w"),
-                                part_in=eng.d_part, x_out=eng.d_x2, kc=kc, vc=vc, **eng._w8kw(p + "qkv.w"))
+                                part_in=eng.d_part, x_out=eng.d_x2, kc=kc, vc=vc, **k8, **eng._w8kw(p + "qkv.w"))
             elif kind == "qkv0":                   # no pending slabs: the prologue reads x only
                 eng._dec_narrow(DEC_ROPE_KV, eng.d_x, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), norm_w=w.view(p + "ln1.w"),
-                                kc=kc, vc=vc, **eng._w8kw(p + "qkv.w"))
+                                kc=kc, vc=vc, **k8, **eng._w8kw(p + "qkv.w"))
             elif kind.startswith("down") and len(kind) > 4 and not kind.startswith("down32"):      # down<ksplit>[w<waves>]: e.g. down3, down4w8
                 import re
                 m = re.fullmatch(r"down(\d)(?:w(\d+))?", kind)
@@ -243,7 +251,7 @@ def chains(a, engines, reset):
             elif kind == "qkvd":
                 eng._dec_narrow(DEC_ROPE_KV, eng.d_h, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), kc=kc, vc=vc, **eng._w8kw(p + "qkv.w"))
             elif kind == "qkv32":
-                eng._dec32(DEC_ROPE_KV, eng.d_h, w.view(p + "qkv.w"), B, 8, bias=w.view(p + "qkv.b"), kc=kc, vc=vc, **eng._w8kw(p + "qkv.w"))
+                eng._dec32(DEC_ROPE_KV, eng.d_h, w.view(p + "qkv.w"), B, 8, bias=w.view(p + "qkv.b"), kc=kc, vc=vc, **k8, **eng._w8kw(p + "qkv.w"))
             elif kind == "merge32":
                 L.kr_attn_decode_merge32(ptr(eng.d_ws), ptr(eng.d_o), B, H, hd, eng.n_split, eng.s)
             elif kind in ("o32", "o32t1", "o32t2"):
@@ -261,6 +269,9 @@ def chains(a, engines, reset):
                 eng._dec32(DEC_PLAIN, eng.d_act, w.view(p + "down.w"), B, eng.down_waves_small, ksplit=2, out_f32=acc if gs else acc[0],
                            atomic_out=True, group_split=gs, tiles_per_wg={"down32a": 0, "down32gs": 0, "down32gs2": 2, "down32gs4": 4}[kind],
                            **({} if gs else eng._w8kw(p + "down.w")))
+            elif kind == "attn" and eng.kv8:
+                L.kr_attn_decode_slots_kv8(ptr(eng.d_q), eng._kv8(i), ptr(eng.d_ctx), ptr(eng.d_fin), ptr(eng.d_ws), B, H, KVH, hd, eng.s_max,
+                                           eng.n_split, hd ** -0.5, eng.s)
             elif kind == "attn":
                 L.kr_attn_decode_fused(ptr(eng.d_q), kc, vc, ptr(eng.d_ctx), 0, ptr(eng.d_ws), 0, B, H, KVH, hd, eng.s_max, eng.n_split,
                                        hd ** -0.5, eng.s)
@@ -270,7 +281,7 @@ def chains(a, engines, reset):
                 eng._dec_narrow(DEC_PLAIN, eng.d_o, w.view(p + "o.w"), B, out=eng.d_x, res=eng.d_x, waves=8, **eng._w8kw(p + "o.w"))
             elif "+" in kind:                      # a group of launches per layer, e.g. attn+merge+o
                 for k in kind.split("+"):
-                    one(k, i)
+                    eng._one(k, i)
             elif kind == "oheads":
                 w8o, sco = eng._w8(p + "o.w")
                 L.kr_oproj_heads(ptr(eng.d_ws), eng.n_split, ptr(w8o if w8o is not None else w.view(p + "o.w")), ptr(sco),
@@ -287,33 +298,49 @@ def chains(a, engines, reset):
             else:
                 raise SystemExit(f"unknown chain kind {kind}")
 
+        eng._one = one
+    # every (variant, kind) captured first, then timed in interleaved rounds: round r runs every variant once, so a drift of the
+    # machine hits them alike; per launch group: median, min and max over the rounds
+    reps = 4
+    graphs = {}
+    for spec, eng in engines:
         reset(eng)
+        nl = eng.cfg.text.num_layers
         for kind in a.chain.split(","):
-            reps = 4
             with torch.cuda.stream(eng.stream):
-                for i in range(t.num_layers):
-                    one(kind, i)                      # eager once (function attributes)
+                for i in range(nl):
+                    eng._one(kind, i)                      # eager once (function attributes)
                 eng.stream.synchronize()
                 g = C.c_void_p()
                 L.kr_graph_begin_capture(eng.s)
                 try:
                     for _ in range(reps):
-                        for i in range(t.num_layers):
-                            one(kind, i)
+                        for i in range(nl):
+                            eng._one(kind, i)
                 finally:
                     L.kr_graph_end_capture(eng.s, C.byref(g))
-                best = None
-                for _ in range(a.rounds):
-                    L.kr_event_record(e0, eng.s)
-                    L.kr_graph_launch(g, eng.s)
-                    L.kr_event_record(e1, eng.s)
-                    L.kr_event_synchronize(e1)
-                    ms = C.c_float()
-                    L.kr_event_elapsed_ms(e0, e1, C.byref(ms))
-                    best = ms.value if best is None else min(best, ms.value)
-                L.kr_graph_destroy(g)
-            print(f"{spec:30s} chain {kind:16s} {best * 1e3 / (reps * t.num_layers):8.2f} us per launch group", flush=True)
-
+                graphs[(spec, kind)] = g
+    times = {k: [] for k in graphs}
+    for r in range(a.rounds + 1):
+        for kind in a.chain.split(","):
+            for spec, eng in engines:
+                L.kr_event_record(e0, eng.s)
+                L.kr_graph_launch(graphs[(spec, kind)], eng.s)
+                L.kr_event_record(e1, eng.s)
+                L.kr_event_synchronize(e1)
+                ms = C.c_float()
+                L.kr_event_elapsed_ms(e0, e1, C.byref(ms))
+                if r:                                      # round 0 warms up
+                    times[(spec, kind)].append(ms.value * 1e3 / (reps * eng.cfg.text.num_layers))
+    for (spec, kind), g in graphs.items():
+        L.kr_graph_destroy(g)
+        t = np.asarray(times[(spec, kind)])
+        eng = dict(engines)[spec]
+        extra = ""
+        if kind == "attn":      # the K / V bytes of the launch over its median time
+            kvb = eng.cfg.text.kv_bytes_per_token // eng.cfg.text.num_layers // (2 if eng.kv8 else 1)
+            extra = f"  {B * (a.ctx + 1) * kvb / 1e6:6.1f} MB of K/V: {B * (a.ctx + 1) * kvb / np.median(t) / 1e6:.2f} TB/s"
+        print(f"{spec:30s} chain {kind:16s} median {np.median(t):8.2f} us per launch group  min {t.min():8.2f}  max {t.max():8.2f}{extra}", flush=True)
 
 if __name__ == "__main__":
     main()

@@ -23,8 +23,9 @@ import torch
 from . import image_processing as IP
 from . import positions as POS
 from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_NONE, EPI_SILU_MUL8, KarantaHipError, Spec, fork_plan,
-                   lib, narrow_opts, ptr)
+                   kv8, kvq_plan, lib, narrow_opts, ptr)
 from .config import ModelConfig
+from .weights import kv_cache_dtype_name, kv_scale_table, kv_scales_from_checkpoint
 from .device_weights import DeviceWeights, _align, narrow_weight_bytes, plan_resident
 from .request import GenerateResult, PageRequest, SpecConfig, children
 from .sampler import DeviceGuide, Sampler
@@ -78,6 +79,7 @@ class Admission:
     n_pages: int = 0
     rows: list = field(default_factory=list)    # `children` of the admission's pages, made once per admission
     forks: list = field(default_factory=list)   # (source slot, prompt length, [sibling slots]) per page with n > 1
+    kvq: list = field(default_factory=list)     # (slot, prompt length) per prefilled page: what kr_kv_quantize converts (fp8 KV cache)
 
     def spans(self, width: int):
         """(first sequence, first slot, slots) of what an activation does per stretch of slots: a whole batch is ONE stretch of
@@ -97,7 +99,7 @@ class Engine:
     def __init__(self, cfg: ModelConfig, device: str = "cuda:0", max_batch: int = 8, s_max: int = 4096,
                  max_patches: int = 8 * 5476, max_prompt_tokens: int = 8 * 2048, decode_splits: int = 16,
                  weight_dtype: str = "bf16", fp8_activations: Optional[bool] = None, admission_cus: Optional[int] = None,
-                 speculative: Optional[SpecConfig] = None, ic_resident_mb: Optional[int] = None):
+                 speculative: Optional[SpecConfig] = None, ic_resident_mb: Optional[int] = None, kv_cache_dtype: str = "auto"):
         if not torch.cuda.is_available():
             raise KarantaHipError("no HIP device: the karanta MI355X engine has no CPU fallback")
         self.L = lib()
@@ -148,6 +150,12 @@ class Engine:
         self.persist_blocks = int(os.environ.get("KARANTA_PERSIST_BLOCKS", "512"))  # 2 persistent workgroups per CU (swept: 256..1024)
         self._refuse_retired_switches()
         v, t = cfg.vision, cfg.text
+        # --kv-cache-dtype: "auto" = bfloat16; "fp8" = "fp8_e4m3": e4m3 codes with one f32 scale per (layer, K or V, kv head)
+        self.kv_cache_dtype = kv_cache_dtype_name(kv_cache_dtype)
+        self.kv8 = self.kv_cache_dtype == "fp8"
+        if self.kv8 and t.head_dim != 128:
+            raise KarantaHipError(f"kv_cache_dtype fp8 needs a text head_dim of 128, this model has {t.head_dim}: the fp8 cache's "
+                                  "quantise, append and attention kernels are written for 128-byte K rows")
         if v.head_dim not in (80, 128) or t.head_dim != 128:
             raise KarantaHipError(f"unsupported head dims vit={v.head_dim} llm={t.head_dim}")
         self.w = DeviceWeights(cfg, self.device, weight_dtype)
@@ -217,8 +225,18 @@ class Engine:
             self.p_as = z(M, dtype=torch.float32)
         self.gemm_scratch = z(GEMM_SCRATCH_BYTES // 4, dtype=torch.float32)   # kr_gemm_bf16_ws (KR_GEMM_SCRATCH_BYTES)
         # KV cache (zero-initialised: masked keys must be finite)
-        self.kcache = z(t.num_layers, B, t.num_kv_heads, self.s_max, t.head_dim)
-        self.vtcache = z(t.num_layers, B, t.num_kv_heads, self.s_max // 64, t.head_dim, 64)
+        kv_dtype = torch.uint8 if self.kv8 else BF16       # fp8: code 0 is 0.0, the zero-initialised cache is still finite padding
+        self.kcache = z(t.num_layers, B, t.num_kv_heads, self.s_max, t.head_dim, dtype=kv_dtype)
+        self.vtcache = z(t.num_layers, B, t.num_kv_heads, self.s_max // 64, t.head_dim, 64, dtype=kv_dtype)
+        if self.kv8:
+            # the prefill and its attention stay on bf16: they write and read ONE layer of bf16 scratch (the strides of a layer of
+            # the bf16 cache, so the prefill plan is unchanged), which kr_kv_quantize converts into layer i after layer i's attention
+            self.p_kscratch = z(B, t.num_kv_heads, self.s_max, t.head_dim)
+            self.p_vtscratch = z(B, t.num_kv_heads, self.s_max // 64, t.head_dim, 64)
+            self.d_kv_scale = torch.ones(t.num_layers, 2, t.num_kv_heads, dtype=torch.float32, device=dev)   # static: graphs read it
+            self.d_kv_clamped = z(1, dtype=torch.int32)
+            self.h_kv_clamped = torch.zeros(1, dtype=torch.int32).pin_memory()    # its host mirror, refreshed behind every admission
+            self.kv_scale_source = "default (1.0)"
         # decode state
         self.d_x = z(R, t.hidden_size)
         self.d_x2 = z(R, t.hidden_size)  # the other residual buffer (deferred split-K ping-pong)
@@ -322,8 +340,37 @@ class Engine:
     def _waves(nchunks: int) -> int:
         return 16 if nchunks >= 64 else 8 if nchunks >= 16 else 4
 
-    def load_weights(self, weights: Dict[str, np.ndarray]):
+    # ------------------------------------------------------------------ fp8 KV cache
+    def set_kv_scales(self, k, v, source: str = "set_kv_scales"):
+        """The scales of the fp8 KV cache: k and v are [L] or [L, KVH] arrays, a code stands for code x scale.  They apply to what
+        enters the cache from now on: set them before the first admission."""
+        if not self.kv8:
+            raise KarantaHipError("set_kv_scales: the KV cache is bfloat16 (kv_cache_dtype=\"fp8\" quantises it)")
+        t = self.cfg.text
+        self.d_kv_scale.copy_(torch.from_numpy(kv_scale_table(k, v, t.num_layers, t.num_kv_heads)).to(self.device))
+        self.kv_scale_source = source
+
+    @property
+    def kv_clamped(self) -> int:
+        """Elements the COMPLETED admissions clamped to +-448 x scale on their way into the fp8 cache (kr_kv_quantize's counter, as
+        of the last admission whose stream has been waited for: generate, admit, admit_end).  No synchronisation here."""
+        return int(self.h_kv_clamped[0]) if self.kv8 else 0
+
+    def kv_cache_bytes(self) -> int:
+        return self.kcache.numel() * self.kcache.element_size() + self.vtcache.numel() * self.vtcache.element_size()
+
+    def _kv8(self, i: int):
+        """kr_kv8* of layer i."""
+        return kv8(ptr(self.kcache[i]), ptr(self.vtcache[i]), ptr(self.d_kv_scale[i]))
+
+    def load_weights(self, weights: Dict[str, np.ndarray], log=None):
         self.w.load(weights)
+        if self.kv8:      # a checkpoint with a kv_cache_scheme ships one k_scale / v_scale per layer: broadcast over the kv heads
+            sc = kv_scales_from_checkpoint(weights, self.cfg)
+            if sc is not None:
+                self.set_kv_scales(*sc, source="checkpoint (self_attn.k_scale / v_scale)")
+            if log is not None:
+                log(f"fp8 KV cache scales: {self.kv_scale_source}")
 
     # ------------------------------------------------------------------ small launch helpers
     def _gemm(self, A, W, C_, M, bias=None, res=None, epi=EPI_NONE, packed=False, w8=None, w_scale=None):
@@ -358,13 +405,21 @@ class Engine:
 
     def _dec_narrow(self, mode, x, W, M, out=None, out_f32=None, bias=None, norm_w=None, res=None, waves=8, ksplit=1,
                     part_in=None, x_out=None, kc=0, vc=0, w8=None, w_scale=None, zero=None, atomic_out=False,
-                    resident=False):
+                    resident=False, kv8_layer=None):
         """kr_linear_decode_narrow: one workgroup per tile (pair); ksplit > 1 = deferred split-K sums in out_f32.
         w8 / w_scale: the fp8 copy of W and its row scales (kr_linear_decode_narrow_fp8).  zero (an f32 tensor the launch
         also zeroes), atomic_out, resident (w_resident: the weights stay in the Infinity Cache): the launch's kr_narrow_opts."""
         t = self.cfg.text
         N, K = W.shape
         o = out if out is not None else out_f32
+        if kv8_layer is not None:     # the qkv launch into the fp8 cache (ROPE_KV8): same launch, the cache as a kr_kv8
+            self.L.kr_linear_decode_narrow_kv8(
+                ptr(x), x.stride(0), ptr(part_in), int(part_in.shape[0]) if part_in is not None else 0, ptr(x_out),
+                x_out.stride(0) if x_out is not None else 0, ptr(w8 if w8 is not None else W), ptr(w_scale), ptr(bias), ptr(norm_w),
+                t.rms_norm_eps, M, N, K, waves, ptr(self.d_cs), self.max_new, ptr(self.d_plen), ptr(self.d_ctx), ptr(self.d_q),
+                self._kv8(kv8_layer), t.num_heads, t.num_kv_heads, self.s_max,
+                narrow_opts(ptr(zero), zero.numel() * 4 if zero is not None else 0, atomic_out, w_resident=resident), self.s)
+            return
         head = (mode, ptr(x), x.stride(0), ptr(part_in), int(part_in.shape[0]) if part_in is not None else 0, ptr(x_out),
                 x_out.stride(0) if x_out is not None else 0)
         args = (ptr(bias), ptr(norm_w), t.rms_norm_eps, ptr(res), res.stride(0) if res is not None else 0, ptr(out),
@@ -377,7 +432,7 @@ class Engine:
             self.L.kr_linear_decode_narrow(*head, ptr(W), *args)
 
     def _dec32(self, mode, xp, W, M, waves_ref, out=None, out_f32=None, bias=None, res=None, ksplit=1, atomic_out=False, zero=None,
-               kc=0, vc=0, w8=None, w_scale=None, tiles_per_wg=0, group_split=False, row_slot=None):
+               kc=0, vc=0, w8=None, w_scale=None, tiles_per_wg=0, group_split=False, row_slot=None, kv8_layer=None):
         """kr_linear_decode32: the decode linears of a 17..32-row batch on PACKED activations (xp: kr_pack_rows32 layout, written
         by kr_decode_resnorm32 / kr_attn_decode_merge32 / the gate/up launch with DEC_OUT_XP), with the K partition of the
         <= 16-row launch of the same layer (waves_ref, ksplit): row for row the bits that launch produces."""
@@ -390,7 +445,9 @@ class Engine:
                   zero.numel() * 4 if zero is not None else 0,
                   ptr(self.d_cs), self.max_new, ptr(self.d_plen), ptr(self.d_ctx), ptr(self.d_q), kc or None, vc or None,
                   t.num_heads, t.num_kv_heads, self.s_max)
-        if row_slot is not None:    # speculative step: cache and rotary row by the row's slot (kr_linear_decode32_rows)
+        if kv8_layer is not None:   # the qkv launch into the fp8 cache (ROPE_KV8), with the row map of a speculative step or without
+            self.L.kr_linear_decode32_kv8(C.byref(a), self._kv8(kv8_layer), ptr(row_slot), self.s)
+        elif row_slot is not None:    # speculative step: cache and rotary row by the row's slot (kr_linear_decode32_rows)
             self.L.kr_linear_decode32_rows(mode, C.byref(a), ptr(row_slot), self.s)
         else:
             self.L.kr_linear_decode32(mode, C.byref(a), self.s)
@@ -570,7 +627,7 @@ class Engine:
             cs[b, :, : t.head_dim // 2], cs[b, :, t.head_dim // 2:] = c_[:, : t.head_dim // 2], s_[:, : t.head_dim // 2]
         forks = [(slots[first[i]], page_lens[i], slots[first[i] + 1:first[i + 1]]) for i in range(len(pages)) if ns[i] > 1]
         return Admission(B, slots, whole_batch, lens, M, src, cos, sin, deltas, plan, last_rows, cs, n_image_tokens_total,
-                         n_pages=len(pages), rows=rows, forks=forks)
+                         n_pages=len(pages), rows=rows, forks=forks, kvq=[(slots[f], n) for f, n in zip(first[:-1], page_lens)])
 
     def _vit_and_prepare(self, pages: Sequence[PageRequest], pixel_values_device=None, slots: Optional[Sequence[int]] = None,
                          budgets: Optional[Sequence[int]] = None, rows: Optional[list] = None) -> Admission:
@@ -610,13 +667,19 @@ class Engine:
                 p = f"llm.{i}."
                 L.kr_rmsnorm(ptr(self.p_x), d, ptr(w.view(p + "ln1.w")), ptr(self.p_h), M, d, t.rms_norm_eps, s)
                 self._gemm(self.p_h, w.view(p + "qkv.w"), self.p_qkv, M, bias=w.view(p + "qkv.b"), packed=True, **self._w8kw(p + "qkv.w"))
-                kc, vc = self.kcache[i], self.vtcache[i]       # [max_batch, kv heads, ...]: the plan's rows count from slot 0
+                # [max_batch, kv heads, ...]: the plan's rows count from slot 0.  fp8 cache: the one-layer bf16 scratch
+                kc, vc = (self.p_kscratch, self.p_vtscratch) if self.kv8 else (self.kcache[i], self.vtcache[i])
                 self._attention(self.p_qkv, t.q_dim, t.q_dim + t.kv_dim, self.p_cos, self.p_sin, dp, self.p_q, kc, kc.stride(1),
                                 vc, vc.stride(1), self.p_o, t.num_heads, t.num_kv_heads, t.head_dim, causal=True)
+                if self.kv8:   # the admission's rows of the scratch -> layer i of the fp8 cache, on the admission's stream
+                    L.kr_kv_quantize(ptr(kc), ptr(vc), self._kv8(i), t.num_kv_heads, t.head_dim, self.B, self.s_max,
+                                     kvq_plan(adm.kvq), ptr(self.d_kv_clamped), s)
                 self._gemm(self.p_o, w.view(p + "o.w"), self.p_x, M, res=self.p_x, packed=True, **self._w8kw(p + "o.w"))
                 L.kr_rmsnorm(ptr(self.p_x), d, ptr(w.view(p + "ln2.w")), ptr(self.p_h), M, d, t.rms_norm_eps, s)
                 self._gemm(self.p_h, w.view(p + "gate_up.w"), self.p_act, M, epi=EPI_SILU_MUL8, packed=True, **self._w8kw(p + "gate_up.w"))
                 self._gemm(self.p_act, w.view(p + "down.w"), self.p_x, M, res=self.p_x, packed=True, **self._w8kw(p + "down.w"))
+            if self.kv8:
+                self.h_kv_clamped.copy_(self.d_kv_clamped, non_blocking=True)
             self.pages_prefilled += adm.n_pages
             if not defer_activation:
                 self._fork(adm.forks)
@@ -629,7 +692,7 @@ class Engine:
         if not groups:
             return
         t, kc, vc = self.cfg.text, self.kcache, self.vtcache
-        self.L.kr_kv_fork(ptr(kc), ptr(vc), kc.stride(0), kc.stride(1), kc.stride(2), vc.stride(0), vc.stride(1), vc.stride(2),
+        (self.L.kr_kv_fork8 if self.kv8 else self.L.kr_kv_fork)(ptr(kc), ptr(vc), kc.stride(0), kc.stride(1), kc.stride(2), vc.stride(0), vc.stride(1), vc.stride(2),
                           t.num_layers, t.num_kv_heads, t.head_dim, self.B, self.s_max, fork_plan(groups), self.s)
         self.sequences_forked += sum(len(g[2]) for g in groups)
 
@@ -777,15 +840,21 @@ class Engine:
                                       x_other.stride(0), ptr(w.view(p + "ln1.w")), t.rms_norm_eps, ptr(self.d_h), B, t.hidden_size,
                                       1 if (gs and pending) else 0, s)
                 self._dec32(DEC_ROPE_KV, self.d_h, w.view(p + "qkv.w"), B, 8, bias=w.view(p + "qkv.b"), kc=kc, vc=vc,
-                            zero=acc, row_slot=row_slot, **self._w8kw(p + "qkv.w"))
+                            zero=acc, row_slot=row_slot, kv8_layer=i if self.kv8 else None, **self._w8kw(p + "qkv.w"))
             else:
                 self._dec_narrow(DEC_ROPE_KV, x, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), norm_w=w.view(p + "ln1.w"),
                                  part_in=pin, x_out=x_other if pending else None, kc=kc, vc=vc, zero=acc,
-                                 resident=(i, "qkv") in self.resident, **self._w8kw(p + "qkv.w"))
+                                 resident=(i, "qkv") in self.resident, kv8_layer=i if self.kv8 else None, **self._w8kw(p + "qkv.w"))
             if pending:
                 x, x_other = x_other, x
             # ---- 2. split-KV attention partials, 3. their merge
-            if row_slot is not None:
+            if self.kv8 and row_slot is not None:
+                L.kr_attn_decode_rows_kv8(ptr(self.d_q), self._kv8(i), ptr(self.d_ctx), ptr(self.d_fin), ptr(row_slot), ptr(self.d_ws), B, H,
+                                          KVH, hd, self.s_max, self.n_split, hd ** -0.5, s)
+            elif self.kv8:
+                L.kr_attn_decode_slots_kv8(ptr(self.d_q), self._kv8(i), ptr(self.d_ctx), ptr(self.d_fin), ptr(self.d_ws), B, H, KVH, hd,
+                                           self.s_max, self.n_split, hd ** -0.5, s)
+            elif row_slot is not None:
                 L.kr_attn_decode_rows(ptr(self.d_q), kc, vc, ptr(self.d_ctx), ptr(self.d_fin), ptr(row_slot), ptr(self.d_ws), B, H, KVH,
                                       hd, self.s_max, self.n_split, hd ** -0.5, s)
             else:

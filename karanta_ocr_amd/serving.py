@@ -596,6 +596,7 @@ class LocalServer:
                 try:
                     pages = [self._page(s["req"]) for s in group]
                     res = self.engine.generate(pages, max(s["req"].max_tokens for s in group))
+                    self._log_kv_clamped()
                     i = 0                    # the result's rows: a request's children consecutive
                     for s in group:
                         for c in range(s["req"].n):
@@ -613,6 +614,15 @@ class LocalServer:
             carry["error"] = "server shutting down"
             carry["done"].set()
 
+
+    def _log_kv_clamped(self):
+        """fp8 KV cache: one line per admission that had to clamp values on their way into the cache (an operator running on
+        scales of 1.0, or on scales that do not fit the model, must see it)."""
+        n = int(getattr(self.engine, "kv_clamped", 0) or 0)
+        if n > getattr(self, "_kv_clamped_seen", 0):
+            self.log(f"fp8 KV cache: the last admission clamped {n - getattr(self, '_kv_clamped_seen', 0)} K/V elements to +-448 x scale "
+                     f"({n} since start; scales: {getattr(self.engine, 'kv_scale_source', '?')})")
+            self._kv_clamped_seen = n
 
     def _static_groups(self, batch):
         """A static batch decodes every sequence for the LONGEST max_tokens of the batch, so a long prompt with a small
@@ -744,6 +754,7 @@ class LocalServer:
                 self._sch = sch
                 continue
             self._running = sch.running
+            self._log_kv_clamped()
             now = (sch.running, len(sch.waiting) + self._q.qsize())
             if now != last:  # vLLM's stats line, printed when it changes (pipeline.py:782-800 scrapes it)
                 self.log(f"Running: {now[0]} reqs, Waiting: {now[1]} reqs")

@@ -149,7 +149,7 @@ def build_tokenizer(cfg: ModelConfig):
 
 def write_checkpoint(out_dir: str, cfg: ModelConfig, seed: int = 0, layout: str = "v4", fp8: bool = False,
                      min_pixels: Optional[int] = 3136, max_pixels: Optional[int] = 1003520, template_file: str = "both",
-                     weights: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+                     weights: Optional[Dict[str, np.ndarray]] = None, kv_scales=None) -> Dict[str, np.ndarray]:
     """Write the directory; returns the fp32 weights the checkpoint MEANS (for --fp8: the dequantised values), keyed by the
     internal (transformers-5) names — what an oracle run on this checkpoint uses."""
     import torch
@@ -182,9 +182,20 @@ def write_checkpoint(out_dir: str, cfg: ModelConfig, seed: int = 0, layout: str 
             t = torch.from_numpy(np.ascontiguousarray(a)).to(torch.bfloat16)
             tensors[hub] = t
             meaning[name] = t.float().numpy()
+    if kv_scales is not None:     # (k [L], v [L]): per-layer `self_attn.k_scale` / `v_scale`, as a compressed-tensors kv_cache_scheme ships them
+        pre_ = "model.layers." if layout == "v4" else "model.language_model.layers."
+        for which, vals in zip(("k_scale", "v_scale"), kv_scales):
+            if len(vals) != cfg.text.num_layers:
+                raise ValueError(f"kv_scales: {len(vals)} {which} values for {cfg.text.num_layers} layers")
+            for i, x in enumerate(vals):
+                tensors[f"{pre_}{i}.self_attn.{which}"] = torch.tensor([float(x)], dtype=torch.float32)
     save_file(tensors, os.path.join(out_dir, "model.safetensors"), metadata={"format": "pt"})
+    hf = hf_config_dict(cfg, layout, fp8)
+    if kv_scales is not None and "quantization_config" in hf:     # a bf16 checkpoint keeps a config.json without quantization_config
+        hf["quantization_config"]["kv_cache_scheme"] = {"num_bits": 8, "type": "float", "strategy": "tensor", "dynamic": False,
+                                                        "symmetric": True}
     with open(os.path.join(out_dir, "config.json"), "w") as f:
-        json.dump(hf_config_dict(cfg, layout, fp8), f, indent=1)
+        json.dump(hf, f, indent=1)
     tk = build_tokenizer(cfg)
     tk.save(os.path.join(out_dir, "tokenizer.json"))
     sp = special_tokens(cfg)
@@ -224,8 +235,13 @@ def main(argv=None) -> int:
     ap.add_argument("--layout", default="v4", choices=("v4", "v5"))
     ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--max-pixels", type=int, default=1003520)
+    ap.add_argument("--kv-scales", type=float, nargs=2, default=None, metavar=("K", "V"),
+                    help="also write per-layer self_attn.k_scale / v_scale tensors (a kv_cache_scheme): layer i gets K x (1 + i / 8), V x (1 + i / 8)")
     a = ap.parse_args(argv)
-    write_checkpoint(a.out_dir, CONFIGS[a.config], a.seed, a.layout, a.fp8, max_pixels=a.max_pixels)
+    cfg = CONFIGS[a.config]
+    ramp = 1.0 + np.arange(cfg.text.num_layers) / 8.0
+    kv = None if a.kv_scales is None else (a.kv_scales[0] * ramp, a.kv_scales[1] * ramp)
+    write_checkpoint(a.out_dir, cfg, a.seed, a.layout, a.fp8, max_pixels=a.max_pixels, kv_scales=kv)
     print(a.out_dir)
     return 0
 

@@ -361,3 +361,58 @@ def fp8_dequantized_weights(weights: Dict[str, np.ndarray], cfg: ModelConfig) ->
 def unpack_w16x64(p: np.ndarray) -> np.ndarray:
     n, k = p.shape
     return np.ascontiguousarray(p.reshape(n // 16, k // 32, 4, 16, 8).transpose(0, 3, 1, 2, 4)).reshape(n, k)
+
+
+# ----------------------------------------------------------------------------- fp8 (e4m3fn) KV cache: the flag and the scales
+KV_CACHE_DTYPES = ("auto", "bfloat16", "fp8", "fp8_e4m3")      # vLLM's --kv-cache-dtype spellings this engine serves
+
+
+def kv_cache_dtype_name(value: str) -> str:
+    """"bf16" or "fp8" from a --kv-cache-dtype value: auto = bfloat16, fp8 = fp8_e4m3 (as in vLLM)."""
+    if value not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype {value!r}: one of {', '.join(KV_CACHE_DTYPES)}")
+    return "fp8" if value.startswith("fp8") else "bf16"
+
+
+def kv_scale_table(k, v, layers: int, kv_heads: int) -> np.ndarray:
+    """The device table [L, 2, KVH] f32 (K scales, then V scales, per layer) from [L] or [L, KVH] arrays."""
+    out = np.empty((layers, 2, kv_heads), np.float32)
+    for j, (name, a) in enumerate((("k", k), ("v", v))):
+        a = np.asarray(a, np.float32)
+        if a.shape == (layers,):
+            a = np.repeat(a[:, None], kv_heads, axis=1)
+        if a.shape != (layers, kv_heads):
+            raise ValueError(f"{name} scales of shape {a.shape}: [{layers}] or [{layers}, {kv_heads}]")
+        if not (np.isfinite(a).all() and (a > 0).all()):
+            raise ValueError(f"{name} scales must be finite and positive")
+        out[:, j] = a
+    return out
+
+
+def load_kv_scales(model_dir: str, cfg: ModelConfig):
+    """`kv_scales_from_checkpoint` of a checkpoint directory, reading nothing but the k_scale / v_scale tensors."""
+    from safetensors import safe_open
+
+    found: Dict[str, np.ndarray] = {}
+    for fn in sorted(f for f in os.listdir(model_dir) if f.endswith(".safetensors")):
+        with safe_open(os.path.join(model_dir, fn), framework="pt") as sf:
+            for k in sf.keys():
+                if k.endswith(".self_attn.k_scale") or k.endswith(".self_attn.v_scale"):
+                    found[canonical_name(k)] = sf.get_tensor(k).float().numpy()
+    return kv_scales_from_checkpoint(found, cfg)
+
+
+def kv_scales_from_checkpoint(tensors: Dict[str, np.ndarray], cfg: ModelConfig):
+    """(k [L], v [L]) from the per-layer `...self_attn.k_scale` / `v_scale` tensors of a checkpoint that ships them
+    (compressed-tensors `kv_cache_scheme`: one per-tensor scale per layer), or None.  All layers or none."""
+    t = cfg.text
+    out = []
+    for which in ("k_scale", "v_scale"):
+        names = [f"model.language_model.layers.{i}.self_attn.{which}" for i in range(t.num_layers)]
+        have = [n for n in names if n in tensors]
+        if not have:
+            return None
+        if len(have) != t.num_layers:
+            raise ValueError(f"the checkpoint ships {which} for {len(have)} of {t.num_layers} layers")
+        out.append(np.asarray([float(as_f32(tensors[n]).reshape(-1)[0]) for n in names], np.float32))
+    return out[0], out[1]
