@@ -39,7 +39,7 @@ typedef uint16_t kr_bf16;
 /* kr_version() of the library this header describes: major * 100 + minor.  The major changes with every incompatible
  * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family); a caller built
  * against major X must refuse a library whose kr_version() / 100 != X. */
-#define KR_ABI_VERSION 409
+#define KR_ABI_VERSION 410
 
 #define KR_OK 0
 #define KR_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -801,6 +801,44 @@ int kr_spec_guide_rows(const kr_spec* a, const kr_spec_guide* g, const int32_t* 
  * tokens the step emitted (read from `history`), except the last one where the step set finished (kr_guide_advance skips the rows
  * kr_sample_greedy has just finished): the state e plain guided steps leave. */
 int kr_spec_guide_advance(const kr_spec* a, const kr_spec_guide* g, kr_stream s);
+
+/* ------------------------------------------------------------------ runaway repetition (vLLM's repetition_detection)
+ * The rule is a function of a sequence's generated tokens y[0..g] alone (the prompt never counts).  Per slot the cfg row holds
+ * min_pattern_size a, max_pattern_size b, min_count c, min_span m with 1 <= a <= b <= KR_REP_MAX_PERIOD, c >= 2, m >= 0; b == 0
+ * switches the slot off (so does a row outside those bounds).  For a period p, run_p(g) is the number of consecutive indices i,
+ * counted back from g, with i >= p and y[i] == y[i - p].  The sequence REPEATS AT g when some p in [a, b] has
+ * run_p(g) >= max((c - 1) p, m - p): the last c p tokens are c copies of one block, and the repeated stretch is at least m tokens long.
+ * The sequence ends at the smallest such g; that token is kept.
+ *
+ * kr_repeat_detect, one workgroup per slot, behind kr_sample_greedy / kr_stop_tokens or kr_spec_accept / kr_spec_accept_rows /
+ * kr_spec_guide_advance.  A slot holds gen = ctx_len - prompt_len + 1 generated tokens after those (capped at hist_rows), token i at
+ * history[i * hist_stride + slot].  A live slot: tokens seen .. gen - 1 are walked in order, run[p] = (g >= p && y[g] == y[g - p]) ?
+ * run[p] + 1 : 0 for the periods a..b; at the first g that repeats, rep_at = g, finished = 1, seen = g + 1 and the walk ends there
+ * (run is the state at g); without one, seen = gen.  So one launch per token and one launch per several tokens leave the same
+ * rep_at, seen and run.  run needs no clearing: at g = 0 every period is reset by g < p, and an admission only sets seen = 0,
+ * rep_at = -1 and the cfg row.
+ * Untouched: a slot that is off, a slot with rep_at >= 0 (it is written once), a finished slot without the freeze bit (its new
+ * tokens are pads) and a finished slot without new tokens (frozen).  A finished slot WITH new tokens under the freeze bit was
+ * finished by this very step — a speculative step that emitted several tokens, the last of them the EOS: the tokens before the
+ * last are walked and only rep_at is written, so the cut is where one-token steps would have made it.
+ * flags: kr_sample_greedy's word; bit 0 (nothing finishes): nothing is recorded and nothing is launched.
+ * KR_ERR_ARG, and nothing launches: a null pointer, slots outside 1..32, hist_stride < slots, hist_rows < 1, unknown flag bits. */
+#define KR_REP_MAX_PERIOD 1024
+typedef struct kr_repeat {
+    int32_t slots;
+    const int32_t* history;            /* [hist_rows][hist_stride]: kr_sample_greedy's token history */
+    int32_t hist_stride;
+    int32_t hist_rows;
+    const int32_t* ctx_len;            /* [slots] */
+    const int32_t* prompt_len;         /* [slots] */
+    int32_t* finished;                 /* [slots] */
+    const int32_t* cfg;                /* [slots][4]: a, b, c, m */
+    int32_t* run;                      /* [slots][KR_REP_MAX_PERIOD]: run[p - 1] of period p */
+    int32_t* seen;                     /* [slots]: generated tokens looked at so far */
+    int32_t* rep_at;                   /* [slots]: the index the sequence repeats at, -1: none */
+    int32_t flags;
+} kr_repeat;
+int kr_repeat_detect(const kr_repeat* a, kr_stream s);
 
 /* kr_linear_decode32, KR_DEC_ROPE_KV only, for the rows of a speculative step: the cache base and the cs_table row of row r come
  * from row_slot[r]; the cache position and the rotary index from the row's own ctx_len / prompt_len entries.  q_out stays per row.

@@ -104,6 +104,7 @@ SIGNATURES = {
     "kr_spec_guide_trim": [c_p, c_p, c_p, c_p],
     "kr_spec_guide_rows": [c_p, c_p, c_p, c_p],
     "kr_spec_guide_advance": [c_p, c_p, c_p],
+    "kr_repeat_detect": [c_p, c_p],
     "kr_linear_decode32_rows": [i32, c_p, c_p, c_p],
     "kr_attn_decode_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
     "kr_kv_quantize": [c_p, c_p, c_p, i32, i32, i32, i32, c_p, c_p, c_p],
@@ -175,6 +176,16 @@ class SpecGuide(C.Structure):
     """kr_spec_guide (include/karanta_hip.h): the guides of a speculative step's rows and the scratch of its three launches."""
     _fields_ = [("guide_trans", c_p), ("guide_masks", c_p), ("guide_state", c_p), ("mask_words", C.c_int32), ("vocab_off", c_p),
                 ("vocab_bytes", c_p), ("draft_state", c_p), ("ctx_before", c_p)]
+
+
+REP_MAX_PERIOD = 1024                   # KR_REP_MAX_PERIOD
+
+
+class Repeat(C.Structure):
+    """kr_repeat (include/karanta_hip.h): the history and the per-slot state kr_repeat_detect walks."""
+    _fields_ = [("slots", C.c_int32), ("history", c_p), ("hist_stride", C.c_int32), ("hist_rows", C.c_int32), ("ctx_len", c_p),
+                ("prompt_len", c_p), ("finished", c_p), ("cfg", c_p), ("run", c_p), ("seen", c_p), ("rep_at", c_p),
+                ("flags", C.c_int32)]
 
 
 class Kv8(C.Structure):

@@ -82,7 +82,26 @@ def build_parser() -> argparse.ArgumentParser:
                          "step the sequences leave free are dealt to the drafts; with \"guided\": true requests with guided_regex / "
                          "response_format speculate too, their drafts checked against the pattern; not with --max-logprobs or "
                          "--static-batching)")
+    ap.add_argument("--repetition-detection", default=None,
+                    help="the default of the requests without a repetition_detection field, as JSON: {\"max_pattern_size\": B, "
+                         "\"min_pattern_size\": A, \"min_count\": C, \"min_span\": M} — a sequence whose last C x p tokens are C "
+                         "copies of one block of p tokens (A <= p <= B <= 1024, at least M tokens of repetition) ends there with "
+                         "finish_reason \"length\" and stop_reason \"repetition\"; checked on the device inside the decode step. "
+                         "Off unless given: no values are shipped")
     return ap
+
+
+def repetition_config(text: str):
+    """RepetitionParams from --repetition-detection; ValueError with the reason."""
+    import json
+    from .sampling import parse_repetition_field
+    try:
+        d = json.loads(text)
+    except ValueError as e:
+        raise ValueError(f"--repetition-detection is not JSON: {e}") from e
+    if not isinstance(d, dict):
+        raise ValueError("--repetition-detection must be a JSON object")
+    return parse_repetition_field(d)
 
 
 def speculative_config(text: str, max_num_seqs: int):
@@ -171,6 +190,12 @@ def parse_args(argv: Optional[List[str]] = None):
             *spec, args.speculative_share_rows = speculative_fields(args.speculative_config, args.max_num_seqs)
             args.speculative = tuple(spec)
             args.speculative_guided = speculative_guided(args.speculative_config)
+        except ValueError as e:
+            ap.error(str(e))
+    args.repetition = None
+    if args.repetition_detection is not None:
+        try:
+            args.repetition = repetition_config(args.repetition_detection)
         except ValueError as e:
             ap.error(str(e))
     args.model_dir = model
@@ -287,7 +312,8 @@ def make_server(args, log=print):
     return LocalServer(eng, front, served_model_name=args.served_model_name, log=log, continuous=not args.static_batching,
                        max_tokens_cap=min(args.max_tokens_cap, args.max_model_len), honor_temperature=not args.greedy,
                        max_logprobs=args.max_logprobs, admit_min=args.admit_min, admit_max_wait=args.admit_max_wait,
-                       prefix_cache=bool(getattr(args, "enable_prefix_caching", False)), **({"speculative": True} if spec else {}))
+                       prefix_cache=bool(getattr(args, "enable_prefix_caching", False)), **({"speculative": True} if spec else {}),
+                       **({"repetition": args.repetition} if getattr(args, "repetition", None) is not None else {}))
 
 
 def main(argv: Optional[List[str]] = None, make=make_server, on_ready=None) -> int:

@@ -171,9 +171,12 @@ class VLLMClient:
         first, usage, now = choices[0], response.get("usage") or {}, time.time()
         echoed = dict(generation_params)
         echoed.pop("messages", None)                  # the prompt (a page image) is not echoed back
+        # "stop_reason": "repetition" where repetition_detection ended the page; a result without a cause keeps the reference's keys
+        why = {"stop_reason": first["stop_reason"]} if first.get("stop_reason") is not None else {}
         return {
             "text": (first.get("message") or {}).get("content"),
             "finish_reason": first.get("finish_reason"),
+            **why,
             "model": response.get("model"),
             "usage": {key: int(usage.get(key) or 0) for key in ("prompt_tokens", "completion_tokens", "total_tokens")},
             "metadata": {"generation_time": now - start_time, "server_url": self.base_url, "generation_params": echoed,

@@ -73,6 +73,7 @@ class Admission:
     guides: Optional[list] = None      # Sampler._guide_rows
     procs: Optional[list] = None       # Sampler._control_rows
     adjs: Optional[list] = None        # Sampler._adjust_rows
+    reps: Optional[list] = None        # per sequence its RepetitionParams or None
     need: StepFeatures = StepFeatures()
     # parallel sampling: B / slots / lens / last_rows / cs count SEQUENCES (children); the prefill (M, src, cos, sin, plan) covers
     # every page once, in child 0's slot, and `forks` names what kr_kv_fork copies afterwards
@@ -306,6 +307,7 @@ class Engine:
         self.d_tok = z(B, dtype=torch.int32)
         self.d_fin = z(R, dtype=torch.int32)[:B]
         self._snap_ring, self._snap_next, self._snap_event, self._copy_stream = None, 0, None, None   # snapshot_slots()
+        self._rep_read = np.full(B, -1, np.int64)     # slot_rep_at()
         self.d_temp = z(R, dtype=torch.float32)[:B]   # per-slot sampling temperature and seed
         self.d_seed = z(R, dtype=torch.int32)[:B]
         if self.spec is not None:
@@ -933,7 +935,7 @@ class Engine:
         dropped before any row is spent on them (kr_spec_guide_trim: behind kr_spec_propose, or between kr_spec_lookup and
         kr_spec_deal), every draft row gets the guide and the DFA state behind its drafts (kr_spec_guide_rows) for the masked Gumbel
         pass, and the slots' states follow the tokens the verification emitted (kr_spec_guide_advance).  An unguided step issues
-        none of them."""
+        none of them.  A step that carries repetition detection ends on kr_repeat_detect, as a plain step does."""
         L, s, R = self.L, self.s, self.rows
         why = self._spec_refusal()
         if why is not None:
@@ -964,6 +966,8 @@ class Engine:
                              self.d_eos.numel(), flags, s)
         if g is not None:
             L.kr_spec_guide_advance(C.byref(a), C.byref(g), s)
+        if self._step.repetition:     # over the 1 .. K + 1 tokens every slot gained: the cut plain steps make
+            self.sampler.repeat_pass(self.B, 0, flags)
 
     def set_draft_script(self, slot: int, tokens: Optional[Sequence[int]]):
         """Test hook: the drafts of `slot` come from a scripted continuation — draft j of a step is tokens[generated + j - 1] —
@@ -1186,17 +1190,23 @@ class Engine:
         self.stream.synchronize()
         t3 = time.perf_counter()
         hist = self.d_hist[:steps_done, :B].cpu().numpy().T  # [B, steps]
-        toks, reasons = [], []
+        toks, reasons, causes = [], [], []
         eos = set(int(e) for e in self.cfg.eos_token_ids)
+        rep_at = self.sampler.d_rep_at[:B].cpu().numpy() if need.repetition else None
         for b in range(B):
             row = hist[b]
-            cut, reason = len(row), "length"
+            cut, reason, cause = len(row), "length", None
             if not ignore_eos:       # a row's own stop ids end it as EOS does (kr_stop_tokens)
                 hit = np.flatnonzero(np.isin(row, list(eos | set(int(x) for x in getattr(rows[b], "stop_token_ids", None) or ()))))
                 if hit.size:
                     cut, reason = int(hit[0]) + 1, "stop"
+                # the token the sequence repeats at is kept; an EOS or stop id at or before it wins (kr_repeat_detect)
+                g = int(rep_at[b]) if rep_at is not None and getattr(rows[b], "repetition", None) is not None else -1
+                if 0 <= g < len(row) and g + 1 < cut + (reason == "length"):
+                    cut, reason, cause = g + 1, "length", "repetition"
             toks.append(row[:cut].astype(np.int64))
             reasons.append(reason)
+            causes.append(cause)
         lps = None
         if self._logprobs is not None:
             lp = self.sampler.d_lp[:steps_done, :B].cpu().numpy()
@@ -1211,7 +1221,7 @@ class Engine:
             tokens=toks, finish_reasons=reasons, prompt_tokens=lens,
             timings={"vit_s": t1 - t0, "prefill_s": t2 - t1, "decode_s": t3 - t2, "total_s": t3 - t0,
                      "decode_steps": steps_done - 1},
-            logits=np.stack(logits_steps, 1) if return_logits else None, logprobs=lps)
+            logits=np.stack(logits_steps, 1) if return_logits else None, logprobs=lps, stop_reasons=causes)
 
     # ------------------------------------------------------------------ slot scheduler API (continuous batching)
     # The decode graph always runs all `max_batch` slots; a slot whose sequence has finished idles in place
@@ -1227,11 +1237,12 @@ class Engine:
             raise KarantaHipError("logprobs must be in 0..20")
         if guided and self.sampler.d_voc_off is None:
             raise KarantaHipError("guided decoding needs the vocabulary's byte strings: call Engine.set_vocab() first")
-        # the sampling controls come with the sampling configuration; the steps carry each pass while a request needs it
+        # the sampling controls come with the sampling configuration; the steps carry each pass while a request needs it.  The
+        # repetition pass chooses no token: every configuration allows it
         sampled = bool(sampling) or bool(guided)
         self._last_batch = self.B
         self._enter_mode(max_new_tokens, ignore_eos=False, freeze_finished=True, want_logits=False,
-                         caps=StepFeatures(sampled, bool(guided), sampled, sampled), step=StepFeatures(), logprobs=logprobs)
+                         caps=StepFeatures(sampled, bool(guided), sampled, sampled, True), step=StepFeatures(), logprobs=logprobs)
         # a scheduler rebuilt after an exception may have left an overlapped admission in flight: without this the counter stays
         # above zero and every later decode_steps() replays the graph on the complement CU subset
         if self._adm_stream is not None:
@@ -1352,14 +1363,16 @@ class Engine:
             self._activate(rec)
         return rec.lens
 
-    def set_step_features(self, sampling: bool, guided: bool, processing: bool = False, adjust: bool = False):
+    def set_step_features(self, sampling: bool, guided: bool, processing: bool = False, adjust: bool = False,
+                          repetition: bool = False):
         """Slot mode: which passes the NEXT decode steps carry, within what begin_slots() allowed.  The scheduler calls it with what
         the requests in the slots need: a server that accepts guided / sampled requests runs the plain argmax graph (no f32 logits
         written and re-read, no DFA advance) while none is decoding — rows with temperature 0 and no guide get the same token from
         either graph.  An admission switches on what its pages need by itself (prefill, admit_end).
         processing: the sampling-control launches (top_k / top_p / min_p / penalties; needs_processing), same rules.
-        adjust: the logit-adjustment launches (logit_bias / min_tokens / stop_token_ids; needs_adjust), same rules."""
-        self._step = StepFeatures(bool(sampling), bool(guided), bool(processing), bool(adjust)) & self._caps
+        adjust: the logit-adjustment launches (logit_bias / min_tokens / stop_token_ids; needs_adjust), same rules.
+        repetition: the repetition pass (PageRequest.repetition), same rules."""
+        self._step = StepFeatures(bool(sampling), bool(guided), bool(processing), bool(adjust), bool(repetition)) & self._caps
 
     def decode_steps(self, n: int, speculative: bool = False):
         """n decode steps over all slots (asynchronous on the engine's stream).  speculative=True: speculative steps (every slot
@@ -1409,7 +1422,14 @@ class Engine:
         self._snap_event = self._snap_counts = None
         fin = self.d_fin.cpu().numpy().astype(bool)
         gen = (self.d_ctx.cpu().numpy() + 1 - self.d_plen.cpu().numpy()).astype(np.int64)
+        self._rep_read = (self.sampler.d_rep_at.cpu().numpy().astype(np.int64) if self.sampler._rep_slots
+                          else np.full(self.B, -1, np.int64))
         return fin, gen
+
+    def slot_rep_at(self) -> np.ndarray:
+        """Per slot the generated-token index its sequence repeats at (kr_repeat_detect; -1: none), as of the flags the host last
+        read with poll_slots() / read_snapshot()."""
+        return self._rep_read
 
     # poll_slots without draining the stream (SlotScheduler launch-ahead): the slot state as of THIS point of the engine's stream is
     # copied to pinned host memory behind an event; the scheduler queues the next decode chunk before it waits for that event, so
@@ -1417,8 +1437,8 @@ class Engine:
     def snapshot_slots(self):
         ring = self._snap_ring
         if ring is None:
-            ring = self._snap_ring = [torch.empty(5 if self.spec is not None else 3, self.B, dtype=torch.int32).pin_memory()
-                                      for _ in range(4)]
+            ring = self._snap_ring = [torch.empty(6 if self.spec is not None else 4, self.B, dtype=torch.int32).pin_memory()
+                                      for _ in range(4)]      # the last row: rep_at, beside the finished flags it explains
         buf = ring[self._snap_next % len(ring)]
         self._snap_next += 1
         with torch.cuda.stream(self.stream):
@@ -1427,6 +1447,10 @@ class Engine:
             buf[2].copy_(self.d_plen, non_blocking=True)
             if self.spec is not None:     # proposed / accepted drafts per slot as of this point: snap["buf"][3], [4]
                 buf[3:5].copy_(self.d_spec_count, non_blocking=True)
+            if self.sampler._rep_slots:   # (no slot carries the feature: no copy is queued)
+                buf[-1].copy_(self.sampler.d_rep_at, non_blocking=True)
+            else:
+                buf[-1].fill_(-1)
             ev = torch.cuda.Event()
             ev.record(self.stream)
         return {"buf": buf, "event": ev}
@@ -1439,7 +1463,8 @@ class Engine:
         fin = a[0].astype(bool)
         gen = (a[1].astype(np.int64) + 1 - a[2])
         self._snap_event = snap["event"]
-        self._snap_counts = (a[3].astype(np.int64), a[4].astype(np.int64)) if a.shape[0] >= 5 else None
+        self._snap_counts = (a[3].astype(np.int64), a[4].astype(np.int64)) if a.shape[0] >= 6 else None
+        self._rep_read = a[-1].astype(np.int64)
         return fin, gen
 
     def _host_copy(self, t: "torch.Tensor") -> np.ndarray:

@@ -10,6 +10,43 @@ import numpy as np
 from ._lib import KarantaHipError
 
 
+REP_MAX_PERIOD = 1024      # KR_REP_MAX_PERIOD (include/karanta_hip.h)
+
+
+@dataclass(frozen=True)
+class RepetitionParams:
+    """vLLM's repetition_detection: the sequence ends ("length", stop_reason "repetition") at the first generated token after which
+    the last min_count x p tokens are min_count copies of one block of p tokens, min_pattern_size <= p <= max_pattern_size, and the
+    repeated stretch is at least min_span tokens long (0: no such floor; it keeps dot leaders and table rules out without raising
+    min_count for long blocks).  The rule reads the output alone (kr_repeat_detect, include/karanta_hip.h).  No field has a
+    default: which values suit real pages is unmeasured."""
+    max_pattern_size: int
+    min_pattern_size: int
+    min_count: int
+    min_span: int = 0
+
+    def __post_init__(self):
+        for name in ("max_pattern_size", "min_pattern_size", "min_count", "min_span"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"repetition_detection: {name} must be an integer, got {v!r}")
+        a, b, c, m = self.row()
+        if not 1 <= a <= b:
+            raise ValueError(f"repetition_detection: 1 <= min_pattern_size ({a}) <= max_pattern_size ({b}) must hold")
+        if b > REP_MAX_PERIOD:
+            raise ValueError(f"repetition_detection: max_pattern_size {b} is above {REP_MAX_PERIOD}")
+        if c < 2:
+            raise ValueError(f"repetition_detection: min_count must be at least 2, got {c}")
+        if m < 0:
+            raise ValueError(f"repetition_detection: min_span must not be negative, got {m}")
+        if max(c, m) > 0x7FFFFFFF:      # the device row is int32
+            raise ValueError("repetition_detection: min_count and min_span must fit 31 bits")
+
+    def row(self):
+        """The kr_repeat cfg row: (a, b, c, m)."""
+        return int(self.min_pattern_size), int(self.max_pattern_size), int(self.min_count), int(self.min_span)
+
+
 @dataclass
 class PageRequest:
     """One page = one sequence: prompt token ids (image placeholders included) + its images."""
@@ -37,6 +74,8 @@ class PageRequest:
     # c = 0..n-1, start (vLLM's seeds for the children of a seeded request) — but its images go through the ViT once and its
     # prompt through the prefill once; the siblings' KV rows are copies of child 0's (kr_kv_fork)
     n: int = 1
+    # runaway repetition (kr_repeat_detect): None = off.  It changes no token choice, only where the sequence ends
+    repetition: Optional[RepetitionParams] = None
 
 
 def children(pages) -> list:
@@ -67,6 +106,7 @@ class GenerateResult:
     logits: Optional[np.ndarray] = None  # [B, steps, V] when return_logits
     logprobs: Optional[List[Optional[Dict[str, np.ndarray]]]] = None   # per page (None where not asked): "token" [n],
     #                                                                    "top_ids" [n, k], "top" [n, k]
+    stop_reasons: Optional[List[Optional[str]]] = None   # per sequence: "repetition" where PageRequest.repetition ended it, else None
 
 
 @dataclass(frozen=True)

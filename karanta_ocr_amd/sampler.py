@@ -6,12 +6,13 @@ switches of the current mode (Engine._caps, _step, _logprobs), which the graph k
 current stream, read at the moment of each launch."""
 from __future__ import annotations
 
+import ctypes as C
 from typing import Dict, Sequence
 
 import numpy as np
 import torch
 
-from ._lib import ADJ_CAP, KarantaHipError, SpecGuide, ptr
+from ._lib import ADJ_CAP, REP_MAX_PERIOD, KarantaHipError, Repeat, SpecGuide, ptr
 from .request import PageRequest
 from .sampling import StepFeatures, adjust_table, needs_processing, sampling_params, temperature
 
@@ -60,6 +61,14 @@ class Sampler:
         self.d_adj_meta = z(B, 4, dtype=torch.int32)
         self.d_adj_saved = z(B, ADJ_CAP, dtype=torch.float32)
         self.d_voc_off = self.d_voc_bytes = None   # set_vocab()
+        # runaway repetition (kr_repeat_detect): per slot its cfg row {a, b, c, m} (b == 0: off), the run counters of the periods, how
+        # many generated tokens the pass has looked at, and the index the sequence repeats at (-1: none).  _rep_slots: the slots whose
+        # cfg row is not zero, so that an admission without the feature writes nothing here
+        self.d_rep_cfg = z(B, 4, dtype=torch.int32)
+        self.d_rep_run = z(B, REP_MAX_PERIOD, dtype=torch.int32)
+        self.d_rep_seen = z(B, dtype=torch.int32)
+        self.d_rep_at = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self._rep_slots: set = set()
         self._guides: Dict[str, DeviceGuide] = {}
         self._slot_guides: Dict[int, DeviceGuide] = {}   # keeps the tables of the running requests alive
         # log-probabilities: [hist][B][1 + 20] / [hist][B][20], allocated with the token history when asked for
@@ -83,6 +92,10 @@ class Sampler:
         self.d_gmasks.zero_()
         self.d_adj_meta.zero_()
         self._slot_guides = {}
+        if self._rep_slots:
+            self.d_rep_cfg.zero_()
+            self.d_rep_at.fill_(-1)
+            self._rep_slots = set()
 
     # ------------------------------------------------------------------ guided decoding
     def set_vocab(self, token_bytes: Sequence[bytes]):
@@ -191,10 +204,11 @@ class Sampler:
         adm.guides = self._guide_rows(rows)
         adm.procs = self._control_rows(rows)
         adm.adjs = self._adjust_rows(rows)
+        adm.reps = [getattr(p, "repetition", None) for p in rows]
 
     def write(self, a):
         """The sampler's share of an admission's activation (Engine._activate): guide tables and start states, sampling controls,
-        logit-adjustment tables of the admission's slots."""
+        logit-adjustment tables and repetition state of the admission's slots."""
         h2d, B = self.eng._h2d, self.eng.B
         gt, gm, gs, dgs = zip(*a.guides)
         for dst, rows in ((self.d_gtrans, np.asarray(gt, np.int64)), (self.d_gmasks, np.asarray(gm, np.int64)),
@@ -224,6 +238,28 @@ class Sampler:
                 continue
             for dst, rows in zip((self.d_adj_ids, self.d_adj_val, self.d_adj_flag, self.d_adj_meta), tab):
                 h2d(dst[j], rows)
+
+        # repetition: the slot's cfg row, and its place and verdict cleared (the run counters clear themselves at token 0); a slot
+        # that neither carries the feature nor carried it is left alone
+        if a.whole_batch and self._rep_slots and not any(r is not None for r in a.reps):
+            self.d_rep_cfg.zero_()
+            self.d_rep_at.fill_(-1)
+            self._rep_slots = set()
+        for r, j in zip(a.reps, a.slots):
+            if r is None and j not in self._rep_slots:
+                continue
+            h2d(self.d_rep_cfg[j], np.asarray(r.row() if r is not None else (0, 0, 0, 0), np.int32))
+            self.d_rep_seen[j:j + 1].zero_()
+            self.d_rep_at[j:j + 1].fill_(-1)
+            (self._rep_slots.add if r is not None else self._rep_slots.discard)(j)
+
+    def repeat_pass(self, B: int, j: int, flags: int):
+        """kr_repeat_detect over slots j .. j + B - 1, behind whatever appended the step's tokens (a plain step's tail, or a
+        speculative step's verification): it finds its own place in every slot's history."""
+        e = self.eng
+        a = Repeat(B, ptr(e.d_hist[:, j:]), e.d_hist.stride(0), e.d_hist.shape[0], ptr(e.d_ctx[j:]), ptr(e.d_plen[j:]), ptr(e.d_fin[j:]),
+                   ptr(self.d_rep_cfg[j:]), ptr(self.d_rep_run[j:]), ptr(self.d_rep_seen[j:]), ptr(self.d_rep_at[j:]), flags)
+        self.L.kr_repeat_detect(C.byref(a), e.s)
 
     def spec_guide_args(self) -> SpecGuide:
         """kr_spec_guide of the engine's guided speculative step (read during the call)."""
@@ -270,7 +306,7 @@ class Sampler:
 
     def post_token(self, logits, B: int, j: int, flags: int):
         """The passes behind the token choice of a plain step: stop tokens, output counts, guide advance, the logits put back,
-        log-probabilities."""
+        log-probabilities, repetition."""
         e, L, t, s = self.eng, self.L, self.cfg.text, self.eng.s
         step = e._step
         adj = self._adj(j) if step.adjust else None
@@ -288,3 +324,5 @@ class Sampler:
                                ptr(self.d_lp_pv), ptr(self.d_lp_pi), ptr(self.d_lp_ms), ptr(e.d_tok[j:]), ptr(e.d_ctx[j:]),
                                ptr(e.d_plen[j:]), ptr(e.d_fin[j:]), ptr(self.d_lp[:, j:]), ptr(self.d_lpi[:, j:]),
                                self.d_lp.shape[0], e.B, 20, B, s)
+        if step.repetition:     # last: the token a sequence repeats at is kept, so its step still records its log-probabilities
+            self.repeat_pass(B, j, flags)

@@ -13,6 +13,7 @@ from typing import Any, Dict, Iterable, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import ADJ_CAP          # KR_ADJ_CAP (include/karanta_hip.h): entries of a row's logit-adjustment table
+from .request import RepetitionParams
 
 # request field -> neutral value ("off")
 NEUTRAL = {"top_k": 0, "top_p": 1.0, "min_p": 0.0, "repetition_penalty": 1.0, "frequency_penalty": 0.0,
@@ -78,15 +79,41 @@ def adjust_table(p, eos_token_ids: Sequence[int], vocab_size: int) -> Optional[T
     return ids.astype(np.int32), vals, flags, np.asarray([len(entries), m, 0, 0], np.int32)
 
 
-class StepFeatures(NamedTuple):
-    """The optional passes of a decode step (part of Engine's graph key): `sampling` the Gumbel-max argmax, `guided` its
-    guide mask and the DFA advance, `processing` the sampling-control launches, `adjust` the logit-adjustment launches
-    (kr_logits_adjust / kr_stop_tokens / kr_logits_restore).  A guided row is masked in the sampling pass and an adjusted
-    row's token is the argmax of that pass over the adjusted logits, so `guided` and `adjust` imply `sampling`."""
+class _LogitPasses(NamedTuple):
     sampling: bool = False
     guided: bool = False
     processing: bool = False
     adjust: bool = False
+
+
+class StepFeatures(_LogitPasses):
+    """The optional passes of a decode step (part of Engine's graph key): `sampling` the Gumbel-max argmax, `guided` its
+    guide mask and the DFA advance, `processing` the sampling-control launches, `adjust` the logit-adjustment launches
+    (kr_logits_adjust / kr_stop_tokens / kr_logits_restore).  A guided row is masked in the sampling pass and an adjusted
+    row's token is the argmax of that pass over the adjusted logits, so `guided` and `adjust` imply `sampling`.
+    Those four work on the logits and are the tuple.  `repetition`, the repetition pass behind the token choice
+    (kr_repeat_detect), touches no logit and implies nothing: it rides beside the tuple as an attribute, and equality and the hash
+    (the graph key) take it in."""
+
+    def __new__(cls, sampling: bool = False, guided: bool = False, processing: bool = False, adjust: bool = False,
+                repetition: bool = False):
+        self = super().__new__(cls, sampling, guided, processing, adjust)
+        self.repetition = bool(repetition)
+        return self
+
+    def __eq__(self, other):
+        same = tuple.__eq__(self, other)
+        return same if same is NotImplemented else same and self.repetition == bool(getattr(other, "repetition", False))
+
+    def __ne__(self, other):
+        same = self.__eq__(other)
+        return same if same is NotImplemented else not same
+
+    def __hash__(self):
+        return hash((tuple(self), self.repetition))
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", repetition={self.repetition})"
 
     @classmethod
     def of(cls, pages: Iterable) -> "StepFeatures":
@@ -95,17 +122,40 @@ class StepFeatures(NamedTuple):
         guided = any(getattr(p, "guide", None) is not None for p in pages)
         adjust = any(needs_adjust(p) for p in pages)
         return cls(guided or adjust or any(temperature(p) > 0 for p in pages), guided, any(needs_processing(p) for p in pages),
-                   adjust)
+                   adjust, any(getattr(p, "repetition", None) is not None for p in pages))
 
     def __or__(self, other: "StepFeatures") -> "StepFeatures":
-        return StepFeatures(*(a or b for a, b in zip(self, other)))
+        return StepFeatures(*(a or b for a, b in zip(self, other)), repetition=self.repetition or other.repetition)
 
     def __and__(self, caps: "StepFeatures") -> "StepFeatures":
         """The clamp to what `caps` allows; a guided or adjusted row that stays so keeps the sampling pass it needs."""
         guided = self.guided and caps.guided
         adjust = self.adjust and caps.adjust
         return StepFeatures((self.sampling and caps.sampling) or guided or adjust, guided, self.processing and caps.processing,
-                            adjust)
+                            adjust, self.repetition and caps.repetition)
+
+
+REPETITION_KEYS = ("max_pattern_size", "min_pattern_size", "min_count", "min_span")
+
+
+def parse_repetition_field(v: Any) -> Optional[RepetitionParams]:
+    """`repetition_detection` of a request body, the server's --repetition-detection or LocalServer(repetition=...): an object
+    with max_pattern_size, min_pattern_size, min_count and (optional, 0) min_span, all integers; None or False: off.  Raises
+    ValueError with the message for the 400 answer: non-integers, a > b, b > 1024, c < 2, m < 0, unknown or missing keys."""
+    if v is None or v is False:
+        return None
+    if isinstance(v, RepetitionParams):
+        return v
+    if not isinstance(v, dict):
+        raise ValueError(f"repetition_detection must be an object, false or null, got {type(v).__name__}")
+    unknown = sorted(k for k in v if k not in REPETITION_KEYS)
+    if unknown:
+        raise ValueError(f"repetition_detection: unknown key(s) {', '.join(map(repr, unknown))} (known: {', '.join(REPETITION_KEYS)})")
+    missing = [k for k in REPETITION_KEYS[:3] if v.get(k) is None]
+    if missing:
+        raise ValueError(f"repetition_detection: {', '.join(missing)} must be given (the server ships no defaults)")
+    kw = {k: _int_field(f"repetition_detection.{k}", v[k]) for k in REPETITION_KEYS if v.get(k) is not None}
+    return RepetitionParams(**kw)
 
 
 def parse_request_fields(req: Dict[str, Any]) -> Dict[str, Any]:

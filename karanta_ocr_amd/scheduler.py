@@ -6,6 +6,8 @@ hipGraph always steps all `max_batch` slots; a sequence that hits EOS (device fl
 its slot, and the next waiting request is prefilled into that slot while the other sequences keep their state —
 instead of the whole batch waiting for its longest member (`Engine.generate`, static batching).  A request's own
 `stop_token_ids` end it on the device as EOS does; its stop strings (`SlotRequest.stop_check`) are looked for at each harvest.
+A page with `repetition` (RepetitionParams; `SlotScheduler(repetition=...)` is the default of the pages that carry none) is ended on
+the device at the token its output starts to repeat at (kr_repeat_detect): "length" with `stop_reason` "repetition".
 
 A request whose page asks for `n` sequences takes n slots at once (one ViT + prefill, the siblings' KV rows forked from child 0's
 slot: `Engine.admit`); its children end one by one, each freeing its slot, and its one result carries them as `choices`.  With
@@ -41,6 +43,8 @@ class SlotRequest:
     # SlotScheduler(prefix_cache=True): identifies the whole prompt (token ids, grids, image bytes); requests with equal keys
     # share the prompt's KV rows while a slot still holds them
     prompt_key: Optional[bytes] = None
+    # the request itself switched repetition detection off: the scheduler's default (SlotScheduler(repetition=...)) does not apply
+    repetition_off: bool = False
 
 
 @dataclass
@@ -55,6 +59,7 @@ class SlotResult:
     logprobs: Optional[Dict[str, np.ndarray]] = None   # when the page asked for them (Engine.slot_logprobs)
     # page.n > 1: one SlotResult per child, in child order (the fields above are child 0's); None for n == 1
     choices: Optional[List["SlotResult"]] = None
+    stop_reason: Optional[str] = None       # "repetition" where the page's RepetitionParams ended the sequence ("length"), else None
 
 
 # Break-even of a speculative chunk: accepted drafts per slot and step below which plain steps emit more tokens per second,
@@ -115,7 +120,7 @@ class SlotScheduler:
                  max_prompt_tokens: Optional[int] = None, max_patches: Optional[int] = None, sampling: bool = False,
                  overlap: bool = False, guided: bool = False, logprobs: Optional[int] = None, admit_min: int = 1,
                  admit_max_wait: int = 4, launch_ahead: bool = True, prefix_cache: bool = False, speculative: bool = False,
-                 spec_policy: Optional[SpecPolicy] = None):
+                 spec_policy: Optional[SpecPolicy] = None, repetition=None):
         if max_tokens_cap < 1 or chunk < 1:
             raise ValueError("max_tokens_cap and chunk must be >= 1")
         self.engine = engine
@@ -171,6 +176,12 @@ class SlotScheduler:
         # GEMMs at several times the rows of a single page — but never longer than `admit_max_wait` scheduler steps.
         self.admit_min, self.admit_max_wait = max(1, int(admit_min)), max(0, int(admit_max_wait))
         self._held = 0                               # scheduler steps the oldest admissible request has been held back
+        # repetition detection: the default of the requests that neither carry their own parameters nor switch it off, and what it did
+        self.repetition = repetition
+        self.repetition_stops = 0                    # sequences ended by it
+        self.repetition_tokens_cut = 0               # sum of max_tokens - completion_tokens over those
+        self._rep_active = 0                         # sequences in the slots that carry it
+        self._rep_on = False
         self.steps = 0                               # decode steps run
         # host wall time by phase (seconds): admission launches, decode-chunk launches, the wait for the GPU in _harvest
         self.phase_s = {"admit": 0.0, "decode_launch": 0.0, "harvest": 0.0}
@@ -197,11 +208,15 @@ class SlotScheduler:
         self._features = ((sampling or guided) and hasattr(engine, "set_step_features")
                           and os.environ.get("KARANTA_STEP_FEATURES", "1") == "1")
         self._features_now = None
+        # a greedy configuration has no optional pass but the repetition pass: it is switched with the requests that carry it
+        self._rep_switch = not (sampling or guided) and hasattr(engine, "set_step_features")
 
     # ------------------------------------------------------------------ public
     def submit(self, req: SlotRequest) -> None:
         if req.max_tokens < 1:
             raise ValueError("max_tokens must be >= 1")
+        if self.repetition is not None and not req.repetition_off and getattr(req.page, "repetition", None) is None:
+            req.page.repetition = self.repetition
         self.waiting.append(req)
 
     @property
@@ -272,8 +287,12 @@ class SlotScheduler:
             need = StepFeatures.of(r.page for r in [*self.active.values(), *pending])
             if need != self._features_now:
                 # (engines older than the adjustment pass take three arguments: it is only named when a request needs it)
-                self.engine.set_step_features(need.sampling, need.guided, need.processing, **({"adjust": True} if need.adjust else {}))
+                self.engine.set_step_features(need.sampling, need.guided, need.processing, **({"adjust": True} if need.adjust else {}),
+                                              **({"repetition": True} if need.repetition else {}))
                 self._features_now = need
+        elif self._rep_switch and (self._rep_active > 0) != self._rep_on:
+            self._rep_on = self._rep_active > 0
+            self.engine.set_step_features(False, False, False, repetition=self._rep_on)
         if self._spec_chunk():
             self.engine.decode_steps(self.chunk, speculative=True)
             self.spec_steps += self.chunk
@@ -338,6 +357,7 @@ class SlotScheduler:
                 j = slots[k]
                 self.active[j], self._child[j], self.prompt_len[j] = r, c, int(lens[k])
                 self._adm_seq[j] = self._snap_seq    # snapshots taken from now on see this request in the slot
+                self._rep_active += getattr(r.page, "repetition", None) is not None
                 if self.prefix_cache and r.prompt_key is not None:
                     self._resident[j] = (r.prompt_key, int(lens[k]))
                 k += 1
@@ -485,6 +505,7 @@ class SlotScheduler:
         fin, gen = flags if flags is not None else self.engine.poll_slots()
         if self.speculative:
             self._spec_account(self.engine.spec_counts() if hasattr(self.engine, "spec_counts") else None, seq)
+        rep_at = self.engine.slot_rep_at() if self._rep_active and hasattr(self.engine, "slot_rep_at") else None
         out: List[SlotResult] = []
         for j in sorted(self.active):
             if seq is not None and self._adm_seq.get(j, 0) > seq:
@@ -497,17 +518,21 @@ class SlotScheduler:
             if not over and (check is None or n < 1):
                 continue
             toks = np.asarray(self.engine.slot_tokens(j, n), np.int64)
-            reason, on_token = "length", False
+            reason, on_token, cause = "length", False, None
             if over:
                 stops = self.eos | set(int(t) for t in getattr(r.page, "stop_token_ids", None) or ())
                 hit = np.flatnonzero(np.isin(toks, list(stops))) if stops else np.zeros(0, np.int64)
                 if hit.size:
                     toks, reason, on_token = toks[: int(hit[0]) + 1], "stop", True
+                # the token the sequence repeats at is kept; an EOS or stop id at or before it wins, and so does max_tokens
+                g = int(rep_at[j]) if rep_at is not None and getattr(r.page, "repetition", None) is not None else -1
+                if 0 <= g < len(toks) - (1 if on_token else 0):
+                    toks, reason, on_token, cause = toks[: g + 1], "length", False, "repetition"
             if check is not None:
                 keep = check(toks)
                 if keep is not None and keep <= len(toks):
                     on_token = on_token and keep == len(toks)
-                    toks, reason = toks[:int(keep)], "stop"
+                    toks, reason, cause = toks[:int(keep)], "stop", None
                 elif not over:
                     continue
             if not fin[j]:
@@ -517,7 +542,11 @@ class SlotScheduler:
             if k is not None and self.logprobs is not None:
                 n_lp = len(toks) - (1 if on_token else 0)     # the step that finishes on EOS / a stop id records nothing
                 lps = self.engine.slot_logprobs(j, n_lp, int(k))
-            res = SlotResult(r.tag, toks, reason, self.prompt_len.pop(j), request=r, logprobs=lps)
+            res = SlotResult(r.tag, toks, reason, self.prompt_len.pop(j), request=r, logprobs=lps, stop_reason=cause)
+            if cause == "repetition":
+                self.repetition_stops += 1
+                self.repetition_tokens_cut += limit - len(toks)
+            self._rep_active -= getattr(r.page, "repetition", None) is not None
             del self.active[j]                       # the child's slot is free for the next admission
             self._child.pop(j, None)
             self._tick += 1
@@ -528,6 +557,6 @@ class SlotScheduler:
                 self._open.pop(id(r), None)
                 if len(kids) > 1:
                     res = SlotResult(r.tag, kids[0].tokens, kids[0].finish_reason, kids[0].prompt_tokens, request=r,
-                                     logprobs=kids[0].logprobs, choices=list(kids))
+                                     logprobs=kids[0].logprobs, choices=list(kids), stop_reason=kids[0].stop_reason)
                 out.append(res)
         return out

@@ -29,6 +29,10 @@ is the sum over the choices.  ``n`` above the server's decode slots is a 400; ``
 grids, image bytes) equals one still resident in a decode slot starts from that slot's rows, without ViT or prefill — the
 reference's retry loop (the same page again at a higher temperature, pipeline.py ``process_page``) becomes decode-only.
 ``guided_regex`` / ``response_format`` / ``logprobs``: guided.py, engine.
+``repetition_detection`` (vLLM's field: ``{"max_pattern_size", "min_pattern_size", "min_count", "min_span"}``; ``false`` / ``null``:
+off for this request; absent: the server's ``--repetition-detection`` default, which is off unless given): the sequence ends with
+``finish_reason: "length"`` and ``stop_reason: "repetition"`` at the token its output starts to repeat at (kr_repeat_detect, inside
+the decode step).  It changes no token choice, so ``--greedy`` honours it.  Every choice carries ``stop_reason`` (``null`` otherwise).
 
 Prompt text: the checkpoint's own ``chat_template`` when the model directory ships one (``chat_template.json`` /
 ``chat_template.jinja`` / ``tokenizer_config.json`` — what vLLM applies, pipeline.py:707-734), rendered with jinja2; the
@@ -50,7 +54,7 @@ import numpy as np
 from . import image_processing as IP
 from .config import ModelConfig
 from .request import PageRequest
-from .sampling import NEUTRAL, StopStrings, parse_adjust_fields, parse_request_fields
+from .sampling import NEUTRAL, StopStrings, parse_adjust_fields, parse_repetition_field, parse_request_fields
 
 DEFAULT_SYSTEM = "You are a helpful assistant."
 
@@ -160,6 +164,10 @@ class ParsedRequest:
     include_stop_str_in_output: bool = False
     n: int = 1                      # choices to return (parallel sampling)
     prompt_key: Optional[bytes] = None   # ChatFrontend(prompt_keys): 16-byte digest of prompt ids, grids and image bytes
+    # repetition_detection: the request's own RepetitionParams, or None with repetition_set = True where it switched detection off;
+    # repetition_set = False: the field was absent and the server's default applies
+    repetition: Any = None
+    repetition_set: bool = False
 
 
 ADJUST_FIELDS = ("logit_bias", "min_tokens", "stop_token_ids")
@@ -391,6 +399,8 @@ class ChatFrontend:
             guide = self._guide_for(req)
             controls.update(parse_adjust_fields(req, self.cfg.text.vocab_size, max_tokens, guided=guide is not None,
                                                 eos_token_ids=self.cfg.eos_token_ids))
+            if "repetition_detection" in req:
+                controls.update(repetition=parse_repetition_field(req["repetition_detection"]), repetition_set=True)
         except BadRequest:
             raise
         except ValueError as e:
@@ -419,8 +429,10 @@ class LocalServer:
                  batch_wait_s: float = 0.005, log=print, continuous: bool = False, max_tokens_cap: int = 4096,
                  chunk: int = 2, honor_temperature: bool = True, max_logprobs: Optional[int] = None, admit_min: int = 1,
                  admit_max_wait: int = 16, overlap_admissions: bool = False, launch_ahead: bool = True,
-                 prefix_cache: bool = False, speculative: bool = False):
+                 prefix_cache: bool = False, speculative: bool = False, repetition=None):
         self.engine, self.frontend, self.name = engine, frontend, served_model_name
+        # the default of the requests without a repetition_detection field (RepetitionParams, its dict form, or None: off)
+        self.repetition = parse_repetition_field(repetition)
         # prompt-lookup speculative decoding (vLLM's --speculative-config, method ngram): continuous mode, an engine built with
         # speculative=SpecConfig(...), no log-probabilities (SlotScheduler(speculative=True))
         self.speculative = bool(speculative)
@@ -486,6 +498,8 @@ class LocalServer:
                 # speculative decoding (vLLM's counter names): drafts proposed / accepted, decode steps of either kind
                 "spec_decode_num_draft_tokens": sch.spec_draft_tokens, "spec_decode_num_accepted_tokens": sch.spec_accepted_tokens,
                 "spec_decode_steps": sch.spec_steps, "plain_decode_steps": sch.plain_steps,
+                # repetition detection: sequences it ended, and the tokens up to their max_tokens that were not generated
+                "repetition_stops": sch.repetition_stops, "repetition_tokens_cut": sch.repetition_tokens_cut,
                 "host_phase_s": {k: round(v, 3) for k, v in sch.phase_s.items()}}
 
     def models(self) -> Tuple[int, dict]:
@@ -535,7 +549,8 @@ class LocalServer:
         for c, ch in enumerate(slot["choices"]):           # one per child, in child order
             toks = ch["tokens"]
             text = ch["text"] if ch.get("text") is not None else self.frontend.tok.decode(toks)   # "text": cut at a stop string
-            choice: Dict[str, Any] = {"index": c, "message": {"role": "assistant", "content": text}, "finish_reason": ch["reason"]}
+            choice: Dict[str, Any] = {"index": c, "message": {"role": "assistant", "content": text}, "finish_reason": ch["reason"],
+                                      "stop_reason": ch.get("stop_reason")}
             if parsed.logprobs is not None:
                 choice["logprobs"] = self._logprobs_json(toks, ch.get("logprobs"), parsed.logprobs)
             choices.append(choice)
@@ -601,7 +616,8 @@ class LocalServer:
                     for s in group:
                         for c in range(s["req"].n):
                             lps = res.logprobs[i] if getattr(res, "logprobs", None) is not None else None
-                            self._finish(s, res.tokens[i], res.finish_reasons[i], c, lps)
+                            why = res.stop_reasons[i] if getattr(res, "stop_reasons", None) is not None else None
+                            self._finish(s, res.tokens[i], res.finish_reasons[i], c, lps, why)
                             i += 1
                 except Exception as e:  # engine failure -> 500 for every request of the group
                     for s in group:
@@ -671,13 +687,15 @@ class LocalServer:
             for name in ADJUST_FIELDS:
                 if getattr(r, name, None):
                     setattr(page, name, getattr(r, name))
+        # repetition detection chooses no token: --greedy serves it too.  The request's field wins over the server's default
+        page.repetition = getattr(r, "repetition", None) if getattr(r, "repetition_set", False) else self.repetition
         return page
 
-    def _finish(self, s: Dict[str, Any], toks, reason: str, c: int = 0, logprobs=None):
+    def _finish(self, s: Dict[str, Any], toks, reason: str, c: int = 0, logprobs=None, stop_reason: Optional[str] = None):
         """Child c of a request is through: its tokens as the response reports them -> s["choices"][c]."""
         mt = s["req"].max_tokens
-        if len(toks) > mt:
-            toks, reason = toks[:mt], "length"
+        if len(toks) > mt:       # (a static batch decodes for its longest member: this one's own limit came first)
+            toks, reason, stop_reason = toks[:mt], "length", None
         eos = set(int(e) for e in self.engine.cfg.eos_token_ids)
         if self.honor_temperature:
             eos |= set(int(t) for t in getattr(s["req"], "stop_token_ids", None) or ())
@@ -690,12 +708,16 @@ class LocalServer:
         if m is not None:
             keep = m.check(toks)
             if keep is not None:
-                toks, reason, text = toks[:keep], "stop", m.text
+                toks, reason, text, stop_reason = toks[:keep], "stop", m.text, None
         n = max(1, int(getattr(s["req"], "n", 1)))
-        s.setdefault("choices", [None] * n)[c] = {"tokens": toks, "reason": reason, "text": text, "logprobs": logprobs}
+        s.setdefault("choices", [None] * n)[c] = {"tokens": toks, "reason": reason, "text": text, "logprobs": logprobs,
+                                                      "stop_reason": stop_reason}
 
     def _spec_kw(self) -> dict:
         return {"speculative": True} if self.speculative else {}      # (only named when on: test fakes of the scheduler's engine)
+
+    def _rep_kw(self) -> dict:
+        return {"repetition": self.repetition} if self.repetition is not None else {}      # (only named when set, as above)
 
     def _loop_continuous(self):
         from .scheduler import SlotRequest, SlotScheduler
@@ -704,7 +726,7 @@ class LocalServer:
             sch = SlotScheduler(self.engine, self.max_tokens_cap, self.chunk, sampling=self.honor_temperature,
                                 guided=self.guided, logprobs=self.max_logprobs, admit_min=self.admit_min,
                                 admit_max_wait=self.admit_max_wait, overlap=self.overlap_admissions,
-                                launch_ahead=self.launch_ahead, prefix_cache=self.prefix_cache, **self._spec_kw())
+                                launch_ahead=self.launch_ahead, prefix_cache=self.prefix_cache, **self._spec_kw(), **self._rep_kw())
         except Exception as e:  # cannot enter slot mode: every request gets a 500
             sch, boot_error = None, f"{type(e).__name__}: {e}"
         self._sch = sch
@@ -732,7 +754,8 @@ class LocalServer:
                     s["stops"] = [self._stop_strings(r) for _ in range(r.n)]
                     sch.submit(SlotRequest(self._page(r), max(1, int(r.max_tokens)), tag=s, stop_check=s["stops"][0],
                                            stop_checks=s["stops"] if r.n > 1 else None,
-                                           prompt_key=r.prompt_key if self.prefix_cache else None))
+                                           prompt_key=r.prompt_key if self.prefix_cache else None,
+                                           repetition_off=getattr(r, "repetition_set", False) and r.repetition is None))
             if self._stop or sch is None:
                 continue
             try:
@@ -748,7 +771,7 @@ class LocalServer:
                     sch = SlotScheduler(self.engine, self.max_tokens_cap, self.chunk, sampling=self.honor_temperature,
                                         guided=self.guided, logprobs=self.max_logprobs, admit_min=self.admit_min,
                                         admit_max_wait=self.admit_max_wait, overlap=self.overlap_admissions,
-                                        launch_ahead=self.launch_ahead, prefix_cache=self.prefix_cache, **self._spec_kw())
+                                        launch_ahead=self.launch_ahead, prefix_cache=self.prefix_cache, **self._spec_kw(), **self._rep_kw())
                 except Exception as e2:
                     sch, boot_error = None, f"{type(e2).__name__}: {e2}"
                 self._sch = sch
@@ -766,7 +789,7 @@ class LocalServer:
                     s["status"] = getattr(res, "status", 500)
                 else:
                     for c, ch in enumerate(res.choices if getattr(res, "choices", None) else [res]):
-                        self._finish(s, ch.tokens, ch.finish_reason, c, ch.logprobs)
+                        self._finish(s, ch.tokens, ch.finish_reason, c, ch.logprobs, getattr(ch, "stop_reason", None))
                 self.pages_done += 1
                 s["done"].set()
         # shutting down: nobody is left waiting forever
