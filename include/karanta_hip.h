@@ -39,7 +39,7 @@ typedef uint16_t kr_bf16;
 /* kr_version() of the library this header describes: major * 100 + minor.  The major changes with every incompatible
  * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family); a caller built
  * against major X must refuse a library whose kr_version() / 100 != X. */
-#define KR_ABI_VERSION 410
+#define KR_ABI_VERSION 411
 
 #define KR_OK 0
 #define KR_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -655,6 +655,21 @@ typedef struct kr_kvq_plan {
 } kr_kvq_plan;
 int kr_kv_quantize(const kr_bf16* k_src, const kr_bf16* vt_src, const kr_kv8* dst, int kv_heads, int hd, int slots, int s_max,
                    const kr_kvq_plan* plan, int32_t* n_clamped, kr_stream s);
+
+/* --calculate-kv-scales: one layer's row of the scale table from the absolute maxima of what kr_kv_quantize is about to convert.
+ * Same scratch, geometry and plan.  Per K and V and per kv head, amax = the largest |x| over the FINITE bf16 elements of K rows
+ * [0, len) and of V keys [0, len) of every listed slot (in the last V^T block the keys at or beyond len are stale and excluded;
+ * NaN and +-inf are skipped; slots not in the plan are never read), and
+ *     scale_out[(K: 0 | V: 1) * kv_heads + h] = amax == 0 ? 1.0f : max(amax / range, FLT_MIN)
+ * with one IEEE f32 division, range = k_range for K, v_range for V.  A maximum does not depend on order: the result is exact.
+ * `work`: device, 2 * kv_heads words owned by the caller (the library allocates nothing), ZERO on entry and zero again when the
+ * call's work completes, so the next layer's call reuses it.  Two launches on `s`: the reduction (pieces and capped, strided grid
+ * as kr_kv_quantize; at most one atomic max per workgroup and (K | V, head) into `work`) and a one-workgroup launch behind it that
+ * writes scale_out and clears `work`; both are complete before the next launch on `s` starts.
+ * KR_ERR_ARG, nothing launched: a null pointer, hd != 128, kv_heads > 64, what kr_kv_quantize refuses of the geometry and the plan,
+ * a range that is not finite and positive, a scratch that is not 16-byte aligned. */
+int kr_kv_absmax(const kr_bf16* k_src, const kr_bf16* vt_src, int kv_heads, int hd, int slots, int s_max, const kr_kvq_plan* plan,
+                 float k_range, float v_range, float* scale_out, uint32_t* work, kr_stream s);
 
 /* kr_kv_fork for a cache of one-byte elements (a piece is hd x 64 bytes): strides in elements = bytes, multiples of 16; hd % 16. */
 int kr_kv_fork8(uint8_t* kcache, uint8_t* vtcache, int64_t k_layer_stride, int64_t k_slot_stride, int64_t k_head_stride,

@@ -108,6 +108,7 @@ SIGNATURES = {
     "kr_linear_decode32_rows": [i32, c_p, c_p, c_p],
     "kr_attn_decode_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
     "kr_kv_quantize": [c_p, c_p, c_p, i32, i32, i32, i32, c_p, c_p, c_p],
+    "kr_kv_absmax": [c_p, c_p, i32, i32, i32, i32, c_p, f32, f32, c_p, c_p, c_p],
     "kr_kv_fork8": [c_p, c_p, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, c_p, c_p],
     "kr_attn_decode_slots_kv8": [c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
     "kr_attn_decode_rows_kv8": [c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],

@@ -70,6 +70,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="vLLM's flag: auto = bfloat16; fp8 = fp8_e4m3: the KV cache as e4m3 codes with one scale per (layer, K or V, "
                          "kv head) — half the cache's bytes and half the decode attention's traffic; scales from the checkpoint's "
                          "k_scale / v_scale tensors where it ships them, else 1.0 (the server logs what an admission had to clamp)")
+    ap.add_argument("--calculate-kv-scales", action="store_true",
+                    help="vLLM's flag, with --kv-cache-dtype fp8: the scales are calculated on the device from the first admission's K "
+                         "and V, scale = max|x| / K_SCALE_CONSTANT (200) or V_SCALE_CONSTANT (100), both read from the environment, "
+                         "per (layer, K or V, kv head); it wins over a checkpoint's scales.  The server's tokens then depend on which "
+                         "admission came first.  With a bfloat16 cache: accepted and ignored with a log line")
     ap.add_argument("--enable-prefix-caching", action="store_true",
                     help="vLLM's flag: a request whose whole prompt (ids, grids, image bytes) is still resident in a decode slot "
                          "starts from that slot's KV rows, without ViT or prefill (continuous mode)")
@@ -252,9 +257,9 @@ def admission_budget(args, cfg, max_pixels: int):
 def make_server(args, log=print):
     """Engine + front end + LocalServer from parsed arguments (weights and tokenizer from args.model_dir)."""
     from . import image_processing as IP
-    from .engine import Engine, SpecConfig
+    from .engine import KV_SCALES_FLAG_WINS, Engine, SpecConfig
     from .serving import ChatFrontend, HFTokenizer, LocalServer, load_chat_template
-    from .weights import load_checkpoint
+    from .weights import kv_cache_dtype_name, kv_scale_ranges_from_env, load_checkpoint
 
     from .dp import load_or_receive_weights, serving_group_env
     from .weights import load_config
@@ -283,10 +288,16 @@ def make_server(args, log=print):
             + (", guided requests included" if spec_guided else ""))
     # ... speculative: every step past the limit may emit K + 1 tokens, and the draft rows write K cache rows ahead
     slack = 1 + 16 * (spec[0] + 1 if spec else 1) + (spec[0] if spec else 0)
+    kv_fp8 = kv_cache_dtype_name(getattr(args, "kv_cache_dtype", "auto")) == "fp8"
+    calc = {}
+    if getattr(args, "calculate_kv_scales", False) and kv_fp8:
+        calc = {"calculate_kv_scales": True, "kv_scale_ranges": kv_scale_ranges_from_env()}
+    elif getattr(args, "calculate_kv_scales", False):
+        log("--calculate-kv-scales: ignored, the KV cache is bfloat16 (it applies to --kv-cache-dtype fp8)")
     eng = Engine(cfg, device="cuda:0", max_batch=args.max_num_seqs, s_max=(args.max_model_len + slack + 63) // 64 * 64,
                  max_patches=max_patches, max_prompt_tokens=max_prompt_tokens,
                  weight_dtype=weight_dtype, fp8_activations=bool(getattr(args, "fp8_activations", False)) or None,
-                 kv_cache_dtype=getattr(args, "kv_cache_dtype", "auto"),
+                 kv_cache_dtype=getattr(args, "kv_cache_dtype", "auto"), **calc,
                  **({"speculative": SpecConfig(*spec, share_rows=share, guided=spec_guided)} if spec else {}))
     # one server: read the checkpoint.  A launch.py group: rank 0 reads it ONCE, the arena goes to the other GPUs over
     # RCCL / xGMI (north_star: "RCCL broadcast of weights over xGMI"); a failure stops every server of the group
@@ -297,9 +308,12 @@ def make_server(args, log=print):
     if eng.kv8:      # every server of a group reads the (tiny) scale tensors itself: only rank 0 reads the weights
         from .weights import load_kv_scales
         sc = load_kv_scales(args.model_dir, cfg)
-        if sc is not None:
+        if sc is not None and calc:
+            log(KV_SCALES_FLAG_WINS)
+        elif sc is not None:
             eng.set_kv_scales(*sc, source="checkpoint (self_attn.k_scale / v_scale)")
-        log(f"fp8 KV cache scales: {eng.kv_scale_source}")
+        log("fp8 KV cache scales: " + (f"to be calculated from the first admission (ranges {calc['kv_scale_ranges'][0]:g} / "
+                                       f"{calc['kv_scale_ranges'][1]:g})" if calc else eng.kv_scale_source))
     if world > 1:
         log(f"weight broadcast: {info['bytes'] / 1e9:.2f} GB in {info['bcast_s']:.3f}s over {info['rccl_ranks']} RCCL ranks")
     template = load_chat_template(args.model_dir)

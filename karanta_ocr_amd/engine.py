@@ -25,7 +25,7 @@ from . import positions as POS
 from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_NONE, EPI_SILU_MUL8, KarantaHipError, Spec, fork_plan,
                    kv8, kvq_plan, lib, narrow_opts, ptr)
 from .config import ModelConfig
-from .weights import kv_cache_dtype_name, kv_scale_table, kv_scales_from_checkpoint
+from .weights import KV_SCALE_RANGES, kv_cache_dtype_name, kv_scale_table, kv_scales_from_checkpoint
 from .device_weights import DeviceWeights, _align, narrow_weight_bytes, plan_resident
 from .request import GenerateResult, PageRequest, SpecConfig, children
 from .sampler import DeviceGuide, Sampler
@@ -45,6 +45,8 @@ IC_RESIDENT_MB = 192
 # a launch is planned only if its expected saving reaches what two identical graphs differ by per launch in that sweep (3-4 us per
 # step over 28 launches): the sub-MB matrices of the test-sized models keep their nontemporal loads
 IC_RESIDENT_MIN_US = 0.1
+KV_SCALES_FLAG_WINS = ("fp8 KV cache scales: the checkpoint ships k_scale / v_scale, but --calculate-kv-scales wins: the first "
+                       "admission calculates them")
 SEQUENCE_SWITCHES = ("KARANTA_NARROW", "KARANTA_NARROW_O", "KARANTA_DEFER_DOWN", "KARANTA_WIDE", "KARANTA_ATOMIC_SLAB", "KARANTA_DEC32")
 
 __all__ = ["Engine", "PageRequest", "SpecConfig", "DeviceWeights", "GenerateResult", "children", "SEQUENCE_SWITCHES", "DeviceGuide"]
@@ -100,7 +102,8 @@ class Engine:
     def __init__(self, cfg: ModelConfig, device: str = "cuda:0", max_batch: int = 8, s_max: int = 4096,
                  max_patches: int = 8 * 5476, max_prompt_tokens: int = 8 * 2048, decode_splits: int = 16,
                  weight_dtype: str = "bf16", fp8_activations: Optional[bool] = None, admission_cus: Optional[int] = None,
-                 speculative: Optional[SpecConfig] = None, ic_resident_mb: Optional[int] = None, kv_cache_dtype: str = "auto"):
+                 speculative: Optional[SpecConfig] = None, ic_resident_mb: Optional[int] = None, kv_cache_dtype: str = "auto",
+                 calculate_kv_scales: bool = False, kv_scale_ranges: Tuple[float, float] = KV_SCALE_RANGES):
         if not torch.cuda.is_available():
             raise KarantaHipError("no HIP device: the karanta MI355X engine has no CPU fallback")
         self.L = lib()
@@ -157,6 +160,17 @@ class Engine:
         if self.kv8 and t.head_dim != 128:
             raise KarantaHipError(f"kv_cache_dtype fp8 needs a text head_dim of 128, this model has {t.head_dim}: the fp8 cache's "
                                   "quantise, append and attention kernels are written for 128-byte K rows")
+        # --calculate-kv-scales: the FIRST prefill writes the scale table from the absolute maxima of its own K / V (kr_kv_absmax):
+        # scale = amax / range per (layer, K or V, kv head).  _kv_calibrate is armed until then (set_kv_scales disarms it)
+        self.calculate_kv_scales = bool(calculate_kv_scales)
+        if self.calculate_kv_scales and not self.kv8:
+            raise KarantaHipError("calculate_kv_scales: the KV cache is bfloat16, there are no scales to calculate "
+                                  "(kv_cache_dtype=\"fp8\" quantises it)")
+        self.kv_scale_ranges = tuple(float(r) for r in kv_scale_ranges)
+        if len(self.kv_scale_ranges) != 2 or not all(np.isfinite(r) and r > 0 for r in self.kv_scale_ranges):
+            raise KarantaHipError(f"kv_scale_ranges {kv_scale_ranges!r}: (K range, V range), finite and positive")
+        self._kv_calibrate = self.calculate_kv_scales
+        self.kv_scales_calibrated = False           # True once the calibrating admission has been launched
         if v.head_dim not in (80, 128) or t.head_dim != 128:
             raise KarantaHipError(f"unsupported head dims vit={v.head_dim} llm={t.head_dim}")
         self.w = DeviceWeights(cfg, self.device, weight_dtype)
@@ -238,6 +252,10 @@ class Engine:
             self.d_kv_clamped = z(1, dtype=torch.int32)
             self.h_kv_clamped = torch.zeros(1, dtype=torch.int32).pin_memory()    # its host mirror, refreshed behind every admission
             self.kv_scale_source = "default (1.0)"
+            # the table's host mirror (kv_scales()): written by set_kv_scales, refreshed behind the calibrating admission
+            self.h_kv_scale = torch.ones(t.num_layers, 2, t.num_kv_heads, dtype=torch.float32).pin_memory()
+            if self.calculate_kv_scales:   # kr_kv_absmax's [2][KVH] words: zero on entry, zero again behind every call
+                self.d_kv_work = z(2 * t.num_kv_heads, dtype=torch.int32)
         # decode state
         self.d_x = z(R, t.hidden_size)
         self.d_x2 = z(R, t.hidden_size)  # the other residual buffer (deferred split-K ping-pong)
@@ -349,8 +367,25 @@ class Engine:
         if not self.kv8:
             raise KarantaHipError("set_kv_scales: the KV cache is bfloat16 (kv_cache_dtype=\"fp8\" quantises it)")
         t = self.cfg.text
-        self.d_kv_scale.copy_(torch.from_numpy(kv_scale_table(k, v, t.num_layers, t.num_kv_heads)).to(self.device))
+        table = torch.from_numpy(kv_scale_table(k, v, t.num_layers, t.num_kv_heads))
+        self.d_kv_scale.copy_(table.to(self.device))
+        self.h_kv_scale.copy_(table)
         self.kv_scale_source = source
+        self._kv_calibrate = False        # calculate_kv_scales: a table set by hand before the first admission stands
+
+    def kv_scales(self) -> np.ndarray:
+        """The [L, 2, KVH] scale table (K scales, then V scales, per layer) from its host mirror: what set_kv_scales put there, or
+        what the calibrating admission calculated — as of the last admission whose stream has been waited for (generate, admit,
+        admit_end), like kv_clamped.  `set_kv_scales(table[:, 0], table[:, 1])` on another engine pins it."""
+        if not self.kv8:
+            raise KarantaHipError("kv_scales: the KV cache is bfloat16 (kv_cache_dtype=\"fp8\" quantises it)")
+        return self.h_kv_scale.numpy().copy()
+
+    @property
+    def kv_scales_ready(self) -> bool:
+        """calculate_kv_scales: the calibrating admission has run on the device and kv_scales() holds what it calculated.  A query
+        of an event, no synchronisation."""
+        return self.kv_scales_calibrated and self._kv_scale_event.query()
 
     @property
     def kv_clamped(self) -> int:
@@ -369,7 +404,10 @@ class Engine:
         self.w.load(weights)
         if self.kv8:      # a checkpoint with a kv_cache_scheme ships one k_scale / v_scale per layer: broadcast over the kv heads
             sc = kv_scales_from_checkpoint(weights, self.cfg)
-            if sc is not None:
+            if sc is not None and self._kv_calibrate:
+                if log is not None:
+                    log(KV_SCALES_FLAG_WINS)
+            elif sc is not None:
                 self.set_kv_scales(*sc, source="checkpoint (self_attn.k_scale / v_scale)")
             if log is not None:
                 log(f"fp8 KV cache scales: {self.kv_scale_source}")
@@ -655,6 +693,9 @@ class Engine:
         rows = adm.rows
         adm.need = self._admit_features(rows)
         M, d = adm.M, t.hidden_size
+        # calculate_kv_scales: the first prefill after construction calibrates — every layer writes its row of the scale table
+        # (kr_kv_absmax over the scratch) right before kr_kv_quantize reads it, on this admission's stream; later ones do not
+        calibrate, self._kv_calibrate = self.kv8 and self._kv_calibrate, False
         with torch.cuda.stream(self.stream):
             self._h2d(self.p_src, adm.src)
             self._h2d(self.p_cos, adm.cos)
@@ -673,6 +714,9 @@ class Engine:
                 kc, vc = (self.p_kscratch, self.p_vtscratch) if self.kv8 else (self.kcache[i], self.vtcache[i])
                 self._attention(self.p_qkv, t.q_dim, t.q_dim + t.kv_dim, self.p_cos, self.p_sin, dp, self.p_q, kc, kc.stride(1),
                                 vc, vc.stride(1), self.p_o, t.num_heads, t.num_kv_heads, t.head_dim, causal=True)
+                if calibrate:
+                    L.kr_kv_absmax(ptr(kc), ptr(vc), t.num_kv_heads, t.head_dim, self.B, self.s_max, kvq_plan(adm.kvq),
+                                   self.kv_scale_ranges[0], self.kv_scale_ranges[1], ptr(self.d_kv_scale[i]), ptr(self.d_kv_work), s)
                 if self.kv8:   # the admission's rows of the scratch -> layer i of the fp8 cache, on the admission's stream
                     L.kr_kv_quantize(ptr(kc), ptr(vc), self._kv8(i), t.num_kv_heads, t.head_dim, self.B, self.s_max,
                                      kvq_plan(adm.kvq), ptr(self.d_kv_clamped), s)
@@ -682,6 +726,13 @@ class Engine:
                 self._gemm(self.p_act, w.view(p + "down.w"), self.p_x, M, res=self.p_x, packed=True, **self._w8kw(p + "down.w"))
             if self.kv8:
                 self.h_kv_clamped.copy_(self.d_kv_clamped, non_blocking=True)
+            if calibrate:
+                self.h_kv_scale.copy_(self.d_kv_scale, non_blocking=True)
+                self.kv_scale_source = (f"calculated from the first admission ({M} prompt tokens; ranges "
+                                        f"{self.kv_scale_ranges[0]:g} / {self.kv_scale_ranges[1]:g})")
+                self._kv_scale_event = torch.cuda.Event()
+                self._kv_scale_event.record(self.stream)
+                self.kv_scales_calibrated = True
             self.pages_prefilled += adm.n_pages
             if not defer_activation:
                 self._fork(adm.forks)

@@ -484,7 +484,7 @@ class LocalServer:
         return 200, {"pages_done": self.pages_done, "uptime_s": round(up, 3), "pages_per_s": round(self.pages_done / up, 4),
                      "running": self._running, "waiting": self._q.qsize(),
                      "latency_s": {"p50": pct(0.50), "p95": pct(0.95), "p99": pct(0.99), "n": len(lat)},
-                     "scheduler": self.scheduler_stats()}
+                     "scheduler": self.scheduler_stats(), "kv_cache": self.kv_cache_stats()}
 
     def scheduler_stats(self) -> Optional[dict]:
         """Continuous mode: where the scheduler thread's wall time went and how full the decode slots were."""
@@ -634,11 +634,32 @@ class LocalServer:
     def _log_kv_clamped(self):
         """fp8 KV cache: one line per admission that had to clamp values on their way into the cache (an operator running on
         scales of 1.0, or on scales that do not fit the model, must see it)."""
+        self._log_kv_scales()
         n = int(getattr(self.engine, "kv_clamped", 0) or 0)
         if n > getattr(self, "_kv_clamped_seen", 0):
             self.log(f"fp8 KV cache: the last admission clamped {n - getattr(self, '_kv_clamped_seen', 0)} K/V elements to +-448 x scale "
                      f"({n} since start; scales: {getattr(self.engine, 'kv_scale_source', '?')})")
             self._kv_clamped_seen = n
+
+    def _log_kv_scales(self):
+        """--calculate-kv-scales: ONE line once the calibrating admission has run — where the scales come from and their spread.  From
+        then on the clamp line above is the signal that a later page outgrew the first admission's headroom."""
+        if getattr(self, "_kv_scales_logged", False) or not getattr(self.engine, "kv_scales_ready", False):
+            return
+        self._kv_scales_logged = True
+        sc = self.engine.kv_scales()
+        self.log(f"fp8 KV cache scales: {self.engine.kv_scale_source}; K scales {sc[:, 0].min():.6g} .. {sc[:, 0].max():.6g}, "
+                 f"V scales {sc[:, 1].min():.6g} .. {sc[:, 1].max():.6g}")
+
+    def kv_cache_stats(self) -> Optional[dict]:
+        """/metrics: the KV cache's dtype and, for an fp8 cache, where its scales come from and what the admissions clamped."""
+        eng = self.engine
+        dtype = getattr(eng, "kv_cache_dtype", None)
+        if dtype is None:
+            return None
+        if not getattr(eng, "kv8", False):
+            return {"dtype": dtype}
+        return {"dtype": dtype, "scale_source": getattr(eng, "kv_scale_source", None), "clamped": int(getattr(eng, "kv_clamped", 0) or 0)}
 
     def _static_groups(self, batch):
         """A static batch decodes every sequence for the LONGEST max_tokens of the batch, so a long prompt with a small

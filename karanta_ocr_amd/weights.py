@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Dict, Iterable, Optional
+from typing import Dict, Iterable, Optional, Tuple
 
 import numpy as np
 
@@ -365,6 +365,25 @@ def unpack_w16x64(p: np.ndarray) -> np.ndarray:
 
 # ----------------------------------------------------------------------------- fp8 (e4m3fn) KV cache: the flag and the scales
 KV_CACHE_DTYPES = ("auto", "bfloat16", "fp8", "fp8_e4m3")      # vLLM's --kv-cache-dtype spellings this engine serves
+# --calculate-kv-scales: scale = amax / range.  vLLM's K_SCALE_CONSTANT / V_SCALE_CONSTANT: the first admission's largest |K| lands
+# on code value 200, its largest |V| on 100, which leaves pages after it 2.24x (K) and 4.48x (V) of headroom below 448
+KV_SCALE_RANGES = (200.0, 100.0)
+
+
+def kv_scale_ranges_from_env(env=None) -> Tuple[float, float]:
+    """(K range, V range) from K_SCALE_CONSTANT / V_SCALE_CONSTANT, the environment variables vLLM reads; unset: KV_SCALE_RANGES."""
+    env = os.environ if env is None else env
+    out = []
+    for name, default in zip(("K_SCALE_CONSTANT", "V_SCALE_CONSTANT"), KV_SCALE_RANGES):
+        raw = env.get(name)
+        try:
+            val = default if raw in (None, "") else float(raw)
+        except ValueError:
+            raise ValueError(f"{name}={raw!r} is not a number") from None
+        if not (np.isfinite(val) and val > 0):
+            raise ValueError(f"{name}={raw!r} must be finite and positive")
+        out.append(float(val))
+    return out[0], out[1]
 
 
 def kv_cache_dtype_name(value: str) -> str:
