@@ -25,6 +25,22 @@ while its reference maximum carries the f32 rounding of max * scale * log2(e) (a
 magnitudes), so the winner's P can sit 2^-9 from its bf16 rounding; the output is rounded to bf16 once more (2^-9) and
 1/l in f32: 2^-9 + 2^-9 + slack < 2^-7.  The decode kernel and the hd 80 path use the same bf16 P above and below the
 line and come out tighter; one tolerance is used everywhere.
+
+The fp8 KV cache (attn_decode2_kernel<KV8>) takes the same patterns in an encoding that is exact in e4m3 (the last section of
+this file).  K holds the four base-16 digits of a(r) as e4m3 codes (0 .. 15 are exact) in four channels of its kv head, q holds
+C_Q8 * (4096, 256, 16, 1) in the same channels (C_Q8 = 2048, powers of two, exact in bf16): q . value(K codes) = 2048 * a, an
+exact integer below 2^24 for a < 8192.  The kernel's score is that integer times f32(f32(hd^-0.5 * log2 e) * k_scale[kvh]):
+adjacent a are 261 * k_scale log2 units apart, so GAP holds for every k_scale >= 0.37 (check_gaps decides, per kv head, with
+that folded f32 scale).  The four channels of a kv head lie in four different 16-channel groups, two in channels 0 .. 63 and
+two in 64 .. 127 (both 16-byte loads of a K row; the bf16 cases leave 64 .. 127 empty); the two heads that meet in a group sit
+in different 8-channel halves of it (both k-steps of a 16-byte piece), in both halves of either load also when there are only two kv
+heads; no channel is shared, so another head's rows score 0; the lane inside the group differs from head to head
+(kv8_channels asserts all of this for 1 .. 4 kv heads).  V codes are the integers 1 .. 15, a code stands for
+value * v_scale[kvh]: the expected row is V_int * f32(v_scale).  Stale V^T columns hold code 0x7E (448).  Tolerance: the
+same.  The winner's P is still exactly 1 (the f32 fold of k_scale moves every score of a head by the same factor, 2^-24
+relative, far inside GAP), and the wave's O = V_int exactly is multiplied by v_scale once in f32 (2^-24) before the merge's one
+bf16 rounding of the output: two 2^-24 terms inside the slack above.  (With power-of-two scales the output is V_int * v_scale
+exactly; with the odd ones the bf16 rounding of that product is the whole error.)
 """
 from __future__ import annotations
 
@@ -34,7 +50,8 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from karanta_ocr_amd import positions as POS
-from karanta_ocr_amd.weights import bf16_round
+from karanta_ocr_amd.weights import bf16_round, f32_to_fp8_e4m3, fp8_e4m3_to_f32
+from tests import kv_fp8_ref as KV8R
 
 C_Q = 512.0
 GAP = 48.0
@@ -52,13 +69,14 @@ PREFILL_LONG, PREFILL_LONG_S_MAX, PREFILL_LONG_HEADS = [1394, 77], 1408, (14, 2)
 DECODE_HEADS = [(12, 2), (14, 2), (28, 4)]
 DECODE_SPLITS = [8, 16, 32]
 DECODE_S_MAX = 2176
-DECODE_CTX = [0, 30, 31, 32, 63, 64, 2047, 2048, 2079, 2080, 2175]
+# 43: the last unit ends inside its keys 8 .. 23 (12 keys), where a key-order permutation of the mask shows (the fp8 kernel's pi)
+DECODE_CTX = [0, 30, 31, 32, 43, 63, 64, 2047, 2048, 2079, 2080, 2175]
 DECODE_PEAKS = [0, 31, 32, 33, 63, 64, "ctx-1", "ctx"]
 # two slots whose finished flag is set sit between the live ones: their workgroups must leave their records alone
-DECODE_BATCH = [(0, 0), (30, 0), (77, 1), (31, 0), (32, 0), (63, 0), (64, 0), (2047, 0), (2048, 0), (2100, 1), (2079, 0),
+DECODE_BATCH = [(0, 0), (30, 0), (77, 1), (31, 0), (32, 0), (43, 0), (63, 0), (64, 0), (2047, 0), (2048, 0), (2100, 1), (2079, 0),
                 (2080, 0), (2175, 0)]
-# the 17..32-row batch of kr_attn_decode_merge32: the same contexts and ten more on and beside unit borders
-DECODE_BATCH32 = [(c, 0) for c in DECODE_CTX + [1, 33, 95, 96, 1023, 1024, 1393, 2015, 2016, 2111]]
+# the 17..32-row batch of kr_attn_decode_merge32: the border contexts and ten more on and beside unit borders (21 rows)
+DECODE_BATCH32 = [(c, 0) for c in [0, 30, 31, 32, 63, 64, 2047, 2048, 2079, 2080, 2175, 1, 33, 95, 96, 1023, 1024, 1393, 2015, 2016, 2111]]
 
 
 def vit_patterns(lens: Sequence[int]) -> List[str]:
@@ -118,15 +136,17 @@ def scores_log2(a: np.ndarray, hd: int, prescaled: bool = False) -> np.ndarray:
     return C_Q * a.astype(np.float64) * float(sl)
 
 
-def check_gaps(a: np.ndarray, visible: np.ndarray, forbidden: Optional[np.ndarray], hd: int, what: str = "") -> np.ndarray:
+def check_gaps(a: np.ndarray, visible: np.ndarray, forbidden: Optional[np.ndarray], hd: int, what: str = "",
+               kv8_k_scale: Optional[float] = None) -> np.ndarray:
     """a [R]; visible / forbidden bool [nq, R].  Returns the winner [nq] (numpy argmax of a over the visible rows) after
-    asserting the two gap preconditions in fp64 (for hd 80 also with the kernel's bf16-rounded prescaled q)."""
+    asserting the two gap preconditions in fp64 (for hd 80 also with the kernel's bf16-rounded prescaled q).  kv8_k_scale: the
+    scores are those of the e4m3 encoding under that K scale (scores_log2_kv8)."""
     a = np.asarray(a, np.int64)
     nq = visible.shape[0]
     assert visible.any(1).all(), f"{what}: a query without a visible key"
     winner = np.where(visible, a[None], -1).argmax(1)
     for prescaled in ([False, True] if hd == 80 else [False]):
-        s = scores_log2(a, hd, prescaled)
+        s = scores_log2(a, hd, prescaled) if kv8_k_scale is None else scores_log2_kv8(a, kv8_k_scale, hd)
         sw = s[winner]
         others = np.where(visible, s[None], -np.inf)
         others[np.arange(nq), winner] = -np.inf
@@ -417,3 +437,275 @@ def decode_reference(case: Case, extra_keys: int = 0, whole_units_only: bool = F
             nk = nk // 32 * 32
         out[b] = ref_attention(case.q[b][:, None], case.k[b, :, :nk], case.v[b, :, :nk], case.hd ** -0.5, False)
     return out
+
+
+# ----------------------------------------------------------------------------- the fp8 KV cache: an encoding exact in e4m3
+C_Q8 = 2048.0
+KV8_WEIGHTS = (4096, 256, 16, 1)                   # q holds C_Q8 times these; K holds the base-16 digits of a
+KV8_CODE_OF_INT = f32_to_fp8_e4m3(np.arange(16, dtype=np.float32))
+# [K | V][kv head] (the first kv_heads columns are used).  pow2: a wrong head's V scale is off by a factor >= 2 and K's entry of
+# a head is not its V entry; odd: no power of two, K >= 0.37, cyclic neighbours' V scales >= 25 % apart
+KV8_SCALE_SETS = {
+    "unit": [[1.0, 1.0, 1.0, 1.0], [1.0, 1.0, 1.0, 1.0]],
+    "pow2": [[1.0, 0.5, 4.0, 2.0], [0.5, 2.0, 0.25, 8.0]],
+    "odd": [[0.37, 1.3, 0.73, 2.9], [1.9, 0.6, 1.45, 0.41]],
+}
+KV8_SCALE_NAMES = list(KV8_SCALE_SETS)
+KV8_EXTRA_SPLITS = [1, 4]            # the split counts of the fp8 bound test that DECODE_SPLITS does not hold
+KV8_ROWS_C, KV8_ROWS_SPLITS = [29, 30, 61, 62, 63], [2, 4]
+KV8_FAULTS = ["mask-fg", "p-unpermuted", "v-scale-next-head", "v-tiles-swapped", "k-halves-swapped"]
+
+
+def kv8_decode_params() -> List[Tuple[str, str]]:
+    """(pattern, scale set) of the fp8 decode runs: every pattern at every scale set (a run takes ~0.1 s on the device)."""
+    return [(p, s) for s in KV8_SCALE_NAMES for p in decode_patterns()]
+
+
+def kv8_scales(name, kv_heads: int) -> np.ndarray:
+    """[2][kv_heads] f32 of a named set (or of a table handed in)."""
+    t = np.asarray(KV8_SCALE_SETS[name] if isinstance(name, str) else name, np.float32)[:, :kv_heads]
+    assert t.shape == (2, kv_heads) and (t > 0).all()
+    return np.ascontiguousarray(t)
+
+
+def _check_scale_sets():
+    for kvh in (1, 2, 4):
+        assert (kv8_scales("unit", kvh) == 1).all()
+        p, o = kv8_scales("pow2", kvh).astype(np.float64), kv8_scales("odd", kvh).astype(np.float64)
+        assert (np.log2(p) % 1 == 0).all() and (np.log2(o) % 1 != 0).all() and (o[0] >= 0.37).all()
+        assert (p[0] != p[1]).all() and (o[0] != o[1]).all()                      # K's entry read for V's shows
+        for row, far in ((p[0], 2.0), (p[1], 2.0), (o[1], 1.25)) if kvh > 1 else ():
+            r = row / np.roll(row, 1)
+            assert (np.maximum(r, 1 / r) >= far).all(), "neighbouring heads' scales are too close"
+
+
+def kv8_channels(kv_heads: int, hd: int = 128) -> List[Tuple[int, int, int, int]]:
+    """The channels of the four digits (most significant first) per kv head; the placement the module docstring states, asserted."""
+    assert hd == 128 and 1 <= kv_heads <= 4
+    out = []
+    for h in range(kv_heads):
+        groups = (h % 4, (h + 2) % 4, 4 + (h + 1) % 4, 4 + (h + 3) % 4)
+        out.append(tuple(16 * gr + 8 * ((h >> 1) ^ (i >> 1) ^ (h & 1)) + (2 * h + 3 * i) % 8 for i, gr in enumerate(groups)))
+    flat = [c for t in out for c in t]
+    assert len(set(flat)) == 4 * kv_heads and 0 <= min(flat) and max(flat) < hd                      # no channel shared
+    for t in out:
+        assert len({c // 16 for c in t}) == 4 and sorted(c // 64 for c in t) == [0, 0, 1, 1]           # 4 groups, two per load
+    for i in range(4):
+        assert len({t[i] % 16 for t in out}) == kv_heads                                                # the lane differs per head
+    for half in (0, 1):                                                                                 # both k-steps of either load
+        assert len({(c % 16) // 8 for c in flat if c // 64 == half}) == (2 if kv_heads > 1 else 1)
+    by_group = {}
+    for c in flat:
+        by_group.setdefault(c // 16, []).append((c % 16) // 8)
+    assert all(len(v) == len(set(v)) for v in by_group.values())                 # heads that meet in a group: different halves
+    if kv_heads == 4:
+        assert all(sorted(v) == [0, 1] for v in by_group.values()) and len(by_group) == 8
+    return out
+
+
+def kv8_k_codes(a: np.ndarray, hd: int = 128) -> np.ndarray:
+    """a int [..., KVH, R] -> K codes uint8 [..., KVH, R, hd]: the base-16 digits of a in the head's four channels, 0 elsewhere."""
+    a = np.asarray(a, np.int64)
+    assert a.min() >= 0 and a.max() < 8192
+    k = np.zeros(a.shape + (hd,), np.uint8)
+    for h, chans in enumerate(kv8_channels(a.shape[-2], hd)):
+        for c, w in zip(chans, KV8_WEIGHTS):
+            k[..., h, :, c] = KV8_CODE_OF_INT[(a[..., h, :] // w) % 16]
+    return k
+
+
+def kv8_q_vectors(heads: int, kv_heads: int, hd: int = 128) -> np.ndarray:
+    """[heads, hd]: C_Q8 * (4096, 256, 16, 1) in the four channels of the head's kv head."""
+    q = np.zeros((heads, hd), np.float32)
+    chans = kv8_channels(kv_heads, hd)
+    for h in range(heads):
+        for c, w in zip(chans[h // (heads // kv_heads)], KV8_WEIGHTS):
+            q[h, c] = C_Q8 * w
+    _assert_bf16_exact(q)
+    return q
+
+
+def scale_log2e_kv8(k_scale, hd: int = 128) -> np.float32:
+    """The kernel's fold: f32(f32(hd^-0.5 * log2 e) * k_scale[kvh])."""
+    return np.float32(scale_log2e(hd) * np.float32(k_scale))
+
+
+def scores_log2_kv8(a: np.ndarray, k_scale, hd: int = 128) -> np.ndarray:
+    """fp64 score, in the kernel's log2 units, of a K row that holds the digits of a, under that K scale."""
+    return C_Q8 * np.asarray(a, np.int64).astype(np.float64) * float(scale_log2e_kv8(k_scale, hd))
+
+
+def _check_kv8_encoding():
+    np.testing.assert_array_equal(fp8_e4m3_to_f32(KV8_CODE_OF_INT), np.arange(16))                 # the digits are e4m3 values
+    a = np.arange(8192)
+    dig = np.stack([(a // w) % 16 for w in KV8_WEIGHTS], -1).astype(np.float32)
+    s = np.zeros(8192, np.float32)
+    for i, w in enumerate(KV8_WEIGHTS):                                          # f32 sums in any order: every partial sum is exact
+        s = s + dig[:, i] * np.float32(C_Q8 * w)
+    np.testing.assert_array_equal(s, np.float32(C_Q8) * a.astype(np.float32))
+    assert C_Q8 * 8191 < 2 ** 24
+    assert fp8_e4m3_to_f32(np.asarray([KV8R.STALE_CODE], np.uint8))[0] == 448.0
+    _check_scale_sets()
+    for kvh in (1, 2, 3, 4):
+        kv8_channels(kvh)
+
+
+@dataclass
+class Case8:
+    """A decode case on an fp8 cache.  q [rows, heads, hd] (bf16 values), k_codes / v_codes uint8 [slots, KVH, s_max, hd] (v_codes
+    token-major: `vt` is what the kernel reads), scales [2][KVH] f32; row r reads slot row_slot[r] (None: slot r)."""
+    hd: int
+    heads: int
+    kv_heads: int
+    q: np.ndarray
+    k_codes: np.ndarray
+    v_codes: np.ndarray
+    scales: np.ndarray
+    s_max: int
+    ctx: np.ndarray
+    finished: np.ndarray
+    row_slot: Optional[np.ndarray] = None
+    units: List[Unit] = field(default_factory=list)
+
+    @property
+    def vt(self) -> np.ndarray:
+        return KV8R.vt_blocks8(self.v_codes)
+
+    def slot_of(self, r: int) -> int:
+        return r if self.row_slot is None else int(self.row_slot[r])
+
+
+def _kv8_case(a_slots: np.ndarray, ctx: np.ndarray, fin: np.ndarray, row_slot: Optional[np.ndarray], heads: int, kv_heads: int,
+              scales, s_max: int, forbid_past_ctx: bool, seed: int, what: str) -> Case8:
+    """a_slots int [slots, s_max]: the ramp of every slot's K rows (the same for all its kv heads).  V holds codes of 1 .. 15 up to
+    the longest context on the slot and STALE_CODE beyond; the candidates of a row are all V rows of its slot, times v_scale."""
+    hd, g = 128, heads // kv_heads
+    S, rows = a_slots.shape[0], len(ctx)
+    sc = kv8_scales(scales, kv_heads)
+    slot = np.arange(rows) if row_slot is None else np.asarray(row_slot, np.int64)
+    rng = np.random.default_rng(seed + heads + rows)
+    q = np.broadcast_to(kv8_q_vectors(heads, kv_heads, hd)[None], (rows, heads, hd)).copy()
+    k_codes = kv8_k_codes(np.broadcast_to(a_slots[:, None], (S, kv_heads, s_max)), hd)
+    v_int = rng.integers(1, 16, size=(S, kv_heads, s_max, hd))
+    v_codes = KV8_CODE_OF_INT[v_int]
+    last = np.full(S, -1, np.int64)
+    np.maximum.at(last, slot, ctx)
+    for s in range(S):
+        v_codes[s, :, last[s] + 1:] = KV8R.STALE_CODE
+    case = Case8(hd, heads, kv_heads, q, k_codes, v_codes, sc, s_max, ctx.astype(np.int32), fin.astype(np.int32),
+                 None if row_slot is None else slot.astype(np.int32))
+    # V_int * f32(v_scale), kept in f32 (one rounding of 2^-24, the kernel's own)
+    cands = [(fp8_e4m3_to_f32(v_codes[s]) * sc[1][:, None, None]).reshape(kv_heads * s_max, hd) for s in range(S)]
+    r_ = np.arange(s_max)
+    for r in range(rows):
+        if fin[r]:
+            continue
+        s, vis = int(slot[r]), (r_ <= ctx[r])[None]
+        for kvh in range(kv_heads):          # the gap is asserted per kv head: its K scale is in the score
+            win = check_gaps(a_slots[s], vis, ~vis if forbid_past_ctx else None, hd, f"{what} row {r} kv head {kvh}", kv8_k_scale=sc[0, kvh])
+
+            def rname(i, r=r, s=s):
+                h, j = divmod(i, s_max)
+                return f"key {j} of kv head {h}" + ("" if row_slot is None else f" of slot {s}") + \
+                    (f" (a stale row: ctx_len is {ctx[r]})" if j > ctx[r] else "")
+
+            for h in range(kvh * g, (kvh + 1) * g):
+                case.units.append(Unit(np.asarray([r]), h, cands[s], kvh * s_max + win,
+                                       (lambda i, r=r: ("slot" if row_slot is None else "row") + f" {r} (ctx_len {ctx[r]})"), rname))
+    return case
+
+
+def decode_case_kv8(batch: Sequence[Tuple[int, int]], heads: int, kv_heads: int, pattern: str, scales,
+                    s_max: int = DECODE_S_MAX, seed: int = 0) -> Case8:
+    """decode_case on an fp8 cache: the same (ctx_len, finished) batches and patterns.  scales: a name of KV8_SCALE_SETS or a
+    [2][kv_heads] table.  The K ramp fills all s_max rows (with `up` every row past the context outranks the winner); the V^T
+    columns past ctx_len hold STALE_CODE."""
+    ctx = np.asarray([c for c, _ in batch], np.int64)
+    fin = np.asarray([f for _, f in batch], np.int32)
+    B, r = len(batch), np.arange(s_max)
+    assert ctx.max() <= s_max - 1
+    if pattern == "up":
+        a1 = np.broadcast_to(r, (B, s_max))
+    elif pattern == "down":
+        a1 = np.broadcast_to(s_max - 1 - r, (B, s_max))
+    else:
+        peak = pattern.split("-", 1)[1]
+        p = ctx if peak == "ctx" else np.maximum(ctx - 1, 0) if peak == "ctx-1" else np.minimum(int(peak), ctx)
+        a1 = 4096 - np.abs(r[None, :] - p[:, None])
+    case = _kv8_case(np.ascontiguousarray(a1), ctx, fin, None, heads, kv_heads, scales, s_max, pattern == "up", seed, f"kv8 decode {pattern}")
+    if pattern in ("up", "down"):
+        for u in case.units:
+            assert u.win[0] % s_max == (ctx[u.rows[0]] if pattern == "up" else 0)
+    return case
+
+
+def rows_case_kv8(c: int, scales="odd", heads: int = 4, kv_heads: int = 2, drafts: int = 3, s_max: int = 128) -> Case8:
+    """The speculative step on an fp8 cache: rows j = 0 .. drafts of slot 0 at contexts c + j and of slot 1 at c + 32 + j, behind the
+    row map row -> slot (1, 0, 1, 0, ...); `up` ramps, so the keys the later draft rows stored — real V codes — outrank a row's own."""
+    rows = 2 * (drafts + 1)
+    row_slot = np.asarray([(r + 1) % 2 for r in range(rows)], np.int64)
+    ctx = np.asarray([(c if row_slot[r] == 0 else c + 32) + r // 2 for r in range(rows)], np.int64)
+    assert ctx.max() <= s_max - 1
+    a = np.broadcast_to(np.arange(s_max), (2, s_max)).copy()
+    case = _kv8_case(a, ctx, np.zeros(rows, np.int32), row_slot, heads, kv_heads, scales, s_max, True, 7 * c, f"kv8 rows c={c}")
+    for u in case.units:
+        assert u.win[0] % s_max == ctx[u.rows[0]]
+    assert (case.v_codes[0, :, :c + drafts + 1] != KV8R.STALE_CODE).all() and (case.v_codes[0, :, c + drafts + 1:] == KV8R.STALE_CODE).all()
+    return case
+
+
+def kv8_swap_8_16(key: np.ndarray) -> np.ndarray:
+    """Keys 8 .. 15 and 16 .. 23 of every 32-key unit exchanged: pi = (0, 2, 1, 3) on the unit's four 8-key groups."""
+    key = np.asarray(key, np.int64)
+    grp = (key >> 3) & 3
+    return key + 8 * (np.asarray([0, 2, 1, 3])[grp] - grp)
+
+
+def decode_reference_kv8(case: Case8, extra_keys: int = 0, whole_units_only: bool = False, fault: Optional[str] = None) -> np.ndarray:
+    """The fp64 softmax over the DEQUANTISED operands (kv_fp8_ref.dequantize) of every live row.  extra_keys / whole_units_only as in
+    decode_reference; fault restates one addressing error of the fp8 kernel (KV8_FAULTS):
+      mask-fg            the mask computed with fg in place of pi(fg): the visible set with keys 8..15 and 16..23 of a unit exchanged
+      p-unpermuted       P applied to V in unpermuted key order: key k's weight meets V of key swap(k)
+      v-scale-next-head  the V scale of kv head (h + 1) % KVH
+      v-tiles-swapped    channel tiles 2i and 2i + 1 of V exchanged
+      k-halves-swapped   K channels 0..63 exchanged with 64..127, on the K side only"""
+    assert fault is None or fault in KV8_FAULTS
+    H, KVH, hd = case.heads, case.kv_heads, case.hd
+    g = H // KVH
+    out = np.zeros((len(case.ctx), H * hd), np.float32)
+    for r, c in enumerate(case.ctx):
+        if case.finished[r]:
+            continue
+        s = case.slot_of(r)
+        nk = min(int(c) + 1 + extra_keys, case.s_max)
+        if whole_units_only and nk >= 32:
+            nk = nk // 32 * 32
+        key = np.arange((nk + 31) // 32 * 32)                      # the whole units the kernel loads: inside the cache
+        vis = (kv8_swap_8_16(key) if fault == "mask-fg" else key) < nk
+        vkey = kv8_swap_8_16(key) if fault == "p-unpermuted" else key
+        for kvh in range(KVH):
+            kd = KV8R.dequantize(case.k_codes[s, kvh, key], case.scales[0, kvh])
+            if fault == "k-halves-swapped":
+                kd = np.roll(kd, 64, -1)
+            vd = KV8R.dequantize(case.v_codes[s, kvh, vkey], case.scales[1, (kvh + 1) % KVH if fault == "v-scale-next-head" else kvh])
+            for h in range(kvh * g, (kvh + 1) * g):
+                sc = np.where(vis, kd @ case.q[r, h].astype(np.float64) * hd ** -0.5, -np.inf)
+                p = np.exp(sc - sc.max())
+                o = (p / p.sum()) @ vd
+                if fault == "v-tiles-swapped":
+                    o = o.reshape(hd // 32, 2, 16)[:, ::-1].reshape(hd)
+                out[r, h * hd:(h + 1) * hd] = o
+    return out
+
+
+def max_ratio(got: np.ndarray, case) -> float:
+    """max |got - V[winner]| / (TOL_ABS + TOL_REL |V[winner]|) over the case's units (<= 1: check_output passes)."""
+    worst = 0.0
+    for u in case.units:
+        g = got[u.rows, u.head * case.hd:(u.head + 1) * case.hd].astype(np.float64)
+        want = u.cand[u.win].astype(np.float64)
+        worst = max(worst, float((np.abs(g - want) / (TOL_ABS + TOL_REL * np.abs(want))).max()))
+    return worst
+
+
+_check_kv8_encoding()

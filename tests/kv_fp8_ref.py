@@ -111,7 +111,19 @@ DECODE_CTX = [1, 31, 32, 33, 64, 65, 1100]     # keys per live row: unit and blo
 DECODE_FINISHED_AT, DECODE_FINISHED_CTX = 3, 40          # one finished row between the live ones
 DECODE_S_MAX = 1152
 DECODE_SPLITS = [1, 4, 16, 32]
-DECODE_SCALES = [(1.0, 1.0), (0.5, 2.0), (0.37, 1.9)]
+# (k_scale, v_scale): a float for all kv heads, or a tuple of per-head values of which the first KVH are used (the last entry: every
+# head reads an entry of its own, in the K row and in the V row of the [2][KVH] table)
+DECODE_SCALES = [(1.0, 1.0), (0.5, 2.0), (0.37, 1.9), ((0.5, 1.3, 0.37, 2.0), (1.9, 0.6, 2.5, 1.0))]
+
+
+def scale_rows(k_scale, v_scale, KVH: int) -> np.ndarray:
+    """[2][KVH] f32, the table the kernels take, from a float or a per-kv-head sequence each (the first KVH values of a longer one)."""
+    out = np.empty((2, KVH), F32)
+    for j, s in enumerate((k_scale, v_scale)):
+        s = np.asarray(s, F32)
+        assert s.ndim == 0 or (s.ndim == 1 and s.size >= KVH), "a scale is a float or a vector with an entry per kv head"
+        out[j] = s if s.ndim == 0 else s[:KVH]
+    return out
 
 
 def decode_rows():
@@ -121,11 +133,12 @@ def decode_rows():
     return rows
 
 
-def decode_case(H: int, KVH: int, k_scale: float, v_scale: float, seed: int = 0):
+def decode_case(H: int, KVH: int, k_scale, v_scale, seed: int = 0):
     """(attn_arith.Case over the DEQUANTISED operands, k_codes [B, KVH, s_max, 128], v_codes likewise): K and V drawn, quantised by
     the rule, and the code values times the scale are what the reference and the bound see.  Rows at or beyond a row's keys hold
-    STALE_CODE (448)."""
+    STALE_CODE (448).  k_scale / v_scale: a float, or per-kv-head values (scale_rows)."""
     from tests import attn_arith as AA
+    sc = scale_rows(k_scale, v_scale, KVH)
     rng = np.random.default_rng(1000 * H + 10 * KVH + seed)
     rows = decode_rows()
     B, hd, G = len(rows), 128, H // KVH
@@ -138,14 +151,14 @@ def decode_case(H: int, KVH: int, k_scale: float, v_scale: float, seed: int = 0)
         for h in range(KVH):
             kr = bf16_round((rng.standard_normal((n, hd)) * (1.0 + 0.5 * h)).astype(F32))
             vr = bf16_round((rng.standard_normal((n, hd)) * 1.5 + 0.25).astype(F32))
-            k_codes[b, h, :n], _ = quantize(kr, k_scale)
-            v_codes[b, h, :n], _ = quantize(vr, v_scale)
+            k_codes[b, h, :n], _ = quantize(kr, sc[0, h])
+            v_codes[b, h, :n], _ = quantize(vr, sc[1, h])
         if fin:
             continue
         for hq in range(H):
             h = hq // G
-            case.probs.append(AA.Prob(np.asarray([b]), hq, h, q[b, hq][None], dequantize(k_codes[b, h, :n], k_scale),
-                                      dequantize(v_codes[b, h, :n], v_scale), None, 32, np.asarray([True]), f"row {b} ({n} keys) head {hq}"))
+            case.probs.append(AA.Prob(np.asarray([b]), hq, h, q[b, hq][None], dequantize(k_codes[b, h, :n], sc[0, h]),
+                                      dequantize(v_codes[b, h, :n], sc[1, h]), None, 32, np.asarray([True]), f"row {b} ({n} keys) head {hq}"))
     return case, k_codes, v_codes
 
 

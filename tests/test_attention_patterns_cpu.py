@@ -77,7 +77,7 @@ def test_a_dropped_partial_unit_is_named():
     with pytest.raises(AssertionError, match=r"slot 4 \(ctx_len 32\) head 0 returned key 31 of kv head 0, expected key 32"):
         AP.check_output(AP.decode_reference(case, whole_units_only=True), case, "nu = ctx >> 5")
     case = AP.decode_case(AP.DECODE_BATCH, 12, 2, "tent-ctx")
-    with pytest.raises(AssertionError, match=r"48 of 132 .*\n.*returned key 31 of kv head 0, expected key 32"):
+    with pytest.raises(AssertionError, match=r"60 of 144 .*\n.*returned key 31 of kv head 0, expected key 32"):
         AP.check_output(AP.decode_reference(case, whole_units_only=True), case, "nu = ctx >> 5")
 
 

@@ -2,7 +2,9 @@
 kr_kv_quantize (byte-exact, nothing else written, the clamp count), the ROPE_KV8 append of the <= 16-row and the 17..32-row qkv
 launches (the codes of exactly the bf16 values the bf16 launch stores, q bit for bit, every other byte untouched), the decode
 attention on fp8 operands with the existing merges (within attn_arith's bound on the dequantised operands, and an independent
-needle check of the operand mapping), and the byte-sized fork."""
+needle check of the operand mapping), and the byte-sized fork.  The bound and the needle do not see a one-key masking, unit or
+key-order error of the fp8 attention (a flat softmax over 1100 keys moves by 1/1100): test_gpu_attention_exact_kv8.py holds the
+to-the-key checks — one winner per query in an e4m3-exact encoding, at every unit border, behind the row map, with per-head scales."""
 import ctypes as C
 
 import numpy as np
@@ -242,9 +244,10 @@ def test_decode_attention_on_fp8_operands_meets_the_bound(L, decode_cases, entry
     """kr_attn_decode_slots_kv8 / _rows_kv8 + kr_attn_decode_merge / _merge32 at 1, 4, 16 and 32 splits over rows of 1, 31, 32, 33,
     64, 65 and 1100 keys and one finished row: |got - o| <= E with attn_arith's reference and bound over the DEQUANTISED operands
     (the conversion is exact; the two folded scales are f32 roundings inside the bound's 2^-12).  The tail beyond a row's keys holds
-    code 0x7E (448): masked, it must not move the output."""
+    code 0x7E (448): masked, it must not move the output.  The last entry of DECODE_SCALES gives every kv head K and V scales of
+    its own: kv_scale[kvh] and kv_scale[kv_heads + kvh] read for another head miss the bound (test_kv_fp8_cpu.py shows it on the model)."""
     case, k_codes, v_codes = decode_cases(H, KVH, ks, vs)
-    sc = np.asarray([[ks] * KVH, [vs] * KVH], F32)
+    sc = R.scale_rows(ks, vs, KVH)
     for n_split in R.DECODE_SPLITS:
         got = run_attention(L, "slots" if entry == "merge32" else entry, case.q, k_codes, v_codes, case.ctx, case.finished, sc, H, KVH,
                             n_split, merge32=entry == "merge32")

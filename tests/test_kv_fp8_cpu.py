@@ -150,6 +150,7 @@ def test_the_bound_over_dequantised_operands_holds_for_the_fp8_kernels_arithmeti
     v_scale): every output within E at every split count the GPU test runs, with room to spare for the f32 arithmetic the model
     leaves out — and a model that forgets a scale misses it."""
     case, k_codes, v_codes = R.decode_case(H, KVH, ks, vs)
+    sc = R.scale_rows(ks, vs, KVH)                                            # a float stands for every kv head
     assert len(case.probs) == H * len(R.DECODE_CTX) and case.l_rounded
     assert (k_codes[0, 0, 1:] == R.STALE_CODE).all()                          # row 0 has one key: the rest is the stale tail
     worst = 0.0
@@ -158,18 +159,52 @@ def test_the_bound_over_dequantised_operands_holds_for_the_fp8_kernels_arithmeti
         e = AA.bound(case, pr, o, spv)
         b, n = int(pr.rows[0]), pr.k.shape[0]
         for n_split in R.DECODE_SPLITS:
-            got = R.model_decode_kv8(pr.q, k_codes[b, pr.kvh, :n], v_codes[b, pr.kvh, :n], ks, vs, n_split, AA.decode_waves(n_split))
+            got = R.model_decode_kv8(pr.q, k_codes[b, pr.kvh, :n], v_codes[b, pr.kvh, :n], sc[0, pr.kvh], sc[1, pr.kvh], n_split,
+                                     AA.decode_waves(n_split))
             err = np.abs(got - o)
             assert (err[e == 0] == 0).all()                                   # a zero V code under one key: met exactly
             worst = max(worst, float((err[e > 0] / e[e > 0]).max()))
     print(f"\nfp8 model H={H} KVH={KVH} scales=({ks}, {vs}): max |model - o| / E = {worst:.3f}")
     assert worst <= 0.75
-    if vs != 1.0:      # the V scale forgotten: far outside the bound
-        pr = case.probs[-1]
+    pr = case.probs[-1]
+    if sc[1, pr.kvh] != 1.0:      # the V scale forgotten: far outside the bound
         o, spv, _ = AA.reference(case, pr)
         n = pr.k.shape[0]
-        got = R.model_decode_kv8(pr.q, k_codes[-1, pr.kvh, :n], v_codes[-1, pr.kvh, :n], ks, 1.0, 4, 8)
+        got = R.model_decode_kv8(pr.q, k_codes[-1, pr.kvh, :n], v_codes[-1, pr.kvh, :n], sc[0, pr.kvh], 1.0, 4, 8)
         assert (np.abs(got - o) / AA.bound(case, pr, o, spv)).max() > 10
+
+
+def worst_ratio_of_the_model(case, k_codes, v_codes, sc, n_split=4):
+    """max |model - o| / E over one q head per (row, kv head) when the model reads the [2][KVH] table sc."""
+    g = case.heads // case.kv_heads
+    worst = 0.0
+    for pr in case.probs:
+        if pr.head % g:
+            continue
+        o, spv, _ = AA.reference(case, pr)
+        e = AA.bound(case, pr, o, spv)
+        b, n = int(pr.rows[0]), pr.k.shape[0]
+        got = R.model_decode_kv8(pr.q, k_codes[b, pr.kvh, :n], v_codes[b, pr.kvh, :n], sc[0, pr.kvh], sc[1, pr.kvh], n_split,
+                                 AA.decode_waves(n_split))
+        worst = max(worst, float((np.abs(got - o)[e > 0] / e[e > 0]).max()))
+    return worst
+
+
+@pytest.mark.parametrize("H,KVH", R.DECODE_HEADS)
+def test_per_head_scales_meet_the_bound_and_another_heads_scale_does_not(H, KVH):
+    """The DECODE_SCALES entry whose K and V scales differ from kv head to kv head, on the model alone: with each head's own entries
+    the bound holds; with the K row of the table rotated by one head (kv_scale[(kvh + 1) % KVH] read for kv_scale[kvh]), or the V
+    row, it is missed by far — what the GPU bound test would see of a kernel that indexes the table by another head."""
+    ks, vs = R.DECODE_SCALES[-1]
+    sc = R.scale_rows(ks, vs, KVH)
+    assert len(set(sc[0])) == KVH and len(set(sc[1])) == KVH and np.ndim(ks) == 1
+    case, k_codes, v_codes = R.decode_case(H, KVH, ks, vs)
+    assert worst_ratio_of_the_model(case, k_codes, v_codes, sc) <= 0.75
+    rot_k = np.stack([np.roll(sc[0], -1), sc[1]])
+    rot_v = np.stack([sc[0], np.roll(sc[1], -1)])
+    rk, rv = worst_ratio_of_the_model(case, k_codes, v_codes, rot_k), worst_ratio_of_the_model(case, k_codes, v_codes, rot_v)
+    print(f"\nfp8 model H={H} KVH={KVH}: K scales rotated {rk:.1f} E, V scales rotated {rv:.1f} E")
+    assert rk > 10 and rv > 10
 
 
 def test_the_needle_case_is_what_it_says():
