@@ -90,8 +90,8 @@ def main():
                   decode_splits=int(over.pop("n_split", 16)), weight_dtype=a.weights,
                   **({"kv_cache_dtype": "fp8"} if over.pop("kv_cache_dtype", a.kv_dtype).startswith("fp8") else {}))
         if eng.kv8:     # codes below the NaN encodings, every value finite (timing does not depend on them)
-            eng.kcache.copy_(torch.randint(0, 0x78, eng.kcache.shape, dtype=torch.uint8, device=eng.device))
-            eng.vtcache.copy_(torch.randint(0, 0x78, eng.vtcache.shape, dtype=torch.uint8, device=eng.device))
+            eng.kv.kcache.copy_(torch.randint(0, 0x78, eng.kv.kcache.shape, dtype=torch.uint8, device=eng.device))
+            eng.kv.vtcache.copy_(torch.randint(0, 0x78, eng.kv.vtcache.shape, dtype=torch.uint8, device=eng.device))
         over.pop("steps_per_graph", None)     # handled where the graph is captured
         if "resident" in over:                # resident=<MB>[:kind@gain+kind@gain]: Infinity-Cache budget (and the planner's gains)
             mb, _, kinds = over.pop("resident").partition(":")
@@ -225,14 +225,14 @@ def chains(a, engines, reset):
 
         def one(kind, i, eng=eng, t=t, w=w, H=H, KVH=KVH, hd=hd):      # bound now: called after the loop has moved on
             p = f"llm.{i}."
-            kc, vc = ptr(eng.kcache[i]), ptr(eng.vtcache[i])
-            k8 = {"kv8_layer": i} if eng.kv8 else {}
+            kc, vc = ptr(eng.kv.kcache[i]), ptr(eng.kv.vtcache[i])
+            cache = eng.kv.qkv(i)           # the product's qkv launches: the cache as the engine's own step hands it over
             if kind == "qkv":
                 eng._dec_narrow(DEC_ROPE_KV, eng.d_x, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), norm_w=w.view(p + "ln1.w"),
-                                part_in=eng.d_part, x_out=eng.d_x2, kc=kc, vc=vc, **k8, **eng._w8kw(p + "qkv.w"))
+                                part_in=eng.d_part, x_out=eng.d_x2, **cache, **eng._w8kw(p + "qkv.w"))
             elif kind == "qkv0":                   # no pending slabs: the prologue reads x only
                 eng._dec_narrow(DEC_ROPE_KV, eng.d_x, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), norm_w=w.view(p + "ln1.w"),
-                                kc=kc, vc=vc, **k8, **eng._w8kw(p + "qkv.w"))
+                                **cache, **eng._w8kw(p + "qkv.w"))
             elif kind.startswith("down") and len(kind) > 4 and not kind.startswith("down32"):      # down<ksplit>[w<waves>]: e.g. down3, down4w8
                 import re
                 m = re.fullmatch(r"down(\d)(?:w(\d+))?", kind)
@@ -251,7 +251,7 @@ def chains(a, engines, reset):
             elif kind == "qkvd":
                 eng._dec_narrow(DEC_ROPE_KV, eng.d_h, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), kc=kc, vc=vc, **eng._w8kw(p + "qkv.w"))
             elif kind == "qkv32":
-                eng._dec32(DEC_ROPE_KV, eng.d_h, w.view(p + "qkv.w"), B, 8, bias=w.view(p + "qkv.b"), kc=kc, vc=vc, **k8, **eng._w8kw(p + "qkv.w"))
+                eng._dec32(DEC_ROPE_KV, eng.d_h, w.view(p + "qkv.w"), B, 8, bias=w.view(p + "qkv.b"), **cache, **eng._w8kw(p + "qkv.w"))
             elif kind == "merge32":
                 L.kr_attn_decode_merge32(ptr(eng.d_ws), ptr(eng.d_o), B, H, hd, eng.n_split, eng.s)
             elif kind in ("o32", "o32t1", "o32t2"):
@@ -270,8 +270,7 @@ def chains(a, engines, reset):
                            atomic_out=True, group_split=gs, tiles_per_wg={"down32a": 0, "down32gs": 0, "down32gs2": 2, "down32gs4": 4}[kind],
                            **({} if gs else eng._w8kw(p + "down.w")))
             elif kind == "attn" and eng.kv8:
-                L.kr_attn_decode_slots_kv8(ptr(eng.d_q), eng._kv8(i), ptr(eng.d_ctx), ptr(eng.d_fin), ptr(eng.d_ws), B, H, KVH, hd, eng.s_max,
-                                           eng.n_split, hd ** -0.5, eng.s)
+                eng.kv.attention(i, B)
             elif kind == "attn":
                 L.kr_attn_decode_fused(ptr(eng.d_q), kc, vc, ptr(eng.d_ctx), 0, ptr(eng.d_ws), 0, B, H, KVH, hd, eng.s_max, eng.n_split,
                                        hd ** -0.5, eng.s)

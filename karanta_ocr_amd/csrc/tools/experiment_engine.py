@@ -149,7 +149,7 @@ class ExperimentEngine(Engine):
         for i in range(nl):
             p = f"llm.{i}."
             # the cache tensor is [layers, max_batch, ...]: hand the kernels layer i's base
-            kc, vc = ptr(self.kcache[i]), ptr(self.vtcache[i])
+            kc, vc = ptr(self.kv.kcache[i]), ptr(self.kv.vtcache[i])
             if self._prefetch_mode == 1:  # diagnostic: serial prefetch of this layer's weights into the Infinity Cache
                 a0 = w.layout[p + "ln1.w"][0]
                 a1 = w.layout[p + "down.w"][0] + 2 * int(np.prod(w.layout[p + "down.w"][1]))

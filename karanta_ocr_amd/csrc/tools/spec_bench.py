@@ -152,7 +152,6 @@ def child_spec(model, B, K, share=False):
     script's choice alone: only the two ends are run, every first draft wrong (0) and every draft right (K)."""
     import numpy as np
     import torch
-    from karanta_ocr_amd._lib import ptr
     eng = _engine(model, B, K, share)
     L, t = eng.L, eng.cfg.text
     g_plain = _plain_graph(eng)
@@ -200,18 +199,14 @@ def child_spec(model, B, K, share=False):
     out["ratio"] = spec_ms / out["plain_ms"]
     out["break_even_accepted_per_slot_step"] = out["ratio"] - 1
     # the attention launches alone: rows x (K + 1) reads of a slot's K/V against one
-    H, KVH, hd = t.num_heads, t.num_kv_heads, t.head_dim
 
     def attn_graph(rows_variant):
         L.kr_graph_begin_capture(eng.s)
         for i in range(t.num_layers):
-            kc, vc = ptr(eng.kcache[i]), ptr(eng.vtcache[i])
             if rows_variant:
-                L.kr_attn_decode_rows(ptr(eng.d_q), kc, vc, ptr(eng.d_ctx), ptr(eng.d_fin), ptr(eng.d_row_slot), ptr(eng.d_ws), eng.rows, H, KVH,
-                                      hd, eng.s_max, eng.n_split, hd ** -0.5, eng.s)
+                eng.kv.attention(i, eng.rows, eng.d_row_slot)
             else:
-                L.kr_attn_decode_slots(ptr(eng.d_q), kc, vc, ptr(eng.d_ctx), ptr(eng.d_fin), ptr(eng.d_ws), B, H, KVH, hd, eng.s_max,
-                                       eng.n_split, hd ** -0.5, eng.s)
+                eng.kv.attention(i, B)
         g = C.c_void_p()
         L.kr_graph_end_capture(eng.s, C.byref(g))
         return g.value

@@ -22,10 +22,12 @@ import torch
 
 from . import image_processing as IP
 from . import positions as POS
-from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_NONE, EPI_SILU_MUL8, KarantaHipError, Spec, fork_plan,
-                   kv8, kvq_plan, lib, narrow_opts, ptr)
+from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_NONE, EPI_SILU_MUL8, KarantaHipError, Spec, lib,
+                   narrow_opts, ptr)
+from . import kv_cache
 from .config import ModelConfig
-from .weights import KV_SCALE_RANGES, kv_cache_dtype_name, kv_scale_table, kv_scales_from_checkpoint
+from .kv_cache import KV_SCALES_FLAG_WINS   # noqa: F401  (cli.py takes it from here)
+from .weights import KV_SCALE_RANGES, kv_cache_dtype_name
 from .device_weights import DeviceWeights, _align, narrow_weight_bytes, plan_resident
 from .request import GenerateResult, PageRequest, SpecConfig, children
 from .sampler import DeviceGuide, Sampler
@@ -45,8 +47,6 @@ IC_RESIDENT_MB = 192
 # a launch is planned only if its expected saving reaches what two identical graphs differ by per launch in that sweep (3-4 us per
 # step over 28 launches): the sub-MB matrices of the test-sized models keep their nontemporal loads
 IC_RESIDENT_MIN_US = 0.1
-KV_SCALES_FLAG_WINS = ("fp8 KV cache scales: the checkpoint ships k_scale / v_scale, but --calculate-kv-scales wins: the first "
-                       "admission calculates them")
 SEQUENCE_SWITCHES = ("KARANTA_NARROW", "KARANTA_NARROW_O", "KARANTA_DEFER_DOWN", "KARANTA_WIDE", "KARANTA_ATOMIC_SLAB", "KARANTA_DEC32")
 
 __all__ = ["Engine", "PageRequest", "SpecConfig", "DeviceWeights", "GenerateResult", "children", "SEQUENCE_SWITCHES", "DeviceGuide"]
@@ -78,11 +78,11 @@ class Admission:
     reps: Optional[list] = None        # per sequence its RepetitionParams or None
     need: StepFeatures = StepFeatures()
     # parallel sampling: B / slots / lens / last_rows / cs count SEQUENCES (children); the prefill (M, src, cos, sin, plan) covers
-    # every page once, in child 0's slot, and `forks` names what kr_kv_fork copies afterwards
+    # every page once, in child 0's slot, and `forks` names what KVCache.fork copies afterwards
     n_pages: int = 0
     rows: list = field(default_factory=list)    # `children` of the admission's pages, made once per admission
     forks: list = field(default_factory=list)   # (source slot, prompt length, [sibling slots]) per page with n > 1
-    kvq: list = field(default_factory=list)     # (slot, prompt length) per prefilled page: what kr_kv_quantize converts (fp8 KV cache)
+    kvq: list = field(default_factory=list)     # (slot, prompt length) per prefilled page: what the fp8 KV cache quantises
 
     def spans(self, width: int):
         """(first sequence, first slot, slots) of what an activation does per stretch of slots: a whole batch is ONE stretch of
@@ -160,8 +160,8 @@ class Engine:
         if self.kv8 and t.head_dim != 128:
             raise KarantaHipError(f"kv_cache_dtype fp8 needs a text head_dim of 128, this model has {t.head_dim}: the fp8 cache's "
                                   "quantise, append and attention kernels are written for 128-byte K rows")
-        # --calculate-kv-scales: the FIRST prefill writes the scale table from the absolute maxima of its own K / V (kr_kv_absmax):
-        # scale = amax / range per (layer, K or V, kv head).  _kv_calibrate is armed until then (set_kv_scales disarms it)
+        # --calculate-kv-scales: the FIRST prefill writes the scale table from the absolute maxima of its own K / V:
+        # scale = amax / range per (layer, K or V, kv head) (kv_cache.KVCacheFp8)
         self.calculate_kv_scales = bool(calculate_kv_scales)
         if self.calculate_kv_scales and not self.kv8:
             raise KarantaHipError("calculate_kv_scales: the KV cache is bfloat16, there are no scales to calculate "
@@ -169,8 +169,6 @@ class Engine:
         self.kv_scale_ranges = tuple(float(r) for r in kv_scale_ranges)
         if len(self.kv_scale_ranges) != 2 or not all(np.isfinite(r) and r > 0 for r in self.kv_scale_ranges):
             raise KarantaHipError(f"kv_scale_ranges {kv_scale_ranges!r}: (K range, V range), finite and positive")
-        self._kv_calibrate = self.calculate_kv_scales
-        self.kv_scales_calibrated = False           # True once the calibrating admission has been launched
         if v.head_dim not in (80, 128) or t.head_dim != 128:
             raise KarantaHipError(f"unsupported head dims vit={v.head_dim} llm={t.head_dim}")
         self.w = DeviceWeights(cfg, self.device, weight_dtype)
@@ -239,23 +237,7 @@ class Engine:
             self.p_a8 = z(M, (max(t.intermediate_size, t.hidden_size, t.q_dim) + 15) // 16 * 16, dtype=torch.uint8)
             self.p_as = z(M, dtype=torch.float32)
         self.gemm_scratch = z(GEMM_SCRATCH_BYTES // 4, dtype=torch.float32)   # kr_gemm_bf16_ws (KR_GEMM_SCRATCH_BYTES)
-        # KV cache (zero-initialised: masked keys must be finite)
-        kv_dtype = torch.uint8 if self.kv8 else BF16       # fp8: code 0 is 0.0, the zero-initialised cache is still finite padding
-        self.kcache = z(t.num_layers, B, t.num_kv_heads, self.s_max, t.head_dim, dtype=kv_dtype)
-        self.vtcache = z(t.num_layers, B, t.num_kv_heads, self.s_max // 64, t.head_dim, 64, dtype=kv_dtype)
-        if self.kv8:
-            # the prefill and its attention stay on bf16: they write and read ONE layer of bf16 scratch (the strides of a layer of
-            # the bf16 cache, so the prefill plan is unchanged), which kr_kv_quantize converts into layer i after layer i's attention
-            self.p_kscratch = z(B, t.num_kv_heads, self.s_max, t.head_dim)
-            self.p_vtscratch = z(B, t.num_kv_heads, self.s_max // 64, t.head_dim, 64)
-            self.d_kv_scale = torch.ones(t.num_layers, 2, t.num_kv_heads, dtype=torch.float32, device=dev)   # static: graphs read it
-            self.d_kv_clamped = z(1, dtype=torch.int32)
-            self.h_kv_clamped = torch.zeros(1, dtype=torch.int32).pin_memory()    # its host mirror, refreshed behind every admission
-            self.kv_scale_source = "default (1.0)"
-            # the table's host mirror (kv_scales()): written by set_kv_scales, refreshed behind the calibrating admission
-            self.h_kv_scale = torch.ones(t.num_layers, 2, t.num_kv_heads, dtype=torch.float32).pin_memory()
-            if self.calculate_kv_scales:   # kr_kv_absmax's [2][KVH] words: zero on entry, zero again behind every call
-                self.d_kv_work = z(2 * t.num_kv_heads, dtype=torch.int32)
+        self.kv = kv_cache.make(self)     # the KV cache: storage, scales and the launches that depend on its dtype
         # decode state
         self.d_x = z(R, t.hidden_size)
         self.d_x2 = z(R, t.hidden_size)  # the other residual buffer (deferred split-K ping-pong)
@@ -360,57 +342,52 @@ class Engine:
     def _waves(nchunks: int) -> int:
         return 16 if nchunks >= 64 else 8 if nchunks >= 16 else 4
 
-    # ------------------------------------------------------------------ fp8 KV cache
+    # ------------------------------------------------------------------ KV cache: the component's public entries
     def set_kv_scales(self, k, v, source: str = "set_kv_scales"):
         """The scales of the fp8 KV cache: k and v are [L] or [L, KVH] arrays, a code stands for code x scale.  They apply to what
         enters the cache from now on: set them before the first admission."""
-        if not self.kv8:
-            raise KarantaHipError("set_kv_scales: the KV cache is bfloat16 (kv_cache_dtype=\"fp8\" quantises it)")
-        t = self.cfg.text
-        table = torch.from_numpy(kv_scale_table(k, v, t.num_layers, t.num_kv_heads))
-        self.d_kv_scale.copy_(table.to(self.device))
-        self.h_kv_scale.copy_(table)
-        self.kv_scale_source = source
-        self._kv_calibrate = False        # calculate_kv_scales: a table set by hand before the first admission stands
+        self.kv.set_scales(k, v, source)
 
     def kv_scales(self) -> np.ndarray:
         """The [L, 2, KVH] scale table (K scales, then V scales, per layer) from its host mirror: what set_kv_scales put there, or
         what the calibrating admission calculated — as of the last admission whose stream has been waited for (generate, admit,
         admit_end), like kv_clamped.  `set_kv_scales(table[:, 0], table[:, 1])` on another engine pins it."""
-        if not self.kv8:
-            raise KarantaHipError("kv_scales: the KV cache is bfloat16 (kv_cache_dtype=\"fp8\" quantises it)")
-        return self.h_kv_scale.numpy().copy()
+        return self.kv.scales()
 
     @property
     def kv_scales_ready(self) -> bool:
         """calculate_kv_scales: the calibrating admission has run on the device and kv_scales() holds what it calculated.  A query
         of an event, no synchronisation."""
-        return self.kv_scales_calibrated and self._kv_scale_event.query()
+        return self.kv.scales_ready
+
+    @property
+    def kv_scales_calibrated(self) -> bool:
+        """True once the calibrating admission has been launched."""
+        return self.kv.calibrated
 
     @property
     def kv_clamped(self) -> int:
         """Elements the COMPLETED admissions clamped to +-448 x scale on their way into the fp8 cache (kr_kv_quantize's counter, as
         of the last admission whose stream has been waited for: generate, admit, admit_end).  No synchronisation here."""
-        return int(self.h_kv_clamped[0]) if self.kv8 else 0
+        return self.kv.clamped
+
+    @property
+    def kv_scale_source(self) -> str:
+        return self.kv.scale_source
 
     def kv_cache_bytes(self) -> int:
-        return self.kcache.numel() * self.kcache.element_size() + self.vtcache.numel() * self.vtcache.element_size()
+        return self.kv.nbytes()
 
-    def _kv8(self, i: int):
-        """kr_kv8* of layer i."""
-        return kv8(ptr(self.kcache[i]), ptr(self.vtcache[i]), ptr(self.d_kv_scale[i]))
+    # the component's tensors under the names they had on the engine, read-only: what tests and operators' scripts inspect.
+    # Properties, not attributes: the tensors have one holder (tests/launch_trace.py names pointers by it)
+    kcache = property(lambda self: self.kv.kcache)
+    vtcache = property(lambda self: self.kv.vtcache)
+    d_kv_scale = property(lambda self: self.kv.d_kv_scale)
+    d_kv_work = property(lambda self: self.kv.d_kv_work)
 
     def load_weights(self, weights: Dict[str, np.ndarray], log=None):
         self.w.load(weights)
-        if self.kv8:      # a checkpoint with a kv_cache_scheme ships one k_scale / v_scale per layer: broadcast over the kv heads
-            sc = kv_scales_from_checkpoint(weights, self.cfg)
-            if sc is not None and self._kv_calibrate:
-                if log is not None:
-                    log(KV_SCALES_FLAG_WINS)
-            elif sc is not None:
-                self.set_kv_scales(*sc, source="checkpoint (self_attn.k_scale / v_scale)")
-            if log is not None:
-                log(f"fp8 KV cache scales: {self.kv_scale_source}")
+        self.kv.load_scales(weights, log)
 
     # ------------------------------------------------------------------ small launch helpers
     def _gemm(self, A, W, C_, M, bias=None, res=None, epi=EPI_NONE, packed=False, w8=None, w_scale=None):
@@ -445,19 +422,20 @@ class Engine:
 
     def _dec_narrow(self, mode, x, W, M, out=None, out_f32=None, bias=None, norm_w=None, res=None, waves=8, ksplit=1,
                     part_in=None, x_out=None, kc=0, vc=0, w8=None, w_scale=None, zero=None, atomic_out=False,
-                    resident=False, kv8_layer=None):
+                    resident=False, kv8=None):
         """kr_linear_decode_narrow: one workgroup per tile (pair); ksplit > 1 = deferred split-K sums in out_f32.
         w8 / w_scale: the fp8 copy of W and its row scales (kr_linear_decode_narrow_fp8).  zero (an f32 tensor the launch
-        also zeroes), atomic_out, resident (w_resident: the weights stay in the Infinity Cache): the launch's kr_narrow_opts."""
+        also zeroes), atomic_out, resident (w_resident: the weights stay in the Infinity Cache): the launch's kr_narrow_opts.
+        kc / vc (addresses) or kv8 (a kr_kv8*): the layer of the cache a qkv launch appends to, as `self.kv.qkv(i)` names it."""
         t = self.cfg.text
         N, K = W.shape
         o = out if out is not None else out_f32
-        if kv8_layer is not None:     # the qkv launch into the fp8 cache (ROPE_KV8): same launch, the cache as a kr_kv8
+        if kv8 is not None:     # the qkv launch into the fp8 cache (ROPE_KV8): same launch, the cache as a kr_kv8
             self.L.kr_linear_decode_narrow_kv8(
                 ptr(x), x.stride(0), ptr(part_in), int(part_in.shape[0]) if part_in is not None else 0, ptr(x_out),
                 x_out.stride(0) if x_out is not None else 0, ptr(w8 if w8 is not None else W), ptr(w_scale), ptr(bias), ptr(norm_w),
                 t.rms_norm_eps, M, N, K, waves, ptr(self.d_cs), self.max_new, ptr(self.d_plen), ptr(self.d_ctx), ptr(self.d_q),
-                self._kv8(kv8_layer), t.num_heads, t.num_kv_heads, self.s_max,
+                kv8, t.num_heads, t.num_kv_heads, self.s_max,
                 narrow_opts(ptr(zero), zero.numel() * 4 if zero is not None else 0, atomic_out, w_resident=resident), self.s)
             return
         head = (mode, ptr(x), x.stride(0), ptr(part_in), int(part_in.shape[0]) if part_in is not None else 0, ptr(x_out),
@@ -472,7 +450,7 @@ class Engine:
             self.L.kr_linear_decode_narrow(*head, ptr(W), *args)
 
     def _dec32(self, mode, xp, W, M, waves_ref, out=None, out_f32=None, bias=None, res=None, ksplit=1, atomic_out=False, zero=None,
-               kc=0, vc=0, w8=None, w_scale=None, tiles_per_wg=0, group_split=False, row_slot=None, kv8_layer=None):
+               kc=0, vc=0, w8=None, w_scale=None, tiles_per_wg=0, group_split=False, row_slot=None, kv8=None):
         """kr_linear_decode32: the decode linears of a 17..32-row batch on PACKED activations (xp: kr_pack_rows32 layout, written
         by kr_decode_resnorm32 / kr_attn_decode_merge32 / the gate/up launch with DEC_OUT_XP), with the K partition of the
         <= 16-row launch of the same layer (waves_ref, ksplit): row for row the bits that launch produces."""
@@ -485,8 +463,8 @@ class Engine:
                   zero.numel() * 4 if zero is not None else 0,
                   ptr(self.d_cs), self.max_new, ptr(self.d_plen), ptr(self.d_ctx), ptr(self.d_q), kc or None, vc or None,
                   t.num_heads, t.num_kv_heads, self.s_max)
-        if kv8_layer is not None:   # the qkv launch into the fp8 cache (ROPE_KV8), with the row map of a speculative step or without
-            self.L.kr_linear_decode32_kv8(C.byref(a), self._kv8(kv8_layer), ptr(row_slot), self.s)
+        if kv8 is not None:   # the qkv launch into the fp8 cache (ROPE_KV8), with the row map of a speculative step or without
+            self.L.kr_linear_decode32_kv8(C.byref(a), kv8, ptr(row_slot), self.s)
         elif row_slot is not None:    # speculative step: cache and rotary row by the row's slot (kr_linear_decode32_rows)
             self.L.kr_linear_decode32_rows(mode, C.byref(a), ptr(row_slot), self.s)
         else:
@@ -693,9 +671,6 @@ class Engine:
         rows = adm.rows
         adm.need = self._admit_features(rows)
         M, d = adm.M, t.hidden_size
-        # calculate_kv_scales: the first prefill after construction calibrates — every layer writes its row of the scale table
-        # (kr_kv_absmax over the scratch) right before kr_kv_quantize reads it, on this admission's stream; later ones do not
-        calibrate, self._kv_calibrate = self.kv8 and self._kv_calibrate, False
         with torch.cuda.stream(self.stream):
             self._h2d(self.p_src, adm.src)
             self._h2d(self.p_cos, adm.cos)
@@ -710,29 +685,15 @@ class Engine:
                 p = f"llm.{i}."
                 L.kr_rmsnorm(ptr(self.p_x), d, ptr(w.view(p + "ln1.w")), ptr(self.p_h), M, d, t.rms_norm_eps, s)
                 self._gemm(self.p_h, w.view(p + "qkv.w"), self.p_qkv, M, bias=w.view(p + "qkv.b"), packed=True, **self._w8kw(p + "qkv.w"))
-                # [max_batch, kv heads, ...]: the plan's rows count from slot 0.  fp8 cache: the one-layer bf16 scratch
-                kc, vc = (self.p_kscratch, self.p_vtscratch) if self.kv8 else (self.kcache[i], self.vtcache[i])
+                kc, vc = self.kv.prefill_target(i)     # [max_batch, kv heads, ...]: the plan's rows count from slot 0
                 self._attention(self.p_qkv, t.q_dim, t.q_dim + t.kv_dim, self.p_cos, self.p_sin, dp, self.p_q, kc, kc.stride(1),
                                 vc, vc.stride(1), self.p_o, t.num_heads, t.num_kv_heads, t.head_dim, causal=True)
-                if calibrate:
-                    L.kr_kv_absmax(ptr(kc), ptr(vc), t.num_kv_heads, t.head_dim, self.B, self.s_max, kvq_plan(adm.kvq),
-                                   self.kv_scale_ranges[0], self.kv_scale_ranges[1], ptr(self.d_kv_scale[i]), ptr(self.d_kv_work), s)
-                if self.kv8:   # the admission's rows of the scratch -> layer i of the fp8 cache, on the admission's stream
-                    L.kr_kv_quantize(ptr(kc), ptr(vc), self._kv8(i), t.num_kv_heads, t.head_dim, self.B, self.s_max,
-                                     kvq_plan(adm.kvq), ptr(self.d_kv_clamped), s)
+                self.kv.prefill_layer_done(i, adm)
                 self._gemm(self.p_o, w.view(p + "o.w"), self.p_x, M, res=self.p_x, packed=True, **self._w8kw(p + "o.w"))
                 L.kr_rmsnorm(ptr(self.p_x), d, ptr(w.view(p + "ln2.w")), ptr(self.p_h), M, d, t.rms_norm_eps, s)
                 self._gemm(self.p_h, w.view(p + "gate_up.w"), self.p_act, M, epi=EPI_SILU_MUL8, packed=True, **self._w8kw(p + "gate_up.w"))
                 self._gemm(self.p_act, w.view(p + "down.w"), self.p_x, M, res=self.p_x, packed=True, **self._w8kw(p + "down.w"))
-            if self.kv8:
-                self.h_kv_clamped.copy_(self.d_kv_clamped, non_blocking=True)
-            if calibrate:
-                self.h_kv_scale.copy_(self.d_kv_scale, non_blocking=True)
-                self.kv_scale_source = (f"calculated from the first admission ({M} prompt tokens; ranges "
-                                        f"{self.kv_scale_ranges[0]:g} / {self.kv_scale_ranges[1]:g})")
-                self._kv_scale_event = torch.cuda.Event()
-                self._kv_scale_event.record(self.stream)
-                self.kv_scales_calibrated = True
+            self.kv.prefill_done(adm)
             self.pages_prefilled += adm.n_pages
             if not defer_activation:
                 self._fork(adm.forks)
@@ -740,13 +701,11 @@ class Engine:
         return adm
 
     def _fork(self, groups):
-        """kr_kv_fork: the prompt's KV rows of every (source slot, prompt length, [destination slots]), in one launch on the
-        engine's current stream."""
+        """The prompt's KV rows of every (source slot, prompt length, [destination slots]), in one launch on the engine's current
+        stream (KVCache.fork)."""
         if not groups:
             return
-        t, kc, vc = self.cfg.text, self.kcache, self.vtcache
-        (self.L.kr_kv_fork8 if self.kv8 else self.L.kr_kv_fork)(ptr(kc), ptr(vc), kc.stride(0), kc.stride(1), kc.stride(2), vc.stride(0), vc.stride(1), vc.stride(2),
-                          t.num_layers, t.num_kv_heads, t.head_dim, self.B, self.s_max, fork_plan(groups), self.s)
+        self.kv.fork(groups)
         self.sequences_forked += sum(len(g[2]) for g in groups)
 
     def _admit_features(self, pages) -> StepFeatures:
@@ -849,7 +808,7 @@ class Engine:
     def _layer_launches(self, B: int, row_slot=None):
         """The layers of a decode step over B rows; returns the residual buffer that holds the last layer's output.  row_slot (a
         speculative step, B = self.rows): row r belongs to slot row_slot[r] — its K/V go to that slot's cache at the row's own
-        position and its attention reads that cache (kr_linear_decode32_rows, kr_attn_decode_rows); the per-row state arrays are
+        position and its attention reads that cache (kr_linear_decode32_rows, KVCache.attention); the per-row state arrays are
         the slots' own, continued behind the slots.
         One decode step = 6 (<= 16 rows) or 7 (17..32 rows) launches per layer + 2 (Qwen2VLDecoderLayer TF:559-624, final norm
         TF:839, lm_head TF:1320-1323).
@@ -862,7 +821,7 @@ class Engine:
         everywhere, two slabs, row-major launches above 16 rows, prefetch branches, fast-residual mode, in-launch merges)
         live in csrc/tools/experiment_engine.py."""
         t, L, w, s = self.cfg.text, self.L, self.w, self.s
-        H, KVH, hd = t.num_heads, t.num_kv_heads, t.head_dim
+        H, hd = t.num_heads, t.head_dim
         nl = t.num_layers
         big = B > 16                              # packed-activation family of 17..32-row batches
         x, x_other = self.d_x, self.d_x2          # residual stream: swaps buffers at every deferred reduction
@@ -880,7 +839,6 @@ class Engine:
             slabs = self.d_part.view(-1)[: 4 * B * t.hidden_size].view(2, 2, B, t.hidden_size)
         for i in range(nl):
             p = f"llm.{i}."
-            kc, vc = ptr(self.kcache[i]), ptr(self.vtcache[i])     # the cache tensors are [layers, max_batch, ...]
             defer = self.defer_down and i + 1 < nl
             # ---- 1. (x += down_proj sums of layer i - 1) -> RMSNorm -> QKV + bias + M-RoPE + KV append
             # this layer's down_proj will ADD into accumulator (i + 1) & 1: the qkv launch zeroes it (it was last read by
@@ -892,27 +850,16 @@ class Engine:
                 L.kr_decode_resnorm32(ptr(x), x.stride(0), ptr(pin), int(pin.shape[0]) if pending else 0, B, ptr(x_other),
                                       x_other.stride(0), ptr(w.view(p + "ln1.w")), t.rms_norm_eps, ptr(self.d_h), B, t.hidden_size,
                                       1 if (gs and pending) else 0, s)
-                self._dec32(DEC_ROPE_KV, self.d_h, w.view(p + "qkv.w"), B, 8, bias=w.view(p + "qkv.b"), kc=kc, vc=vc,
-                            zero=acc, row_slot=row_slot, kv8_layer=i if self.kv8 else None, **self._w8kw(p + "qkv.w"))
+                self._dec32(DEC_ROPE_KV, self.d_h, w.view(p + "qkv.w"), B, 8, bias=w.view(p + "qkv.b"), zero=acc,
+                            row_slot=row_slot, **self.kv.qkv(i), **self._w8kw(p + "qkv.w"))
             else:
                 self._dec_narrow(DEC_ROPE_KV, x, w.view(p + "qkv.w"), B, bias=w.view(p + "qkv.b"), norm_w=w.view(p + "ln1.w"),
-                                 part_in=pin, x_out=x_other if pending else None, kc=kc, vc=vc, zero=acc,
-                                 resident=(i, "qkv") in self.resident, kv8_layer=i if self.kv8 else None, **self._w8kw(p + "qkv.w"))
+                                 part_in=pin, x_out=x_other if pending else None, zero=acc,
+                                 resident=(i, "qkv") in self.resident, **self.kv.qkv(i), **self._w8kw(p + "qkv.w"))
             if pending:
                 x, x_other = x_other, x
             # ---- 2. split-KV attention partials, 3. their merge
-            if self.kv8 and row_slot is not None:
-                L.kr_attn_decode_rows_kv8(ptr(self.d_q), self._kv8(i), ptr(self.d_ctx), ptr(self.d_fin), ptr(row_slot), ptr(self.d_ws), B, H,
-                                          KVH, hd, self.s_max, self.n_split, hd ** -0.5, s)
-            elif self.kv8:
-                L.kr_attn_decode_slots_kv8(ptr(self.d_q), self._kv8(i), ptr(self.d_ctx), ptr(self.d_fin), ptr(self.d_ws), B, H, KVH, hd,
-                                           self.s_max, self.n_split, hd ** -0.5, s)
-            elif row_slot is not None:
-                L.kr_attn_decode_rows(ptr(self.d_q), kc, vc, ptr(self.d_ctx), ptr(self.d_fin), ptr(row_slot), ptr(self.d_ws), B, H, KVH,
-                                      hd, self.s_max, self.n_split, hd ** -0.5, s)
-            else:
-                L.kr_attn_decode_slots(ptr(self.d_q), kc, vc, ptr(self.d_ctx), ptr(self.d_fin), ptr(self.d_ws), B, H, KVH, hd, self.s_max,
-                                       self.n_split, hd ** -0.5, s)
+            self.kv.attention(i, B, row_slot)
             (L.kr_attn_decode_merge32 if big else L.kr_attn_decode_merge)(ptr(self.d_ws), ptr(self.d_o), B, H, hd, self.n_split, s)
             # ---- 4. o_proj + residual
             if big:
@@ -1325,7 +1272,7 @@ class Engine:
         """Start sequences from prompts that are already resident: pages[i] from the KV rows and the last-token hidden row that
         an earlier admission of the SAME prompt left in slot srcs[i] — no ViT, no prefill.  ``slots`` / ``budgets``: one entry per
         sequence as in `admit` (a page's n children consecutive).  A sequence whose slot is its source is re-activated in place;
-        the others get the prompt's rows by one kr_kv_fork (the source may be decoding: its rows below the prompt length never
+        the others get the prompt's rows by one fork launch (the source may be decoding: its rows below the prompt length never
         change).  Runs on the decode stream only.  The caller vouches that srcs[i] holds this page's prompt; what the engine
         can check is its length.  Returns prompt lengths per sequence."""
         rows = children(pages)

@@ -1,11 +1,13 @@
 """The engine issues the launches it issued when tests/golden/launch_trace.json was recorded: the same entry points in the same
 order with the same arguments (tests/launch_trace.py), over whole-batch generation with and without sampling controls and a
-guide, slot mode with every kind of admission, the packed 17..32-row family on bf16 and fp8 weights, and speculative steps.
+guide, slot mode with every kind of admission, the packed 17..32-row family on bf16 and fp8 weights, and speculative steps;
+and over the same scenarios with the fp8 KV cache (a calibrating admission, pinned scales, the fork, both row maps).
 A change that only moves host code leaves every trace as it is; one that adds, drops, reorders or re-parameterises a launch
 fails here with the first call that differs.
 
 The fixture is recorded by `python -m tests.test_gpu_launch_trace` on a tree whose launches are the wanted ones (it was made
-on the commit before engine.py was split into modules)."""
+on the commit before engine.py was split into modules; the fp8-cache keys were added on the commit before the KV cache moved
+into kv_cache.py, with every older key unchanged)."""
 import hashlib
 import json
 import os
@@ -43,6 +45,19 @@ def _traced(eng, out, key, fn):
     out[key] = calls
 
 
+def _slot_scenario(eng, pages):
+    """Slot mode with every kind of admission: a fork, a reused prompt, an overlapped admission."""
+    cfg = eng.cfg
+    eng.begin_slots(8, sampling=True)
+    # two pages, three sequences: the page with n = 2 takes slots 0 and 3
+    eng.admit([pages[0], page_of(cfg, 64, variant=1, temperature=0.7, top_k=5, seed=9, n=2)], [2, 0, 3])
+    eng.decode_steps(2)
+    eng.admit_reuse([page_of(cfg, 40, variant=0, logit_bias={3: 1.0})], [2], [1])
+    handle = eng.admit_begin([pages[2]], [3])
+    eng.admit_end(handle)
+    eng.decode_steps(1)
+
+
 def group_tiny():
     """a: whole batches on the tiny model, eager; b: the same engine in slot mode."""
     from karanta_ocr_amd.serving import ByteTokenizer
@@ -55,26 +70,16 @@ def group_tiny():
              page_of(cfg, 64, variant=1, temperature=0.7, top_k=5, repetition_penalty=1.1, logit_bias={3: 1.0}, logprobs=2, seed=5),
              page_of(cfg, 100, variant=2, guide=GUIDE_PATTERN)]
     _traced(eng, out, "a_controls", lambda: eng.generate(mixed, 4, use_graph=False))
-
-    def slots():
-        eng.begin_slots(8, sampling=True)
-        # two pages, three sequences: the page with n = 2 takes slots 0 and 3
-        eng.admit([pages[0], page_of(cfg, 64, variant=1, temperature=0.7, top_k=5, seed=9, n=2)], [2, 0, 3])
-        eng.decode_steps(2)
-        eng.admit_reuse([page_of(cfg, 40, variant=0, logit_bias={3: 1.0})], [2], [1])
-        handle = eng.admit_begin([pages[2]], [3])
-        eng.admit_end(handle)
-        eng.decode_steps(1)
-    _traced(eng, out, "b_slots", slots)
+    _traced(eng, out, "b_slots", lambda: _slot_scenario(eng, pages))
     eng.close()
     return out
 
 
-def _group_rows32(dtype):
+def _group_rows32(dtype, key="c_", **kw):
     """c: 18 pages at once, the packed 17..32-row decode family."""
-    eng, out = _engine("tiny-w512", max_batch=21, weight_dtype=dtype), {}
+    eng, out = _engine("tiny-w512", max_batch=21, weight_dtype=dtype, **kw), {}
     pages = [page_of(eng.cfg, LENGTHS[b % 3], variant=b) for b in range(18)]
-    _traced(eng, out, "c_" + dtype, lambda: eng.generate(pages, 3))
+    _traced(eng, out, key + dtype, lambda: eng.generate(pages, 3))
     eng.close()
     return out
 
@@ -87,9 +92,9 @@ def group_rows32_fp8():
     return _group_rows32("fp8")
 
 
-def group_spec():
+def group_spec(key="d_spec", **kw):
     """d: four slots with K = 3 are 16 rows, which run as 17."""
-    eng, out = _engine("tiny-w512", max_batch=4, speculative=SpecConfig(3, 2, 4)), {}
+    eng, out = _engine("tiny-w512", max_batch=4, speculative=SpecConfig(3, 2, 4), **kw), {}
     pages = [page_of(eng.cfg, LENGTHS[b % 3], variant=b) for b in range(4)]
 
     def steps():
@@ -98,12 +103,47 @@ def group_spec():
         eng.set_draft_script(1, [7, 8, 9, 10, 11, 12, 13, 14])
         eng.decode_steps(2, speculative=True)
         eng.decode_steps(1)
-    _traced(eng, out, "d_spec", steps)
+    _traced(eng, out, key, steps)
     eng.close()
     return out
 
 
-GROUPS = {"tiny": group_tiny, "rows32_bf16": group_rows32_bf16, "rows32_fp8": group_rows32_fp8, "spec": group_spec}
+def group_kv8_tiny():
+    """e: the fp8 KV cache on the tiny model.  The first admission calculates the scales (kr_kv_absmax before kr_kv_quantize in
+    every layer), then the slot scenario of b, whose fork is kr_kv_fork8; a second engine with a table set by hand calculates
+    nothing."""
+    eng, out = _engine("tiny", max_batch=4, kv_cache_dtype="fp8", calculate_kv_scales=True), {}
+    t = eng.cfg.text
+    pages = [page_of(eng.cfg, P, variant=b) for b, P in enumerate(LENGTHS)]
+    _traced(eng, out, "e_kv8_calibrate", lambda: eng.generate(pages, 4, use_graph=False))
+    _traced(eng, out, "e_kv8_slots", lambda: _slot_scenario(eng, pages))
+    eng.close()
+    eng = _engine("tiny", max_batch=4, kv_cache_dtype="fp8", calculate_kv_scales=True)
+    heads = np.arange(t.num_layers * t.num_kv_heads, dtype=np.float32).reshape(t.num_layers, t.num_kv_heads)
+    eng.set_kv_scales(0.5 + heads / 8, 0.25 + heads / 16)
+    _traced(eng, out, "e_kv8_pinned", lambda: eng.generate(pages, 4, use_graph=False))
+    assert "kr_kv_absmax" not in names(out["e_kv8_pinned"]) and "kr_kv_absmax" in names(out["e_kv8_calibrate"])
+    eng.close()
+    return out
+
+
+def group_kv8_rows32_bf16():
+    """f: the packed family appending to and reading the fp8 cache, without a row map."""
+    return _group_rows32("bf16", key="f_kv8_rows32_", kv_cache_dtype="fp8")
+
+
+def group_kv8_rows32_fp8():
+    return _group_rows32("fp8", key="f_kv8_rows32_", kv_cache_dtype="fp8")
+
+
+def group_kv8_spec():
+    """g: the speculative steps of d on the fp8 cache: the row map in the qkv launch and in the attention."""
+    return group_spec(key="g_kv8_spec", kv_cache_dtype="fp8")
+
+
+GROUPS = {"tiny": group_tiny, "rows32_bf16": group_rows32_bf16, "rows32_fp8": group_rows32_fp8, "spec": group_spec,
+          "kv8_tiny": group_kv8_tiny, "kv8_rows32_bf16": group_kv8_rows32_bf16, "kv8_rows32_fp8": group_kv8_rows32_fp8,
+          "kv8_spec": group_kv8_spec}
 
 
 def _arg_digests(calls):
