@@ -48,7 +48,8 @@ __global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16*
     __shared__ __attribute__((aligned(16))) float o_s[WAVES][16][HD];
     __shared__ float m_s[WAVES][16], l_s[WAVES][16];
     __shared__ int last_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the wave index in a scalar register: the branch on this part's unit count below is a scalar branch
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fg = lane >> 4;
     // group (= heads / kv_heads) and n_split (= gridDim.x) are arguments: a runtime division and a read of the dispatch
     // packet would both sit in front of the first loads
@@ -78,118 +79,147 @@ __global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16*
 #pragma unroll
     for (int t = 0; t < DT; ++t) o[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float m_run = -1e30f, l_run = 0.f;
-    // unit = 32 keys (half a V^T block); wave `part` takes units part, part + n_part, ...: at the contexts of a page
-    // (1.4k .. 2.4k keys = 44 .. 76 units) 64 parts leave one unit — one memory round trip — per wave; a wave with
-    // more requests unit u + n_part before it computes unit u
+    // unit = 32 keys (half a V^T block); wave `part` takes units part, part + n_part, ...: 64 parts leave one unit — one
+    // memory round trip — per wave up to 2048 keys; a page runs from 1.4k to 2.5k keys (46 .. 78 units), so past 2048 keys
+    // parts 0 .. nu - 65 carry two units, both requested before the first is folded
     const int nu = (ctx + 31) >> 5;
     // KV8: a unit is half the registers — K [kt][j] and V^T [i] of 16 bytes each
     constexpr int KI = KV8 ? 2 : 4, VI = KV8 ? 4 : DT;
     bf16x8 kf[2][KI], vf[VI], kf2[2][KI], vf2[VI];
-    auto load_unit = [&](int u, bf16x8 (&kk)[2][KI], bf16x8 (&vv)[VI]) {
+    auto load_k = [&](int u, bf16x8 (&kk)[2][KI]) {
         const int key0 = u * 32;
-        if constexpr (KV8) {
-            const char* kb = reinterpret_cast<const char*>(kc);
-            const char* vb = reinterpret_cast<const char*>(vc);
 #pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-                const char* kp = kb + (int64_t)(key0 + 8 * ((((fr >> 2) & 1) << 1) | (fr >> 3)) + 4 * kt + (fr & 3)) * HD + fg * 16;
+        for (int kt = 0; kt < 2; ++kt) {
+            if constexpr (KV8) {
+                const char* kp = reinterpret_cast<const char*>(kc) +
+                                 (int64_t)(key0 + 8 * ((((fr >> 2) & 1) << 1) | (fr >> 3)) + 4 * kt + (fr & 3)) * HD + fg * 16;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) kk[kt][j] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(kp + j * 64));
+            } else {
+                const kr_bf16* kp = kc + (int64_t)(key0 + 8 * (fr >> 2) + 4 * kt + (fr & 3)) * HD + fg * 8;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) kk[kt][i] = KR_ATTN_DEC_LD(kp + i * 32);
             }
-            const char* vp = vb + (int64_t)(u >> 1) * (HD * 64) + (u & 1) * (HD * 32) + ((fg >> 1) * 16 + fr) * 32 + (fg & 1) * 16;
+        }
+    };
+    auto load_v = [&](int u, bf16x8 (&vv)[VI]) {
+        if constexpr (KV8) {
+            const char* vp = reinterpret_cast<const char*>(vc) + (int64_t)(u >> 1) * (HD * 64) + (u & 1) * (HD * 32) +
+                             ((fg >> 1) * 16 + fr) * 32 + (fg & 1) * 16;
 #pragma unroll
             for (int i = 0; i < 4; ++i) vv[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(vp + i * (32 * 32)));
         } else {
+            // the unit's half of its V^T block is contiguous ([2][HD][32]: kr_common.h): 16 channel rows x 64 B per instruction = 1 KiB of
+            // whole lines (rounds 1-3: [HD][64], half of every line — 4.0 against 6.5 TB/s for this shape, profiles/r04_halfline_read.txt)
+            const kr_bf16* vp = vc + (int64_t)(u >> 1) * (HD * 64) + (u & 1) * (HD * 32) + fg * 8;
 #pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-            const kr_bf16* kp = kc + (int64_t)(key0 + 8 * (fr >> 2) + 4 * kt + (fr & 3)) * HD + fg * 8;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) kk[kt][i] = KR_ATTN_DEC_LD(kp + i * 32);
-        }
-        // the unit's half of its V^T block is contiguous ([2][HD][32]: kr_common.h): 16 channel rows x 64 B per instruction = 1 KiB of
-        // whole lines (rounds 1-3: [HD][64], half of every line — 4.0 against 6.5 TB/s for this shape, profiles/r04_halfline_read.txt)
-        const kr_bf16* vp = vc + (int64_t)(u >> 1) * (HD * 64) + (u & 1) * (HD * 32) + fg * 8;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) vv[dt] = KR_ATTN_DEC_LD(vp + (dt * 16 + fr) * 32);
+            for (int dt = 0; dt < DT; ++dt) vv[dt] = KR_ATTN_DEC_LD(vp + (dt * 16 + fr) * 32);
         }
     };
-    int u = part;
-    if (u < nu) load_unit(u, kf, vf);
-    while (u < nu) {
-        const int un = u + n_part;
-        if (un < nu) load_unit(un, kf2, vf2);
-        {
-            const int key0 = u * 32;
-            f32x4 s[2];
+    auto load_unit = [&](int u, bf16x8 (&kk)[2][KI], bf16x8 (&vv)[VI]) {
+        load_k(u, kk);
+        load_v(u, vv);
+    };
+    // fold one unit into the running (m, l, o): QK^T needs the unit's K registers only, PV its V^T registers — in straight-line
+    // code each waits (counted vmcnt) for exactly the loads it reads, younger loads stay in flight
+    auto fold_unit = [&](int u, const bf16x8 (&kk)[2][KI], const bf16x8 (&vv)[VI]) {
+        const int key0 = u * 32;
+        f32x4 s[2];
 #pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-                s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int kt = 0; kt < 2; ++kt) {
+            s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    bf16x8 ka;
-                    if constexpr (KV8) {
-                        const u32x4 w = __builtin_bit_cast(u32x4, kf[kt][i >> 1]);
-                        ka = kv8_to_bf16x8(w[2 * (i & 1)], w[2 * (i & 1) + 1]);
-                    } else {
-                        ka = kf[kt][i];
-                    }
-                    s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[i], s[kt], 0, 0, 0);
+            for (int i = 0; i < 4; ++i) {
+                bf16x8 ka;
+                if constexpr (KV8) {
+                    const u32x4 w = __builtin_bit_cast(u32x4, kk[kt][i >> 1]);
+                    ka = kv8_to_bf16x8(w[2 * (i & 1)], w[2 * (i & 1) + 1]);
+                } else {
+                    ka = kk[kt][i];
                 }
-            }
-            float mx = -INFINITY;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key = key0 + 8 * pfg + 4 * kt + r;
-                    const float v = key < ctx ? s[kt][r] * sl2 : -INFINITY;
-                    s[kt][r] = v;
-                    mx = fmaxf(mx, v);
-                }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-            m_run = m_new;
-            bf16x8 pf;
-            float psum = 0.f;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const __bf16 pb = f2bf(__builtin_amdgcn_exp2f(s[kt][r] - m_new));
-                    psum += bf2f(pb);
-                    pf[kt * 4 + r] = pb;
-                }
-            l_run = l_run * alpha + psum;
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
-                if constexpr (!KV8) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt], pf, o[dt], 0, 0, 0);
-            }
-            if constexpr (KV8) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    // load i after the swap of the halves: channel tile 2i in the low registers, 2i + 1 in the high ones
-                    const u32x4 w = __builtin_bit_cast(u32x4, vf[i]);
-                    const auto s0 = __builtin_amdgcn_permlane32_swap(w[0], w[2], false, false);
-                    const auto s1 = __builtin_amdgcn_permlane32_swap(w[1], w[3], false, false);
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-                        o[2 * i + h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kv8_to_bf16x8(s0[h], s1[h]), pf, o[2 * i + h], 0, 0, 0);
-                }
+                s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[i], s[kt], 0, 0, 0);
             }
         }
-        if (un < nu) {
+        float mx = -INFINITY;
 #pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
+        for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-                for (int i = 0; i < KI; ++i) kf[kt][i] = kf2[kt][i];
+            for (int r = 0; r < 4; ++r) {
+                const int key = key0 + 8 * pfg + 4 * kt + r;
+                const float v = key < ctx ? s[kt][r] * sl2 : -INFINITY;
+                s[kt][r] = v;
+                mx = fmaxf(mx, v);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx);
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        m_run = m_new;
+        bf16x8 pf;
+        float psum = 0.f;
 #pragma unroll
-            for (int dt = 0; dt < VI; ++dt) vf[dt] = vf2[dt];
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const __bf16 pb = f2bf(__builtin_amdgcn_exp2f(s[kt][r] - m_new));
+                psum += bf2f(pb);
+                pf[kt * 4 + r] = pb;
+            }
+        l_run = l_run * alpha + psum;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
+            if constexpr (!KV8) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vv[dt], pf, o[dt], 0, 0, 0);
         }
-        u = un;
+        if constexpr (KV8) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                // load i after the swap of the halves: channel tile 2i in the low registers, 2i + 1 in the high ones
+                const u32x4 w = __builtin_bit_cast(u32x4, vv[i]);
+                const auto s0 = __builtin_amdgcn_permlane32_swap(w[0], w[2], false, false);
+                const auto s1 = __builtin_amdgcn_permlane32_swap(w[1], w[3], false, false);
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+                    o[2 * i + h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kv8_to_bf16x8(s0[h], s1[h]), pf, o[2 * i + h], 0, 0, 0);
+            }
+        }
+    };
+    // One wave-uniform branch on this part's unit count; the bodies for one and two units are branch-free from their first load on.
+    // (A load group under `if (un < nu)` in front of the fold makes the fold's waits count the group that MAY be in flight: with
+    // two units the first QK^T then waited for the second unit's 16 loads as well — DESIGN §5, lesson 1.)  Every body folds
+    // the units part, part + n_part, ... in that order with the same instructions: the records are the same bits.
+    const int u0 = part, u1 = part + n_part;
+    if (u1 + n_part < nu) {             // three or more units: unit u + n_part is requested before unit u is folded
+        int u = u0;
+        load_unit(u, kf, vf);
+        while (u < nu) {
+            const int un = u + n_part;
+            if (un < nu) load_unit(un, kf2, vf2);
+            fold_unit(u, kf, vf);
+            if (un < nu) {
+#pragma unroll
+                for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                    for (int i = 0; i < KI; ++i) kf[kt][i] = kf2[kt][i];
+#pragma unroll
+                for (int dt = 0; dt < VI; ++dt) vf[dt] = vf2[dt];
+            }
+            u = un;
+        }
+    } else if (u1 < nu) {               // two units (2049 .. 4096 keys at 64 parts): all 32 loads in flight at once, both K first —
+        load_k(u0, kf);                 // 0.2 us per launch against K, V^T, K, V^T at 2176 .. 2485 keys (profiles/r07_attn_ctx_sweep.txt)
+        load_k(u1, kf2);
+        load_v(u0, vf);
+        load_v(u1, vf2);
+        __builtin_amdgcn_sched_barrier(0);      // every load leaves before the first wait: the scheduler would sink V^T below QK^T
+        fold_unit(u0, kf, vf);
+        __builtin_amdgcn_sched_barrier(0);      // the folds one after the other, each product behind the wait for its own operand
+        fold_unit(u1, kf2, vf2);
+    } else if (u0 < nu) {               // one unit
+        load_unit(u0, kf, vf);
+        __builtin_amdgcn_sched_barrier(0);
+        fold_unit(u0, kf, vf);
     }
     l_run += __shfl_xor(l_run, 16, 64);
     l_run += __shfl_xor(l_run, 32, 64);
@@ -388,8 +418,8 @@ static int attn_decode_impl(const kr_bf16* q, const typename KvElem<KV8>::T* kca
     KR_CHECK_ARG(!out || n_split <= 16, "kr_attn_decode_fused: the in-launch merge takes at most 16 splits");
     KR_CHECK_ARG(!out || n_split == 1 || (workspace && counters), "kr_attn_decode_fused: split needs workspace + counters");
     KR_CHECK_ARG(workspace || n_split == 1, "kr_attn_decode_fused: the split partials need a workspace");
-    // Workgroup shape: n_split x WAVES parts of 32-key units, so that at page contexts (1.4k .. 2.4k keys = 44 .. 76 units)
-    // a wave fetches ONE unit (one memory round trip).  r2 chain timings (B = 8, ctx 1906, launch + dependent-launch gap):
+    // Workgroup shape: n_split x WAVES parts of 32-key units: 64 parts give a wave ONE unit (one memory round trip) up to
+    // 2048 keys; the page contexts (1.4k .. 2.5k keys = 46 .. 78 units) run past that, the first nu - 64 parts then hold two.  r2 chain timings (B = 8, ctx 1906, launch + dependent-launch gap):
     // 8 splits x 8 waves (128 workgroups) 7.8 us; 16 splits x 4 waves (256 workgroups, every CU loads) 5.8 us;
     // 6 x 8 (two units per wave) 12.7 us.  Hence: up to 8 splits 8 waves, up to 16 splits 4 waves, beyond 2 waves
     // (KARANTA_ATTN_WAVES = 2 / 4 / 8 overrides for A/B runs).

@@ -1,6 +1,6 @@
 """A/B timing of the decode step (one process, interleaved rounds: cdna_hip_programming.md §5.4 rule 24).
 
-    python karanta_ocr_amd/csrc/tools/decode_ab.py [--model Qwen2-VL-2B] [--batch 8] [--ctx 1906] [--steps 64] \
+    python karanta_ocr_amd/csrc/tools/decode_ab.py [--model Qwen2-VL-2B] [--batch 8] [--ctx 1906[,2304,...]] [--steps 64] \
         [--rounds 5] variant [variant ...]
 
 A variant is a comma-separated list of Engine attribute overrides, e.g. `base`, `attn_fused_merge=1`,
@@ -47,7 +47,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="Qwen2-VL-2B")
     ap.add_argument("--batch", type=int, default=8)
-    ap.add_argument("--ctx", type=int, default=1906, help="cached tokens per sequence (bench mean: P + T_out / 2)")
+    ap.add_argument("--ctx", default="1906", help="cached tokens per sequence (bench mean: P + T_out / 2); a comma-separated list "
+                                                  "times every variant at each context in turn (plain steps and --chain)")
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--weights", default="bf16")
@@ -65,6 +66,8 @@ def main():
                          "= two independent 16-row decode batches side by side), and report the wall time per step of the group")
     ap.add_argument("variants", nargs="+")
     a = ap.parse_args()
+    a.ctx_list = [int(x) for x in a.ctx.split(",")]
+    a.ctx = max(a.ctx_list)                 # sizes the cache; the graphs read the context from the device
     cfg = CONFIGS[a.model]
     L = lib()
     B = a.batch
@@ -117,10 +120,11 @@ def main():
                         step=eng._step, logprobs=None)
         engines.append((spec, eng))
 
-    def reset(eng):
+    def reset(eng, ctx=None):
+        ctx = a.ctx if ctx is None else ctx
         with torch.cuda.stream(eng.stream):
-            eng.d_ctx.fill_(a.ctx)          # the state a decode step finds: ctx tokens cached, decode position ctx - plen = 0
-            eng.d_plen.fill_(a.ctx)
+            eng.d_ctx.fill_(ctx)            # the state a decode step finds: ctx tokens cached, decode position ctx - plen = 0
+            eng.d_plen.fill_(ctx)
             eng.d_fin.zero_()
             eng.d_x.copy_((torch.randn(eng.d_x.shape, device=eng.device) * 0.5).to(torch.bfloat16))
         eng.stream.synchronize()
@@ -191,25 +195,26 @@ def main():
         return
     e0, e1 = C.c_void_p(), C.c_void_p()
     L.kr_event_create(C.byref(e0)); L.kr_event_create(C.byref(e1))
-    times = {spec: [] for spec, _ in engines}
-    for r in range(a.rounds + 1):
+    for ctx in a.ctx_list:
+        times = {spec: [] for spec, _ in engines}
+        for r in range(a.rounds + 1):
+            for spec, eng in engines:
+                reset(eng, ctx)
+                L.kr_event_record(e0, eng.s)
+                for _ in range(a.steps // per_graph[spec]):
+                    L.kr_graph_launch(graphs[spec], eng.s)
+                L.kr_event_record(e1, eng.s)
+                L.kr_event_synchronize(e1)
+                ms = C.c_float()
+                L.kr_event_elapsed_ms(e0, e1, C.byref(ms))
+                if r:                                  # round 0 warms up
+                    times[spec].append(ms.value / a.steps)
         for spec, eng in engines:
-            reset(eng)
-            L.kr_event_record(e0, eng.s)
-            for _ in range(a.steps // per_graph[spec]):
-                L.kr_graph_launch(graphs[spec], eng.s)
-            L.kr_event_record(e1, eng.s)
-            L.kr_event_synchronize(e1)
-            ms = C.c_float()
-            L.kr_event_elapsed_ms(e0, e1, C.byref(ms))
-            if r:                                  # round 0 warms up
-                times[spec].append(ms.value / a.steps)
-    for spec, eng in engines:
-        kvb = cfg.text.kv_bytes_per_token // (2 if eng.kv8 else 1)       # the bytes THIS variant's step streams
-        roof_ms = (cfg.decoder_weight_bytes(a.weights) + B * (a.ctx + a.steps / 2) * kvb) / 8e12 * 1e3
-        t = np.asarray(times[spec])
-        print(f"{spec:50s} median {np.median(t):.4f} ms/step  min {t.min():.4f}  max {t.max():.4f}  ({roof_ms / np.median(t) * 100:.1f} % of the 8 TB/s step roofline)",
-              flush=True)
+            kvb = cfg.text.kv_bytes_per_token // (2 if eng.kv8 else 1)       # the bytes THIS variant's step streams
+            roof_ms = (cfg.decoder_weight_bytes(a.weights) + B * (ctx + a.steps / 2) * kvb) / 8e12 * 1e3
+            t = np.asarray(times[spec])
+            print(f"{spec:50s} ctx {ctx:5d} median {np.median(t):.4f} ms/step  min {t.min():.4f}  max {t.max():.4f}  "
+                  f"({roof_ms / np.median(t) * 100:.1f} % of the 8 TB/s step roofline)", flush=True)
 
 
 def chains(a, engines, reset):
@@ -319,27 +324,32 @@ def chains(a, engines, reset):
                 finally:
                     L.kr_graph_end_capture(eng.s, C.byref(g))
                 graphs[(spec, kind)] = g
-    times = {k: [] for k in graphs}
-    for r in range(a.rounds + 1):
-        for kind in a.chain.split(","):
-            for spec, eng in engines:
-                L.kr_event_record(e0, eng.s)
-                L.kr_graph_launch(graphs[(spec, kind)], eng.s)
-                L.kr_event_record(e1, eng.s)
-                L.kr_event_synchronize(e1)
-                ms = C.c_float()
-                L.kr_event_elapsed_ms(e0, e1, C.byref(ms))
-                if r:                                      # round 0 warms up
-                    times[(spec, kind)].append(ms.value * 1e3 / (reps * eng.cfg.text.num_layers))
-    for (spec, kind), g in graphs.items():
+    for ctx in a.ctx_list:         # a chain launch does not move the context: one reset per context
+        for spec, eng in engines:
+            reset(eng, ctx)
+        times = {k: [] for k in graphs}
+        for r in range(a.rounds + 1):
+            for kind in a.chain.split(","):
+                for spec, eng in engines:
+                    L.kr_event_record(e0, eng.s)
+                    L.kr_graph_launch(graphs[(spec, kind)], eng.s)
+                    L.kr_event_record(e1, eng.s)
+                    L.kr_event_synchronize(e1)
+                    ms = C.c_float()
+                    L.kr_event_elapsed_ms(e0, e1, C.byref(ms))
+                    if r:                                      # round 0 warms up
+                        times[(spec, kind)].append(ms.value * 1e3 / (reps * eng.cfg.text.num_layers))
+        for (spec, kind), g in graphs.items():
+            t = np.asarray(times[(spec, kind)])
+            eng = dict(engines)[spec]
+            extra = ""
+            if "attn" in kind.split("+"):      # the K / V bytes of the launch over its median time
+                kvb = eng.cfg.text.kv_bytes_per_token // eng.cfg.text.num_layers // (2 if eng.kv8 else 1)
+                extra = f"  {B * (ctx + 1) * kvb / 1e6:6.1f} MB of K/V: {B * (ctx + 1) * kvb / np.median(t) / 1e6:.2f} TB/s"
+            print(f"{spec:30s} ctx {ctx:5d} chain {kind:16s} median {np.median(t):8.2f} us per launch group  min {t.min():8.2f}  max {t.max():8.2f}{extra}",
+                  flush=True)
+    for g in graphs.values():
         L.kr_graph_destroy(g)
-        t = np.asarray(times[(spec, kind)])
-        eng = dict(engines)[spec]
-        extra = ""
-        if kind == "attn":      # the K / V bytes of the launch over its median time
-            kvb = eng.cfg.text.kv_bytes_per_token // eng.cfg.text.num_layers // (2 if eng.kv8 else 1)
-            extra = f"  {B * (a.ctx + 1) * kvb / 1e6:6.1f} MB of K/V: {B * (a.ctx + 1) * kvb / np.median(t) / 1e6:.2f} TB/s"
-        print(f"{spec:30s} chain {kind:16s} median {np.median(t):8.2f} us per launch group  min {t.min():8.2f}  max {t.max():8.2f}{extra}", flush=True)
 
 if __name__ == "__main__":
     main()
