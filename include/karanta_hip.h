@@ -39,7 +39,7 @@ typedef uint16_t kr_bf16;
 /* kr_version() of the library this header describes: major * 100 + minor.  The major changes with every incompatible
  * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family); a caller built
  * against major X must refuse a library whose kr_version() / 100 != X. */
-#define KR_ABI_VERSION 411
+#define KR_ABI_VERSION 412
 
 #define KR_OK 0
 #define KR_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -555,6 +555,27 @@ int kr_gumbel_argmax_processed(const float* logits, int64_t ld_logits, int vocab
 int kr_sample_count(const int32_t* tokens, const int32_t* live, int32_t* counts, int64_t ld_counts, int vocab, int batch,
                     kr_stream s);
 
+/* The two launches above over the rows of a speculative step (kr_spec).  Row r belongs to slot row_slot[r] (clamped to
+ * 0..slots-1) and depth[r] drafts of that slot lie in front of it (kr_spec_controls_rows; clamped to 0..k): params, counts and
+ * prompt_bits are read at the SLOT, [slots] rows of them, and the count of token i is counts[slot][i] + #{e < depth[r] :
+ * draft_tok[slot * k + e] == i} — the output so far of a row whose drafts were all accepted.  Everything else is per row, `batch` =
+ * rows entries: logits, temperature, seed, ctx_len, prompt_len, guide_masks / guide_state, finished, work, threshold, live and the
+ * partials.  The contract of a row is equality: threshold, partials (value bits and index) are those of kr_sample_threshold /
+ * kr_gumbel_argmax_processed on a one-row batch that holds the slot's params and prompt bits and the counts above; a row at depth 0
+ * or of a slot without penalties never looks at draft_tok.  1 <= slots <= batch <= 32, 1 <= k < 32. */
+int kr_sample_threshold_rows(const float* logits, int64_t ld_logits, int vocab, const float* temperature, const float* params,
+                             const int32_t* counts, int64_t ld_counts, const uint32_t* prompt_bits, int bits_words,
+                             const uint64_t* guide_masks, const int32_t* guide_state, int mask_words, const int32_t* finished,
+                             int ignore_eos, float* work, int64_t ld_work, uint32_t* threshold, int32_t* live, int batch,
+                             const int32_t* row_slot, const int32_t* depth, const int32_t* draft_tok, int k, int slots, kr_stream s);
+int kr_gumbel_argmax_processed_rows(const float* logits, int64_t ld_logits, int vocab, const float* temperature,
+                                    const uint32_t* seed, const int32_t* ctx_len, const int32_t* prompt_len, float* amax_val,
+                                    int32_t* amax_idx, int n_part, int batch, const uint64_t* guide_masks,
+                                    const int32_t* guide_state, int mask_words, int fallback_token, const float* params,
+                                    const int32_t* counts, int64_t ld_counts, const uint32_t* prompt_bits, int bits_words,
+                                    const uint32_t* threshold, const int32_t* row_slot, const int32_t* depth,
+                                    const int32_t* draft_tok, int k, int slots, kr_stream s);
+
 /* ------------------------------------------------------------------ per-request logit adjustments (vLLM's logit_bias,
  * min_tokens and stop_token_ids).  Per row b a table of adj_meta[b * 4 + 0] = n_entries <= KR_ADJ_CAP entries, every token id
  * at most once in a row (the host merges bias keys, stop ids and the model's EOS ids); entry e of row b, at
@@ -571,6 +592,15 @@ int kr_sample_count(const int32_t* tokens, const int32_t* live, int32_t* counts,
 int kr_logits_adjust(float* logits, int64_t ld_logits, int vocab, const int32_t* adj_ids, const float* adj_val,
                      const int32_t* adj_flag, const int32_t* adj_meta, const int32_t* ctx_len, const int32_t* prompt_len,
                      float* saved, int batch, kr_stream s);
+
+/* kr_logits_adjust over the rows of a speculative step: row r is adjusted with the table of slot row_slot[r] (clamped to
+ * 0..slots-1; the tables hold [slots] rows) at the row's own n = ctx_len[r] + 1 - prompt_len[r]; logits, ctx_len, prompt_len and
+ * saved are per row (`batch` = rows entries).  The adjusted row equals kr_logits_adjust's on a one-row batch with that table.  A
+ * speculative step has no kr_logits_restore: nothing reads the logits behind the token choice there (log-probabilities keep a
+ * step plain), and the next lm_head launch overwrites them. */
+int kr_logits_adjust_rows(float* logits, int64_t ld_logits, int vocab, const int32_t* adj_ids, const float* adj_val,
+                          const int32_t* adj_flag, const int32_t* adj_meta, const int32_t* ctx_len, const int32_t* prompt_len,
+                          float* saved, int batch, const int32_t* row_slot, int slots, kr_stream s);
 
 /* After the sampler: logits[b][id] = saved[b][e] for every entry — the buffer equals what the lm_head wrote, bit for bit
  * (kr_logprobs_topk and returned logits report the unadjusted values). */
@@ -816,6 +846,40 @@ int kr_spec_guide_rows(const kr_spec* a, const kr_spec_guide* g, const int32_t* 
  * tokens the step emitted (read from `history`), except the last one where the step set finished (kr_guide_advance skips the rows
  * kr_sample_greedy has just finished): the state e plain guided steps leave. */
 int kr_spec_guide_advance(const kr_spec* a, const kr_spec_guide* g, kr_stream s);
+
+/* Controlled slots in a speculative step: sampling controls (kr_sample_threshold_rows / kr_gumbel_argmax_processed_rows) and logit
+ * adjustments (kr_logits_adjust_rows) on draft rows.  Row (slot, j) chooses t_j, which counts only if drafts 1..j were accepted: its
+ * output so far is the slot's plus d_1..d_j.  Params, prompt bits and the adjustment table are the slot's; min_tokens needs nothing,
+ * n = ctx_len + 1 - prompt_len is per row already; the output counts take in the drafts in front of the row (depth); the stop entries
+ * are kept out of the drafts, because kr_spec_accept knows the EOS ids only.  Three launches of integer work around the step, in
+ * either layout, beside kr_spec_guide_*'s (both trims may run: each only lowers the count). */
+typedef struct kr_spec_controls {
+    const int32_t* adj_ids;            /* [slots][KR_ADJ_CAP] the slots' adjustment tables (kr_logits_adjust) */
+    const int32_t* adj_flag;
+    const int32_t* adj_meta;           /* [slots][4] */
+    int32_t* counts;                   /* [slots][ld_counts] output-token counts (kr_sample_count's) */
+    int64_t ld_counts;                 /* >= kr_spec.vocab */
+    int32_t* depth;                    /* [rows] drafts in front of the row: what the _rows launches take */
+    int32_t* ctx_before;               /* [slots] scratch: ctx_len at the start of the step (kr_spec_guide.ctx_before may be the same array) */
+} kr_spec_controls;
+
+/* Before any row is spent on a draft; n_count as for kr_spec_guide_trim (n_draft behind kr_spec_propose, n_want between kr_spec_lookup
+ * and kr_spec_deal).  Per slot: ctx_before = ctx_len, always.  A finished slot, or one whose table is empty, keeps its count and its
+ * drafts.  Otherwise the count is cut to j - 1 at the first draft j that is a stop entry (adj_flag bit 0) of the slot's table, whatever
+ * min_tokens says, and draft_tok at and beyond the new count becomes pad_id.  Then a stop token can only be the last token the step
+ * emits, and kr_stop_tokens over tokens_out behind kr_spec_accept / kr_spec_accept_rows finishes the slot as in a plain step. */
+int kr_spec_controls_trim(const kr_spec* a, const kr_spec_controls* c, int32_t* n_count, kr_stream s);
+
+/* After the trims (static layout, draft_row == NULL) or after kr_spec_deal (draft_row: its map).  depth[r] for every row r < rows: j
+ * for the row of draft (slot, j) with j <= n_draft[slot], 0 for every other row (a slot's own, inactive, parked, padding).  Static
+ * layout only: a row (slot, j) with j > n_draft[slot] also gets finished = 1, as from kr_spec_guide_rows. */
+int kr_spec_controls_rows(const kr_spec* a, const kr_spec_controls* c, const int32_t* draft_row, kr_stream s);
+
+/* After kr_spec_accept / kr_spec_accept_rows (and kr_stop_tokens).  Per slot: counts[slot][t] += 1 for each of the e = ctx_len -
+ * ctx_before tokens the step emitted (0 <= e <= k + 1, read from `history`), a finishing EOS or stop token included — a plain step
+ * counts it too (kr_sample_threshold's live is taken before the token).  A finished slot frozen in place has e = 0 (speculative
+ * steps run under the freeze bit). */
+int kr_spec_controls_count(const kr_spec* a, const kr_spec_controls* c, kr_stream s);
 
 /* ------------------------------------------------------------------ runaway repetition (vLLM's repetition_detection)
  * The rule is a function of a sequence's generated tokens y[0..g] alone (the prompt never counts).  Per slot the cfg row holds

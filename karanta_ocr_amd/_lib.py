@@ -83,8 +83,13 @@ SIGNATURES = {
     "kr_sample_threshold": [c_p, i64, i32, c_p, c_p, c_p, i64, c_p, i32, c_p, c_p, i32, c_p, i32, c_p, i64, c_p, c_p, i32, c_p],
     "kr_gumbel_argmax_processed": [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, c_p, c_p, i32, i32, c_p, c_p, i64, c_p,
                                    i32, c_p, c_p],
+    "kr_sample_threshold_rows": [c_p, i64, i32, c_p, c_p, c_p, i64, c_p, i32, c_p, c_p, i32, c_p, i32, c_p, i64, c_p, c_p, i32, c_p, c_p,
+                                 c_p, i32, i32, c_p],
+    "kr_gumbel_argmax_processed_rows": [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, c_p, c_p, i32, i32, c_p, c_p, i64, c_p,
+                                        i32, c_p, c_p, c_p, c_p, i32, i32, c_p],
     "kr_sample_count": [c_p, c_p, c_p, i64, i32, i32, c_p],
     "kr_logits_adjust": [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p],
+    "kr_logits_adjust_rows": [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p, i32, c_p],
     "kr_logits_restore": [c_p, i64, i32, c_p, c_p, c_p, i32, c_p],
     "kr_stop_tokens": [c_p, c_p, c_p, c_p, c_p, i32, i32, c_p],
     "kr_guide_advance": [c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, c_p],
@@ -104,6 +109,9 @@ SIGNATURES = {
     "kr_spec_guide_trim": [c_p, c_p, c_p, c_p],
     "kr_spec_guide_rows": [c_p, c_p, c_p, c_p],
     "kr_spec_guide_advance": [c_p, c_p, c_p],
+    "kr_spec_controls_trim": [c_p, c_p, c_p, c_p],
+    "kr_spec_controls_rows": [c_p, c_p, c_p, c_p],
+    "kr_spec_controls_count": [c_p, c_p, c_p],
     "kr_repeat_detect": [c_p, c_p],
     "kr_linear_decode32_rows": [i32, c_p, c_p, c_p],
     "kr_attn_decode_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
@@ -177,6 +185,13 @@ class SpecGuide(C.Structure):
     """kr_spec_guide (include/karanta_hip.h): the guides of a speculative step's rows and the scratch of its three launches."""
     _fields_ = [("guide_trans", c_p), ("guide_masks", c_p), ("guide_state", c_p), ("mask_words", C.c_int32), ("vocab_off", c_p),
                 ("vocab_bytes", c_p), ("draft_state", c_p), ("ctx_before", c_p)]
+
+
+class SpecControls(C.Structure):
+    """kr_spec_controls (include/karanta_hip.h): the slots' adjustment tables and output counts, the rows' depths and the scratch of
+    the three launches that let controlled requests take part in a speculative step."""
+    _fields_ = [("adj_ids", c_p), ("adj_flag", c_p), ("adj_meta", c_p), ("counts", c_p), ("ld_counts", C.c_int64), ("depth", c_p),
+                ("ctx_before", c_p)]
 
 
 REP_MAX_PERIOD = 1024                   # KR_REP_MAX_PERIOD

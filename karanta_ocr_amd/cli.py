@@ -85,8 +85,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "\"prompt_lookup_max\": 4} — prompt-lookup drafts verified K at a time, the same tokens as without it "
                          "(--max-num-seqs x (K + 1) <= 32, or with \"share_rows\": true any --max-num-seqs up to 31: the rows of a "
                          "step the sequences leave free are dealt to the drafts; with \"guided\": true requests with guided_regex / "
-                         "response_format speculate too, their drafts checked against the pattern; not with --max-logprobs or "
-                         "--static-batching)")
+                         "response_format speculate too, their drafts checked against the pattern; with \"controls\": true so do "
+                         "requests with top_k / top_p / min_p, penalties, logit_bias, min_tokens or stop_token_ids; not with "
+                         "--max-logprobs or --static-batching)")
     ap.add_argument("--repetition-detection", default=None,
                     help="the default of the requests without a repetition_detection field, as JSON: {\"max_pattern_size\": B, "
                          "\"min_pattern_size\": A, \"min_count\": C, \"min_span\": M} — a sequence whose last C x p tokens are C "
@@ -165,6 +166,21 @@ def speculative_guided(text: str) -> bool:
     return guided
 
 
+def speculative_controls(text: str) -> bool:
+    """SpecConfig.controls from --speculative-config: the key "controls", true or false (absent: false); ValueError with the reason."""
+    import json
+    try:
+        d = json.loads(text)
+    except ValueError as e:
+        raise ValueError(f"--speculative-config is not JSON: {e}") from e
+    if not isinstance(d, dict):
+        raise ValueError("--speculative-config must be a JSON object")
+    controls = d.get("controls", False)
+    if not isinstance(controls, bool):
+        raise ValueError(f"--speculative-config: controls must be true or false, not {controls!r}")
+    return controls
+
+
 def parse_args(argv: Optional[List[str]] = None):
     ap = build_parser()
     args, unknown = ap.parse_known_args(argv)
@@ -185,7 +201,7 @@ def parse_args(argv: Optional[List[str]] = None):
         ap.error("--max-num-seqs must be in 1..32 (above 16: hidden_size <= 2048 or == 3584)")
     if args.max_num_batched_tokens is not None and args.max_num_batched_tokens < args.max_model_len:
         ap.error("--max-num-batched-tokens must be >= --max-model-len (the longest prompt one request may carry)")
-    args.speculative, args.speculative_share_rows, args.speculative_guided = None, False, False
+    args.speculative, args.speculative_share_rows, args.speculative_guided, args.speculative_controls = None, False, False, False
     if args.speculative_config is not None:
         if args.max_logprobs is not None:
             ap.error("--speculative-config cannot be combined with --max-logprobs: a draft row records no log-probabilities")
@@ -195,6 +211,7 @@ def parse_args(argv: Optional[List[str]] = None):
             *spec, args.speculative_share_rows = speculative_fields(args.speculative_config, args.max_num_seqs)
             args.speculative = tuple(spec)
             args.speculative_guided = speculative_guided(args.speculative_config)
+            args.speculative_controls = speculative_controls(args.speculative_config)
         except ValueError as e:
             ap.error(str(e))
     args.repetition = None
@@ -282,10 +299,12 @@ def make_server(args, log=print):
     # with launch-ahead) + the parking row
     spec, share = getattr(args, "speculative", None), bool(getattr(args, "speculative_share_rows", False))
     spec_guided = bool(getattr(args, "speculative_guided", False))
+    spec_controls = bool(getattr(args, "speculative_controls", False))
     if spec is not None:
         log(f"speculative decoding: ngram, {spec[0]} draft tokens per step, prompt lookup {spec[1]}..{spec[2]}"
             + (", draft rows shared between the sequences" if share else "")
-            + (", guided requests included" if spec_guided else ""))
+            + (", guided requests included" if spec_guided else "")
+            + (", requests with sampling controls or logit adjustments included" if spec_controls else ""))
     # ... speculative: every step past the limit may emit K + 1 tokens, and the draft rows write K cache rows ahead
     slack = 1 + 16 * (spec[0] + 1 if spec else 1) + (spec[0] if spec else 0)
     kv_fp8 = kv_cache_dtype_name(getattr(args, "kv_cache_dtype", "auto")) == "fp8"
@@ -298,7 +317,7 @@ def make_server(args, log=print):
                  max_patches=max_patches, max_prompt_tokens=max_prompt_tokens,
                  weight_dtype=weight_dtype, fp8_activations=bool(getattr(args, "fp8_activations", False)) or None,
                  kv_cache_dtype=getattr(args, "kv_cache_dtype", "auto"), **calc,
-                 **({"speculative": SpecConfig(*spec, share_rows=share, guided=spec_guided)} if spec else {}))
+                 **({"speculative": SpecConfig(*spec, share_rows=share, guided=spec_guided, controls=spec_controls)} if spec else {}))
     # one server: read the checkpoint.  A launch.py group: rank 0 reads it ONCE, the arena goes to the other GPUs over
     # RCCL / xGMI (north_star: "RCCL broadcast of weights over xGMI"); a failure stops every server of the group
     info = load_or_receive_weights(eng.w, rank, world, lambda: eng.load_weights(load_checkpoint(args.model_dir)[1]),

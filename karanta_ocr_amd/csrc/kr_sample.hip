@@ -3,6 +3,8 @@
 //   gumbel_argmax_kernel  temperature sampling as an argmax (Gumbel-max) over the logits, guide mask applied
 //   sample_threshold_kernel / gumbel_argmax_proc_kernel / sample_count_kernel  vLLM's sampling controls (top_k, top_p,
 //                         min_p, repetition / frequency / presence penalties) around the same argmax; DESIGN.md §5c
+//   <..., ROWS>           the same two bodies over the rows of a speculative step (ROWS): params, counts and prompt bits are those
+//                         of the row's slot, and the counts take in the drafts in front of the row; DESIGN.md §5o
 //   sample_greedy_kernel  final argmax over the partials, token history, EOS bookkeeping, next-token embedding gather,
 //                         context advance.  (The rotary table of every decode position is built once per request on the host.)
 #include "kr_decode_common.h"
@@ -67,6 +69,38 @@ __device__ __forceinline__ float kr_penalise(float l, uint32_t in_prompt, int c,
     const float cf = (float)c;
     const float sub = freq * cf + pres * (c > 0 ? 1.0f : 0.0f);
     return l - sub;
+}
+
+// A row of a speculative step (ROWS): the sampler state of a row is its slot's, and its output so far is the slot's plus the drafts
+// d_1..d_depth in front of it (draft_tok [slots][k]).  nx = how many of them the penalties have to look at: 0 for a slot's own
+// row, a parked row and a row without penalties, so those run the loop-free expression.  Everything here is uniform per workgroup.
+struct SpecRow {
+    int slot, nx;
+    const int32_t* dt;
+};
+
+template <bool ROWS>
+__device__ __forceinline__ int kr_row_slot(int b, const int32_t* row_slot, int slots) {
+    return ROWS ? min(max(row_slot[b], 0), slots - 1) : b;      // (a corrupt map cannot reach past the slots' arrays)
+}
+
+template <bool ROWS>
+__device__ __forceinline__ SpecRow kr_spec_row(int b, bool pen, const int32_t* row_slot, const int32_t* depth,
+                                               const int32_t* draft_tok, int k, int slots) {
+    SpecRow r{b, 0, nullptr};
+    if constexpr (ROWS) {
+        r.slot = kr_row_slot<ROWS>(b, row_slot, slots);
+        r.nx = pen ? min(max(depth[b], 0), k) : 0;
+        r.dt = draft_tok + (int64_t)r.slot * k;
+    }
+    return r;
+}
+
+// the count of token i in the row's output so far: the slot's, plus the drafts in front of the row that are token i
+__device__ __forceinline__ int kr_row_count(const int32_t* cnt, int i, const SpecRow& r) {
+    int c = cnt[i];
+    for (int e = 0; e < r.nx; ++e) c += (r.dt[e] == i) ? 1 : 0;
+    return c;
 }
 
 __device__ __forceinline__ unsigned long long wave_incl_scan_u64(unsigned long long x, int lane) {
@@ -168,6 +202,10 @@ __device__ uint32_t radix_select(const float* __restrict__ w, int vocab, uint32_
 // v_max, then the min_p / top_k / top_p threshold key -> thr[b] (0: keep every allowed token).  Rows with T == 0 or
 // neutral truncation stop after writing 0.  live[b]: whether kr_sample_greedy appends a real token to this row in this
 // step (not a finished row's pad token) — what kr_sample_count counts.
+// ROWS (kr_sample_threshold_rows): b is a row of a speculative step; logits, temperature, guide, finished, work, thr and live are per
+// row, params / counts / prompt_bits per slot (kr_spec_row).  One kernel template, as dec32_kernel<..., ROWS>: the plain launch
+// passes null for the row map and compiles to the code it had without it.
+template <bool ROWS>
 __global__ void __launch_bounds__(SEL_T) sample_threshold_kernel(const float* __restrict__ logits, int64_t ld, int vocab,
                                                                  const float* __restrict__ temperature,
                                                                  const float* __restrict__ params,
@@ -177,12 +215,16 @@ __global__ void __launch_bounds__(SEL_T) sample_threshold_kernel(const float* __
                                                                  const int32_t* __restrict__ guide_state, int mask_words,
                                                                  const int32_t* __restrict__ finished, int ignore_eos,
                                                                  float* __restrict__ work, int64_t ld_work,
-                                                                 uint32_t* __restrict__ thr, int32_t* __restrict__ live) {
+                                                                 uint32_t* __restrict__ thr, int32_t* __restrict__ live,
+                                                                 const int32_t* __restrict__ row_slot,
+                                                                 const int32_t* __restrict__ depth,
+                                                                 const int32_t* __restrict__ draft_tok, int k, int slots) {
     __shared__ unsigned long long hist[2048];
     __shared__ unsigned long long s_misc[4];
     __shared__ float s_m[SEL_T / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* prm = params + (int64_t)b * KR_SP_STRIDE;
+    const int sl = kr_row_slot<ROWS>(b, row_slot, slots);
+    const float* prm = params + (int64_t)sl * KR_SP_STRIDE;
     if (tid == 0) live[b] = ((ignore_eos & 1) != 0 || finished[b] == 0) ? 1 : 0;
     const float T = temperature[b];
     const int top_k = (int)prm[0];
@@ -195,9 +237,10 @@ __global__ void __launch_bounds__(SEL_T) sample_threshold_kernel(const float* __
     const float inv_t = 1.0f / T;
     const bool pen = kr_sp_penalised(prm);
     const float rep = prm[3], freq = prm[4], pres = prm[5];
+    const SpecRow sr = kr_spec_row<ROWS>(b, pen, row_slot, depth, draft_tok, k, slots);
     const float* row = logits + (int64_t)b * ld;
-    const int32_t* cnt = counts + (int64_t)b * ld_counts;
-    const uint32_t* pb = prompt_bits + (int64_t)b * bits_words;
+    const int32_t* cnt = counts + (int64_t)sl * ld_counts;
+    const uint32_t* pb = prompt_bits + (int64_t)sl * bits_words;
     float* wr = work + (int64_t)b * ld_work;
     const uint32_t* allow = kr_guide_row(guide_masks, guide_state, mask_words, b);
     float m = -INFINITY;
@@ -205,7 +248,7 @@ __global__ void __launch_bounds__(SEL_T) sample_threshold_kernel(const float* __
         float v = -INFINITY;
         if (allow == nullptr || ((allow[i >> 5] >> (i & 31)) & 1u)) {
             float lp = row[i];
-            if (pen) lp = kr_penalise(lp, (pb[i >> 5] >> (i & 31)) & 1u, cnt[i], rep, freq, pres);
+            if (pen) lp = kr_penalise(lp, (pb[i >> 5] >> (i & 31)) & 1u, kr_row_count(cnt, i, sr), rep, freq, pres);
             v = lp * inv_t;
         }
         wr[i] = v;
@@ -240,13 +283,15 @@ __global__ void __launch_bounds__(SEL_T) sample_threshold_kernel(const float* __
 // One body for both launches.  PROC (gumbel_argmax_proc_kernel) adds the penalties and the truncation threshold of
 // sample_threshold_kernel; a row with neutral parameters (no penalty, threshold 0) runs the value expression of the plain
 // launch and gets its partials bit for bit.
-template <bool PROC>
+template <bool PROC, bool ROWS = false>
 __device__ __forceinline__ void gumbel_argmax_body(const float* logits, int64_t ld, int vocab, const float* temperature,
                                                    const unsigned* seed, const int32_t* ctx_len, const int32_t* prompt_len,
                                                    float* amax_val, int32_t* amax_idx, const uint64_t* guide_masks,
                                                    const int32_t* guide_state, int mask_words, int fallback_token,
                                                    const float* params, const int32_t* counts, int64_t ld_counts,
-                                                   const uint32_t* prompt_bits, int bits_words, const uint32_t* thr) {
+                                                   const uint32_t* prompt_bits, int bits_words, const uint32_t* thr,
+                                                   const int32_t* row_slot = nullptr, const int32_t* depth = nullptr,
+                                                   const int32_t* draft_tok = nullptr, int k = 0, int slots = 0) {
     __shared__ float s_v[4];
     __shared__ int s_i[4];
     const int p = blockIdx.x, n_part = gridDim.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -261,13 +306,16 @@ __device__ __forceinline__ void gumbel_argmax_body(const float* logits, int64_t 
     const int32_t* cnt = nullptr;
     const uint32_t* pb = nullptr;
     uint32_t th = 0u;
+    SpecRow sr{b, 0, nullptr};
     if constexpr (PROC) {
-        const float* prm = params + (int64_t)b * KR_SP_STRIDE;
+        const int sl = kr_row_slot<ROWS>(b, row_slot, slots);     // (ROWS: params, counts and prompt bits are the slot's, thr is the row's)
+        const float* prm = params + (int64_t)sl * KR_SP_STRIDE;
         pen = kr_sp_penalised(prm);
         rep = prm[3], freq = prm[4], pres = prm[5];
-        cnt = counts + (int64_t)b * ld_counts;
-        pb = prompt_bits + (int64_t)b * bits_words;
+        cnt = counts + (int64_t)sl * ld_counts;
+        pb = prompt_bits + (int64_t)sl * bits_words;
         th = T > 0.f ? thr[b] : 0u;    // greedy rows: truncation cannot move the argmax
+        sr = kr_spec_row<ROWS>(b, pen, row_slot, depth, draft_tok, k, slots);
     }
     const uint32_t* allow = kr_guide_row(guide_masks, guide_state, mask_words, b);
     float bv = -INFINITY;
@@ -275,7 +323,7 @@ __device__ __forceinline__ void gumbel_argmax_body(const float* logits, int64_t 
     for (int i = i0 + tid; i < i1; i += 256) {
         if (allow != nullptr && !((allow[i >> 5] >> (i & 31)) & 1u)) continue;
         float lp = row[i];
-        if (PROC && pen) lp = kr_penalise(lp, (pb[i >> 5] >> (i & 31)) & 1u, cnt[i], rep, freq, pres);
+        if (PROC && pen) lp = kr_penalise(lp, (pb[i >> 5] >> (i & 31)) & 1u, kr_row_count(cnt, i, sr), rep, freq, pres);
         float v = lp * inv_t;
         if (PROC && th != 0u && kr_fkey(v) < th) continue;
         if (T > 0.f) v += kr_gumbel_noise(base, i);
@@ -329,6 +377,18 @@ __global__ void __launch_bounds__(256) gumbel_argmax_proc_kernel(const float* __
                                                                  const uint32_t* __restrict__ thr) {
     gumbel_argmax_body<true>(logits, ld, vocab, temperature, seed, ctx_len, prompt_len, amax_val, amax_idx, guide_masks,
                              guide_state, mask_words, fallback_token, params, counts, ld_counts, prompt_bits, bits_words, thr);
+}
+
+__global__ void __launch_bounds__(256) gumbel_argmax_proc_rows_kernel(
+    const float* __restrict__ logits, int64_t ld, int vocab, const float* __restrict__ temperature, const unsigned* __restrict__ seed,
+    const int32_t* __restrict__ ctx_len, const int32_t* __restrict__ prompt_len, float* __restrict__ amax_val,
+    int32_t* __restrict__ amax_idx, const uint64_t* __restrict__ guide_masks, const int32_t* __restrict__ guide_state, int mask_words,
+    int fallback_token, const float* __restrict__ params, const int32_t* __restrict__ counts, int64_t ld_counts,
+    const uint32_t* __restrict__ prompt_bits, int bits_words, const uint32_t* __restrict__ thr, const int32_t* __restrict__ row_slot,
+    const int32_t* __restrict__ depth, const int32_t* __restrict__ draft_tok, int k, int slots) {
+    gumbel_argmax_body<true, true>(logits, ld, vocab, temperature, seed, ctx_len, prompt_len, amax_val, amax_idx, guide_masks,
+                                   guide_state, mask_words, fallback_token, params, counts, ld_counts, prompt_bits, bits_words, thr,
+                                   row_slot, depth, draft_tok, k, slots);
 }
 
 // after kr_sample_greedy: counts[b][tokens[b]] += 1 where live[b] (sample_threshold_kernel)
@@ -465,9 +525,10 @@ extern "C" int kr_sample_threshold(const float* logits, int64_t ld_logits, int v
                  batch > 0, "kr_sample_threshold: bad sizes");
     KR_CHECK_ARG(guide_masks == nullptr || (guide_state != nullptr && (int64_t)mask_words * 32 >= vocab),
                  "kr_sample_threshold: guide_state missing or mask_words * 32 < vocab");
-    sample_threshold_kernel<<<batch, SEL_T, 0, kr_hs(s)>>>(logits, ld_logits, vocab, temperature, params, counts, ld_counts,
-                                                           prompt_bits, bits_words, guide_masks, guide_state, mask_words, finished,
-                                                           ignore_eos, work, ld_work, threshold, live);
+    sample_threshold_kernel<false><<<batch, SEL_T, 0, kr_hs(s)>>>(logits, ld_logits, vocab, temperature, params, counts, ld_counts,
+                                                                  prompt_bits, bits_words, guide_masks, guide_state, mask_words,
+                                                                  finished, ignore_eos, work, ld_work, threshold, live, nullptr,
+                                                                  nullptr, nullptr, 0, 0);
     KR_CHECK_LAUNCH();
     return KR_OK;
 }
@@ -489,6 +550,58 @@ extern "C" int kr_gumbel_argmax_processed(const float* logits, int64_t ld_logits
                                                                          prompt_len, amax_val, amax_idx, guide_masks, guide_state,
                                                                          mask_words, fallback_token, params, counts, ld_counts,
                                                                          prompt_bits, bits_words, threshold);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+// Host-side checks of the row map of the two _rows entry points: the map itself lives on the device (kr_spec_controls_rows wrote the
+// depths, kr_spec_propose / kr_spec_deal the slots), so only its shape is checked here; the kernels clamp the depth to [0, k].
+#define KR_CHECK_ROW_MAP(who)                                                                                                 \
+    do {                                                                                                                      \
+        KR_CHECK_ARG(row_slot && depth && draft_tok, who ": null row_slot / depth / draft_tok");                              \
+        KR_CHECK_ARG(slots >= 1 && slots <= batch && batch <= 32 && k >= 1 && k < 32, who ": slots=%d rows=%d k=%d "          \
+                     "(1 <= slots <= rows <= 32, 1 <= k < 32)", slots, batch, k);                                             \
+    } while (0)
+
+extern "C" int kr_sample_threshold_rows(const float* logits, int64_t ld_logits, int vocab, const float* temperature, const float* params,
+                                        const int32_t* counts, int64_t ld_counts, const uint32_t* prompt_bits, int bits_words,
+                                        const uint64_t* guide_masks, const int32_t* guide_state, int mask_words,
+                                        const int32_t* finished, int ignore_eos, float* work, int64_t ld_work, uint32_t* threshold,
+                                        int32_t* live, int batch, const int32_t* row_slot, const int32_t* depth,
+                                        const int32_t* draft_tok, int k, int slots, kr_stream s) {
+    KR_CHECK_ARG(logits && temperature && params && counts && prompt_bits && finished && work && threshold && live,
+                 "kr_sample_threshold_rows: null pointer");
+    KR_CHECK_ARG(vocab > 0 && ld_logits >= vocab && ld_counts >= vocab && ld_work >= vocab && (int64_t)bits_words * 32 >= vocab &&
+                 batch > 0, "kr_sample_threshold_rows: bad sizes");
+    KR_CHECK_ARG(guide_masks == nullptr || (guide_state != nullptr && (int64_t)mask_words * 32 >= vocab),
+                 "kr_sample_threshold_rows: guide_state missing or mask_words * 32 < vocab");
+    KR_CHECK_ROW_MAP("kr_sample_threshold_rows");
+    sample_threshold_kernel<true><<<batch, SEL_T, 0, kr_hs(s)>>>(logits, ld_logits, vocab, temperature, params, counts, ld_counts,
+                                                                 prompt_bits, bits_words, guide_masks, guide_state, mask_words,
+                                                                 finished, ignore_eos, work, ld_work, threshold, live, row_slot, depth,
+                                                                 draft_tok, k, slots);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_gumbel_argmax_processed_rows(const float* logits, int64_t ld_logits, int vocab, const float* temperature,
+                                               const uint32_t* seed, const int32_t* ctx_len, const int32_t* prompt_len,
+                                               float* amax_val, int32_t* amax_idx, int n_part, int batch, const uint64_t* guide_masks,
+                                               const int32_t* guide_state, int mask_words, int fallback_token, const float* params,
+                                               const int32_t* counts, int64_t ld_counts, const uint32_t* prompt_bits, int bits_words,
+                                               const uint32_t* threshold, const int32_t* row_slot, const int32_t* depth,
+                                               const int32_t* draft_tok, int k, int slots, kr_stream s) {
+    KR_CHECK_ARG(logits && temperature && seed && ctx_len && prompt_len && amax_val && amax_idx && params && counts && prompt_bits &&
+                 threshold, "kr_gumbel_argmax_processed_rows: null pointer");
+    KR_CHECK_ARG(vocab > 0 && ld_logits >= vocab && ld_counts >= vocab && (int64_t)bits_words * 32 >= vocab && n_part > 0 &&
+                 n_part <= 65535 && batch > 0, "kr_gumbel_argmax_processed_rows: bad sizes");
+    KR_CHECK_ARG(guide_masks == nullptr || (guide_state != nullptr && (int64_t)mask_words * 32 >= vocab),
+                 "kr_gumbel_argmax_processed_rows: guide_state missing or mask_words * 32 < vocab");
+    KR_CHECK_ARG(fallback_token >= 0 && fallback_token < vocab, "kr_gumbel_argmax_processed_rows: fallback_token out of vocabulary");
+    KR_CHECK_ROW_MAP("kr_gumbel_argmax_processed_rows");
+    gumbel_argmax_proc_rows_kernel<<<dim3(n_part, batch), 256, 0, kr_hs(s)>>>(
+        logits, ld_logits, vocab, temperature, seed, ctx_len, prompt_len, amax_val, amax_idx, guide_masks, guide_state, mask_words,
+        fallback_token, params, counts, ld_counts, prompt_bits, bits_words, threshold, row_slot, depth, draft_tok, k, slots);
     KR_CHECK_LAUNCH();
     return KR_OK;
 }

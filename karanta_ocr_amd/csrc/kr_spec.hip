@@ -13,6 +13,9 @@
 //   spec_accept_kernel   with a map: draft j of a slot is verified on row draft_row[slot * k + j - 1].
 // Guided slots (kr_spec_guide_trim -> kr_spec_guide_rows -> ... -> kr_spec_guide_advance, around either layout): the drafts a slot's
 // guide forbids are dropped, every draft row gets the DFA state behind its drafts, the slot's state follows the emitted tokens.
+// Controlled slots (kr_spec_controls_trim -> kr_spec_controls_rows -> ... -> kr_stop_tokens -> kr_spec_controls_count, around either
+// layout and beside the guide's three): a draft that is a stop entry of its slot ends the slot's drafts, every row learns how many
+// drafts lie in front of it (the sampler's row-mapped passes add them to the slot's output counts), the counts follow the emitted tokens.
 #include "kr_decode_common.h"
 #include "kr_spec_deal.h"
 
@@ -413,7 +416,106 @@ int spec_guide_check(const kr_spec* a, const kr_spec_guide* g, const char* who, 
     return KR_OK;
 }
 
+// ---------------------------------------------------------------- controlled slots in a speculative step (kr_spec_controls)
+// The sampler's per-slot state per draft: output counts and stop entries.  Integer work only.
+//   spec_controls_trim_kernel   per slot, before any row is spent: the drafts end in front of the first one that is a stop entry of
+//                               the slot's adjustment table, so a stop token can only be the LAST token a step emits and
+//                               kr_stop_tokens behind the verification finishes the slot as it does in a plain step.
+//   spec_controls_rows_kernel   ONE workgroup: depth[r] = how many drafts lie in front of row r (0: a slot's own row, a row nobody has).
+//   spec_controls_count_kernel  per slot, after the verification: counts[slot][t] += 1 over the tokens the step emitted.
+__global__ void __launch_bounds__(64) spec_controls_trim_kernel(const kr_spec a, const kr_spec_controls c, int32_t* __restrict__ n_count) {
+    const int slot = blockIdx.x, tid = threadIdx.x, K = a.k;
+    if (tid == 0) c.ctx_before[slot] = a.ctx_len[slot];
+    const int ne = min(max(c.adj_meta[slot * 4], 0), KR_ADJ_CAP);
+    if (ne == 0 || a.finished[slot]) return;          // (uniform per workgroup) the slot keeps its count and its drafts
+    const int n = max(0, min(K, n_count[slot]));
+    const int64_t t0 = (int64_t)slot * KR_ADJ_CAP;
+    int first = n;                                    // 0-based index of the first draft that is a stop entry
+    for (int e = tid; e < ne; e += 64) {
+        if ((c.adj_flag[t0 + e] & 1) == 0) continue;
+        const int id = c.adj_ids[t0 + e];
+        for (int j = 0; j < first; ++j)
+            if (a.draft_tok[slot * K + j] == id) first = j;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+    if (tid != 0 || first >= n) return;
+    n_count[slot] = first;
+    for (int j = first; j < K; ++j) a.draft_tok[slot * K + j] = a.pad_id;
+}
+
+// draft_row == nullptr: the static layout (draft j of a slot on row j * slots + slot); else the map kr_spec_deal wrote.  As in
+// spec_guide_rows_kernel every global write is indexed by a row taken from the thread index, never by a computed row.
+__global__ void __launch_bounds__(64) spec_controls_rows_kernel(const kr_spec a, const kr_spec_controls c,
+                                                                const int32_t* __restrict__ draft_row) {
+    __shared__ int s_owner[SPEC_MAX_ROWS];
+    const int tid = threadIdx.x, B = a.slots, K = a.k, R = a.rows;
+    if (tid < SPEC_MAX_ROWS) {
+        int e = -1;
+        if (draft_row == nullptr && tid >= B && tid < B * (K + 1)) e = (tid % B) * K + tid / B - 1;
+        s_owner[tid] = e;
+    }
+    __syncthreads();
+    if (draft_row != nullptr)
+        for (int e = tid; e < B * K; e += 64) {
+            const int r = draft_row[e];
+            if (r >= B && r < R) s_owner[r] = e;       // (rows are distinct: one writer per entry)
+        }
+    __syncthreads();
+    const int r = tid;
+    if (r >= R) return;
+    const int e = r < B ? -1 : s_owner[r];
+    const int slot = e < 0 ? 0 : e / K, j = e < 0 ? 0 : e - slot * K + 1;
+    const bool live = e >= 0 && j <= a.n_draft[slot];
+    c.depth[r] = live ? j : 0;
+    if (draft_row == nullptr && e >= 0 && !live) a.finished[r] = 1;     // kr_spec_propose ran before the trim
+}
+
+__global__ void __launch_bounds__(64) spec_controls_count_kernel(const kr_spec a, const kr_spec_controls c) {
+    const int slot = blockIdx.x;
+    if (threadIdx.x != 0) return;           // at most k + 1 tokens, and two of them may be one id: one thread adds them in turn
+    const int before = c.ctx_before[slot], plen = a.prompt_len[slot];
+    const int e = max(0, min(a.k + 1, a.ctx_len[slot] - before));      // (a frozen finished slot: 0)
+    for (int i = 0; i < e; ++i) {
+        const int h = before + 1 - plen + i;
+        if (h < 0 || h >= a.hist_rows) continue;
+        const int t = a.history[(int64_t)h * a.hist_stride + slot];
+        if (t >= 0 && t < a.vocab) c.counts[(int64_t)slot * c.ld_counts + t] += 1;
+    }
+}
+
+int spec_controls_check(const kr_spec* a, const kr_spec_controls* c, const char* who, bool shared_rows) {
+    if (const int rc = spec_check(a, who, shared_rows)) return rc;
+    KR_CHECK_ARG(c, "%s: null controls args", who);
+    KR_CHECK_ARG(c->adj_ids && c->adj_flag && c->adj_meta && c->counts && c->depth && c->ctx_before, "%s: null pointer in kr_spec_controls",
+                 who);
+    KR_CHECK_ARG(c->ld_counts >= a->vocab, "%s: ld_counts=%lld below the vocabulary", who, (long long)c->ld_counts);
+    return KR_OK;
+}
+
 }  // namespace
+
+extern "C" int kr_spec_controls_trim(const kr_spec* a, const kr_spec_controls* c, int32_t* n_count, kr_stream s) {
+    if (const int rc = spec_controls_check(a, c, "kr_spec_controls_trim", true)) return rc;
+    KR_CHECK_ARG(n_count, "kr_spec_controls_trim: null n_count");
+    spec_controls_trim_kernel<<<a->slots, 64, 0, kr_hs(s)>>>(*a, *c, n_count);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_spec_controls_rows(const kr_spec* a, const kr_spec_controls* c, const int32_t* draft_row, kr_stream s) {
+    if (const int rc = spec_controls_check(a, c, "kr_spec_controls_rows", draft_row != nullptr)) return rc;
+    spec_controls_rows_kernel<<<1, 64, 0, kr_hs(s)>>>(*a, *c, draft_row);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_spec_controls_count(const kr_spec* a, const kr_spec_controls* c, kr_stream s) {
+    if (const int rc = spec_controls_check(a, c, "kr_spec_controls_count", true)) return rc;
+    spec_controls_count_kernel<<<a->slots, 64, 0, kr_hs(s)>>>(*a, *c);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
 
 extern "C" int kr_spec_guide_trim(const kr_spec* a, const kr_spec_guide* g, int32_t* n_count, kr_stream s) {
     if (const int rc = spec_guide_check(a, g, "kr_spec_guide_trim", true)) return rc;

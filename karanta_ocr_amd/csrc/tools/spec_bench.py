@@ -27,6 +27,14 @@ Random weights (timing only), context about 1900, graphs replayed as the engine 
     _advance) over the guided plain step of the PARENT commit (--parent-tree; without it this tree's own guided plain step stands in
     and the file says so), in alternating child processes, and the same engine's unguided pair beside it.
 
+    python karanta_ocr_amd/csrc/tools/spec_bench.py --controls [--parent-tree DIR] [--out profiles/r08_spec_controls.json]
+
+  * --controls: the leg for SpecConfig(controls=True): the 2B decoder with 8 slots x K = 3 and with 24 slots on shared rows, every slot
+    with top_p and a repetition penalty, scripted full-acceptance drafts.  Per layout, in alternating child processes on this tree and
+    (--parent-tree) on the parent commit: the controlled plain step, the uncontrolled plain step and the uncontrolled speculative
+    step — the legs the parent can run; then, on this tree, the controlled speculative step (kr_spec_controls_trim / _rows / _count
+    and the three row-mapped logit passes) with t_spec / t_plain for controlled steps and its break-even.
+
 Every measurement is a child process under a time limit of its own; a child that fails ends the run."""
 import argparse
 import ctypes as C
@@ -49,14 +57,15 @@ def _token_bytes(i: int) -> bytes:
     return bytes(base + (i // 10 ** p) % 10 for p in range(3))
 
 
-def _engine(model, B, spec_k=0, share=False, guided=False):
+def _engine(model, B, spec_k=0, share=False, guided=False, controls=False):
     import torch
     from karanta_ocr_amd.config import CONFIGS
     from karanta_ocr_amd.engine import Engine
     kw = {}
     if spec_k:
         from karanta_ocr_amd.engine import SpecConfig
-        kw["speculative"] = (SpecConfig(spec_k, share_rows=share, guided=True) if guided
+        kw["speculative"] = (SpecConfig(spec_k, share_rows=share, controls=True) if controls
+                             else SpecConfig(spec_k, share_rows=share, guided=True) if guided
                              else SpecConfig(spec_k, share_rows=True) if share else SpecConfig(spec_k))
     n_new = STEPS * (ROUNDS + 3) * (spec_k + 1) + 16
     eng = Engine(CONFIGS[model], max_batch=B, s_max=(CTX + n_new + 128) // 64 * 64, max_patches=64, max_prompt_tokens=64, **kw)
@@ -91,6 +100,30 @@ def _guide_slots(eng, on=True):
     _reset(eng)
 
 
+TOP_P, REPETITION, TEMPERATURE = 0.9, 1.2, 0.8        # --controls: every slot's request
+
+
+def _control_slots(eng, on=True):
+    """Every slot with TOP_P and REPETITION at TEMPERATURE over a prompt bit set that holds every seventh token, or (off) the same
+    temperature without controls: the steps carry the Gumbel pass and, on, the threshold pass, the penalised argmax and the counts."""
+    import numpy as np
+    import torch
+    from karanta_ocr_amd.sampling import StepFeatures
+    B, sm, V = eng.B, eng.sampler, eng.cfg.text.vocab_size
+    eng.stream.synchronize()
+    eng._caps = eng._step = StepFeatures(True, False, bool(on), False)
+    row = np.asarray([0, TOP_P, 0, REPETITION, 0, 0, 0, 0] if on else [0, 1, 0, 1, 0, 0, 0, 0], np.float32)
+    sm.d_sp[:B].copy_(torch.from_numpy(np.tile(row, (B, 1))).to(eng.device))
+    bits = np.zeros(sm.bits_words, np.uint32)
+    ids = np.arange(0, V, 7)
+    np.bitwise_or.at(bits, ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
+    sm.d_pbits[:B].copy_(torch.from_numpy(np.tile(bits.view(np.int32), (B, 1))).to(eng.device))
+    eng.d_temp[:B].fill_(TEMPERATURE)
+    eng.d_seed[:B].copy_(torch.arange(1, B + 1, dtype=torch.int32, device=eng.device))
+    eng._controls = bool(on)
+    _reset(eng)
+
+
 def _reset(eng):
     import torch
     with torch.cuda.stream(eng.stream):
@@ -98,6 +131,8 @@ def _reset(eng):
         eng.d_plen.fill_(CTX)
         eng.d_fin.zero_()
         eng.d_x[:eng.B].copy_(eng._x0)
+        if getattr(eng, "_controls", False):       # the output counts start from an empty output, as the recorded continuation did
+            eng.sampler.d_counts.zero_()
         if getattr(eng, "_guide", None) is not None:
             eng.sampler.d_gstate[:eng.B].fill_(eng._guide.start)
     eng.stream.synchronize()
@@ -315,6 +350,44 @@ def child_guided(model, B, K):
     return out
 
 
+def child_controls_plain(model, B):
+    """The uncontrolled and the controlled plain step on an engine without `speculative`: uses nothing the parent commit lacks."""
+    import numpy as np
+    eng = _engine(model, B)
+    out = {}
+    for name, on in (("uncontrolled", False), ("controlled", True)):
+        _control_slots(eng, on)
+        ts = _time(eng, _plain_graph(eng))
+        out[name] = {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "rounds_ms": [round(t, 5) for t in ts]}
+    eng.close()
+    return out
+
+
+def child_pair(model, B, K, share):
+    """The uncontrolled plain and speculative steps (temperature alone) at scripted full acceptance on SpecConfig(K[, share_rows]):
+    uses nothing the parent commit lacks."""
+    eng = _engine(model, B, K, share)
+    _control_slots(eng, False)
+    r = _full_acceptance_pair(eng, K)
+    r.pop("tokens")
+    eng.close()
+    return r
+
+
+def child_controls(model, B, K, share):
+    """SpecConfig(controls=True): the same engine's uncontrolled pair (plain step, speculative step), then the controlled pair."""
+    eng = _engine(model, B, K, share, controls=True)
+    out = {"model": model, "slots": B, "K": K, "rows": eng.rows, "share_rows": bool(share), "ctx": CTX, "top_p": TOP_P,
+           "repetition_penalty": REPETITION, "temperature": TEMPERATURE}
+    for name, on in (("uncontrolled", False), ("controlled", True)):
+        _control_slots(eng, on)
+        r = _full_acceptance_pair(eng, K)
+        r.pop("tokens")
+        out[name] = r
+    eng.close()
+    return out
+
+
 def run_child(args, tree, limit, sizes=None):
     """This file as a child process with `tree`'s package on the path (the child imports karanta_ocr_amd from its working directory).
     sizes: the plain child's batch sizes, for a tree whose engine this file's --sizes is to drive."""
@@ -397,6 +470,63 @@ def main_guided(a):
     return 0
 
 
+def main_controls(a):
+    """8 slots x K = 3 and 24 slots on shared rows, every slot with top_p and a repetition penalty; the legs the parent can run on both
+    trees in alternating child processes, the controlled speculative step on this tree.  --layouts picks a subset (one call may be
+    short of time for both); the report file is read back and extended."""
+    import numpy as np
+    K = 3
+    report = {"context": CTX, "steps_per_round": STEPS, "rounds": ROUNDS, "weights": "random bf16 (timing only)", "K": K, "top_p": TOP_P,
+              "repetition_penalty": REPETITION, "temperature": TEMPERATURE, "layouts": {}}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            report = json.load(f)
+
+    def save():
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(report, f, indent=1)
+            f.write("\n")
+    trees = [("this", ROOT)] + ([("parent", os.path.abspath(a.parent_tree))] if a.parent_tree else [])
+    for name in a.layouts.split(","):
+        B, share = {"8x3": (8, False), "24shared": (24, True)}[name]
+        lay = report["layouts"][name] = {"slots": B, "share_rows": share}
+        runs = {t: {"plain": [], "pair": []} for t, _ in trees}
+        for _ in range(a.repeats):
+            for t, tree in trees:
+                runs[t]["plain"].append(run_child(["--child", "controls-plain", "--slots", str(B)], tree, 300))
+                runs[t]["pair"].append(run_child(["--child", "pair", "--slots", str(B), "--k", str(K)] + (["--share"] if share else []),
+                                                 tree, 300))
+        legs = {"controlled_plain": lambda r: r["plain"], "uncontrolled_plain": lambda r: r["plain"], "uncontrolled_spec": lambda r: r["pair"]}
+        pick = {"controlled_plain": lambda x: x["controlled"]["median_ms"], "uncontrolled_plain": lambda x: x["uncontrolled"]["median_ms"],
+                "uncontrolled_spec": lambda x: x["spec_ms"]}
+        for leg in legs:
+            mine = [pick[leg](x) for x in legs[leg](runs["this"])]
+            theirs = [pick[leg](x) for x in legs[leg](runs["parent"])] if a.parent_tree else []
+            lay[leg] = {"this_tree_ms": mine, "parent_ms": theirs, "aa_spread_ms": max(mine) - min(mine)}
+            if theirs:
+                lay[leg]["parent_spread_ms"] = max(theirs) - min(theirs)
+                lay[leg]["difference_of_medians_ms"] = float(np.median(mine) - np.median(theirs))
+                lay[leg]["within_parent_spread"] = bool(abs(lay[leg]["difference_of_medians_ms"]) <= lay[leg]["parent_spread_ms"])
+                lay[leg]["within_this_trees_spread"] = bool(abs(lay[leg]["difference_of_medians_ms"]) <= lay[leg]["aa_spread_ms"])
+        lay["tokens_equal_plain_uncontrolled"] = all(x["tokens_equal_plain"] for t, _ in trees for x in runs[t]["pair"])
+        save()
+        spec = run_child(["--child", "controls", "--slots", str(B), "--k", str(K)] + (["--share"] if share else []), ROOT, 420)
+        lay["spec"] = spec
+        base = lay["controlled_plain"]["parent_ms"] or lay["controlled_plain"]["this_tree_ms"]
+        lay["t_plain_controlled_from"] = "parent commit" if lay["controlled_plain"]["parent_ms"] else "THIS tree (no --parent-tree given)"
+        lay["t_plain_controlled_ms"] = float(np.median(base))
+        lay["t_spec_controlled_ms"] = spec["controlled"]["spec_ms"]
+        lay["t_spec_over_t_plain_controlled"] = spec["controlled"]["spec_ms"] / lay["t_plain_controlled_ms"]
+        lay["break_even_accepted_per_slot_step"] = lay["t_spec_over_t_plain_controlled"] - 1
+        lay["t_spec_over_t_plain_uncontrolled_same_engine"] = spec["uncontrolled"]["ratio"]
+        lay["controlled_spec_step_minus_uncontrolled_spec_step_ms"] = spec["controlled"]["spec_ms"] - spec["uncontrolled"]["spec_ms"]
+        lay["controlled_plain_step_minus_uncontrolled_plain_step_ms"] = spec["controlled"]["plain_ms"] - spec["uncontrolled"]["plain_ms"]
+        save()
+    print(json.dumps(report, indent=1))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", default=None)
@@ -409,6 +539,9 @@ def main():
     ap.add_argument("--shared", action="store_true", help="the shared-rows leg alone: 24 slots x K = 3 (profiles/r06_spec_shared_rows.json)")
     ap.add_argument("--guided", action="store_true", help="the guided leg alone: 8 slots x K = 3, every slot under a guide "
                                                           "(profiles/r07_spec_guided.json)")
+    ap.add_argument("--controls", action="store_true", help="the controls leg alone: 8 slots x K = 3 and 24 slots shared, every slot with "
+                                                            "top_p and a repetition penalty (profiles/r08_spec_controls.json)")
+    ap.add_argument("--layouts", default="8x3,24shared", help="(--controls) which of the two layouts to run")
     ap.add_argument("--share", action="store_true", help="(child) SpecConfig(share_rows=True)")
     ap.add_argument("--sizes", default="8,32", help="(child plain) the batch sizes")
     ap.add_argument("--out", default=None)
@@ -418,12 +551,17 @@ def main():
         res = (child_plain(a.model, [int(x) for x in a.sizes.split(",")]) if a.child == "plain"
                else child_guided_plain(a.model, a.slots) if a.child == "guided-plain"
                else child_guided(a.model, a.slots, a.k) if a.child == "guided"
+               else child_controls_plain(a.model, a.slots) if a.child == "controls-plain"
+               else child_pair(a.model, a.slots, a.k, a.share) if a.child == "pair"
+               else child_controls(a.model, a.slots, a.k, a.share) if a.child == "controls"
                else child_spec(a.model, a.slots, a.k, a.share))
         print(json.dumps(res), flush=True)
         return 0
     import numpy as np
-    a.out = a.out or os.path.join(ROOT, "profiles", "r07_spec_guided.json" if a.guided else
+    a.out = a.out or os.path.join(ROOT, "profiles", "r08_spec_controls.json" if a.controls else "r07_spec_guided.json" if a.guided else
                                   "r06_spec_shared_rows.json" if a.shared else "r05_spec_decode.json")
+    if a.controls:
+        return main_controls(a)
     if a.guided:
         return main_guided(a)
     if a.shared:

@@ -126,6 +126,8 @@ class Engine:
         self.share_rows = speculative is not None and bool(speculative.share_rows)
         # guided steps speculate too (SpecConfig.guided); the slot scheduler reads this before it asks for a speculative chunk
         self.spec_guided = speculative is not None and bool(speculative.guided)
+        # so do steps with sampling controls or logit adjustments (SpecConfig.controls)
+        self.spec_controls = speculative is not None and bool(speculative.controls)
         self.spec_steps = self.plain_steps = 0
         self._snap_counts = None
         self.s_max = _align(s_max, 64)
@@ -906,16 +908,18 @@ class Engine:
         """Why the next steps cannot be speculative (None: they can).  A draft row sees the logits of its own position only: the
         passes that carry state from token to token (the penalties' counts, min_tokens) or record per step (log-probabilities)
         would need that state per draft.  A guide's DFA state is had per draft (kr_spec_guide_*) where the engine was built with
-        SpecConfig(guided=True)."""
+        SpecConfig(guided=True), the sampler's counts and stop entries (kr_spec_controls_*, the _rows launches) where it was built
+        with SpecConfig(controls=True)."""
         step = self._step
         if self.spec is None:
             return "the engine was built without speculative=SpecConfig(...)"
         if not self._freeze_finished:
             return "speculative steps run in slot mode (begin_slots)"
+        controlled = (step.processing or step.adjust) and not self.spec_controls
         if self.spec_guided:
-            if step.processing or step.adjust:
+            if controlled:
                 return "the step carries sampling controls or logit adjustments"
-        elif step.guided or step.processing or step.adjust:
+        elif step.guided or controlled:
             return ("the step carries guided decoding, sampling controls or logit adjustments"
                     + (" (guided requests speculate on an engine built with SpecConfig(guided=True))" if step.guided else ""))
         if self._logprobs is not None:
@@ -933,35 +937,58 @@ class Engine:
         dropped before any row is spent on them (kr_spec_guide_trim: behind kr_spec_propose, or between kr_spec_lookup and
         kr_spec_deal), every draft row gets the guide and the DFA state behind its drafts (kr_spec_guide_rows) for the masked Gumbel
         pass, and the slots' states follow the tokens the verification emitted (kr_spec_guide_advance).  An unguided step issues
-        none of them.  A step that carries repetition detection ends on kr_repeat_detect, as a plain step does."""
+        none of them.  A step that carries sampling controls or logit adjustments (SpecConfig(controls=True)) has the same shape:
+        kr_spec_controls_trim behind the guide's trim (a draft that is a stop entry of its slot ends the slot's drafts),
+        kr_spec_controls_rows behind the guide's rows (every row's depth, for the row-mapped sampler passes Sampler.pre_token picks),
+        kr_stop_tokens behind the verification where the step carries adjustments, and kr_spec_controls_count where it carries
+        controls (the slots' output counts follow the emitted tokens).  A step without either issues none of them.
+        A step that carries repetition detection ends on kr_repeat_detect, as a plain step does."""
         L, s, R = self.L, self.s, self.rows
         why = self._spec_refusal()
         if why is not None:
             raise KarantaHipError("speculative decode step refused: " + why)
+        step = self._step
         a = self._spec_args()
-        g = self.sampler.spec_guide_args() if self._step.guided else None
+        g = self.sampler.spec_guide_args() if step.guided else None
+        c = self.sampler.spec_controls_args() if (step.processing or step.adjust) else None
         if self.share_rows:
             L.kr_spec_lookup(C.byref(a), ptr(self.d_nwant), s)
             if g is not None:
                 L.kr_spec_guide_trim(C.byref(a), C.byref(g), ptr(self.d_nwant), s)
+            if c is not None:
+                L.kr_spec_controls_trim(C.byref(a), C.byref(c), ptr(self.d_nwant), s)
             L.kr_spec_deal(C.byref(a), ptr(self.d_nwant), ptr(self.d_draft_row), s)
             if g is not None:
                 L.kr_spec_guide_rows(C.byref(a), C.byref(g), ptr(self.d_draft_row), s)
+            if c is not None:
+                L.kr_spec_controls_rows(C.byref(a), C.byref(c), ptr(self.d_draft_row), s)
         else:
             L.kr_spec_propose(C.byref(a), s)
             if g is not None:
                 L.kr_spec_guide_trim(C.byref(a), C.byref(g), ptr(self.d_ndraft), s)
+            if c is not None:
+                L.kr_spec_controls_trim(C.byref(a), C.byref(c), ptr(self.d_ndraft), s)
+            if g is not None:
                 L.kr_spec_guide_rows(C.byref(a), C.byref(g), None, s)
+            if c is not None:
+                L.kr_spec_controls_rows(C.byref(a), C.byref(c), None, s)
         x = self._layer_launches(R, self.d_row_slot)
         logits, n_part = self._lm_head(R, x)
         flags = self._flags()
-        n_part = self.sampler.pre_token(logits, n_part, R, 0, flags)     # (the refusal above leaves it the Gumbel pass alone)
+        # (an uncontrolled step: the Gumbel pass alone; a controlled one: the row-mapped adjustment and control passes)
+        n_part = self.sampler.pre_token(logits, n_part, R, 0, flags, spec=True)
         if self.share_rows:
             L.kr_spec_accept_rows(C.byref(a), ptr(self.d_draft_row), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(self.d_tok),
                                   ptr(self.d_eos), self.d_eos.numel(), flags, s)
         else:
             L.kr_spec_accept(C.byref(a), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(self.d_tok), ptr(self.d_eos),
                              self.d_eos.numel(), flags, s)
+        if step.adjust:       # a stop entry can only be the step's last token (kr_spec_controls_trim): the plain step's launch
+            sm = self.sampler
+            L.kr_stop_tokens(ptr(self.d_tok), ptr(sm.d_adj_ids), ptr(sm.d_adj_flag), ptr(sm.d_adj_meta), ptr(self.d_fin), flags,
+                             self.B, s)
+        if step.processing:
+            L.kr_spec_controls_count(C.byref(a), C.byref(c), s)
         if g is not None:
             L.kr_spec_guide_advance(C.byref(a), C.byref(g), s)
         if self._step.repetition:     # over the 1 .. K + 1 tokens every slot gained: the cut plain steps make
@@ -1375,8 +1402,8 @@ class Engine:
     def decode_steps(self, n: int, speculative: bool = False):
         """n decode steps over all slots (asynchronous on the engine's stream).  speculative=True: speculative steps (every slot
         advances by 1 .. K + 1 tokens per step, the same tokens as plain steps give); raises where the steps carry guided decoding
-        (without SpecConfig(guided=True)), sampling controls or logit adjustments, or record log-probabilities.  While an admission
-        is in flight on a CU-masked stream the captured graph replays on the complementary compute units (same kernels, same grids: the same tokens), ordered
+        (without SpecConfig(guided=True)), sampling controls or logit adjustments (without SpecConfig(controls=True)), or record
+        log-probabilities.  While an admission is in flight on a CU-masked stream the captured graph replays on the complementary compute units (same kernels, same grids: the same tokens), ordered
         against the engine's stream by events on both sides."""
         spec = bool(speculative)
         if spec:

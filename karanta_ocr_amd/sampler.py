@@ -12,7 +12,7 @@ from typing import Dict, Sequence
 import numpy as np
 import torch
 
-from ._lib import ADJ_CAP, REP_MAX_PERIOD, KarantaHipError, Repeat, SpecGuide, ptr
+from ._lib import ADJ_CAP, REP_MAX_PERIOD, KarantaHipError, Repeat, SpecControls, SpecGuide, ptr
 from .request import PageRequest
 from .sampling import StepFeatures, adjust_table, needs_processing, sampling_params, temperature
 
@@ -40,9 +40,16 @@ class Sampler:
         self.d_gtrans = z(G, dtype=torch.int64)
         self.d_gmasks = z(G, dtype=torch.int64)
         self.d_gstate = z(G, dtype=torch.int32)
-        if self.spec_guided:    # kr_spec_guide's scratch: the state behind every draft, ctx_len at the start of the step
+        # an engine that speculates on controlled steps (SpecConfig(controls=True)) runs the sampler's passes over ROWS: the scratch of
+        # the threshold pass, the threshold keys, the live flags and the saved logits are per row there, and every row has a depth
+        self.spec_controls = spec is not None and bool(getattr(spec, "controls", False))
+        W = max(B, eng.rows) if self.spec_controls else B
+        if self.spec_guided:    # kr_spec_guide's scratch: the state behind every draft
             self.d_draft_state = z(B, eng.K, dtype=torch.int32)
+        if self.spec_guided or self.spec_controls:    # ctx_len at the start of the step (both trims write it)
             self.d_ctx_before = z(B, dtype=torch.int32)
+        if self.spec_controls:
+            self.d_depth = z(eng.rows, dtype=torch.int32)
         self.mask_words = 2 * ((t.vocab_size + 63) // 64)
         # sampling controls: per-slot params (sampling_params), output-token counts, prompt-token bit set, the threshold pass's
         # scratch scores, threshold keys and live flags (kr_sample_threshold / kr_gumbel_argmax_processed / kr_sample_count)
@@ -50,16 +57,16 @@ class Sampler:
         self.d_counts = z(B, t.vocab_size, dtype=torch.int32)
         self.bits_words = (t.vocab_size + 31) // 32
         self.d_pbits = z(B, self.bits_words, dtype=torch.int32)
-        self.d_work = z(B, t.vocab_size, dtype=torch.float32)
-        self.d_thr = z(B, dtype=torch.int32)
-        self.d_live = z(B, dtype=torch.int32)
+        self.d_work = z(W, t.vocab_size, dtype=torch.float32)
+        self.d_thr = z(W, dtype=torch.int32)
+        self.d_live = z(W, dtype=torch.int32)
         # logit adjustments: per-slot tables (sampling.adjust_table; a row with n_entries == 0 is left alone) and the values
         # kr_logits_adjust saves for kr_logits_restore
         self.d_adj_ids = z(B, ADJ_CAP, dtype=torch.int32)
         self.d_adj_val = z(B, ADJ_CAP, dtype=torch.float32)
         self.d_adj_flag = z(B, ADJ_CAP, dtype=torch.int32)
         self.d_adj_meta = z(B, 4, dtype=torch.int32)
-        self.d_adj_saved = z(B, ADJ_CAP, dtype=torch.float32)
+        self.d_adj_saved = z(W, ADJ_CAP, dtype=torch.float32)
         self.d_voc_off = self.d_voc_bytes = None   # set_vocab()
         # runaway repetition (kr_repeat_detect): per slot its cfg row {a, b, c, m} (b == 0: off), the run counters of the periods, how
         # many generated tokens the pass has looked at, and the index the sequence repeats at (-1: none).  _rep_slots: the slots whose
@@ -266,17 +273,42 @@ class Sampler:
         return SpecGuide(ptr(self.d_gtrans), ptr(self.d_gmasks), ptr(self.d_gstate), self.mask_words, ptr(self.d_voc_off),
                          ptr(self.d_voc_bytes), ptr(self.d_draft_state), ptr(self.d_ctx_before))
 
+    def spec_controls_args(self) -> SpecControls:
+        """kr_spec_controls of the engine's controlled speculative step (read during the call)."""
+        V = self.cfg.text.vocab_size
+        return SpecControls(ptr(self.d_adj_ids), ptr(self.d_adj_flag), ptr(self.d_adj_meta), ptr(self.d_counts), V, ptr(self.d_depth),
+                            ptr(self.d_ctx_before))
+
     # ------------------------------------------------------------------ the step's tail around the token choice
     def _adj(self, j):
         return ptr(self.d_adj_ids[j:]), ptr(self.d_adj_val[j:]), ptr(self.d_adj_flag[j:]), ptr(self.d_adj_meta[j:])
 
-    def pre_token(self, logits, n_part: int, B: int, j: int, flags: int) -> int:
+    def pre_token(self, logits, n_part: int, B: int, j: int, flags: int, spec: bool = False) -> int:
         """The passes between the lm_head and the token choice over rows j .. j + B - 1; returns the number of argmax partials
-        per row the choice reads (`n_part` as the lm_head launch wrote them, at most 64 after a Gumbel pass)."""
+        per row the choice reads (`n_part` as the lm_head launch wrote them, at most 64 after a Gumbel pass).
+        spec: the rows are those of a speculative step (j = 0, B = the engine's rows) — the adjustment and control passes are the
+        row-mapped launches: a row takes its slot's table, params, prompt bits and counts, and the counts take in the drafts in
+        front of it (d_depth, kr_spec_controls_rows)."""
         e, L, t, s = self.eng, self.L, self.cfg.text, self.eng.s
         step = e._step
         gm, gs = (ptr(self.d_gmasks[j:]), ptr(self.d_gstate[j:])) if step.guided else (None, None)
-        if step.adjust:
+        if spec and (step.adjust or step.processing):
+            V, ld = t.vocab_size, e.d_logits.stride(0)
+            rows = (ptr(e.d_row_slot), ptr(self.d_depth), ptr(e.d_draft), e.K, e.B)
+            if step.adjust:     # (no kr_logits_restore behind the token: nothing reads a speculative step's logits after it)
+                L.kr_logits_adjust_rows(ptr(logits), ld, V, *self._adj(0), ptr(e.d_ctx), ptr(e.d_plen), ptr(self.d_adj_saved), B,
+                                        ptr(e.d_row_slot), e.B, s)
+            if step.processing:
+                n_part = min(64, n_part)
+                L.kr_sample_threshold_rows(ptr(logits), ld, V, ptr(e.d_temp), ptr(self.d_sp), ptr(self.d_counts), V, ptr(self.d_pbits),
+                                           self.bits_words, gm, gs, self.mask_words, ptr(e.d_fin), flags, ptr(self.d_work), V,
+                                           ptr(self.d_thr), ptr(self.d_live), B, *rows, s)
+                L.kr_gumbel_argmax_processed_rows(ptr(logits), ld, V, ptr(e.d_temp), ptr(e.d_seed), ptr(e.d_ctx), ptr(e.d_plen),
+                                                  ptr(e.d_amax_v), ptr(e.d_amax_i), n_part, B, gm, gs, self.mask_words,
+                                                  int(self.cfg.eos_token_ids[0]), ptr(self.d_sp), ptr(self.d_counts), V,
+                                                  ptr(self.d_pbits), self.bits_words, ptr(self.d_thr), *rows, s)
+                return n_part
+        elif step.adjust:
             # logit_bias / min_tokens somewhere in the batch: applied in place before the sampler (vLLM's order), undone after it
             L.kr_logits_adjust(ptr(logits), e.d_logits.stride(0), t.vocab_size, *self._adj(j), ptr(e.d_ctx[j:]), ptr(e.d_plen[j:]),
                                ptr(self.d_adj_saved[j:]), B, s)

@@ -153,9 +153,9 @@ class SlotScheduler:
         self.launch_ahead = (bool(launch_ahead) and not self.overlap
                              and all(hasattr(engine, m) for m in ("snapshot_slots", "read_snapshot")))
         # speculative: the chunks are speculative steps (Engine(speculative=SpecConfig(...)): up to K + 1 tokens per slot and step, the
-        # same tokens) while no request in a slot needs sampling controls, logit adjustments or log-probabilities — or guided decoding,
-        # unless the engine speculates on guided steps (engine.spec_guided: SpecConfig(guided=True)) — and the policy finds them worth
-        # their price; every other chunk is plain
+        # same tokens) while no request in a slot needs log-probabilities — or sampling controls or logit adjustments, unless the engine
+        # speculates on such steps (engine.spec_controls: SpecConfig(controls=True)), or guided decoding, unless it speculates on guided
+        # steps (engine.spec_guided: SpecConfig(guided=True)) — and the policy finds them worth their price; every other chunk is plain
         self.speculative = bool(speculative)
         self.spec_k = int(getattr(engine, "K", 0) or 0) if self.speculative else 0
         if self.speculative and self.spec_k < 1:
@@ -310,7 +310,7 @@ class SlotScheduler:
             return False
         pending = self._inflight[1] if self._inflight is not None else []
         need = StepFeatures.of(r.page for r in [*self.active.values(), *pending])
-        if need.processing or need.adjust:
+        if (need.processing or need.adjust) and not getattr(self.engine, "spec_controls", False):   # SpecConfig(controls=True)
             return False
         if need.guided and not getattr(self.engine, "spec_guided", False):     # Engine(speculative=SpecConfig(guided=True))
             return False
