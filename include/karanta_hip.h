@@ -37,9 +37,10 @@ typedef void* kr_stream; /* hipStream_t */
 typedef uint16_t kr_bf16;
 
 /* kr_version() of the library this header describes: major * 100 + minor.  The major changes with every incompatible
- * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family); a caller built
- * against major X must refuse a library whose kr_version() / 100 != X. */
-#define KR_ABI_VERSION 412
+ * change of a signature or struct below (r4: kr_narrow_opts argument of round 3, packed 17..32-row family; r9:
+ * kr_narrow_opts.x_packed, which the library reads from every caller's struct); a caller built against major X must refuse a
+ * library whose kr_version() / 100 != X. */
+#define KR_ABI_VERSION 500
 
 #define KR_OK 0
 #define KR_ERR_ARG (-1)    /* unsupported shape / null pointer */
@@ -299,6 +300,8 @@ int kr_argmax(const float* logits, int64_t ld_logits, int vocab, int32_t* out, i
 #define KR_DEC_SILU8 4      /* SILU with 8-row interleave: one tile per workgroup -> 2x the workgroups of KR_DEC_SILU */
 #define KR_DEC_OUT_XP 0x100 /* kr_linear_decode_wide*, OR-ed into KR_DEC_SILU8 at 17..32 rows: `out` is written in the packed
                              * activation layout of kr_pack_rows32 (ldc ignored) — the input format of kr_linear_decode32 */
+#define KR_DEC_OUT_XP16 0x200 /* the same at <= 16 rows: `out` is written in the XP16 layout (below, kr_narrow_opts.x_packed; ldc
+                               * ignored; N/2 * 32 bytes) — the x operand of the down_proj launch kr_linear_decode_narrow */
 int kr_linear_decode(int mode, const kr_bf16* x, int64_t ldx, const kr_bf16* w_packed, const kr_bf16* bias,
                      const kr_bf16* norm_w, float norm_eps, const kr_bf16* residual, int64_t ldr,
                      kr_bf16* out, float* out_f32, int64_t ldc, int M, int N, int K, int waves, int max_blocks, int ksplit,
@@ -333,13 +336,24 @@ int kr_linear_decode_wide(int mode, const kr_bf16* x, int64_t ldx, const kr_bf16
  *   w_resident != 0 : the launch loads its weights with the default cache policy instead of nontemporal loads, so their
  *                     lines stay in the 256 MiB Infinity Cache for the next call on the same weights (the other launches'
  *                     nontemporal streams do not displace them: profiles/r05_ic_residency.txt).  The caller keeps the sum of
- *                     the weights it marks below the cache size.  Same bytes loaded, same output bits. */
+ *                     the weights it marks below the cache size.  Same bytes loaded, same output bits.
+ *   x_packed != 0   : x is not a row-major tensor but an XP16 buffer: the packed activation layout below restricted to one
+ *                     column tile of R row slots, R = 8 for M <= 8 and 16 above:
+ *                     [K/64 chunks][2 k-steps of 32][4 groups of 8 k][R rows][8] bf16, element (row b, column k) at byte
+ *                     (k/64)*R*128 + (k/32 % 2)*R*64 + (R*(k/8 % 4) + b)*16 + (k%8)*2.  The buffer is K * 32 bytes whatever M
+ *                     is.  KR_DEC_PLAIN without norm_w (o_proj, down_proj), M <= 16; ldx is not used.  A wave then fetches the
+ *                     operand of an MFMA as R * 64 bytes of whole cache lines instead of 16 rows x 64 B (at 8 live rows:
+ *                     eight half lines).  The same values enter the same MFMAs: the output bits are those of the row-major
+ *                     launch.  Row slots >= M are read and never used (they reach accumulator columns the epilogue drops),
+ *                     so they may hold anything.  Producers, with the same M: kr_attn_decode_merge16,
+ *                     kr_linear_decode_wide(KR_DEC_SILU8 | KR_DEC_OUT_XP16). */
 typedef struct kr_narrow_opts {
     float* zero_ptr;
     uint64_t zero_bytes;
     int32_t atomic_out;
     int32_t part_rows;
     int32_t w_resident;
+    int32_t x_packed;
 } kr_narrow_opts;
 
 /* Narrow decode linears (qkv, o_proj, down_proj): one workgroup per 16-row tile (ROPE_KV: per rotary tile
@@ -471,6 +485,11 @@ int kr_attn_decode_merge(const float* workspace, kr_bf16* out, int batch, int he
 /* kr_attn_decode_merge with the merged heads written in the packed activation layout (row = sequence, column =
  * head * 128 + d; batch <= 32; out_xp: heads * 128 * 64 bytes) — the o_proj launch of a 17..32-row batch reads it. */
 int kr_attn_decode_merge32(const float* workspace, kr_bf16* out_xp, int batch, int heads, int hd, int n_split,
+                           kr_stream s);
+
+/* The same for batch <= 16 in the XP16 layout at M = batch (kr_narrow_opts.x_packed; out_xp16: heads * 128 * 32 bytes; row
+ * slots >= batch are not written) — the o_proj launch of a <= 16-row batch reads it.  One kernel body with the two above. */
+int kr_attn_decode_merge16(const float* workspace, kr_bf16* out_xp16, int batch, int heads, int hd, int n_split,
                            kr_stream s);
 
 /* GPU image front end.  kr_image_resize_bicubic_u8: HWC uint8 RGB [h][w][3] -> [rh][rw][3], bit-identical to

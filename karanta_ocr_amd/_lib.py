@@ -51,6 +51,7 @@ SIGNATURES = {
     "kr_pack_rows32": [c_p, i64, i32, i32, c_p, c_p],
     "kr_linear_decode32": [i32, c_p, c_p],
     "kr_attn_decode_merge32": [c_p, c_p, i32, i32, i32, i32, c_p],
+    "kr_attn_decode_merge16": [c_p, c_p, i32, i32, i32, i32, c_p],
     "kr_quantize_rows_fp8": [c_p, i64, c_p, i64, c_p, i64, i32, c_p],
     "kr_gemm_fp8a": [c_p, i64, c_p, c_p, c_p, c_p, c_p, i64, c_p, i64, i64, i32, i32, i32, c_p],
     "kr_gemm_bf16_ws": [c_p, i64, c_p, c_p, c_p, i64, c_p, i64, i64, i32, i32, i32, i32, c_p, C.c_size_t, c_p],
@@ -154,12 +155,21 @@ class NarrowOpts(C.Structure):
                 ("w_resident", C.c_int32)]
 
 
-def narrow_opts(zero_ptr: int = 0, zero_bytes: int = 0, atomic_out: bool = False, part_rows: int = 0, w_resident: bool = False):
+class NarrowOptsXP(C.Structure):
+    """kr_narrow_opts of a launch on a packed x operand (x_packed = 1).  The same 32 bytes as NarrowOpts, whose tail ctypes
+    zero-fills: a launch on row-major x keeps the record it had before the field existed (tests/launch_trace.py lists a struct
+    by its fields)."""
+    _fields_ = NarrowOpts._fields_ + [("x_packed", C.c_int32)]
+
+
+def narrow_opts(zero_ptr: int = 0, zero_bytes: int = 0, atomic_out: bool = False, part_rows: int = 0, w_resident: bool = False,
+                x_packed: bool = False):
     """A kr_narrow_opts* for one launch (0 = NULL when every field is at its default).  The struct is read during the
     call only, so the temporary may die right after it."""
-    if not (zero_bytes or atomic_out or part_rows or w_resident):
+    if not (zero_bytes or atomic_out or part_rows or w_resident or x_packed):
         return None
-    return C.byref(NarrowOpts(zero_ptr or None, int(zero_bytes), 1 if atomic_out else 0, int(part_rows), 1 if w_resident else 0))
+    head = (zero_ptr or None, int(zero_bytes), 1 if atomic_out else 0, int(part_rows), 1 if w_resident else 0)
+    return C.byref(NarrowOptsXP(*head, 1) if x_packed else NarrowOpts(*head))
 
 class Dec32(C.Structure):
     """kr_dec32 (include/karanta_hip.h): the arguments of kr_linear_decode32."""
@@ -257,8 +267,9 @@ def fork_plan(groups):
     return C.byref(p)
 
 
-ABI_MAJOR = 4              # include/karanta_hip.h KR_ABI_VERSION / 100: the header this binding was written against
+ABI_MAJOR = 5              # include/karanta_hip.h KR_ABI_VERSION / 100: the header this binding was written against
 DEC_OUT_XP = 0x100         # KR_DEC_OUT_XP
+DEC_OUT_XP16 = 0x200       # KR_DEC_OUT_XP16
 ADJ_CAP = 320              # KR_ADJ_CAP: entries per row of the logit-adjustment tables (kr_logits_adjust)
 EPI_NONE, EPI_QUICK_GELU, EPI_GELU_ERF, EPI_SILU_MUL, EPI_SILU_MUL8 = 0, 1, 2, 3, 4
 DEC_PLAIN, DEC_SILU, DEC_ROPE_KV, DEC_ARGMAX, DEC_SILU8 = 0, 1, 2, 3, 4

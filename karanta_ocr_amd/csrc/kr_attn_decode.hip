@@ -359,8 +359,11 @@ __global__ void __launch_bounds__(WAVES * 64) attn_decode2_kernel(const kr_bf16*
 // (Cheaper end-to-end than replicating the merge in every o_proj workgroup's prologue: measured.)
 // NS > 0: all n_split records are requested at once (one memory round trip instead of two dependent loops).
 template <int NS>
-__global__ void __launch_bounds__(128) attn_merge_kernel(const float* __restrict__ ws, kr_bf16* __restrict__ out, int n_split, int heads_xp) {
-    // heads_xp > 0: out is the XP layout of a 17..32-row batch (row = sequence, column = head * 128 + d), heads_xp = heads
+__global__ void __launch_bounds__(128) attn_merge_kernel(const float* __restrict__ ws, kr_bf16* __restrict__ out, int n_split, int heads_xp,
+                                                         int xp16) {
+    // heads_xp > 0: out is the XP layout of a 17..32-row batch (row = sequence, column = head * 128 + d), heads_xp = heads;
+    // with xp16 > 0 the XP16 layout of a <= 16-row batch at xp16 row slots (kr_common.h: the x_packed operand of the narrow
+    // o_proj launch)
     constexpr int HD = 128, REC = HD + 4;
     const int bh = blockIdx.x, d = threadIdx.x;
     float acc = 0.f, ll = 0.f;
@@ -395,7 +398,7 @@ __global__ void __launch_bounds__(128) attn_merge_kernel(const float* __restrict
     const kr_bf16 r = __builtin_bit_cast(kr_bf16, f2bf(ll > 0.f ? acc / ll : 0.f));
     if (heads_xp > 0) {
         const int b = bh / heads_xp, hh = bh - b * heads_xp;
-        *reinterpret_cast<kr_bf16*>(reinterpret_cast<char*>(out) + kr_xp_byte_offset(b, hh * HD + d)) = r;
+        *reinterpret_cast<kr_bf16*>(reinterpret_cast<char*>(out) + (xp16 ? kr_xp16_byte_offset(b, hh * HD + d, xp16) : kr_xp_byte_offset(b, hh * HD + d))) = r;
     } else {
         out[(int64_t)bh * HD + d] = r;
     }
@@ -486,14 +489,16 @@ extern "C" int kr_attn_decode_rows_kv8(const kr_bf16* q, const kr_kv8* kv, const
 static int merge_impl(const float* workspace, kr_bf16* out, int batch, int heads, int hd, int n_split, int xp, kr_stream s) {
     KR_CHECK_ARG(workspace && out && batch > 0 && heads > 0 && n_split > 0, "kr_attn_decode_merge: bad args");
     KR_CHECK_ARG(hd == 128, "kr_attn_decode_merge: hd=%d (only 128)", hd);
-    KR_CHECK_ARG(!xp || (batch <= 32 && ((uintptr_t)out & 15) == 0), "kr_attn_decode_merge32: batch=%d (<= 32)", batch);
-    const int hx = xp ? heads : 0;
+    // xp: 0 row-major rows, 1 the XP layout (<= 32 rows), 2 the XP16 layout (<= 16 rows)
+    KR_CHECK_ARG(!xp || (batch <= (xp == 2 ? 16 : 32) && ((uintptr_t)out & 15) == 0), "kr_attn_decode_merge%d: batch=%d (<= %d)",
+                 xp == 2 ? 16 : 32, batch, xp == 2 ? 16 : 32);
+    const int hx = xp ? heads : 0, xp16 = xp == 2 ? kr_xp16_rows(batch) : 0;
     switch (n_split) {
-        case 4: attn_merge_kernel<4><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
-        case 8: attn_merge_kernel<8><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
-        case 16: attn_merge_kernel<16><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
-        case 32: attn_merge_kernel<32><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx); break;
-        default: attn_merge_kernel<0><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx);
+        case 4: attn_merge_kernel<4><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx, xp16); break;
+        case 8: attn_merge_kernel<8><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx, xp16); break;
+        case 16: attn_merge_kernel<16><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx, xp16); break;
+        case 32: attn_merge_kernel<32><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx, xp16); break;
+        default: attn_merge_kernel<0><<<batch * heads, 128, 0, kr_hs(s)>>>(workspace, out, n_split, hx, xp16);
     }
     KR_CHECK_LAUNCH();
     return KR_OK;
@@ -507,6 +512,11 @@ extern "C" int kr_attn_decode_merge(const float* workspace, kr_bf16* out, int ba
 extern "C" int kr_attn_decode_merge32(const float* workspace, kr_bf16* out_xp, int batch, int heads, int hd, int n_split,
                                       kr_stream s) {
     return merge_impl(workspace, out_xp, batch, heads, hd, n_split, 1, s);
+}
+
+extern "C" int kr_attn_decode_merge16(const float* workspace, kr_bf16* out_xp16, int batch, int heads, int hd, int n_split,
+                                      kr_stream s) {
+    return merge_impl(workspace, out_xp16, batch, heads, hd, n_split, 2, s);
 }
 
 // =====================================================================================

@@ -86,6 +86,14 @@ __device__ __forceinline__ bf16x8 ld8_nt(const kr_bf16* p) {
 __host__ __device__ __forceinline__ int64_t kr_xp_byte_offset(int b, int k) {
     return (int64_t)(k >> 6) * 4096 + (b >> 4) * 2048 + ((k >> 5) & 1) * 1024 + ((((k >> 3) & 3) * 16 + (b & 15)) * 16) + (k & 7) * 2;
 }
+// The same for a batch of at most 16 rows (XP16): column tile 0 alone, with R = kr_xp16_rows(M) row slots — 8 for M <= 8, where
+// 16 slots would make every fragment load fetch as many lines of unused rows as of live ones, else 16:
+// [K/64][2 k-steps][4 lane groups][R rows][8] bf16, R * 128 bytes per chunk — the x operand of the <= 16-row narrow launches
+// (kr_narrow_opts.x_packed).  Lanes fr >= R read row fr - R again.  A buffer is sized for 16 rows whatever M is: K * 32 bytes.
+__host__ __device__ __forceinline__ int kr_xp16_rows(int M) { return M <= 8 ? 8 : 16; }
+__host__ __device__ __forceinline__ int64_t kr_xp16_byte_offset(int b, int k, int R) {
+    return (int64_t)(k >> 6) * (R * 128) + ((k >> 5) & 1) * (R * 64) + ((((k >> 3) & 3) * R + b) * 16) + (k & 7) * 2;
+}
 
 // ---------------------------------------------------------------- V^T blocks of the KV cache / the ViT's V^T buffer
 // A block holds 64 keys of one head, transposed, as TWO CONTIGUOUS 32-KEY HALVES: [2][HD channels][32 keys] (rounds 1-3:

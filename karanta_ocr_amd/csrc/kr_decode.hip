@@ -74,7 +74,8 @@ struct DecLinArgs {
     int w_resident;
     // SILU8 output in the XP layout of 17..32-row batches (kr_common.h, kr_xp_byte_offset): the down_proj launch of such a
     // batch (kr_linear_decode32) reads its x fragments as whole cache lines
-    int out_xp;
+    int out_xp;     // 1: XP (two column tiles), 2: XP16 (M <= 16, KR_DEC_OUT_XP16: the x_packed operand of the narrow down_proj launch)
+    int x_packed;   // narrow kernel, direct path: x is an XP16 buffer (kr_narrow_opts.x_packed)
     // ROPE_KV8: the fp8 cache of this layer (kcache / vtcache unused)
     Kv8 kv8;
 };
@@ -680,8 +681,9 @@ __device__ __forceinline__ void dec_wide_body(const WideHot& h, const DecLinArgs
                     bf16x4 o;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) o[j] = f2bf(act_silu(acc[mt][j]) * u4[j]);
-                    if (MT == 2 && a.out_xp)
-                        *reinterpret_cast<bf16x4*>(reinterpret_cast<char*>(a.out) + kr_xp_byte_offset(b, t * 8 + fg * 4)) = o;
+                    if (a.out_xp)
+                        *reinterpret_cast<bf16x4*>(reinterpret_cast<char*>(a.out) + (MT == 2 ? kr_xp_byte_offset(b, t * 8 + fg * 4)
+                                                                                             : kr_xp16_byte_offset(b, t * 8 + fg * 4, kr_xp16_rows(M)))) = o;
                     else
                         *reinterpret_cast<bf16x4*>(a.out + (int64_t)b * a.ldc + t * 8 + fg * 4) = o;
                 }
@@ -1058,6 +1060,7 @@ int launch_wide(DecLinArgs& a, int blocks, int waves, kr_stream s) {
 //   down_proj   : EPI PARTIAL, ksplit 2 -> 192 workgroups instead of 96, slabs [2][M][d] f32
 //   next qkv    : NORM prologue with PKS = 2: x_new = bf16(x + slab0 + slab1) (workgroup 0 stores it to x_out,
 //                 the other residual buffer), RMSNorm of x_new, QKV + bias + M-RoPE + KV append as before
+enum NarrowX { NARROW_X_ROWS = 0, NARROW_X_PACKED = 1, NARROW_X_BOUND = 2 };   // dec_narrow_kernel's XM
 template <int NCH> struct NarrowCfg { static constexpr int RL = 8; };
 template <> struct NarrowCfg<24> { static constexpr int RL = 3; };
 template <> struct NarrowCfg<32> { static constexpr int RL = 4; };
@@ -1066,7 +1069,12 @@ template <> struct NarrowCfg<56> { static constexpr int RL = 7; };
 // U = ring depth in 64-wide K chunks: the host picks the smallest instantiated U that covers a wave's share of K
 // (then every chunk is requested up front and at most one request per wave is redundant), else the deepest ring.
 // RES: the weight loads use the default cache policy instead of the nontemporal one (WChunk::load); nothing else differs.
-template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8, int MT, bool RES>
+// XM: where the x fragments of the !NORM path come from (NarrowX): the row-major tensor (16 rows x 64 B per wave instruction:
+// at 8 live rows eight half cache lines); the XP16 buffer of kr_common.h (kr_narrow_opts.x_packed: 1 KiB of whole lines per
+// wave instruction at 16 row slots, 512 B at 8, the same values into the same MFMAs; rows >= M of the buffer only reach
+// accumulator columns the epilogue drops); or, in a -DKR_NARROW_XBOUND build only, one cache line for every load (the timing bound of
+// profiles/r09_narrow_x_operand.txt; wrong values).
+template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8, int MT, bool RES, int XM>
 __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* hx, const kr_bf16* hwp, const kr_bf16* hnorm_w, const float* hpart_in,
                                                                 int64_t hldx, int hM, int hN, int hK, int hcpb, float hnorm_eps,
                                                                 int hprows, const DecLinArgs a) {
@@ -1131,6 +1139,15 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
     const char* xg[MT];   // x fragments: + c*128 + WC::x_byte(h, fg)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) xg[mt] = reinterpret_cast<const char*>(hx + (int64_t)rb[mt] * hldx);
+    auto xfrag = [&](const int mt, const int c, const int h) {   // operand h of K chunk c, column tile mt (!NORM)
+        if constexpr (XM == NARROW_X_BOUND)   // same count of loads, all of them in chunk cb0 of row 0
+            return *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(hx) + cb0 * 128 + WC::x_byte(h, fg));
+        else if constexpr (XM == NARROW_X_PACKED)   // hldx carries the row slots R of the buffer (8 or 16: a preloaded argument)
+            return *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(hx) + c * ((int)hldx * 128) +
+                                                    WC::xp16_off(h, fr & ((int)hldx - 1), fg, (int)hldx));
+        else
+            return *reinterpret_cast<const bf16x8*>(xg[mt] + c * 128 + WC::x_byte(h, fg));
+    };
     if (NORM) {
         const int b = wave < M ? wave : 0;
 #pragma unroll
@@ -1153,8 +1170,8 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
             const int c = min(max(min(c0 + u, c1 - 1), cb0), nchunks - 1);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
-                xf[u][mt][0] = *reinterpret_cast<const bf16x8*>(xg[mt] + c * 128 + WC::x_byte(0, fg));
-                xf[u][mt][1] = *reinterpret_cast<const bf16x8*>(xg[mt] + c * 128 + WC::x_byte(1, fg));
+                xf[u][mt][0] = xfrag(mt, c, 0);
+                xf[u][mt][1] = xfrag(mt, c, 1);
             }
         }
     }
@@ -1350,8 +1367,8 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
                     if (!NORM) {
 #pragma unroll
                         for (int mt = 0; mt < MT; ++mt) {
-                            xf[u][mt][0] = *reinterpret_cast<const bf16x8*>(xg[mt] + cn * 128 + WC::x_byte(0, fg));
-                            xf[u][mt][1] = *reinterpret_cast<const bf16x8*>(xg[mt] + cn * 128 + WC::x_byte(1, fg));
+                            xf[u][mt][0] = xfrag(mt, cn, 0);
+                            xf[u][mt][1] = xfrag(mt, cn, 1);
                         }
                     }
 #pragma unroll
@@ -1478,13 +1495,13 @@ __global__ void __launch_bounds__(WAVES * 64) dec_narrow_kernel(const kr_bf16* h
     }
 }
 
-template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8, int MT, bool RES>
+template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8, int MT, bool RES, int XM>
 int launch_narrow_m(DecLinArgs& a, int groups, kr_stream s) {
     const int nchunks = a.K >> 6, cpb = (nchunks + a.ksplit - 1) / a.ksplit;
     const size_t xbytes = NORM ? (((size_t)a.M * (cpb * 128 + 16) + 127) & ~(size_t)127) : 0;
     const size_t lds = xbytes + (size_t)WAVES * NT * 256 * 4;
     KR_CHECK_ARG(lds <= 160 * 1024, "kr_linear_decode_narrow: M=%d K=%d needs %zu bytes of LDS", a.M, a.K, lds);
-    auto fn = &dec_narrow_kernel<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, MT, RES>;
+    auto fn = &dec_narrow_kernel<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, MT, RES, XM>;
     static KrPerDeviceOnce attr;
     if (attr.need()) {
         KR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1498,26 +1515,29 @@ int launch_narrow_m(DecLinArgs& a, int groups, kr_stream s) {
 
 // M > 16: two batch column tiles.  Only on 8-wave workgroups (the x fragments of the direct path double) and not
 // with the K = 3584 row registers; the engine sizes its batches accordingly.
-template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8, bool RES>
+template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, bool W8, bool RES, int XM>
 int launch_narrow_w(DecLinArgs& a, int groups, kr_stream s) {
     if (a.M > 16) {
-        if constexpr (WAVES == 8 && NCH != 56) {
-            return launch_narrow_m<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, 2, RES>(a, groups, s);
+        if constexpr (XM != NARROW_X_ROWS) {   // one column tile only (kr_linear_decode32 is the packed form above 16 rows)
+            kr_set_error("kr_linear_decode_narrow: opts x_packed takes M <= 16 (M=%d)", a.M);
+            return KR_ERR_ARG;
+        } else if constexpr (WAVES == 8 && NCH != 56) {
+            return launch_narrow_m<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, 2, RES, XM>(a, groups, s);
         } else {
             kr_set_error("kr_linear_decode_narrow: M=%d > 16 needs 8-wave workgroups and K != 3584", a.M);
             return KR_ERR_ARG;
         }
     }
-    return launch_narrow_m<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, 1, RES>(a, groups, s);
+    return launch_narrow_m<NT, EPI, WAVES, NCH, PKS, NORM, U, W8, 1, RES, XM>(a, groups, s);
 }
 
-template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U>
+template <int NT, int EPI, int WAVES, int NCH, int PKS, bool NORM, int U, int XM = NARROW_X_ROWS>
 int launch_narrow_u(DecLinArgs& a, int groups, kr_stream s) {
     if (a.w_resident)
-        return a.w_scale ? launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, true, true>(a, groups, s)
-                         : launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, false, true>(a, groups, s);
-    return a.w_scale ? launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, true, false>(a, groups, s)
-                     : launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, false, false>(a, groups, s);
+        return a.w_scale ? launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, true, true, XM>(a, groups, s)
+                         : launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, false, true, XM>(a, groups, s);
+    return a.w_scale ? launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, true, false, XM>(a, groups, s)
+                     : launch_narrow_w<NT, EPI, WAVES, NCH, PKS, NORM, U, false, false, XM>(a, groups, s);
 }
 
 // chunks of K the busiest wave of a workgroup owns
@@ -1527,7 +1547,7 @@ inline int narrow_share(const DecLinArgs& a, int waves) {
 }
 
 // x fragments straight from global memory (o_proj, down_proj): rings of 3 / 5 / 8 chunks (x + weights = 16 U VGPRs)
-template <int EPI, int WAVES>
+template <int EPI, int WAVES, int XM>
 int launch_narrow_direct(DecLinArgs& a, int groups, kr_stream s) {
     const int share = narrow_share(a, WAVES);
     if constexpr (EPI == DEPI_PARTIAL) {
@@ -1541,17 +1561,31 @@ int launch_narrow_direct(DecLinArgs& a, int groups, kr_stream s) {
         const char* e = getenv("KARANTA_NARROW_NT2");
         const bool nt2 = e ? atoi(e) != 0 : groups >= 192;
         if (nt2 && (groups & 1) == 0 && (a.M <= 16 || WAVES == 8)) {   // two batch column tiles: 8-wave workgroups only
-            if constexpr (WAVES == 16) return launch_narrow_u<2, EPI, WAVES, 0, 0, false, 3>(a, groups / 2, s);
-            else return launch_narrow_u<2, EPI, WAVES, 0, 0, false, 5>(a, groups / 2, s);
+            if constexpr (WAVES == 16) return launch_narrow_u<2, EPI, WAVES, 0, 0, false, 3, XM>(a, groups / 2, s);
+            else return launch_narrow_u<2, EPI, WAVES, 0, 0, false, 5, XM>(a, groups / 2, s);
         }
     }
-    if (share <= 3) return launch_narrow_u<1, EPI, WAVES, 0, 0, false, 3>(a, groups, s);
+    if (share <= 3) return launch_narrow_u<1, EPI, WAVES, 0, 0, false, 3, XM>(a, groups, s);
     if constexpr (WAVES == 16) {  // 128-VGPR budget
-        return launch_narrow_u<1, EPI, WAVES, 0, 0, false, 5>(a, groups, s);
+        return launch_narrow_u<1, EPI, WAVES, 0, 0, false, 5, XM>(a, groups, s);
     } else {
-        if (share <= 5) return launch_narrow_u<1, EPI, WAVES, 0, 0, false, 5>(a, groups, s);
-        return launch_narrow_u<1, EPI, WAVES, 0, 0, false, 8>(a, groups, s);
+        if (share <= 5) return launch_narrow_u<1, EPI, WAVES, 0, 0, false, 5, XM>(a, groups, s);
+        return launch_narrow_u<1, EPI, WAVES, 0, 0, false, 8, XM>(a, groups, s);
     }
+}
+
+// the direct launch of an epilogue: 8 or 16 waves; a -DKR_NARROW_XBOUND build (csrc/tools/build_variant.py) also holds the
+// timing-only kernels whose x loads all hit one cache line, picked per launch by KARANTA_NARROW_XBOUND=1 (decode_ab.py)
+template <int EPI>
+int launch_narrow_direct_w(DecLinArgs& a, int groups, int waves, kr_stream s) {
+#ifdef KR_NARROW_XBOUND
+    const char* e = getenv("KARANTA_NARROW_XBOUND");
+    if (e && atoi(e) != 0)
+        return waves == 16 ? launch_narrow_direct<EPI, 16, NARROW_X_BOUND>(a, groups, s) : launch_narrow_direct<EPI, 8, NARROW_X_BOUND>(a, groups, s);
+#endif
+    if (a.x_packed)
+        return waves == 16 ? launch_narrow_direct<EPI, 16, NARROW_X_PACKED>(a, groups, s) : launch_narrow_direct<EPI, 8, NARROW_X_PACKED>(a, groups, s);
+    return waves == 16 ? launch_narrow_direct<EPI, 16, NARROW_X_ROWS>(a, groups, s) : launch_narrow_direct<EPI, 8, NARROW_X_ROWS>(a, groups, s);
 }
 
 // NORM kernels are specialised on K (x row registers); PKS = 2 only where the registers allow it
@@ -1840,6 +1874,11 @@ static int wide_impl(int mode, const kr_bf16* x, int64_t ldx, const void* w_pack
                      "kr_linear_decode_wide: KR_DEC_OUT_XP is for SILU8 at 17..32 rows, N/2 %% 64 == 0");
         a.out_xp = 1;
         mode &= ~KR_DEC_OUT_XP;
+    } else if (mode & KR_DEC_OUT_XP16) {   // the same at <= 16 rows: one column tile of 8 or 16 row slots (kr_xp16_byte_offset)
+        KR_CHECK_ARG((mode & ~KR_DEC_OUT_XP16) == DEPI_SILU8 && M <= 16 && (N / 2) % 64 == 0 && ((uintptr_t)out & 15) == 0,
+                     "kr_linear_decode_wide: KR_DEC_OUT_XP16 is for SILU8 at <= 16 rows, N/2 %% 64 == 0");
+        a.out_xp = 2;
+        mode &= ~KR_DEC_OUT_XP16;
     }
     switch (mode) {
         case DEPI_PLAIN:
@@ -1908,6 +1947,10 @@ static int narrow_impl(int mode, const kr_bf16* x, int64_t ldx, const float* par
     a.n_part = part_in ? n_part_in : 0;
     a.zero_ptr = o.zero_bytes ? o.zero_ptr : nullptr; a.zero_n16 = (int)(o.zero_bytes >> 4); a.part_atomic = o.atomic_out ? 1 : 0;
     a.w_resident = o.w_resident ? 1 : 0;
+    a.x_packed = o.x_packed ? 1 : 0;
+    if (a.x_packed) a.ldx = kr_xp16_rows(M);   // the kernel's preloaded ldx argument: the row slots of the packed buffer
+    KR_CHECK_ARG(!a.x_packed || (mode == DEPI_PLAIN && !norm_w && M <= 16 && ((uintptr_t)x & 15) == 0),
+                 "kr_linear_decode_narrow: opts x_packed is for PLAIN launches without a norm prologue at M <= 16 (x 16-byte aligned)");
     KR_CHECK_ARG(!a.part_atomic || (ksplit == 2 && mode == DEPI_PLAIN), "kr_linear_decode_narrow: atomic_out is for ksplit 2 (order-free sum)");
     KR_CHECK_ARG(a.part_rows == 0 || (part_in && a.part_rows >= M), "kr_linear_decode_narrow: part rows %d < M %d", a.part_rows, M);
     if (KR_EXP && pf_blocks > 0) {   // experiment builds: prefetch workgroups ride on this launch
@@ -1924,13 +1967,11 @@ static int narrow_impl(int mode, const kr_bf16* x, int64_t ldx, const float* par
             if (ksplit > 1) {  // deferred split-K: f32 slabs [ksplit][M][ldc], summed by the consumer
                 KR_CHECK_ARG(out_f32 && !out && !bias && !residual && !norm_w,
                              "kr_linear_decode_narrow: split-K writes f32 slabs only (no bias / residual / norm)");
-                return waves == 16 ? launch_narrow_direct<DEPI_PARTIAL, 16>(a, ntiles, s)
-                                   : launch_narrow_direct<DEPI_PARTIAL, 8>(a, ntiles, s);
+                return launch_narrow_direct_w<DEPI_PARTIAL>(a, ntiles, waves, s);
             }
             KR_CHECK_ARG(out || out_f32, "kr_linear_decode_narrow: PLAIN output");
             if (norm_w) return launch_narrow_norm<1, DEPI_PLAIN>(a, ntiles, s);  // x rows live in registers: 8 waves
-            return waves == 16 ? launch_narrow_direct<DEPI_PLAIN, 16>(a, ntiles, s)
-                               : launch_narrow_direct<DEPI_PLAIN, 8>(a, ntiles, s);
+            return launch_narrow_direct_w<DEPI_PLAIN>(a, ntiles, waves, s);
         case DEPI_ROPE_KV:
             if (kv8) {   // kr_linear_decode_narrow_kv8: the fp8 cache, the fused norm prologue only (the engine's <= 16-row qkv launch)
                 KR_CHECK_ARG(bias && cs_table && prompt_len && ctx_len && q_out && kv8->k && kv8->vt && kv8->scale && cs_stride > 0 && norm_w,

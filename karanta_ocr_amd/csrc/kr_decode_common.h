@@ -42,6 +42,8 @@ template <> struct WChunk<false> {
     static __device__ __forceinline__ int x_byte(int h, int fg) { return h * 64 + fg * 16; }
     // lane (fr, fg) of k-step h holds k = 32h + 8fg .. +7: block h, lane's own 16 bytes
     static __device__ __forceinline__ int xp_off(int h, int fr, int fg) { return h * 1024 + (fg * 16 + fr) * 16; }
+    // the same inside a chunk of R row slots (XP16 layout, kr_common.h): row fr < R
+    static __device__ __forceinline__ int xp16_off(int h, int fr, int fg, int R) { return h * (R * 64) + (fg * R + fr) * 16; }
 };
 template <> struct WChunk<true> {
     static constexpr int BYTES = 1024;
@@ -65,6 +67,9 @@ template <> struct WChunk<true> {
     static __device__ __forceinline__ int x_byte(int h, int fg) { return fg * 32 + h * 16; }
     // fp8 chunk: lane (fr, fg) of k-step h holds k = 16fg + 8h .. +7 = block (fg >> 1), lane group 2 (fg & 1) + h
     static __device__ __forceinline__ int xp_off(int h, int fr, int fg) { return (fg >> 1) * 1024 + ((((fg & 1) << 1) | h) * 16 + fr) * 16; }
+    static __device__ __forceinline__ int xp16_off(int h, int fr, int fg, int R) {
+        return (fg >> 1) * (R * 64) + ((((fg & 1) << 1) | h) * R + fr) * 16;
+    }
 };
 
 __device__ __forceinline__ void apply_w_scale(const float* w_scale, int n, f32x4& acc) {

@@ -8,11 +8,15 @@ A variant is a comma-separated list of Engine attribute overrides, e.g. `base`, 
 launches' weights (Engine.set_resident_budget; kinds qkv, o, down; without kinds: the engine's measured gains), e.g.
 `resident=177:qkv` = qkv alone, `resident=240:qkv@0.07+o@0.02` = the planner on those gains; `kv_cache_dtype=fp8` builds that variant's
 engine with the fp8 KV cache (`--kv-dtype fp8`: every variant that does not say otherwise), e.g. `base kv_cache_dtype=fp8` = bf16
-against fp8 cache in interleaved rounds.  The weight arena is filled with random bf16 values ON THE DEVICE (timing does not depend
-on the values), the decode state is set up directly (every sequence at context `ctx`), and each variant's decode step
+against fp8 cache in interleaved rounds; `KARANTA_<NAME>=<v>` sets that environment variable while the variant's engine is built
+AND while its launches are captured (the switches the library reads per launch, e.g. `base KARANTA_NARROW_XBOUND=1` against a
+-DKR_NARROW_XBOUND library of build_variant.py: the narrow launches with their x operand from one cache line, timing only);
+`narrow_xp=0`: o_proj / down_proj of a <= 16-row step on row-major x.  The weight arena is filled with random bf16 values ON THE
+DEVICE (timing does not depend on the values), the decode state is set up directly (every sequence at context `ctx`), and each variant's decode step
 is captured in a hipGraph and replayed `steps` times between two HIP events; rounds alternate between the variants.
 Prints per variant: median and min ms/step, and the HBM-roofline fraction of the step."""
 import argparse
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -30,6 +34,22 @@ EXPERIMENT_KEYS = {"fast_residual", "attn_fused_merge", "merge_in_o_proj", "_pre
                    "narrow_mode", "narrow_o", "defer_down", "atomic_slab", "resnorm_qkv"}   # only ExperimentEngine branches on these
 EXPERIMENT_ENV = {"KARANTA_PREFETCH", "KARANTA_FAST_RESIDUAL", "KARANTA_ATTN_FUSED", "KARANTA_MERGE_IN_OPROJ", "KARANTA_EXTRA_NULLS",
                   "KARANTA_RESNORM_QKV", *SEQUENCE_SWITCHES}      # the superseded launch sequences: the product engine refuses them
+
+
+@contextlib.contextmanager
+def spec_env(spec):
+    """The KARANTA_* assignments of a variant spec, in the environment for the duration of the block."""
+    env = dict(kv.split("=") for kv in spec.split(",") if kv.startswith("KARANTA_"))
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def fill_random(arena: torch.Tensor):
@@ -139,7 +159,7 @@ def main():
             if kv.startswith("steps_per_graph="):
                 k = int(kv.split("=")[1])
         per_graph[spec] = k
-        with torch.cuda.stream(eng.stream):
+        with spec_env(spec), torch.cuda.stream(eng.stream):
             eng._decode_step_launches(B)          # eager once (function attributes), then captured
             eng.stream.synchronize()
             if k == 1:
@@ -219,7 +239,7 @@ def main():
 
 def chains(a, engines, reset):
     """Per-launch time of single kinds of decode launches (see --chain)."""
-    from karanta_ocr_amd._lib import DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, ptr
+    from karanta_ocr_amd._lib import DEC_OUT_XP, DEC_OUT_XP16, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, ptr
     L = lib()
     B = a.batch
     e0, e1 = C.c_void_p(), C.c_void_p()
@@ -230,6 +250,8 @@ def chains(a, engines, reset):
 
         def one(kind, i, eng=eng, t=t, w=w, H=H, KVH=KVH, hd=hd):      # bound now: called after the loop has moved on
             p = f"llm.{i}."
+            xp16 = B <= 16 and eng.narrow_xp     # merge, o, gateup, down: the packed x operands of the product step (`narrow_xp=0`: row-major)
+            xpkw = {"x_packed": True} if xp16 else {}
             kc, vc = ptr(eng.kv.kcache[i]), ptr(eng.kv.vtcache[i])
             cache = eng.kv.qkv(i)           # the product's qkv launches: the cache as the engine's own step hands it over
             if kind == "qkv":
@@ -279,10 +301,13 @@ def chains(a, engines, reset):
             elif kind == "attn":
                 L.kr_attn_decode_fused(ptr(eng.d_q), kc, vc, ptr(eng.d_ctx), 0, ptr(eng.d_ws), 0, B, H, KVH, hd, eng.s_max, eng.n_split,
                                        hd ** -0.5, eng.s)
+            elif kind == "merge" and xp16:
+                L.kr_attn_decode_merge16(ptr(eng.d_ws), ptr(eng.d_o_xp), B, H, hd, eng.n_split, eng.s)
             elif kind == "merge":
                 L.kr_attn_decode_merge(ptr(eng.d_ws), ptr(eng.d_o), B, H, hd, eng.n_split, eng.s)
             elif kind == "o":
-                eng._dec_narrow(DEC_PLAIN, eng.d_o, w.view(p + "o.w"), B, out=eng.d_x, res=eng.d_x, waves=8, **eng._w8kw(p + "o.w"))
+                eng._dec_narrow(DEC_PLAIN, eng.d_o_xp if xp16 else eng.d_o, w.view(p + "o.w"), B, out=eng.d_x, res=eng.d_x, waves=8, **xpkw,
+                                **eng._w8kw(p + "o.w"))
             elif "+" in kind:                      # a group of launches per layer, e.g. attn+merge+o
                 for k in kind.split("+"):
                     eng._one(k, i)
@@ -291,14 +316,14 @@ def chains(a, engines, reset):
                 L.kr_oproj_heads(ptr(eng.d_ws), eng.n_split, ptr(w8o if w8o is not None else w.view(p + "o.w")), ptr(sco),
                                  ptr(eng.d_xacc), eng.d_xacc.stride(0), B, t.hidden_size, H, eng.s)
             elif kind == "gateup":
-                eng._dec_wide(DEC_SILU8, eng.d_x, w.view(p + "gate_up.w"), B, out=eng.d_act, norm_w=w.view(p + "ln2.w"),
-                              **eng._w8kw(p + "gate_up.w"))
+                eng._dec_wide(DEC_SILU8 | (DEC_OUT_XP16 if xp16 else 0), eng.d_x, w.view(p + "gate_up.w"), B,
+                              out=eng.d_act_xp if xp16 else eng.d_act, norm_w=w.view(p + "ln2.w"), **eng._w8kw(p + "gate_up.w"))
             elif kind == "gateup32":
                 eng._dec_wide(DEC_SILU8, None, w.view(p + "gate_up.w"), B, out=eng.d_act, norm_w=w.view(p + "ln2.w"), x_f32=eng.d_xacc,
                               x_out=eng.d_x, **eng._w8kw(p + "gate_up.w"))
             elif kind == "down":
-                eng._dec_narrow(DEC_PLAIN, eng.d_act, w.view(p + "down.w"), B, out_f32=eng.d_part, waves=eng.down_waves_small if B <= 16 else 8, ksplit=2,
-                                **eng._w8kw(p + "down.w"))
+                eng._dec_narrow(DEC_PLAIN, eng.d_act_xp if xp16 else eng.d_act, w.view(p + "down.w"), B, out_f32=eng.d_part,
+                                waves=eng.down_waves_small if B <= 16 else 8, ksplit=2, **xpkw, **eng._w8kw(p + "down.w"))
             else:
                 raise SystemExit(f"unknown chain kind {kind}")
 
@@ -311,7 +336,7 @@ def chains(a, engines, reset):
         reset(eng)
         nl = eng.cfg.text.num_layers
         for kind in a.chain.split(","):
-            with torch.cuda.stream(eng.stream):
+            with spec_env(spec), torch.cuda.stream(eng.stream):
                 for i in range(nl):
                     eng._one(kind, i)                      # eager once (function attributes)
                 eng.stream.synchronize()

@@ -32,7 +32,11 @@ from karanta_ocr_amd.engine import Engine
 
 
 class ExperimentEngine(Engine):
-    def __init__(self, *args, fast_residual: Optional[bool] = None, **kw):
+    def __init__(self, *args, fast_residual: Optional[bool] = None, narrow_xp: bool = False, **kw):
+        # narrow_xp=False says what this class does anyway: its step hands o_proj and down_proj ROW-MAJOR activations at every
+        # batch size — at <= 16 rows and the default switches the product's launches without the packed x operands of DESIGN 5-r9
+        if narrow_xp:
+            raise KarantaHipError("ExperimentEngine's sequences read row-major activations: narrow_xp=True is the product Engine")
         super().__init__(*args, **kw)
         t, dev, B = self.cfg.text, self.device, self.B
         self._extra_nulls = int(os.environ.get("KARANTA_EXTRA_NULLS", "0"))
@@ -46,6 +50,7 @@ class ExperimentEngine(Engine):
             raise KarantaHipError("KARANTA_PREFETCH / KARANTA_FAST_RESIDUAL / KARANTA_ATTN_FUSED need a library built with "
                                   "-DKR_EXPERIMENTS (csrc/tools/build_variant.py), loaded through KARANTA_HIP_LIB")
         self.family32 = False          # round 3's sequence: row-major narrow launches at every batch size
+        self.narrow_xp = False         # and row-major x operands of o_proj / down_proj at <= 16 rows
         on = lambda k: os.environ.get(k, "1") == "1"
         self.narrow_mode = on("KARANTA_NARROW")
         self.narrow_o = self.narrow_mode and on("KARANTA_NARROW_O")

@@ -22,7 +22,7 @@ import torch
 
 from . import image_processing as IP
 from . import positions as POS
-from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_NONE, EPI_SILU_MUL8, KarantaHipError, Spec, lib,
+from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_OUT_XP16, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_NONE, EPI_SILU_MUL8, KarantaHipError, Spec, lib,
                    narrow_opts, ptr)
 from . import kv_cache
 from .config import ModelConfig
@@ -275,6 +275,15 @@ class Engine:
         # down_proj split over 2 workgroups per tile with the reduction deferred to the next layer's qkv prologue
         # (K = 1536 / 2048 / 3584 only)
         self.defer_down = t.hidden_size in (1536, 2048, 3584)
+        # <= 16 rows at those widths: o_proj and down_proj read their x operand PACKED (the XP16 layout, kr_narrow_opts.x_packed:
+        # whole cache lines instead of 16 rows x 64 B per wave instruction; same bits), written by
+        # kr_attn_decode_merge16 and the gate/up launch with DEC_OUT_XP16.  Sized for 16 rows whatever the batch (8 row slots per
+        # chunk up to 8 rows, 16 above: the launches of a step agree through their M); row slots >= B are never stored by that step
+        # and never used: they hold the zeros of the allocation or an earlier step's finite values.
+        self.narrow_xp = self.defer_down and self.narrow_mode and not self.kv8
+        if self.narrow_xp:
+            self.d_o_xp = z(16, t.q_dim)
+            self.d_act_xp = z(16, t.intermediate_size)
         # gate/up and lm_head: one wave per 16-row tile (kr_linear_decode_wide) when K allows it
         self.wide_mode = t.hidden_size % 512 == 0 and t.hidden_size <= 4096
         self.wide_blocks = int(os.environ.get("KARANTA_WIDE_BLOCKS", "256"))
@@ -424,10 +433,11 @@ class Engine:
 
     def _dec_narrow(self, mode, x, W, M, out=None, out_f32=None, bias=None, norm_w=None, res=None, waves=8, ksplit=1,
                     part_in=None, x_out=None, kc=0, vc=0, w8=None, w_scale=None, zero=None, atomic_out=False,
-                    resident=False, kv8=None):
+                    resident=False, kv8=None, x_packed=False):
         """kr_linear_decode_narrow: one workgroup per tile (pair); ksplit > 1 = deferred split-K sums in out_f32.
         w8 / w_scale: the fp8 copy of W and its row scales (kr_linear_decode_narrow_fp8).  zero (an f32 tensor the launch
-        also zeroes), atomic_out, resident (w_resident: the weights stay in the Infinity Cache): the launch's kr_narrow_opts.
+        also zeroes), atomic_out, resident (w_resident: the weights stay in the Infinity Cache), x_packed (x is a packed
+        buffer, d_o_xp / d_act_xp): the launch's kr_narrow_opts.
         kc / vc (addresses) or kv8 (a kr_kv8*): the layer of the cache a qkv launch appends to, as `self.kv.qkv(i)` names it."""
         t = self.cfg.text
         N, K = W.shape
@@ -445,7 +455,8 @@ class Engine:
         args = (ptr(bias), ptr(norm_w), t.rms_norm_eps, ptr(res), res.stride(0) if res is not None else 0, ptr(out),
                 ptr(out_f32), o.stride(-2) if o is not None else 0, M, N, K, waves, ksplit, ptr(self.d_cs), self.max_new,
                 ptr(self.d_plen), ptr(self.d_ctx), ptr(self.d_q), kc, vc, t.num_heads, t.num_kv_heads, self.s_max,
-                narrow_opts(ptr(zero), zero.numel() * 4 if zero is not None else 0, atomic_out, w_resident=resident), self.s)
+                narrow_opts(ptr(zero), zero.numel() * 4 if zero is not None else 0, atomic_out, w_resident=resident,
+                            x_packed=x_packed), self.s)
         if w8 is not None:
             self.L.kr_linear_decode_narrow_fp8(*head, ptr(w8), ptr(w_scale), *args)
         else:
@@ -797,13 +808,13 @@ class Engine:
         """One plain decode step over the B slots: the layers, then lm_head and the sampler."""
         self._lm_head_and_sample(B, self._layer_launches(B))
 
-    def _gate_up(self, x, i: int, B: int, out_xp: bool = False):
+    def _gate_up(self, x, i: int, B: int, out_xp: bool = False, out_xp16: bool = False):
         """RMSNorm + gate/up + SiLU*mul of layer i over B rows of x into d_act; out_xp: in the packed layout kr_linear_decode32
-        reads."""
+        reads; out_xp16: into d_act_xp, in the packed layout the <= 16-row down_proj launch reads with x_packed."""
         w, p = self.w, f"llm.{i}."
         if self.wide_mode:
-            self._dec_wide(DEC_SILU8 | (DEC_OUT_XP if out_xp else 0), x, w.view(p + "gate_up.w"), B, out=self.d_act,
-                           norm_w=w.view(p + "ln2.w"), **self._w8kw(p + "gate_up.w"))
+            self._dec_wide(DEC_SILU8 | (DEC_OUT_XP if out_xp else DEC_OUT_XP16 if out_xp16 else 0), x, w.view(p + "gate_up.w"), B,
+                           out=self.d_act_xp if out_xp16 else self.d_act, norm_w=w.view(p + "ln2.w"), **self._w8kw(p + "gate_up.w"))
         else:
             self._dec(DEC_SILU8, x, w.view(p + "gate_up.w"), B, out=self.d_act, norm_w=w.view(p + "ln2.w"), waves=self.wv_wide)
 
@@ -826,6 +837,7 @@ class Engine:
         H, hd = t.num_heads, t.head_dim
         nl = t.num_layers
         big = B > 16                              # packed-activation family of 17..32-row batches
+        xp16 = not big and self.narrow_xp         # <= 16 rows, production widths: o_proj / down_proj on packed x (one column tile)
         x, x_other = self.d_x, self.d_x2          # residual stream: swaps buffers at every deferred reduction
         pending = False                           # down_proj's split-K sums of the previous layer waiting in d_part
         # deferred split-K: down_proj's two K ranges add into one f32 accumulator; two accumulators alternate by layer parity
@@ -862,13 +874,16 @@ class Engine:
                 x, x_other = x_other, x
             # ---- 2. split-KV attention partials, 3. their merge
             self.kv.attention(i, B, row_slot)
-            (L.kr_attn_decode_merge32 if big else L.kr_attn_decode_merge)(ptr(self.d_ws), ptr(self.d_o), B, H, hd, self.n_split, s)
+            if xp16:
+                L.kr_attn_decode_merge16(ptr(self.d_ws), ptr(self.d_o_xp), B, H, hd, self.n_split, s)
+            else:
+                (L.kr_attn_decode_merge32 if big else L.kr_attn_decode_merge)(ptr(self.d_ws), ptr(self.d_o), B, H, hd, self.n_split, s)
             # ---- 4. o_proj + residual
             if big:
                 self._dec32(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, self.o_waves, out=x, res=x, **self._w8kw(p + "o.w"))
             else:
-                self._dec_narrow(DEC_PLAIN, self.d_o, w.view(p + "o.w"), B, out=x, res=x, waves=self.o_waves,
-                                 resident=(i, "o") in self.resident, **self._w8kw(p + "o.w"))
+                self._dec_narrow(DEC_PLAIN, self.d_o_xp if xp16 else self.d_o, w.view(p + "o.w"), B, out=x, res=x, waves=self.o_waves,
+                                 resident=(i, "o") in self.resident, x_packed=xp16, **self._w8kw(p + "o.w"))
             # ---- 5. RMSNorm + gate/up + SiLU*mul (the kernel bench.py's roofline object is measured on)
             if self._prof_on:
                 # [e0][e1] gate/up [e2]: the empty bracket e0..e1 measures what two back-to-back event
@@ -876,7 +891,7 @@ class Engine:
                 (e0, e1), (e2, _) = self._prof_event_pair(), self._prof_event_pair()
                 L.kr_event_record(e0, s)
                 L.kr_event_record(e1, s)
-            self._gate_up(x, i, B, out_xp=big)
+            self._gate_up(x, i, B, out_xp=big, out_xp16=xp16)
             if self._prof_on:
                 L.kr_event_record(e2, s)
             # ---- 6. down_proj: two K ranges per tile whose sums the next layer's first launch adds to x (deferred split-K),
@@ -888,8 +903,9 @@ class Engine:
             elif big:
                 self._dec32(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, self.down_waves_small, **down, **self._w8kw(p + "down.w"))
             else:
-                self._dec_narrow(DEC_PLAIN, self.d_act, w.view(p + "down.w"), B, waves=self.down_waves_small, **down,
-                                 resident=(i, "down") in self.resident, **self._w8kw(p + "down.w"))
+                self._dec_narrow(DEC_PLAIN, self.d_act_xp if xp16 else self.d_act, w.view(p + "down.w"), B,
+                                 waves=self.down_waves_small, **down, resident=(i, "down") in self.resident, x_packed=xp16,
+                                 **self._w8kw(p + "down.w"))
             pending = defer
         return x
 
