@@ -615,8 +615,8 @@ int kr_logits_adjust(float* logits, int64_t ld_logits, int vocab, const int32_t*
 /* kr_logits_adjust over the rows of a speculative step: row r is adjusted with the table of slot row_slot[r] (clamped to
  * 0..slots-1; the tables hold [slots] rows) at the row's own n = ctx_len[r] + 1 - prompt_len[r]; logits, ctx_len, prompt_len and
  * saved are per row (`batch` = rows entries).  The adjusted row equals kr_logits_adjust's on a one-row batch with that table.  A
- * speculative step has no kr_logits_restore: nothing reads the logits behind the token choice there (log-probabilities keep a
- * step plain), and the next lm_head launch overwrites them. */
+ * speculative step that records nothing has no restore launch: nothing reads the logits behind the token choice there and the
+ * next lm_head launch overwrites them; one that records log-probabilities puts them back with kr_logits_restore_rows. */
 int kr_logits_adjust_rows(float* logits, int64_t ld_logits, int vocab, const int32_t* adj_ids, const float* adj_val,
                           const int32_t* adj_flag, const int32_t* adj_meta, const int32_t* ctx_len, const int32_t* prompt_len,
                           float* saved, int batch, const int32_t* row_slot, int slots, kr_stream s);
@@ -625,6 +625,13 @@ int kr_logits_adjust_rows(float* logits, int64_t ld_logits, int vocab, const int
  * (kr_logprobs_topk and returned logits report the unadjusted values). */
 int kr_logits_restore(float* logits, int64_t ld_logits, int vocab, const int32_t* adj_ids, const int32_t* adj_meta,
                       const float* saved, int batch, kr_stream s);
+
+/* kr_logits_restore over the rows of a speculative step, the inverse of kr_logits_adjust_rows: logits[r][id] = saved[r][e] for
+ * every entry of the table of slot row_slot[r] (clamped to 0..slots-1; n_entries and ids clamped / skipped as there), so the buffer
+ * equals what the lm_head wrote, bit for bit, on every row — kr_logprobs_topk_rows reports the unadjusted values, as
+ * kr_logprobs_topk does in a plain step.  1 <= slots <= batch <= 32. */
+int kr_logits_restore_rows(float* logits, int64_t ld_logits, int vocab, const int32_t* adj_ids, const int32_t* adj_meta,
+                           const float* saved, int batch, const int32_t* row_slot, int slots, kr_stream s);
 
 /* After kr_sample_greedy: finished[b] = 1 where the row was still live (finished[b] == 0: it appended a sampled token, not a
  * pad) and tokens[b] is one of its stop entries — from here on the row is what an EOS row is (frozen in slot mode, no
@@ -899,6 +906,42 @@ int kr_spec_controls_rows(const kr_spec* a, const kr_spec_controls* c, const int
  * counts it too (kr_sample_threshold's live is taken before the token).  A finished slot frozen in place has e = 0 (speculative
  * steps run under the freeze bit). */
 int kr_spec_controls_count(const kr_spec* a, const kr_spec_controls* c, kr_stream s);
+
+/* Log-probabilities of a speculative step: one record per token the step emitted and a plain step would have recorded, written
+ * where the plain steps would have written it.  Token j of a slot (j = 0: on the slot's own row) was chosen on the row of its draft
+ * j, and that row's logits are the bits a one-row step at that context computes, so the contract of a record is equality: it is, bit
+ * for bit, what kr_logprobs_topk writes with the same n_part and k on a one-row batch holding that logits row (same slice
+ * partition, same max / sum-exp fold order, same tie rule). */
+typedef struct kr_spec_logprobs {
+    int32_t k_top;                     /* 0..20: kr_logprobs_topk's k */
+    int32_t n_part;                    /* vocabulary slices: ceil(vocab / n_part) <= 4096, n_part <= 1024 */
+    float* part_val;                   /* [rows][n_part][max(k_top, 1)] scratch, as kr_logprobs_topk's */
+    int32_t* part_idx;
+    float* part_ms;                    /* [rows][n_part][2] */
+    float* out_lp;                     /* [hist_len][hist_batch][1 + k_stride], as kr_logprobs_topk's */
+    int32_t* out_idx;                  /* [hist_len][hist_batch][k_stride] */
+    int32_t hist_len, hist_batch, k_stride;
+    const int32_t* ctx_before;         /* [slots]: ctx_len at the start of the step (a trim's, or kr_spec_mark's) */
+} kr_spec_logprobs;
+
+/* At the head of a speculative step that records log-probabilities and carries neither kr_spec_guide_trim nor
+ * kr_spec_controls_trim (both write the array always): ctx_before[slot] = ctx_len[slot] for every slot, nothing else. */
+int kr_spec_mark(const kr_spec* a, int32_t* ctx_before, kr_stream s);
+
+/* After kr_spec_accept (draft_row == NULL: draft j of a slot on row j * slots + slot) / kr_spec_accept_rows (draft_row: kr_spec_deal's
+ * map) and kr_stop_tokens, before kr_repeat_detect.  logits [rows][ld_logits]: what the lm_head wrote (after kr_logits_restore_rows
+ * where the step adjusted them).  Per slot e = ctx_len - ctx_before tokens were emitted (0 <= e <= k + 1; a finished slot frozen in
+ * place: 0) and n_rec = e - (finished != 0) of them record: the token that finished the slot (EOS, stop entry) records nothing, as
+ * in a plain step.  For j = 0 .. n_rec - 1: the row is `slot` (j = 0), else the draft's; h = ctx_before + 1 + j - prompt_len; the
+ * token is history[h][slot]; out_lp[h][slot][0] = log p(token) (-inf for a token outside the vocabulary), out_lp[h][slot][1 + i] /
+ * out_idx[h][slot][i] = the i-th most probable token of that row (ties: lowest id), i < k_top.  Nothing is written for h outside
+ * [0, hist_len) or at or past kr_spec.hist_rows, nor for a row outside [0, rows).  The logits and partials of a row that records
+ * nothing are never read (parked rows may hold anything) and no partial is computed for it: two launches, grids (n_part,
+ * slots * (k + 1)) and slots * (k + 1), whose other workgroups return at once.
+ * KR_ERR_ARG, nothing launched: what kr_spec_accept / kr_spec_accept_rows refuse of kr_spec, a null pointer, ld_logits < vocab,
+ * slots > hist_batch, hist_len < 1, and kr_logprobs_topk's bounds on k_top, k_stride, n_part. */
+int kr_logprobs_topk_rows(const kr_spec* a, const kr_spec_logprobs* p, const int32_t* draft_row, const float* logits,
+                          int64_t ld_logits, kr_stream s);
 
 /* ------------------------------------------------------------------ runaway repetition (vLLM's repetition_detection)
  * The rule is a function of a sequence's generated tokens y[0..g] alone (the prompt never counts).  Per slot the cfg row holds

@@ -92,6 +92,7 @@ SIGNATURES = {
     "kr_logits_adjust": [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p],
     "kr_logits_adjust_rows": [c_p, i64, i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, c_p, i32, c_p],
     "kr_logits_restore": [c_p, i64, i32, c_p, c_p, c_p, i32, c_p],
+    "kr_logits_restore_rows": [c_p, i64, i32, c_p, c_p, c_p, i32, c_p, i32, c_p],
     "kr_stop_tokens": [c_p, c_p, c_p, c_p, c_p, i32, i32, c_p],
     "kr_guide_advance": [c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, c_p],
     "kr_kv_fork": [c_p, c_p, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, c_p, c_p],
@@ -113,6 +114,8 @@ SIGNATURES = {
     "kr_spec_controls_trim": [c_p, c_p, c_p, c_p],
     "kr_spec_controls_rows": [c_p, c_p, c_p, c_p],
     "kr_spec_controls_count": [c_p, c_p, c_p],
+    "kr_spec_mark": [c_p, c_p, c_p],
+    "kr_logprobs_topk_rows": [c_p, c_p, c_p, c_p, i64, c_p],
     "kr_repeat_detect": [c_p, c_p],
     "kr_linear_decode32_rows": [i32, c_p, c_p, c_p],
     "kr_attn_decode_rows": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i32, i32, i32, i32, i32, i32, f32, c_p],
@@ -202,6 +205,13 @@ class SpecControls(C.Structure):
     the three launches that let controlled requests take part in a speculative step."""
     _fields_ = [("adj_ids", c_p), ("adj_flag", c_p), ("adj_meta", c_p), ("counts", c_p), ("ld_counts", C.c_int64), ("depth", c_p),
                 ("ctx_before", c_p)]
+
+
+class SpecLogprobs(C.Structure):
+    """kr_spec_logprobs (include/karanta_hip.h): the scratch and the history kr_logprobs_topk_rows records a speculative step's
+    tokens into."""
+    _fields_ = [("k_top", C.c_int32), ("n_part", C.c_int32), ("part_val", c_p), ("part_idx", c_p), ("part_ms", c_p), ("out_lp", c_p),
+                ("out_idx", c_p), ("hist_len", C.c_int32), ("hist_batch", C.c_int32), ("k_stride", C.c_int32), ("ctx_before", c_p)]
 
 
 REP_MAX_PERIOD = 1024                   # KR_REP_MAX_PERIOD

@@ -210,15 +210,15 @@ def main(argv=None):
     ap.add_argument("--speculative-config", default=None,
                     help="the server's flag (cli.py), passed through: JSON with method \"ngram\"; --slots x (K + 1) <= 32, or "
                          "\"share_rows\": true and up to 31 slots; \"guided\": true lets the guided requests speculate, \"controls\": true those with sampling "
-                         "controls or logit adjustments")
+                         "controls or logit adjustments, \"logprobs\": true keeps speculation on a server that records log-probabilities")
     args = ap.parse_args(argv)
     spec = None
     if args.speculative_config:
-        from .cli import speculative_controls, speculative_fields, speculative_guided
+        from .cli import speculative_controls, speculative_fields, speculative_guided, speculative_logprobs
         try:
-            # SpecConfig's fields, share_rows, guided and controls among them
+            # SpecConfig's fields, share_rows, guided, controls and logprobs among them
             spec = (*speculative_fields(args.speculative_config, args.slots), speculative_guided(args.speculative_config),
-                    speculative_controls(args.speculative_config))
+                    speculative_controls(args.speculative_config), speculative_logprobs(args.speculative_config))
         except ValueError as e:
             ap.error(str(e))
     if args.gpus is not None:

@@ -21,6 +21,7 @@ LIB = os.path.join(HERE, "libkaranta_hip.so")
 SOURCES = ["kr_api.hip", "kr_elementwise.hip", "kr_gemm.hip", "kr_attention.hip", "kr_decode.hip", "kr_decode32.hip", "kr_attn_decode.hip", "kr_sample.hip", "kr_spec.hip", "kr_repeat.hip", "kr_logit_adjust.hip", "kr_kv_fork.hip", "kr_kv_fp8.hip",
            "kr_image.hip", "kr_guide.hip", "kr_comm.hip", "kr_selftest.hip"]
 HEADERS = [os.path.join(CSRC, "kr_common.h"), os.path.join(CSRC, "kr_decode_common.h"), os.path.join(CSRC, "kr_spec_deal.h"),
+           os.path.join(CSRC, "kr_logprobs.h"),
            os.path.join(os.path.dirname(HERE), "include", "karanta_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=fast",

@@ -86,8 +86,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "(--max-num-seqs x (K + 1) <= 32, or with \"share_rows\": true any --max-num-seqs up to 31: the rows of a "
                          "step the sequences leave free are dealt to the drafts; with \"guided\": true requests with guided_regex / "
                          "response_format speculate too, their drafts checked against the pattern; with \"controls\": true so do "
-                         "requests with top_k / top_p / min_p, penalties, logit_bias, min_tokens or stop_token_ids; not with "
-                         "--max-logprobs or --static-batching)")
+                         "requests with top_k / top_p / min_p, penalties, logit_bias, min_tokens or stop_token_ids; with \"logprobs\": true "
+                         "a server started with --max-logprobs speculates too, every emitted token recorded as without it; not with "
+                         "--max-logprobs unless that key is set, nor with --static-batching)")
     ap.add_argument("--repetition-detection", default=None,
                     help="the default of the requests without a repetition_detection field, as JSON: {\"max_pattern_size\": B, "
                          "\"min_pattern_size\": A, \"min_count\": C, \"min_span\": M} — a sequence whose last C x p tokens are C "
@@ -181,6 +182,21 @@ def speculative_controls(text: str) -> bool:
     return controls
 
 
+def speculative_logprobs(text: str) -> bool:
+    """SpecConfig.logprobs from --speculative-config: the key "logprobs", true or false (absent: false); ValueError with the reason."""
+    import json
+    try:
+        d = json.loads(text)
+    except ValueError as e:
+        raise ValueError(f"--speculative-config is not JSON: {e}") from e
+    if not isinstance(d, dict):
+        raise ValueError("--speculative-config must be a JSON object")
+    logprobs = d.get("logprobs", False)
+    if not isinstance(logprobs, bool):
+        raise ValueError(f"--speculative-config: logprobs must be true or false, not {logprobs!r}")
+    return logprobs
+
+
 def parse_args(argv: Optional[List[str]] = None):
     ap = build_parser()
     args, unknown = ap.parse_known_args(argv)
@@ -202,8 +218,13 @@ def parse_args(argv: Optional[List[str]] = None):
     if args.max_num_batched_tokens is not None and args.max_num_batched_tokens < args.max_model_len:
         ap.error("--max-num-batched-tokens must be >= --max-model-len (the longest prompt one request may carry)")
     args.speculative, args.speculative_share_rows, args.speculative_guided, args.speculative_controls = None, False, False, False
+    args.speculative_logprobs = False
     if args.speculative_config is not None:
-        if args.max_logprobs is not None:
+        try:
+            args.speculative_logprobs = speculative_logprobs(args.speculative_config)
+        except ValueError as e:
+            ap.error(str(e))
+        if args.max_logprobs is not None and not args.speculative_logprobs:
             ap.error("--speculative-config cannot be combined with --max-logprobs: a draft row records no log-probabilities")
         if args.static_batching:
             ap.error("--speculative-config needs the slot scheduler: not with --static-batching")
@@ -300,11 +321,13 @@ def make_server(args, log=print):
     spec, share = getattr(args, "speculative", None), bool(getattr(args, "speculative_share_rows", False))
     spec_guided = bool(getattr(args, "speculative_guided", False))
     spec_controls = bool(getattr(args, "speculative_controls", False))
+    spec_logprobs = bool(getattr(args, "speculative_logprobs", False))
     if spec is not None:
         log(f"speculative decoding: ngram, {spec[0]} draft tokens per step, prompt lookup {spec[1]}..{spec[2]}"
             + (", draft rows shared between the sequences" if share else "")
             + (", guided requests included" if spec_guided else "")
-            + (", requests with sampling controls or logit adjustments included" if spec_controls else ""))
+            + (", requests with sampling controls or logit adjustments included" if spec_controls else "")
+            + (", log-probabilities recorded in speculative steps" if spec_logprobs else ""))
     # ... speculative: every step past the limit may emit K + 1 tokens, and the draft rows write K cache rows ahead
     slack = 1 + 16 * (spec[0] + 1 if spec else 1) + (spec[0] if spec else 0)
     kv_fp8 = kv_cache_dtype_name(getattr(args, "kv_cache_dtype", "auto")) == "fp8"
@@ -317,7 +340,8 @@ def make_server(args, log=print):
                  max_patches=max_patches, max_prompt_tokens=max_prompt_tokens,
                  weight_dtype=weight_dtype, fp8_activations=bool(getattr(args, "fp8_activations", False)) or None,
                  kv_cache_dtype=getattr(args, "kv_cache_dtype", "auto"), **calc,
-                 **({"speculative": SpecConfig(*spec, share_rows=share, guided=spec_guided, controls=spec_controls)} if spec else {}))
+                 **({"speculative": SpecConfig(*spec, share_rows=share, guided=spec_guided, controls=spec_controls,
+                                                    logprobs=spec_logprobs)} if spec else {}))
     # one server: read the checkpoint.  A launch.py group: rank 0 reads it ONCE, the arena goes to the other GPUs over
     # RCCL / xGMI (north_star: "RCCL broadcast of weights over xGMI"); a failure stops every server of the group
     info = load_or_receive_weights(eng.w, rank, world, lambda: eng.load_weights(load_checkpoint(args.model_dir)[1]),

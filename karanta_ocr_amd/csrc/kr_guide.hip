@@ -11,13 +11,9 @@
 //   logprob_partial_kernel     per vocabulary slice (LDS resident): max, sum exp, top-k by k rounds of block argmax
 //   logprob_merge_kernel       per sequence: log-sum-exp, log-prob of the sampled token, merged top-k -> history
 // All of it is integer / selection work except the log-sum-exp (fp32, expf / logf).
-#include "kr_common.h"
+#include "kr_logprobs.h"
 
 namespace {
-
-__device__ __forceinline__ void better_lp(float& bv, int& bi, float v, int i) {
-    if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-}
 
 // one thread per (state, token): grid (mask_words * 32 / 256, n_states)
 __global__ void __launch_bounds__(256) guide_build_masks_kernel(const uint16_t* __restrict__ trans,
@@ -63,65 +59,14 @@ __global__ void __launch_bounds__(64) guide_advance_kernel(const int32_t* __rest
 }
 
 // ---------------------------------------------------------------- log-probabilities
-constexpr int LP_MAX_K = 20;       // OpenAI's top_logprobs bound
-constexpr int LP_SLICE = 4096;     // floats of one vocabulary slice held in LDS
-constexpr size_t LP_MERGE_LDS = 160 * 1024 - 1024;   // largest candidate table of the merge (bytes of dynamic LDS)
-
-__device__ __forceinline__ void block_argmax(float& bv, int& bi, float* s_v, int* s_i) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        better_lp(bv, bi, ov, oi);
-    }
-    __syncthreads();                 // s_v / s_i of the previous round have been read by everyone
-    if (lane == 0) { s_v[wave] = bv; s_i[wave] = bi; }
-    __syncthreads();
-    bv = s_v[0]; bi = s_i[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) better_lp(bv, bi, s_v[w], s_i[w]);
-}
-
+// (the arithmetic: kr_logprobs.h, shared with kr_logprobs_topk_rows of a speculative step)
 // grid (n_part, batch); part_val/part_idx [batch][n_part][k], part_ms [batch][n_part][2] = (max, sum exp(v - max))
 __global__ void __launch_bounds__(256) logprob_partial_kernel(const float* __restrict__ logits, int64_t ld, int vocab, int k,
                                                               float* __restrict__ part_val, int32_t* __restrict__ part_idx,
                                                               float* __restrict__ part_ms) {
-    __shared__ float sl[LP_SLICE];
-    __shared__ float s_v[4];
-    __shared__ int s_i[4];
-    const int p = blockIdx.x, n_part = gridDim.x, b = blockIdx.y, tid = threadIdx.x;
-    const int per = (vocab + n_part - 1) / n_part;          // <= LP_SLICE (checked by the launcher)
-    const int i0 = p * per, n = max(0, min(vocab, i0 + per) - i0);
-    const float* row = logits + (int64_t)b * ld + i0;
-    float mx = -INFINITY;
-    for (int i = tid; i < n; i += 256) { const float v = row[i]; sl[i] = v; mx = fmaxf(mx, v); }
-    int dummy = 0;
-    block_argmax(mx, dummy, s_v, s_i);                       // (value only; the index is unused)
-    float se = 0.f;
-    for (int i = tid; i < n; i += 256) se += expf(sl[i] - mx);
-    se = wave_sum(se);
-    __shared__ float s_se[4];
-    if ((tid & 63) == 0) s_se[tid >> 6] = se;
-    __syncthreads();
-    if (tid == 0) {
-        part_ms[((int64_t)b * n_part + p) * 2] = mx;
-        part_ms[((int64_t)b * n_part + p) * 2 + 1] = n > 0 ? s_se[0] + s_se[1] + s_se[2] + s_se[3] : 0.f;
-    }
-    for (int r = 0; r < k; ++r) {
-        float bv = -INFINITY;
-        int bi = 0x7fffffff;
-        for (int i = tid; i < n; i += 256) {
-            const float v = sl[i];
-            if (v != -INFINITY) better_lp(bv, bi, v, i);     // retired elements never come back
-        }
-        block_argmax(bv, bi, s_v, s_i);
-        if (tid == 0) {
-            part_val[((int64_t)b * n_part + p) * k + r] = bv;
-            part_idx[((int64_t)b * n_part + p) * k + r] = bi == 0x7fffffff ? 0x7fffffff : i0 + bi;
-        }
-        if (bi != 0x7fffffff && tid == (bi & 255)) sl[bi] = -INFINITY;   // the owner of that element retires it
-    }
+    const int p = blockIdx.x, n_part = gridDim.x, b = blockIdx.y;
+    const int64_t bp = (int64_t)b * n_part + p;
+    logprob_partial_body(logits + (int64_t)b * ld, vocab, k, p, n_part, part_val + bp * k, part_idx + bp * k, part_ms + bp * 2);
 }
 
 // one workgroup per sequence.  out_lp [hist][batch][1 + k]: log-prob of the sampled token, then of the top-k;
@@ -138,48 +83,13 @@ __global__ void __launch_bounds__(256) logprob_merge_kernel(const float* __restr
                                                             float* __restrict__ out_lp, int32_t* __restrict__ out_idx,
                                                             int hist_len, int hist_batch, int k_stride) {
     extern __shared__ float cand[];                          // n_part * k values, then as many indices
-    __shared__ float s_v[4];
-    __shared__ int s_i[4];
-    const int b = blockIdx.x, tid = threadIdx.x, nc = n_part * k;
-    int* cidx = reinterpret_cast<int*>(cand + nc);
+    const int b = blockIdx.x, nc = n_part * k;
     if (finished[b]) return;                                 // uniform per workgroup
     const int h = ctx_len[b] - prompt_len[b];
     if (h < 0 || h >= hist_len) return;
-    for (int i = tid; i < nc; i += 256) { cand[i] = part_val[(int64_t)b * nc + i]; cidx[i] = part_idx[(int64_t)b * nc + i]; }
-    float mx = -INFINITY;
-    for (int i = tid; i < n_part; i += 256) mx = fmaxf(mx, part_ms[((int64_t)b * n_part + i) * 2]);
-    int dummy = 0;
-    block_argmax(mx, dummy, s_v, s_i);
-    float se = 0.f;
-    for (int i = tid; i < n_part; i += 256) {
-        const float m = part_ms[((int64_t)b * n_part + i) * 2], sv = part_ms[((int64_t)b * n_part + i) * 2 + 1];
-        if (sv > 0.f) se += sv * expf(m - mx);
-    }
-    se = wave_sum(se);
-    __shared__ float s_se[4];
-    if ((tid & 63) == 0) s_se[tid >> 6] = se;
-    __syncthreads();
-    const float lse = mx + logf(s_se[0] + s_se[1] + s_se[2] + s_se[3]);
-    float* lp = out_lp + ((int64_t)h * hist_batch + b) * (1 + k_stride);
-    int32_t* ix = out_idx + ((int64_t)h * hist_batch + b) * k_stride;
-    if (tid == 0) {
-        const int tok = tokens[b];
-        lp[0] = (tok >= 0 && tok < vocab) ? logits[(int64_t)b * ld + tok] - lse : -INFINITY;
-    }
-    for (int r = 0; r < k; ++r) {
-        float bv = -INFINITY;
-        int bi = 0x7fffffff, bslot = -1;
-        for (int i = tid; i < nc; i += 256) {
-            const float v = cand[i];
-            const int id = cidx[i];
-            if (v != -INFINITY && (v > bv || (v == bv && id < bi))) { bv = v; bi = id; bslot = i; }
-        }
-        // block argmax on (value, token id); the winning candidate slot is found again by its unique token id
-        block_argmax(bv, bi, s_v, s_i);
-        if (tid == 0) { lp[1 + r] = bv - lse; ix[r] = bi; }
-        if (bslot >= 0 && cidx[bslot] == bi && cand[bslot] == bv) cand[bslot] = -INFINITY;
-        __syncthreads();
-    }
+    logprob_merge_body(part_val + (int64_t)b * nc, part_idx + (int64_t)b * nc, part_ms + (int64_t)b * n_part * 2, n_part, k,
+                       logits + (int64_t)b * ld, vocab, tokens[b], out_lp + ((int64_t)h * hist_batch + b) * (1 + k_stride),
+                       out_idx + ((int64_t)h * hist_batch + b) * k_stride, cand);
 }
 
 }  // namespace
@@ -214,13 +124,9 @@ extern "C" int kr_logprobs_topk(const float* logits, int64_t ld_logits, int voca
     KR_CHECK_ARG(logits && part_val && part_idx && part_ms && tokens && ctx_len && prompt_len && finished && out_lp && out_idx,
                  "kr_logprobs_topk: null pointer");
     KR_CHECK_ARG(vocab > 0 && ld_logits >= vocab && batch > 0 && batch <= hist_batch && hist_len > 0, "kr_logprobs_topk: bad sizes");
-    KR_CHECK_ARG(k >= 0 && k <= LP_MAX_K && k <= k_stride, "kr_logprobs_topk: k must be in 0..%d and <= k_stride", LP_MAX_K);
-    KR_CHECK_ARG(n_part > 0 && n_part <= 1024 && (vocab + n_part - 1) / n_part <= LP_SLICE,
-                 "kr_logprobs_topk: a vocabulary slice (vocab / n_part) must fit %d floats", LP_SLICE);
-    // the merge's candidate table (n_part * k values and ids) next to its 48 static bytes: checked before anything is launched,
-    // and the kernel's dynamic-LDS limit (64 KiB by default) raised to what the check accepts
+    if (const int rc = logprob_check_sizes("kr_logprobs_topk", vocab, k, k_stride, n_part)) return rc;
+    // the kernel's dynamic-LDS limit (64 KiB by default) raised to what the check accepts
     const size_t lds = (size_t)n_part * (k > 0 ? k : 1) * 8;
-    KR_CHECK_ARG(lds <= LP_MERGE_LDS, "kr_logprobs_topk: n_part * k candidates exceed the LDS");
     static KrPerDeviceOnce attr;
     if (attr.need()) {
         KR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&logprob_merge_kernel),

@@ -6,8 +6,10 @@
 //                          kr_logprobs_topk and return_logits
 //   stop_tokens_kernel     after kr_sample_greedy: a live row whose token is one of its stop entries finishes as on EOS
 //   logits_adjust_rows_kernel  the adjust body over the rows of a speculative step (ROWS): a row is adjusted with the table of its
-//                          slot at the row's own token index; saved is per row.  A speculative step has no restore launch: nothing
-//                          reads the logits behind the token choice while log-probabilities keep steps plain
+//                          slot at the row's own token index; saved is per row
+//   logits_restore_rows_kernel  its inverse, for a speculative step that records log-probabilities (kr_logprobs_topk_rows reads the
+//                          lm_head's bits); a step that records nothing has no restore launch: nothing reads the
+//                          logits behind the token choice and the next lm_head launch overwrites them
 // Tables, per row, KR_ADJ_CAP entries wide, every id at most once in a row (the host merges bias keys, stop ids and EOS ids):
 // adj_ids / adj_val / adj_flag (bit 0 = stop entry) and adj_meta[b] = {n_entries, min_tokens, 0, 0}.  One wave per row, the
 // entries strided over its lanes; unique ids: plain loads and stores, no atomics.  n_entries is clamped to the table width
@@ -77,6 +79,23 @@ __global__ void __launch_bounds__(64) logits_restore_kernel(float* __restrict__ 
     }
 }
 
+// row b is restored with the table of its slot (clamped as in logits_adjust_body<true>); saved is per row
+__global__ void __launch_bounds__(64) logits_restore_rows_kernel(float* __restrict__ logits, int64_t ld, int vocab,
+                                                                 const int32_t* __restrict__ adj_ids,
+                                                                 const int32_t* __restrict__ adj_meta, const float* __restrict__ saved,
+                                                                 const int32_t* __restrict__ row_slot, int slots) {
+    const int b = blockIdx.x;
+    const int sl = min(max(row_slot[b], 0), slots - 1);
+    const int n = adj_entries(adj_meta + (int64_t)sl * ADJ_META);
+    float* row = logits + (int64_t)b * ld;
+    const int64_t t0 = (int64_t)sl * KR_ADJ_CAP, s0 = (int64_t)b * KR_ADJ_CAP;
+    for (int e = threadIdx.x; e < n; e += 64) {
+        const int id = adj_ids[t0 + e];
+        if (id < 0 || id >= vocab) continue;
+        row[id] = saved[s0 + e];
+    }
+}
+
 __global__ void __launch_bounds__(64) stop_tokens_kernel(const int32_t* __restrict__ tokens, const int32_t* __restrict__ adj_ids,
                                                          const int32_t* __restrict__ adj_flag, const int32_t* __restrict__ adj_meta,
                                                          int32_t* __restrict__ finished) {
@@ -124,6 +143,17 @@ extern "C" int kr_logits_restore(float* logits, int64_t ld_logits, int vocab, co
     KR_CHECK_ARG(logits && adj_ids && adj_meta && saved, "kr_logits_restore: null pointer");
     KR_CHECK_ARG(vocab > 0 && ld_logits >= vocab && batch > 0, "kr_logits_restore: bad sizes");
     logits_restore_kernel<<<batch, 64, 0, kr_hs(s)>>>(logits, ld_logits, vocab, adj_ids, adj_meta, saved);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_logits_restore_rows(float* logits, int64_t ld_logits, int vocab, const int32_t* adj_ids, const int32_t* adj_meta,
+                                      const float* saved, int batch, const int32_t* row_slot, int slots, kr_stream s) {
+    KR_CHECK_ARG(logits && adj_ids && adj_meta && saved && row_slot, "kr_logits_restore_rows: null pointer");
+    KR_CHECK_ARG(vocab > 0 && ld_logits >= vocab && batch > 0, "kr_logits_restore_rows: bad sizes");
+    KR_CHECK_ARG(slots >= 1 && slots <= batch && batch <= 32, "kr_logits_restore_rows: slots=%d rows=%d (1 <= slots <= rows <= 32)",
+                 slots, batch);
+    logits_restore_rows_kernel<<<batch, 64, 0, kr_hs(s)>>>(logits, ld_logits, vocab, adj_ids, adj_meta, saved, row_slot, slots);
     KR_CHECK_LAUNCH();
     return KR_OK;
 }

@@ -16,7 +16,10 @@
 // Controlled slots (kr_spec_controls_trim -> kr_spec_controls_rows -> ... -> kr_stop_tokens -> kr_spec_controls_count, around either
 // layout and beside the guide's three): a draft that is a stop entry of its slot ends the slot's drafts, every row learns how many
 // drafts lie in front of it (the sampler's row-mapped passes add them to the slot's output counts), the counts follow the emitted tokens.
+// Recorded slots (kr_spec_mark -> ... -> kr_logprobs_topk_rows, around either layout and beside the guide's and the controls' launches):
+// every token the step emitted gets the log-probability record a plain step would have written for it, from the logits row that chose it.
 #include "kr_decode_common.h"
+#include "kr_logprobs.h"
 #include "kr_spec_deal.h"
 
 namespace {
@@ -493,7 +496,88 @@ int spec_controls_check(const kr_spec* a, const kr_spec_controls* c, const char*
     return KR_OK;
 }
 
+// ---------------------------------------------------------------- log-probabilities of a speculative step (kr_spec_logprobs)
+// One record per token the step emitted and a plain step would have recorded: token j of a slot was chosen on the row of draft j
+// (j = 0: the slot's own row), and a draft row's logits are the bits a one-row step at that context computes, so the record is
+// kr_logprobs_topk's on a one-row batch holding that row (kr_logprobs.h: the same two bodies).
+//   spec_mark_kernel            ctx_before = ctx_len where neither trim ran
+//   spec_logprob_partial_kernel grid (n_part, slots * (k + 1)): the slices of the rows that record; every other workgroup returns at once
+//   spec_logprob_merge_kernel   grid slots * (k + 1): the record of (slot, j) at its token's history index
+__global__ void __launch_bounds__(64) spec_mark_kernel(const int32_t* __restrict__ ctx_len, int32_t* __restrict__ ctx_before, int slots) {
+    const int slot = threadIdx.x;
+    if (slot < slots) ctx_before[slot] = ctx_len[slot];
+}
+
+// Whether token j of `slot` records, on which row and at which history index (uniform per workgroup).  e tokens were emitted; the
+// one that finished the slot (EOS, stop entry) records nothing, as in a plain step; a slot that idled (finished, frozen) has e = 0.
+__device__ __forceinline__ bool spec_logprob_record(const kr_spec& a, const kr_spec_logprobs& p, const int32_t* __restrict__ draft_row,
+                                                    int slot, int j, int& row, int& h) {
+    const int before = p.ctx_before[slot];
+    const int e = max(0, min(a.k + 1, a.ctx_len[slot] - before));
+    const int n_rec = e - (a.finished[slot] != 0 ? 1 : 0);
+    if (j >= n_rec) return false;
+    row = j == 0 ? slot : draft_row == nullptr ? j * a.slots + slot : draft_row[slot * a.k + j - 1];
+    if (row < 0 || row >= a.rows) return false;
+    h = before + 1 + j - a.prompt_len[slot];
+    return h >= 0 && h < p.hist_len && h < a.hist_rows;      // (the token is read from history[h]: kr_spec_accept wrote none past it)
+}
+
+__global__ void __launch_bounds__(256) spec_logprob_partial_kernel(const kr_spec a, const kr_spec_logprobs p,
+                                                                   const int32_t* __restrict__ draft_row,
+                                                                   const float* __restrict__ logits, int64_t ld) {
+    const int part = blockIdx.x, slot = blockIdx.y / (a.k + 1), j = blockIdx.y - slot * (a.k + 1);
+    int row, h;
+    if (!spec_logprob_record(a, p, draft_row, slot, j, row, h)) return;
+    const int64_t bp = (int64_t)row * p.n_part + part;
+    logprob_partial_body(logits + (int64_t)row * ld, a.vocab, p.k_top, part, p.n_part, p.part_val + bp * p.k_top,
+                         p.part_idx + bp * p.k_top, p.part_ms + bp * 2);
+}
+
+__global__ void __launch_bounds__(256) spec_logprob_merge_kernel(const kr_spec a, const kr_spec_logprobs p,
+                                                                 const int32_t* __restrict__ draft_row,
+                                                                 const float* __restrict__ logits, int64_t ld) {
+    extern __shared__ float cand[];                          // n_part * k_top values, then as many indices
+    const int slot = blockIdx.x / (a.k + 1), j = blockIdx.x - slot * (a.k + 1);
+    int row, h;
+    if (!spec_logprob_record(a, p, draft_row, slot, j, row, h)) return;
+    const int k = p.k_top, nc = p.n_part * k;
+    const int tok = a.history[(int64_t)h * a.hist_stride + slot];
+    const int64_t o = (int64_t)h * p.hist_batch + slot;
+    logprob_merge_body(p.part_val + (int64_t)row * nc, p.part_idx + (int64_t)row * nc, p.part_ms + (int64_t)row * p.n_part * 2, p.n_part,
+                       k, logits + (int64_t)row * ld, a.vocab, tok, p.out_lp + o * (1 + p.k_stride), p.out_idx + o * p.k_stride, cand);
+}
+
 }  // namespace
+
+extern "C" int kr_spec_mark(const kr_spec* a, int32_t* ctx_before, kr_stream s) {
+    if (const int rc = spec_check(a, "kr_spec_mark", true)) return rc;
+    KR_CHECK_ARG(ctx_before, "kr_spec_mark: null ctx_before");
+    spec_mark_kernel<<<1, 64, 0, kr_hs(s)>>>(a->ctx_len, ctx_before, a->slots);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
+
+extern "C" int kr_logprobs_topk_rows(const kr_spec* a, const kr_spec_logprobs* p, const int32_t* draft_row, const float* logits,
+                                     int64_t ld_logits, kr_stream s) {
+    if (const int rc = spec_check(a, "kr_logprobs_topk_rows", draft_row != nullptr)) return rc;
+    KR_CHECK_ARG(p, "kr_logprobs_topk_rows: null log-probability args");
+    KR_CHECK_ARG(logits && p->part_val && p->part_idx && p->part_ms && p->out_lp && p->out_idx && p->ctx_before,
+                 "kr_logprobs_topk_rows: null pointer");
+    KR_CHECK_ARG(ld_logits >= a->vocab && a->slots <= p->hist_batch && p->hist_len > 0, "kr_logprobs_topk_rows: bad sizes");
+    if (const int rc = logprob_check_sizes("kr_logprobs_topk_rows", a->vocab, p->k_top, p->k_stride, p->n_part)) return rc;
+    const size_t lds = (size_t)p->n_part * (p->k_top > 0 ? p->k_top : 1) * 8;
+    static KrPerDeviceOnce attr;
+    if (attr.need()) {
+        KR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&spec_logprob_merge_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)LP_MERGE_LDS));
+    }
+    const int n_tok = a->slots * (a->k + 1);
+    spec_logprob_partial_kernel<<<dim3(p->n_part, n_tok), 256, 0, kr_hs(s)>>>(*a, *p, draft_row, logits, ld_logits);
+    KR_CHECK_LAUNCH();
+    spec_logprob_merge_kernel<<<n_tok, 256, lds, kr_hs(s)>>>(*a, *p, draft_row, logits, ld_logits);
+    KR_CHECK_LAUNCH();
+    return KR_OK;
+}
 
 extern "C" int kr_spec_controls_trim(const kr_spec* a, const kr_spec_controls* c, int32_t* n_count, kr_stream s) {
     if (const int rc = spec_controls_check(a, c, "kr_spec_controls_trim", true)) return rc;

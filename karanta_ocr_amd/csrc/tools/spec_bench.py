@@ -35,6 +35,14 @@ Random weights (timing only), context about 1900, graphs replayed as the engine 
     step — the legs the parent can run; then, on this tree, the controlled speculative step (kr_spec_controls_trim / _rows / _count
     and the three row-mapped logit passes) with t_spec / t_plain for controlled steps and its break-even.
 
+    python karanta_ocr_amd/csrc/tools/spec_bench.py --logprobs [--out profiles/r10_spec_logprobs.json]
+
+  * --logprobs: the leg for SpecConfig(logprobs=True): the 2B decoder with 8 slots x K = 3 and with 24 slots on shared rows, every slot
+    sampling at one temperature, k = 5 records, scripted full-acceptance drafts.  Per layout one engine runs four graphs in turn, twice
+    over: the plain and the speculative step without records, then both with them (kr_logprobs_topk; kr_spec_mark and
+    kr_logprobs_topk_rows).  Reported: the speculative step with records over the same step without them, and over the plain step
+    with records, whose excess over 1 is the break-even acceptance of a server that records.
+
 Every measurement is a child process under a time limit of its own; a child that fails ends the run."""
 import argparse
 import ctypes as C
@@ -57,14 +65,15 @@ def _token_bytes(i: int) -> bytes:
     return bytes(base + (i // 10 ** p) % 10 for p in range(3))
 
 
-def _engine(model, B, spec_k=0, share=False, guided=False, controls=False):
+def _engine(model, B, spec_k=0, share=False, guided=False, controls=False, logprobs=False):
     import torch
     from karanta_ocr_amd.config import CONFIGS
     from karanta_ocr_amd.engine import Engine
     kw = {}
     if spec_k:
         from karanta_ocr_amd.engine import SpecConfig
-        kw["speculative"] = (SpecConfig(spec_k, share_rows=share, controls=True) if controls
+        kw["speculative"] = (SpecConfig(spec_k, share_rows=share, logprobs=True) if logprobs
+                             else SpecConfig(spec_k, share_rows=share, controls=True) if controls
                              else SpecConfig(spec_k, share_rows=share, guided=True) if guided
                              else SpecConfig(spec_k, share_rows=True) if share else SpecConfig(spec_k))
     n_new = STEPS * (ROUNDS + 3) * (spec_k + 1) + 16
@@ -388,6 +397,43 @@ def child_controls(model, B, K, share):
     return out
 
 
+LOGPROBS_K = 5          # --logprobs: the reference's bulk requests ask for top_logprobs 5
+
+
+def child_logprobs(model, B, K, share):
+    """SpecConfig(logprobs=True): one engine's plain and speculative step at scripted full acceptance, without records and with them,
+    the four graphs in turn and the turn twice, so that each figure has a neighbour taken minutes apart on the same process."""
+    import numpy as np
+    eng = _engine(model, B, K, share, logprobs=True)
+    _control_slots(eng, False)
+    # the log-probability history is allocated once (no graph exists yet); from here on the switch alone picks the graphs
+    eng._enter_mode(eng._req_max_new, ignore_eos=True, freeze_finished=True, want_logits=False, caps=eng._caps, step=eng._step,
+                    logprobs=LOGPROBS_K)
+    out = {"model": model, "slots": B, "K": K, "rows": eng.rows, "share_rows": bool(share), "ctx": CTX, "top_logprobs": LOGPROBS_K,
+           "temperature": TEMPERATURE, "turns": []}
+    for _ in range(2):
+        turn = {}
+        for name, k in (("without_records", None), ("with_records", LOGPROBS_K)):
+            eng._logprobs = k
+            r = _full_acceptance_pair(eng, K)
+            r.pop("tokens")
+            turn[name] = r
+        out["turns"].append(turn)
+    med = lambda name, key: float(np.median([t[name][key] for t in out["turns"]]))
+    for name in ("without_records", "with_records"):
+        out[name] = {"plain_ms": med(name, "plain_ms"), "spec_ms": med(name, "spec_ms"),
+                     "plain_turns_ms": [t[name]["plain_ms"] for t in out["turns"]], "spec_turns_ms": [t[name]["spec_ms"] for t in out["turns"]],
+                     "accepted_per_slot_step": med(name, "accepted_per_slot_step"),
+                     "tokens_equal_plain": all(t[name]["tokens_equal_plain"] for t in out["turns"])}
+    out["spec_with_records_over_spec_without"] = out["with_records"]["spec_ms"] / out["without_records"]["spec_ms"]
+    out["plain_with_records_over_plain_without"] = out["with_records"]["plain_ms"] / out["without_records"]["plain_ms"]
+    out["t_spec_over_t_plain_with_records"] = out["with_records"]["spec_ms"] / out["with_records"]["plain_ms"]
+    out["t_spec_over_t_plain_without_records"] = out["without_records"]["spec_ms"] / out["without_records"]["plain_ms"]
+    out["break_even_accepted_per_slot_step_with_records"] = out["t_spec_over_t_plain_with_records"] - 1
+    eng.close()
+    return out
+
+
 def run_child(args, tree, limit, sizes=None):
     """This file as a child process with `tree`'s package on the path (the child imports karanta_ocr_amd from its working directory).
     sizes: the plain child's batch sizes, for a tree whose engine this file's --sizes is to drive."""
@@ -527,6 +573,25 @@ def main_controls(a):
     return 0
 
 
+def main_logprobs(a):
+    """8 slots x K = 3 and 24 slots on shared rows, k = 5 records: one child per layout (--layouts picks a subset; the report file is
+    read back and extended)."""
+    report = {"context": CTX, "steps_per_round": STEPS, "rounds": ROUNDS, "weights": "random bf16 (timing only)", "K": 3,
+              "top_logprobs": LOGPROBS_K, "layouts": {}}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            report = json.load(f)
+    for name in a.layouts.split(","):
+        B, share = {"8x3": (8, False), "24shared": (24, True)}[name]
+        report["layouts"][name] = run_child(["--child", "logprobs", "--slots", str(B), "--k", "3"] + (["--share"] if share else []), ROOT, 420)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(report, f, indent=1)
+            f.write("\n")
+    print(json.dumps(report, indent=1))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", default=None)
@@ -541,7 +606,9 @@ def main():
                                                           "(profiles/r07_spec_guided.json)")
     ap.add_argument("--controls", action="store_true", help="the controls leg alone: 8 slots x K = 3 and 24 slots shared, every slot with "
                                                             "top_p and a repetition penalty (profiles/r08_spec_controls.json)")
-    ap.add_argument("--layouts", default="8x3,24shared", help="(--controls) which of the two layouts to run")
+    ap.add_argument("--logprobs", action="store_true", help="the log-probability leg alone: 8 slots x K = 3 and 24 slots shared, k = 5 "
+                                                            "records (profiles/r10_spec_logprobs.json)")
+    ap.add_argument("--layouts", default="8x3,24shared", help="(--controls, --logprobs) which of the two layouts to run")
     ap.add_argument("--share", action="store_true", help="(child) SpecConfig(share_rows=True)")
     ap.add_argument("--sizes", default="8,32", help="(child plain) the batch sizes")
     ap.add_argument("--out", default=None)
@@ -554,12 +621,15 @@ def main():
                else child_controls_plain(a.model, a.slots) if a.child == "controls-plain"
                else child_pair(a.model, a.slots, a.k, a.share) if a.child == "pair"
                else child_controls(a.model, a.slots, a.k, a.share) if a.child == "controls"
+               else child_logprobs(a.model, a.slots, a.k, a.share) if a.child == "logprobs"
                else child_spec(a.model, a.slots, a.k, a.share))
         print(json.dumps(res), flush=True)
         return 0
     import numpy as np
-    a.out = a.out or os.path.join(ROOT, "profiles", "r08_spec_controls.json" if a.controls else "r07_spec_guided.json" if a.guided else
+    a.out = a.out or os.path.join(ROOT, "profiles", "r10_spec_logprobs.json" if a.logprobs else "r08_spec_controls.json" if a.controls else "r07_spec_guided.json" if a.guided else
                                   "r06_spec_shared_rows.json" if a.shared else "r05_spec_decode.json")
+    if a.logprobs:
+        return main_logprobs(a)
     if a.controls:
         return main_controls(a)
     if a.guided:

@@ -128,6 +128,8 @@ class Engine:
         self.spec_guided = speculative is not None and bool(speculative.guided)
         # so do steps with sampling controls or logit adjustments (SpecConfig.controls)
         self.spec_controls = speculative is not None and bool(speculative.controls)
+        # and steps that record log-probabilities (SpecConfig.logprobs)
+        self.spec_logprobs = speculative is not None and bool(speculative.logprobs)
         self.spec_steps = self.plain_steps = 0
         self._snap_counts = None
         self.s_max = _align(s_max, 64)
@@ -925,7 +927,8 @@ class Engine:
         passes that carry state from token to token (the penalties' counts, min_tokens) or record per step (log-probabilities)
         would need that state per draft.  A guide's DFA state is had per draft (kr_spec_guide_*) where the engine was built with
         SpecConfig(guided=True), the sampler's counts and stop entries (kr_spec_controls_*, the _rows launches) where it was built
-        with SpecConfig(controls=True)."""
+        with SpecConfig(controls=True), a record per emitted token (kr_logprobs_topk_rows) where it was built with
+        SpecConfig(logprobs=True)."""
         step = self._step
         if self.spec is None:
             return "the engine was built without speculative=SpecConfig(...)"
@@ -938,7 +941,7 @@ class Engine:
         elif step.guided or controlled:
             return ("the step carries guided decoding, sampling controls or logit adjustments"
                     + (" (guided requests speculate on an engine built with SpecConfig(guided=True))" if step.guided else ""))
-        if self._logprobs is not None:
+        if self._logprobs is not None and not self.spec_logprobs:
             return "log-probabilities are recorded"
         return None
 
@@ -958,6 +961,10 @@ class Engine:
         kr_spec_controls_rows behind the guide's rows (every row's depth, for the row-mapped sampler passes Sampler.pre_token picks),
         kr_stop_tokens behind the verification where the step carries adjustments, and kr_spec_controls_count where it carries
         controls (the slots' output counts follow the emitted tokens).  A step without either issues none of them.
+        A step that records log-probabilities (SpecConfig(logprobs=True)) starts on kr_spec_mark where no trim ran (the trims write
+        ctx_before themselves) and, behind the verification and kr_stop_tokens, puts the adjusted logits back
+        (kr_logits_restore_rows, where the step carries adjustments) and records every emitted token from the row that chose it
+        (kr_logprobs_topk_rows) — Sampler.post_token's order.  A step that records nothing issues none of them.
         A step that carries repetition detection ends on kr_repeat_detect, as a plain step does."""
         L, s, R = self.L, self.s, self.rows
         why = self._spec_refusal()
@@ -967,6 +974,9 @@ class Engine:
         a = self._spec_args()
         g = self.sampler.spec_guide_args() if step.guided else None
         c = self.sampler.spec_controls_args() if (step.processing or step.adjust) else None
+        record = self._logprobs is not None
+        if record and g is None and c is None:
+            L.kr_spec_mark(C.byref(a), ptr(self.sampler.d_ctx_before), s)
         if self.share_rows:
             L.kr_spec_lookup(C.byref(a), ptr(self.d_nwant), s)
             if g is not None:
@@ -1003,6 +1013,8 @@ class Engine:
             sm = self.sampler
             L.kr_stop_tokens(ptr(self.d_tok), ptr(sm.d_adj_ids), ptr(sm.d_adj_flag), ptr(sm.d_adj_meta), ptr(self.d_fin), flags,
                              self.B, s)
+        if record:
+            self.sampler.spec_record(a, logits, ptr(self.d_draft_row) if self.share_rows else None, R)
         if step.processing:
             L.kr_spec_controls_count(C.byref(a), C.byref(c), s)
         if g is not None:
@@ -1419,7 +1431,7 @@ class Engine:
         """n decode steps over all slots (asynchronous on the engine's stream).  speculative=True: speculative steps (every slot
         advances by 1 .. K + 1 tokens per step, the same tokens as plain steps give); raises where the steps carry guided decoding
         (without SpecConfig(guided=True)), sampling controls or logit adjustments (without SpecConfig(controls=True)), or record
-        log-probabilities.  While an admission is in flight on a CU-masked stream the captured graph replays on the complementary compute units (same kernels, same grids: the same tokens), ordered
+        log-probabilities (without SpecConfig(logprobs=True)).  While an admission is in flight on a CU-masked stream the captured graph replays on the complementary compute units (same kernels, same grids: the same tokens), ordered
         against the engine's stream by events on both sides."""
         spec = bool(speculative)
         if spec:

@@ -123,13 +123,17 @@ class SpecConfig:
     controls: steps that carry sampling controls (top_k, top_p, min_p, penalties) or logit adjustments (logit_bias, min_tokens,
     stop_token_ids) speculate too — a draft row runs the sampler's passes with its slot's parameters and the output counts behind
     its drafts, and a draft that is a stop entry of its slot ends the slot's drafts (kr_spec_controls_trim / kr_spec_controls_rows /
-    kr_spec_controls_count, the _rows launches of the sampler).  Off, such steps are plain steps, as before the option existed."""
+    kr_spec_controls_count, the _rows launches of the sampler).  Off, such steps are plain steps, as before the option existed.
+    logprobs: steps that record log-probabilities (begin_slots(logprobs=k)) speculate too — every token a step emits gets the record
+    the plain steps would have written, from the logits row that chose it (kr_spec_mark / kr_logits_restore_rows /
+    kr_logprobs_topk_rows).  Off, such steps are plain steps, as before the option existed."""
     num_tokens: int = 3
     ngram_min: int = 2
     ngram_max: int = 4
     share_rows: bool = False
     guided: bool = False
     controls: bool = False
+    logprobs: bool = False
 
     def rows(self, max_batch: int) -> int:
         """Rows of a speculative step: never fewer than 17 (the packed 17..32-row family)."""
@@ -146,6 +150,8 @@ class SpecConfig:
             raise KarantaHipError(f"speculative: guided {self.guided!r} must be True or False")
         if not isinstance(self.controls, (bool, np.bool_)):
             raise KarantaHipError(f"speculative: controls {self.controls!r} must be True or False")
+        if not isinstance(self.logprobs, (bool, np.bool_)):
+            raise KarantaHipError(f"speculative: logprobs {self.logprobs!r} must be True or False")
         if self.share_rows:
             if k > 31:
                 raise KarantaHipError(f"speculative: num_tokens {k} > 31, the draft rows a 32-row decode step can hold")

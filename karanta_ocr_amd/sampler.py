@@ -12,7 +12,7 @@ from typing import Dict, Sequence
 import numpy as np
 import torch
 
-from ._lib import ADJ_CAP, REP_MAX_PERIOD, KarantaHipError, Repeat, SpecControls, SpecGuide, ptr
+from ._lib import ADJ_CAP, REP_MAX_PERIOD, KarantaHipError, Repeat, SpecControls, SpecGuide, SpecLogprobs, ptr
 from .request import PageRequest
 from .sampling import StepFeatures, adjust_table, needs_processing, sampling_params, temperature
 
@@ -46,7 +46,10 @@ class Sampler:
         W = max(B, eng.rows) if self.spec_controls else B
         if self.spec_guided:    # kr_spec_guide's scratch: the state behind every draft
             self.d_draft_state = z(B, eng.K, dtype=torch.int32)
-        if self.spec_guided or self.spec_controls:    # ctx_len at the start of the step (both trims write it)
+        # an engine that speculates on recording steps (SpecConfig(logprobs=True)) records from any ROW of the step
+        self.spec_logprobs = spec is not None and bool(getattr(spec, "logprobs", False))
+        if self.spec_guided or self.spec_controls or self.spec_logprobs:    # ctx_len at the start of the step (both trims and
+            #                                                                   kr_spec_mark write it)
             self.d_ctx_before = z(B, dtype=torch.int32)
         if self.spec_controls:
             self.d_depth = z(eng.rows, dtype=torch.int32)
@@ -81,9 +84,10 @@ class Sampler:
         # log-probabilities: [hist][B][1 + 20] / [hist][B][20], allocated with the token history when asked for
         self.lp_part = max(64 if t.vocab_size > 4096 else 1, -(-t.vocab_size // 4096))   # slices of <= 4096 logits
         self.d_lp = self.d_lpi = None
-        self.d_lp_pv = z(B, self.lp_part, 20, dtype=torch.float32)
-        self.d_lp_pi = z(B, self.lp_part, 20, dtype=torch.int32)
-        self.d_lp_ms = z(B, self.lp_part, 2, dtype=torch.float32)
+        P = max(B, eng.rows) if self.spec_logprobs else B      # the partials are per row (kr_logprobs_topk_rows)
+        self.d_lp_pv = z(P, self.lp_part, 20, dtype=torch.float32)
+        self.d_lp_pi = z(P, self.lp_part, 20, dtype=torch.int32)
+        self.d_lp_ms = z(P, self.lp_part, 2, dtype=torch.float32)
 
     def ensure_logprob_history(self, rows: int) -> bool:
         """The log-prob history sized for `rows` steps when log-probabilities are recorded; True where it was (re)allocated."""
@@ -279,6 +283,22 @@ class Sampler:
         return SpecControls(ptr(self.d_adj_ids), ptr(self.d_adj_flag), ptr(self.d_adj_meta), ptr(self.d_counts), V, ptr(self.d_depth),
                             ptr(self.d_ctx_before))
 
+    def spec_logprobs_args(self) -> SpecLogprobs:
+        """kr_spec_logprobs of the engine's recording speculative step (read during the call)."""
+        return SpecLogprobs(int(self.eng._logprobs), self.lp_part, ptr(self.d_lp_pv), ptr(self.d_lp_pi), ptr(self.d_lp_ms), ptr(self.d_lp),
+                            ptr(self.d_lpi), self.d_lp.shape[0], self.eng.B, 20, ptr(self.d_ctx_before))
+
+    def spec_record(self, a, logits, draft_row, B: int):
+        """Behind a speculative step's verification (and kr_stop_tokens): the logits of its B rows put back where the step adjusted
+        them, then the log-probability record of every token the step emitted — Sampler.post_token's order."""
+        e, L, t, s = self.eng, self.L, self.cfg.text, self.eng.s
+        ld = e.d_logits.stride(0)
+        if e._step.adjust:
+            L.kr_logits_restore_rows(ptr(logits), ld, t.vocab_size, ptr(self.d_adj_ids), ptr(self.d_adj_meta), ptr(self.d_adj_saved), B,
+                                     ptr(e.d_row_slot), e.B, s)
+        p = self.spec_logprobs_args()
+        L.kr_logprobs_topk_rows(C.byref(a), C.byref(p), draft_row, ptr(logits), ld, s)
+
     # ------------------------------------------------------------------ the step's tail around the token choice
     def _adj(self, j):
         return ptr(self.d_adj_ids[j:]), ptr(self.d_adj_val[j:]), ptr(self.d_adj_flag[j:]), ptr(self.d_adj_meta[j:])
@@ -295,7 +315,7 @@ class Sampler:
         if spec and (step.adjust or step.processing):
             V, ld = t.vocab_size, e.d_logits.stride(0)
             rows = (ptr(e.d_row_slot), ptr(self.d_depth), ptr(e.d_draft), e.K, e.B)
-            if step.adjust:     # (no kr_logits_restore behind the token: nothing reads a speculative step's logits after it)
+            if step.adjust:     # (put back behind the token only where the step records log-probabilities: Sampler.spec_record)
                 L.kr_logits_adjust_rows(ptr(logits), ld, V, *self._adj(0), ptr(e.d_ctx), ptr(e.d_plen), ptr(self.d_adj_saved), B,
                                         ptr(e.d_row_slot), e.B, s)
             if step.processing:

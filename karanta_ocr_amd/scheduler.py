@@ -153,7 +153,8 @@ class SlotScheduler:
         self.launch_ahead = (bool(launch_ahead) and not self.overlap
                              and all(hasattr(engine, m) for m in ("snapshot_slots", "read_snapshot")))
         # speculative: the chunks are speculative steps (Engine(speculative=SpecConfig(...)): up to K + 1 tokens per slot and step, the
-        # same tokens) while no request in a slot needs log-probabilities — or sampling controls or logit adjustments, unless the engine
+        # same tokens) while the scheduler records no log-probabilities, unless the engine speculates on recording steps
+        # (engine.spec_logprobs: SpecConfig(logprobs=True)), and no request in a slot needs sampling controls or logit adjustments, unless it
         # speculates on such steps (engine.spec_controls: SpecConfig(controls=True)), or guided decoding, unless it speculates on guided
         # steps (engine.spec_guided: SpecConfig(guided=True)) — and the policy finds them worth their price; every other chunk is plain
         self.speculative = bool(speculative)
@@ -306,7 +307,9 @@ class SlotScheduler:
     def _spec_chunk(self) -> bool:
         """Whether the next chunk is speculative: the scheduler's mode, the requests in the slots (and in the admission in flight),
         the engine's own conditions, then the policy."""
-        if not self.speculative or self.logprobs is not None:
+        if not self.speculative:
+            return False
+        if self.logprobs is not None and not getattr(self.engine, "spec_logprobs", False):     # SpecConfig(logprobs=True)
             return False
         pending = self._inflight[1] if self._inflight is not None else []
         need = StepFeatures.of(r.page for r in [*self.active.values(), *pending])

@@ -434,11 +434,13 @@ class LocalServer:
         # the default of the requests without a repetition_detection field (RepetitionParams, its dict form, or None: off)
         self.repetition = parse_repetition_field(repetition)
         # prompt-lookup speculative decoding (vLLM's --speculative-config, method ngram): continuous mode, an engine built with
-        # speculative=SpecConfig(...), no log-probabilities (SlotScheduler(speculative=True))
+        # speculative=SpecConfig(...), and log-probabilities only on an engine that records them in speculative steps
+        # (SpecConfig(logprobs=True); SlotScheduler(speculative=True))
         self.speculative = bool(speculative)
-        if self.speculative and (not continuous or max_logprobs is not None or not getattr(engine, "K", 0)):
+        if self.speculative and (not continuous or not getattr(engine, "K", 0)
+                                 or (max_logprobs is not None and not getattr(engine, "spec_logprobs", False))):
             raise ValueError("speculative=True needs continuous=True, max_logprobs=None and an engine built with "
-                             "speculative=SpecConfig(...)")
+                             "speculative=SpecConfig(...) (max_logprobs: one built with SpecConfig(logprobs=True))")
         self.honor_temperature = bool(honor_temperature)   # False: every request is served greedy
         # guided decoding needs the tokenizer's byte strings on the device; engines without set_vocab (test fakes)
         # answer guided requests with 400
