@@ -214,11 +214,9 @@ def main(argv=None):
     args = ap.parse_args(argv)
     spec = None
     if args.speculative_config:
-        from .cli import speculative_controls, speculative_fields, speculative_guided, speculative_logprobs
+        from .cli import speculative_spec
         try:
-            # SpecConfig's fields, share_rows, guided, controls and logprobs among them
-            spec = (*speculative_fields(args.speculative_config, args.slots), speculative_guided(args.speculative_config),
-                    speculative_controls(args.speculative_config), speculative_logprobs(args.speculative_config))
+            spec = speculative_spec(args.speculative_config, args.slots)
         except ValueError as e:
             ap.error(str(e))
     if args.gpus is not None:
@@ -229,7 +227,7 @@ def main(argv=None):
     from karanta_ocr_amd import serving as S
     from karanta_ocr_amd.clients import VLLMClient
     from karanta_ocr_amd.config import CONFIGS
-    from karanta_ocr_amd.engine import Engine, SpecConfig
+    from karanta_ocr_amd.engine import Engine
     from karanta_ocr_amd.weights import random_weights
 
     cfg = CONFIGS[args.model]
@@ -246,10 +244,10 @@ def main(argv=None):
     n_patch = int(np.prod(probe.grids[0]))
     B = args.slots
     # speculative: the steps a slot runs past its limit emit up to K + 1 tokens each, and the draft rows write K cache rows ahead
-    slack = 2 * args.chunk * (spec[0] + 1) + spec[0] if spec else args.chunk
+    slack = 2 * args.chunk * (spec.num_tokens + 1) + spec.num_tokens if spec else args.chunk
     eng = Engine(cfg, max_batch=B, s_max=(P + args.t_max + slack + 64 + 63) // 64 * 64,
                  max_patches=args.admit * n_patch, max_prompt_tokens=args.admit * P, admission_cus=args.overlap_cus or None,
-                 **({"speculative": SpecConfig(*spec)} if spec else {}))
+                 **({"speculative": spec} if spec else {}))
     eng.load_weights(random_weights(cfg, 0, as_bits=True))
     srv = S.LocalServer(eng, front, log=lambda *_: None, continuous=True, max_tokens_cap=args.t_max, chunk=args.chunk,
                         honor_temperature=False, admit_min=args.admit_min, admit_max_wait=args.admit_max_wait,

@@ -111,20 +111,30 @@ def repetition_config(text: str):
     return parse_repetition_field(d)
 
 
-def speculative_config(text: str, max_num_seqs: int):
-    """(num_tokens, ngram_min, ngram_max) from --speculative-config; ValueError with the reason for what this engine does not do."""
-    return speculative_fields(text, max_num_seqs)[:3]
-
-
-def speculative_fields(text: str, max_num_seqs: int):
-    """SpecConfig's fields (num_tokens, ngram_min, ngram_max, share_rows) from --speculative-config; ValueError with the reason."""
+def speculative_spec(text: str, max_num_seqs: int, max_logprobs: Optional[int] = None, static_batching: bool = False):
+    """The SpecConfig of --speculative-config for a server of `max_num_seqs` slots (and, where given, its --max-logprobs and
+    --static-batching); ValueError with the reason for what this engine does not do.  The checks run in the order the messages
+    have always won in: the "logprobs" key and what depends on it, SpecConfig's fields, "guided", "controls"."""
     import json
+    from .request import SpecConfig
     try:
         d = json.loads(text)
     except ValueError as e:
         raise ValueError(f"--speculative-config is not JSON: {e}") from e
     if not isinstance(d, dict):
         raise ValueError("--speculative-config must be a JSON object")
+
+    def flag(name):
+        v = d.get(name, False)
+        if not isinstance(v, bool):
+            raise ValueError(f"--speculative-config: {name} must be true or false, not {v!r}")
+        return v
+
+    logprobs = flag("logprobs")
+    if max_logprobs is not None and not logprobs:
+        raise ValueError("--speculative-config cannot be combined with --max-logprobs: a draft row records no log-probabilities")
+    if static_batching:
+        raise ValueError("--speculative-config needs the slot scheduler: not with --static-batching")
     method = d.get("method")
     if method != "ngram":
         raise ValueError(f"--speculative-config: method {method!r} is not supported (only \"ngram\": prompt-lookup drafts; there is no "
@@ -137,9 +147,7 @@ def speculative_fields(text: str, max_num_seqs: int):
             raise ValueError(f"--speculative-config: {name} must be an integer >= 1, not {v!r}")
     if not lo <= hi <= 8:
         raise ValueError(f"--speculative-config: prompt_lookup_min {lo} <= prompt_lookup_max {hi} <= 8 does not hold")
-    share = d.get("share_rows", False)
-    if not isinstance(share, bool):
-        raise ValueError(f"--speculative-config: share_rows must be true or false, not {share!r}")
+    share = flag("share_rows")
     if share:
         if k > 31:
             raise ValueError(f"--speculative-config: num_speculative_tokens {k} > 31, the draft rows a 32-row decode step can hold")
@@ -149,52 +157,36 @@ def speculative_fields(text: str, max_num_seqs: int):
     elif max_num_seqs * (k + 1) > 32:
         raise ValueError(f"--speculative-config: --max-num-seqs {max_num_seqs} x (num_speculative_tokens {k} + 1) = "
                          f"{max_num_seqs * (k + 1)} rows per decode step, the kernels take 32")
-    return k, lo, hi, share
+    return SpecConfig(k, lo, hi, share, flag("guided"), flag("controls"), logprobs)
+
+
+# Views of speculative_spec, as callers have them.  The three flag views take no slot count, so they validate the whole text
+# as a one-slot server's: a text that speculative_spec refuses (no "method", another faulty key, more rows than one slot may
+# have) raises its message here too, the "logprobs" key's first, where each view once read its own key alone.
+def speculative_fields(text: str, max_num_seqs: int):
+    """SpecConfig's fields (num_tokens, ngram_min, ngram_max, share_rows) from --speculative-config; ValueError with the reason."""
+    sc = speculative_spec(text, max_num_seqs)
+    return sc.num_tokens, sc.ngram_min, sc.ngram_max, sc.share_rows
+
+
+def speculative_config(text: str, max_num_seqs: int):
+    """(num_tokens, ngram_min, ngram_max) from --speculative-config; ValueError with the reason for what this engine does not do."""
+    return speculative_fields(text, max_num_seqs)[:3]
 
 
 def speculative_guided(text: str) -> bool:
     """SpecConfig.guided from --speculative-config: the key "guided", true or false (absent: false); ValueError with the reason."""
-    import json
-    try:
-        d = json.loads(text)
-    except ValueError as e:
-        raise ValueError(f"--speculative-config is not JSON: {e}") from e
-    if not isinstance(d, dict):
-        raise ValueError("--speculative-config must be a JSON object")
-    guided = d.get("guided", False)
-    if not isinstance(guided, bool):
-        raise ValueError(f"--speculative-config: guided must be true or false, not {guided!r}")
-    return guided
+    return speculative_spec(text, 1).guided
 
 
 def speculative_controls(text: str) -> bool:
     """SpecConfig.controls from --speculative-config: the key "controls", true or false (absent: false); ValueError with the reason."""
-    import json
-    try:
-        d = json.loads(text)
-    except ValueError as e:
-        raise ValueError(f"--speculative-config is not JSON: {e}") from e
-    if not isinstance(d, dict):
-        raise ValueError("--speculative-config must be a JSON object")
-    controls = d.get("controls", False)
-    if not isinstance(controls, bool):
-        raise ValueError(f"--speculative-config: controls must be true or false, not {controls!r}")
-    return controls
+    return speculative_spec(text, 1).controls
 
 
 def speculative_logprobs(text: str) -> bool:
     """SpecConfig.logprobs from --speculative-config: the key "logprobs", true or false (absent: false); ValueError with the reason."""
-    import json
-    try:
-        d = json.loads(text)
-    except ValueError as e:
-        raise ValueError(f"--speculative-config is not JSON: {e}") from e
-    if not isinstance(d, dict):
-        raise ValueError("--speculative-config must be a JSON object")
-    logprobs = d.get("logprobs", False)
-    if not isinstance(logprobs, bool):
-        raise ValueError(f"--speculative-config: logprobs must be true or false, not {logprobs!r}")
-    return logprobs
+    return speculative_spec(text, 1).logprobs
 
 
 def parse_args(argv: Optional[List[str]] = None):
@@ -221,20 +213,11 @@ def parse_args(argv: Optional[List[str]] = None):
     args.speculative_logprobs = False
     if args.speculative_config is not None:
         try:
-            args.speculative_logprobs = speculative_logprobs(args.speculative_config)
+            sc = speculative_spec(args.speculative_config, args.max_num_seqs, args.max_logprobs, args.static_batching)
         except ValueError as e:
             ap.error(str(e))
-        if args.max_logprobs is not None and not args.speculative_logprobs:
-            ap.error("--speculative-config cannot be combined with --max-logprobs: a draft row records no log-probabilities")
-        if args.static_batching:
-            ap.error("--speculative-config needs the slot scheduler: not with --static-batching")
-        try:
-            *spec, args.speculative_share_rows = speculative_fields(args.speculative_config, args.max_num_seqs)
-            args.speculative = tuple(spec)
-            args.speculative_guided = speculative_guided(args.speculative_config)
-            args.speculative_controls = speculative_controls(args.speculative_config)
-        except ValueError as e:
-            ap.error(str(e))
+        args.speculative, args.speculative_share_rows = (sc.num_tokens, sc.ngram_min, sc.ngram_max), sc.share_rows
+        args.speculative_guided, args.speculative_controls, args.speculative_logprobs = sc.guided, sc.controls, sc.logprobs
     args.repetition = None
     if args.repetition_detection is not None:
         try:

@@ -22,7 +22,7 @@ import torch
 
 from . import image_processing as IP
 from . import positions as POS
-from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_OUT_XP16, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_NONE, EPI_SILU_MUL8, KarantaHipError, Spec, lib,
+from ._lib import (DEC_ARGMAX, DEC_OUT_XP, DEC_OUT_XP16, DEC_PLAIN, DEC_ROPE_KV, DEC_SILU8, Dec32, EPI_NONE, EPI_SILU_MUL8, KarantaHipError, lib,
                    narrow_opts, ptr)
 from . import kv_cache
 from .config import ModelConfig
@@ -31,7 +31,8 @@ from .weights import KV_SCALE_RANGES, kv_cache_dtype_name
 from .device_weights import DeviceWeights, _align, narrow_weight_bytes, plan_resident
 from .request import GenerateResult, PageRequest, SpecConfig, children
 from .sampler import DeviceGuide, Sampler
-from .sampling import StepFeatures, has_penalties
+from .sampling import StepFeatures, has_penalties, spec_refusal
+from .speculative import Speculator
 from .vision import DevicePlan, VisionTower, device_plan
 
 BF16 = torch.bfloat16
@@ -117,19 +118,12 @@ class Engine:
             raise KarantaHipError("max_batch > 32: the decode kernels take at most two 16-row column tiles")
         # a speculative step runs max_batch x (K + 1) rows through the packed 17..32-row family (never fewer than 17 rows: its
         # gate/up launch writes packed activations above 16 rows only); without `speculative` the rows are the slots.
-        # share_rows: at most 32 of them — the rows behind the slots' own are dealt per step (kr_spec_deal)
+        # (SpecConfig.rows; with shared rows at most 32 of them: the rows behind the slots' own are dealt per step)
         self.spec = speculative
         if speculative is not None:
             speculative.check(max_batch)
         self.K = int(speculative.num_tokens) if speculative is not None else 0
         self.rows = speculative.rows(max_batch) if speculative is not None else max_batch
-        self.share_rows = speculative is not None and bool(speculative.share_rows)
-        # guided steps speculate too (SpecConfig.guided); the slot scheduler reads this before it asks for a speculative chunk
-        self.spec_guided = speculative is not None and bool(speculative.guided)
-        # so do steps with sampling controls or logit adjustments (SpecConfig.controls)
-        self.spec_controls = speculative is not None and bool(speculative.controls)
-        # and steps that record log-probabilities (SpecConfig.logprobs)
-        self.spec_logprobs = speculative is not None and bool(speculative.logprobs)
         self.spec_steps = self.plain_steps = 0
         self._snap_counts = None
         self.s_max = _align(s_max, 64)
@@ -312,7 +306,7 @@ class Engine:
         self.d_amax_v = z(R, self.n_amax, dtype=torch.float32)
         self.d_amax_i = z(R, self.n_amax, dtype=torch.int32)
         # per-ROW state (prompt length, context, finished, temperature, seed): the slots' entries are in front — what every launch of
-        # a plain step and the host read — and kr_spec_propose writes the entries of a speculative step's draft rows behind them
+        # a plain step and the host read — and a speculative step writes the entries of its draft rows behind them
         self.d_plen = z(R, dtype=torch.int32)[:B]
         self.d_cs = None  # [B][max_new][128] rotary table of the decode positions, built per request
         self.d_ctx = z(R, dtype=torch.int32)[:B]
@@ -323,21 +317,8 @@ class Engine:
         self._rep_read = np.full(B, -1, np.int64)     # slot_rep_at()
         self.d_temp = z(R, dtype=torch.float32)[:B]   # per-slot sampling temperature and seed
         self.d_seed = z(R, dtype=torch.int32)[:B]
-        if self.spec is not None:
-            # the slot of every row (a slot's own row: itself), the prompt ids per slot (written at every admission), the drafts
-            # and the counters of proposed / accepted drafts, and the scripted continuations of the test hook (set_draft_script)
-            self.d_row_slot = torch.arange(R, dtype=torch.int32, device=dev) % B
-            self.d_prompt_ids = z(B, self.s_max, dtype=torch.int32)
-            self.d_ndraft = z(B, dtype=torch.int32)
-            self.d_draft = z(B, self.K, dtype=torch.int32)
-            if self.share_rows:   # what every slot's lookup found, and the row each draft was dealt (-1: none)
-                self.d_nwant = z(B, dtype=torch.int32)
-                self.d_draft_row = torch.full((B, self.K), -1, dtype=torch.int32, device=dev)
-            self.d_spec_count = z(2, B, dtype=torch.int32)
-            self.d_script = z(B, dtype=torch.int64)
-            self.d_script_len = z(B, dtype=torch.int32)
-            self._scripts: Dict[int, torch.Tensor] = {}
         self.sampler = Sampler(self)
+        self.speculator = Speculator(self) if self.spec is not None else None     # the speculative step: speculative.py
         self.max_new = 0          # size of the token history / rotary tables (only grows: graphs hold their addresses)
         self._req_max_new = 0     # what the current generate() / begin_slots() asked for (capacity checks use this)
         self.d_hist = None
@@ -755,9 +736,8 @@ class Engine:
                 self._h2d(self.d_cs[j:], a.cs[b:b + n])
             for _, j, n in a.spans(self.B):
                 self.d_fin[j:j + n].zero_()
-            if self.spec is not None:     # kr_spec_propose looks the drafts up in prompt + history
-                for p, j in zip(a.rows, a.slots):
-                    self._h2d(self.d_prompt_ids[j], np.asarray(p.input_ids, np.int64).reshape(-1).astype(np.int32))
+            if self.speculator is not None:
+                self.speculator.write_prompts(a)
             self.sampler.write(a)
         if tokens:
             d = self.cfg.text.hidden_size
@@ -773,7 +753,7 @@ class Engine:
 
     # ------------------------------------------------------------------ the step's tail: lm_head -> sampler passes -> tokens
     def _flags(self) -> int:
-        """The flags word of kr_sample_greedy / kr_spec_accept and the sampler's passes."""
+        """The flags word of kr_sample_greedy, of a speculative step's verification and of the sampler's passes."""
         return (1 if self._ignore_eos else 0) | (2 if self._freeze_finished else 0)
 
     def _lm_head(self, B: int, x, j: int = 0):
@@ -911,160 +891,40 @@ class Engine:
             pending = defer
         return x
 
-    # ------------------------------------------------------------------ speculative step
-    def _spec_args(self) -> Spec:
-        """kr_spec of this engine's speculative step (read during the call: rebuilt per launch, the history may have grown)."""
-        t, sp = self.cfg.text, self.spec
-        return Spec(self.B, self.K, self.rows, int(sp.ngram_min), int(sp.ngram_max), self.s_max, ptr(self.d_prompt_ids),
-                    self.d_prompt_ids.stride(0), ptr(self.d_hist), self.d_hist.stride(0), self.d_hist.shape[0], ptr(self.d_script),
-                    ptr(self.d_script_len), ptr(self.d_row_slot), ptr(self.d_ctx), ptr(self.d_plen), ptr(self.d_fin), ptr(self.d_temp),
-                    ptr(self.d_seed), ptr(self.d_ndraft), ptr(self.d_draft), ptr(self.w.view("llm.embed")), t.hidden_size,
-                    self.cfg.pad_token_id, t.vocab_size, ptr(self.d_x), self.d_x.stride(0), ptr(self.d_spec_count[0]),
-                    ptr(self.d_spec_count[1]))
+    # ------------------------------------------------------------------ speculative step: the component's public entries
+    # SpecConfig's options as the slot scheduler (before it asks for a speculative chunk) and the tests read them
+    share_rows = property(lambda self: self.spec is not None and bool(self.spec.share_rows))
+    spec_guided = property(lambda self: self.spec is not None and bool(self.spec.guided))
+    spec_controls = property(lambda self: self.spec is not None and bool(self.spec.controls))
+    spec_logprobs = property(lambda self: self.spec is not None and bool(self.spec.logprobs))
+    # the component's tensors that tools read off the engine, read-only: one holder each, as for the KV cache's
+    d_spec_count = property(lambda self: self._need_speculator("d_spec_count").d_spec_count)
+    d_row_slot = property(lambda self: self._need_speculator("d_row_slot").d_row_slot)
+
+    def _need_speculator(self, who: str) -> Speculator:
+        if self.speculator is None:
+            raise KarantaHipError(who + ": the engine was built without speculative=SpecConfig(...)")
+        return self.speculator
 
     def _spec_refusal(self) -> Optional[str]:
-        """Why the next steps cannot be speculative (None: they can).  A draft row sees the logits of its own position only: the
-        passes that carry state from token to token (the penalties' counts, min_tokens) or record per step (log-probabilities)
-        would need that state per draft.  A guide's DFA state is had per draft (kr_spec_guide_*) where the engine was built with
-        SpecConfig(guided=True), the sampler's counts and stop entries (kr_spec_controls_*, the _rows launches) where it was built
-        with SpecConfig(controls=True), a record per emitted token (kr_logprobs_topk_rows) where it was built with
-        SpecConfig(logprobs=True)."""
-        step = self._step
-        if self.spec is None:
-            return "the engine was built without speculative=SpecConfig(...)"
-        if not self._freeze_finished:
-            return "speculative steps run in slot mode (begin_slots)"
-        controlled = (step.processing or step.adjust) and not self.spec_controls
-        if self.spec_guided:
-            if controlled:
-                return "the step carries sampling controls or logit adjustments"
-        elif step.guided or controlled:
-            return ("the step carries guided decoding, sampling controls or logit adjustments"
-                    + (" (guided requests speculate on an engine built with SpecConfig(guided=True))" if step.guided else ""))
-        if self._logprobs is not None and not self.spec_logprobs:
-            return "log-probabilities are recorded"
-        return None
-
-    def _spec_step_launches(self):
-        """One speculative step: drafts (kr_spec_propose) -> the layers over all rows -> lm_head -> the Gumbel pass when a request
-        samples -> verification and bookkeeping (kr_spec_accept, in kr_sample_greedy's place).  It leaves d_ctx, d_tok, d_x[slot],
-        the history and d_fin in the form a plain step leaves them, so the two kinds alternate freely.
-        share_rows: the drafts are looked up (kr_spec_lookup), the rows behind the slots dealt to them (kr_spec_deal) and the
-        verification reads each draft at the row it was dealt (kr_spec_accept_rows); everything between is the same launches —
-        they take the row-to-slot map as it comes.
-        A step that carries guided requests (SpecConfig(guided=True)) has three launches more: the drafts a slot's guide forbids are
-        dropped before any row is spent on them (kr_spec_guide_trim: behind kr_spec_propose, or between kr_spec_lookup and
-        kr_spec_deal), every draft row gets the guide and the DFA state behind its drafts (kr_spec_guide_rows) for the masked Gumbel
-        pass, and the slots' states follow the tokens the verification emitted (kr_spec_guide_advance).  An unguided step issues
-        none of them.  A step that carries sampling controls or logit adjustments (SpecConfig(controls=True)) has the same shape:
-        kr_spec_controls_trim behind the guide's trim (a draft that is a stop entry of its slot ends the slot's drafts),
-        kr_spec_controls_rows behind the guide's rows (every row's depth, for the row-mapped sampler passes Sampler.pre_token picks),
-        kr_stop_tokens behind the verification where the step carries adjustments, and kr_spec_controls_count where it carries
-        controls (the slots' output counts follow the emitted tokens).  A step without either issues none of them.
-        A step that records log-probabilities (SpecConfig(logprobs=True)) starts on kr_spec_mark where no trim ran (the trims write
-        ctx_before themselves) and, behind the verification and kr_stop_tokens, puts the adjusted logits back
-        (kr_logits_restore_rows, where the step carries adjustments) and records every emitted token from the row that chose it
-        (kr_logprobs_topk_rows) — Sampler.post_token's order.  A step that records nothing issues none of them.
-        A step that carries repetition detection ends on kr_repeat_detect, as a plain step does."""
-        L, s, R = self.L, self.s, self.rows
-        why = self._spec_refusal()
-        if why is not None:
-            raise KarantaHipError("speculative decode step refused: " + why)
-        step = self._step
-        a = self._spec_args()
-        g = self.sampler.spec_guide_args() if step.guided else None
-        c = self.sampler.spec_controls_args() if (step.processing or step.adjust) else None
-        record = self._logprobs is not None
-        if record and g is None and c is None:
-            L.kr_spec_mark(C.byref(a), ptr(self.sampler.d_ctx_before), s)
-        if self.share_rows:
-            L.kr_spec_lookup(C.byref(a), ptr(self.d_nwant), s)
-            if g is not None:
-                L.kr_spec_guide_trim(C.byref(a), C.byref(g), ptr(self.d_nwant), s)
-            if c is not None:
-                L.kr_spec_controls_trim(C.byref(a), C.byref(c), ptr(self.d_nwant), s)
-            L.kr_spec_deal(C.byref(a), ptr(self.d_nwant), ptr(self.d_draft_row), s)
-            if g is not None:
-                L.kr_spec_guide_rows(C.byref(a), C.byref(g), ptr(self.d_draft_row), s)
-            if c is not None:
-                L.kr_spec_controls_rows(C.byref(a), C.byref(c), ptr(self.d_draft_row), s)
-        else:
-            L.kr_spec_propose(C.byref(a), s)
-            if g is not None:
-                L.kr_spec_guide_trim(C.byref(a), C.byref(g), ptr(self.d_ndraft), s)
-            if c is not None:
-                L.kr_spec_controls_trim(C.byref(a), C.byref(c), ptr(self.d_ndraft), s)
-            if g is not None:
-                L.kr_spec_guide_rows(C.byref(a), C.byref(g), None, s)
-            if c is not None:
-                L.kr_spec_controls_rows(C.byref(a), C.byref(c), None, s)
-        x = self._layer_launches(R, self.d_row_slot)
-        logits, n_part = self._lm_head(R, x)
-        flags = self._flags()
-        # (an uncontrolled step: the Gumbel pass alone; a controlled one: the row-mapped adjustment and control passes)
-        n_part = self.sampler.pre_token(logits, n_part, R, 0, flags, spec=True)
-        if self.share_rows:
-            L.kr_spec_accept_rows(C.byref(a), ptr(self.d_draft_row), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(self.d_tok),
-                                  ptr(self.d_eos), self.d_eos.numel(), flags, s)
-        else:
-            L.kr_spec_accept(C.byref(a), ptr(self.d_amax_v), ptr(self.d_amax_i), n_part, ptr(self.d_tok), ptr(self.d_eos),
-                             self.d_eos.numel(), flags, s)
-        if step.adjust:       # a stop entry can only be the step's last token (kr_spec_controls_trim): the plain step's launch
-            sm = self.sampler
-            L.kr_stop_tokens(ptr(self.d_tok), ptr(sm.d_adj_ids), ptr(sm.d_adj_flag), ptr(sm.d_adj_meta), ptr(self.d_fin), flags,
-                             self.B, s)
-        if record:
-            self.sampler.spec_record(a, logits, ptr(self.d_draft_row) if self.share_rows else None, R)
-        if step.processing:
-            L.kr_spec_controls_count(C.byref(a), C.byref(c), s)
-        if g is not None:
-            L.kr_spec_guide_advance(C.byref(a), C.byref(g), s)
-        if self._step.repetition:     # over the 1 .. K + 1 tokens every slot gained: the cut plain steps make
-            self.sampler.repeat_pass(self.B, 0, flags)
-
-    def set_draft_script(self, slot: int, tokens: Optional[Sequence[int]]):
-        """Test hook: the drafts of `slot` come from a scripted continuation — draft j of a step is tokens[generated + j - 1] —
-        instead of the n-gram lookup, until None is set (an admission does not clear it)."""
-        if self.spec is None:
-            raise KarantaHipError("set_draft_script: the engine was built without speculative=SpecConfig(...)")
-        if not 0 <= int(slot) < self.B:
-            raise KarantaHipError(f"set_draft_script: slot {slot} outside 0..{self.B - 1}")
-        j = int(slot)
-        with torch.cuda.stream(self.stream):
-            if tokens is None:
-                self.d_script[j:j + 1].zero_()
-                self.d_script_len[j:j + 1].zero_()
-                self.stream.synchronize()       # a queued step may still read the tensor this drops
-                self._scripts.pop(j, None)
-                return
-            arr = np.ascontiguousarray(np.asarray(tokens, np.int64).reshape(-1).astype(np.int32))
-            buf = torch.zeros(max(1, arr.size), dtype=torch.int32, device=self.device)
-            self._h2d(buf, arr)
-            self._h2d(self.d_script[j:j + 1], np.asarray([buf.data_ptr()], np.int64))
-            self._h2d(self.d_script_len[j:j + 1], np.asarray([arr.size], np.int32))
-            self.stream.synchronize()
-            self._scripts[j] = buf
+        """Why the next steps cannot be speculative (None: they can): sampling.spec_refusal."""
+        return spec_refusal(self.spec, self._step, self._freeze_finished, self._logprobs is not None)
 
     def can_speculate(self) -> bool:
         """Whether decode_steps(speculative=True) would run with the passes the next steps carry."""
         return self._spec_refusal() is None
 
+    def _spec_step_launches(self):
+        self._need_speculator("speculative decode step refused").step_launches()
+
+    def set_draft_script(self, slot: int, tokens: Optional[Sequence[int]]):
+        self._need_speculator("set_draft_script").set_draft_script(slot, tokens)
+
     def spec_counts(self) -> Optional[Tuple[np.ndarray, np.ndarray]]:
-        """(proposed[B], accepted[B]) as of the state the host last read: the snapshot given to read_snapshot(), else (after
-        poll_slots()) the device's counters now."""
-        if self.spec is None:
-            return None
-        if self._snap_counts is not None:
-            return self._snap_counts
-        return self.spec_counters()
+        return None if self.speculator is None else self.speculator.counts()
 
     def spec_counters(self) -> Tuple[np.ndarray, np.ndarray]:
-        """(proposed[B], accepted[B]): draft tokens proposed / accepted per slot since begin_slots (synchronises)."""
-        if self.spec is None:
-            raise KarantaHipError("spec_counters: the engine was built without speculative=SpecConfig(...)")
-        self.stream.synchronize()
-        c = self.d_spec_count.cpu().numpy().astype(np.int64)
-        return c[0], c[1]
+        return self._need_speculator("spec_counters").counters()
 
     # ------------------------------------------------------------------ live kernel timing (bench.py roofline)
     def _prof_event_pair(self):
@@ -1309,8 +1169,8 @@ class Engine:
             self.d_ctx.zero_()
             self.d_plen.zero_()
             self.d_x.zero_()
-            if self.spec is not None:
-                self.d_spec_count.zero_()
+            if self.speculator is not None:
+                self.speculator.reset_counters()
         self.spec_steps = self.plain_steps = 0
         self.stream.synchronize()
 
@@ -1499,7 +1359,7 @@ class Engine:
             buf[1].copy_(self.d_ctx, non_blocking=True)
             buf[2].copy_(self.d_plen, non_blocking=True)
             if self.spec is not None:     # proposed / accepted drafts per slot as of this point: snap["buf"][3], [4]
-                buf[3:5].copy_(self.d_spec_count, non_blocking=True)
+                buf[3:5].copy_(self.speculator.d_spec_count, non_blocking=True)
             if self.sampler._rep_slots:   # (no slot carries the feature: no copy is queued)
                 buf[-1].copy_(self.sampler.d_rep_at, non_blocking=True)
             else:

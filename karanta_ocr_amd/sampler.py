@@ -12,7 +12,7 @@ from typing import Dict, Sequence
 import numpy as np
 import torch
 
-from ._lib import ADJ_CAP, REP_MAX_PERIOD, KarantaHipError, Repeat, SpecControls, SpecGuide, SpecLogprobs, ptr
+from ._lib import ADJ_CAP, REP_MAX_PERIOD, KarantaHipError, Repeat, ptr
 from .request import PageRequest
 from .sampling import StepFeatures, adjust_table, needs_processing, sampling_params, temperature
 
@@ -32,27 +32,17 @@ class Sampler:
         t, dev, B = self.cfg.text, self.device, eng.B
         z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
         # guided decoding: per slot the device addresses of its pattern's tables (0 = unconstrained) + its DFA state.  An engine that
-        # speculates on guided steps (SpecConfig(guided=True)) keeps them per ROW, the slots' entries in front: kr_spec_guide_rows
-        # writes those of a speculative step's draft rows behind them, and admissions, reset_slots and plain steps stay per slot
-        spec = getattr(eng, "spec", None)
-        self.spec_guided = spec is not None and bool(spec.guided)
-        G = max(B, eng.rows) if self.spec_guided else B
+        # speculates on guided steps (SpecConfig(guided=True)) keeps them per ROW, the slots' entries in front: the step writes
+        # those of its draft rows behind them, and admissions, reset_slots and plain steps stay per slot
+        spec = eng.spec
+        per_row = lambda on: max(B, eng.rows) if on else B      # (the option of an engine without a SpecConfig: off)
+        G = per_row(spec is not None and spec.guided)
         self.d_gtrans = z(G, dtype=torch.int64)
         self.d_gmasks = z(G, dtype=torch.int64)
         self.d_gstate = z(G, dtype=torch.int32)
         # an engine that speculates on controlled steps (SpecConfig(controls=True)) runs the sampler's passes over ROWS: the scratch of
-        # the threshold pass, the threshold keys, the live flags and the saved logits are per row there, and every row has a depth
-        self.spec_controls = spec is not None and bool(getattr(spec, "controls", False))
-        W = max(B, eng.rows) if self.spec_controls else B
-        if self.spec_guided:    # kr_spec_guide's scratch: the state behind every draft
-            self.d_draft_state = z(B, eng.K, dtype=torch.int32)
-        # an engine that speculates on recording steps (SpecConfig(logprobs=True)) records from any ROW of the step
-        self.spec_logprobs = spec is not None and bool(getattr(spec, "logprobs", False))
-        if self.spec_guided or self.spec_controls or self.spec_logprobs:    # ctx_len at the start of the step (both trims and
-            #                                                                   kr_spec_mark write it)
-            self.d_ctx_before = z(B, dtype=torch.int32)
-        if self.spec_controls:
-            self.d_depth = z(eng.rows, dtype=torch.int32)
+        # the threshold pass, the threshold keys, the live flags and the saved logits are per row there
+        W = per_row(spec is not None and spec.controls)
         self.mask_words = 2 * ((t.vocab_size + 63) // 64)
         # sampling controls: per-slot params (sampling_params), output-token counts, prompt-token bit set, the threshold pass's
         # scratch scores, threshold keys and live flags (kr_sample_threshold / kr_gumbel_argmax_processed / kr_sample_count)
@@ -84,7 +74,8 @@ class Sampler:
         # log-probabilities: [hist][B][1 + 20] / [hist][B][20], allocated with the token history when asked for
         self.lp_part = max(64 if t.vocab_size > 4096 else 1, -(-t.vocab_size // 4096))   # slices of <= 4096 logits
         self.d_lp = self.d_lpi = None
-        P = max(B, eng.rows) if self.spec_logprobs else B      # the partials are per row (kr_logprobs_topk_rows)
+        # an engine that speculates on recording steps (SpecConfig(logprobs=True)) records from any ROW of the step: partials per row
+        P = per_row(spec is not None and spec.logprobs)
         self.d_lp_pv = z(P, self.lp_part, 20, dtype=torch.float32)
         self.d_lp_pi = z(P, self.lp_part, 20, dtype=torch.int32)
         self.d_lp_ms = z(P, self.lp_part, 2, dtype=torch.float32)
@@ -272,52 +263,25 @@ class Sampler:
                    ptr(self.d_rep_cfg[j:]), ptr(self.d_rep_run[j:]), ptr(self.d_rep_seen[j:]), ptr(self.d_rep_at[j:]), flags)
         self.L.kr_repeat_detect(C.byref(a), e.s)
 
-    def spec_guide_args(self) -> SpecGuide:
-        """kr_spec_guide of the engine's guided speculative step (read during the call)."""
-        return SpecGuide(ptr(self.d_gtrans), ptr(self.d_gmasks), ptr(self.d_gstate), self.mask_words, ptr(self.d_voc_off),
-                         ptr(self.d_voc_bytes), ptr(self.d_draft_state), ptr(self.d_ctx_before))
-
-    def spec_controls_args(self) -> SpecControls:
-        """kr_spec_controls of the engine's controlled speculative step (read during the call)."""
-        V = self.cfg.text.vocab_size
-        return SpecControls(ptr(self.d_adj_ids), ptr(self.d_adj_flag), ptr(self.d_adj_meta), ptr(self.d_counts), V, ptr(self.d_depth),
-                            ptr(self.d_ctx_before))
-
-    def spec_logprobs_args(self) -> SpecLogprobs:
-        """kr_spec_logprobs of the engine's recording speculative step (read during the call)."""
-        return SpecLogprobs(int(self.eng._logprobs), self.lp_part, ptr(self.d_lp_pv), ptr(self.d_lp_pi), ptr(self.d_lp_ms), ptr(self.d_lp),
-                            ptr(self.d_lpi), self.d_lp.shape[0], self.eng.B, 20, ptr(self.d_ctx_before))
-
-    def spec_record(self, a, logits, draft_row, B: int):
-        """Behind a speculative step's verification (and kr_stop_tokens): the logits of its B rows put back where the step adjusted
-        them, then the log-probability record of every token the step emitted — Sampler.post_token's order."""
-        e, L, t, s = self.eng, self.L, self.cfg.text, self.eng.s
-        ld = e.d_logits.stride(0)
-        if e._step.adjust:
-            L.kr_logits_restore_rows(ptr(logits), ld, t.vocab_size, ptr(self.d_adj_ids), ptr(self.d_adj_meta), ptr(self.d_adj_saved), B,
-                                     ptr(e.d_row_slot), e.B, s)
-        p = self.spec_logprobs_args()
-        L.kr_logprobs_topk_rows(C.byref(a), C.byref(p), draft_row, ptr(logits), ld, s)
-
     # ------------------------------------------------------------------ the step's tail around the token choice
     def _adj(self, j):
         return ptr(self.d_adj_ids[j:]), ptr(self.d_adj_val[j:]), ptr(self.d_adj_flag[j:]), ptr(self.d_adj_meta[j:])
 
-    def pre_token(self, logits, n_part: int, B: int, j: int, flags: int, spec: bool = False) -> int:
+    def pre_token(self, logits, n_part: int, B: int, j: int, flags: int, rows=None) -> int:
         """The passes between the lm_head and the token choice over rows j .. j + B - 1; returns the number of argmax partials
         per row the choice reads (`n_part` as the lm_head launch wrote them, at most 64 after a Gumbel pass).
-        spec: the rows are those of a speculative step (j = 0, B = the engine's rows) — the adjustment and control passes are the
-        row-mapped launches: a row takes its slot's table, params, prompt bits and counts, and the counts take in the drafts in
-        front of it (d_depth, kr_spec_controls_rows)."""
+        rows: the row map of a speculative step that carries adjustments or controls (j = 0, B = the engine's rows), as the
+        row-mapped launches end on it — (row -> slot, row -> depth, the drafts, K, slots): a row takes its slot's table, params,
+        prompt bits and counts, and the counts take in the drafts in front of it."""
         e, L, t, s = self.eng, self.L, self.cfg.text, self.eng.s
         step = e._step
         gm, gs = (ptr(self.d_gmasks[j:]), ptr(self.d_gstate[j:])) if step.guided else (None, None)
-        if spec and (step.adjust or step.processing):
+        if rows is not None:
+            row_slot, _depth, _draft, _K, slots = rows
             V, ld = t.vocab_size, e.d_logits.stride(0)
-            rows = (ptr(e.d_row_slot), ptr(self.d_depth), ptr(e.d_draft), e.K, e.B)
-            if step.adjust:     # (put back behind the token only where the step records log-probabilities: Sampler.spec_record)
+            if step.adjust:     # (put back behind the token only where the step records log-probabilities)
                 L.kr_logits_adjust_rows(ptr(logits), ld, V, *self._adj(0), ptr(e.d_ctx), ptr(e.d_plen), ptr(self.d_adj_saved), B,
-                                        ptr(e.d_row_slot), e.B, s)
+                                        row_slot, slots, s)
             if step.processing:
                 n_part = min(64, n_part)
                 L.kr_sample_threshold_rows(ptr(logits), ld, V, ptr(e.d_temp), ptr(self.d_sp), ptr(self.d_counts), V, ptr(self.d_pbits),

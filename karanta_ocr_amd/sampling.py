@@ -135,6 +135,30 @@ class StepFeatures(_LogitPasses):
                             adjust, self.repetition and caps.repetition)
 
 
+def spec_refusal(spec, step: StepFeatures, slot_mode: bool, recording: bool) -> Optional[str]:
+    """Why the steps that carry `step` cannot be speculative on an engine built with the SpecConfig `spec` (None: without one), in slot
+    mode or not, recording log-probabilities or not; None: they can.  A draft row sees the logits of its own position only: the
+    passes that carry state from token to token (the penalties' counts, min_tokens) or record per step (log-probabilities)
+    would need that state per draft.  A guide's DFA state is had per draft (kr_spec_guide_*) where the engine was built with
+    SpecConfig(guided=True), the sampler's counts and stop entries (kr_spec_controls_*, the _rows launches) where it was built
+    with SpecConfig(controls=True), a record per emitted token (kr_logprobs_topk_rows) where it was built with
+    SpecConfig(logprobs=True)."""
+    if spec is None:
+        return "the engine was built without speculative=SpecConfig(...)"
+    if not slot_mode:
+        return "speculative steps run in slot mode (begin_slots)"
+    controlled = (step.processing or step.adjust) and not spec.controls
+    if spec.guided:
+        if controlled:
+            return "the step carries sampling controls or logit adjustments"
+    elif step.guided or controlled:
+        return ("the step carries guided decoding, sampling controls or logit adjustments"
+                + (" (guided requests speculate on an engine built with SpecConfig(guided=True))" if step.guided else ""))
+    if recording and not spec.logprobs:
+        return "log-probabilities are recorded"
+    return None
+
+
 REPETITION_KEYS = ("max_pattern_size", "min_pattern_size", "min_count", "min_span")
 
 

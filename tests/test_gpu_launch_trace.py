@@ -1,13 +1,16 @@
 """The engine issues the launches it issued when tests/golden/launch_trace.json was recorded: the same entry points in the same
 order with the same arguments (tests/launch_trace.py), over whole-batch generation with and without sampling controls and a
 guide, slot mode with every kind of admission, the packed 17..32-row family on bf16 and fp8 weights, and speculative steps;
-and over the same scenarios with the fp8 KV cache (a calibrating admission, pinned scales, the fork, both row maps).
+over the same scenarios with the fp8 KV cache (a calibrating admission, pinned scales, the fork, both row maps); and over
+speculative steps in both row layouts with guided requests, sampling controls, logit adjustments, log-probabilities and the
+repetition pass.
 A change that only moves host code leaves every trace as it is; one that adds, drops, reorders or re-parameterises a launch
 fails here with the first call that differs.
 
 The fixture is recorded by `python -m tests.test_gpu_launch_trace` on a tree whose launches are the wanted ones (it was made
 on the commit before engine.py was split into modules; the fp8-cache keys were added on the commit before the KV cache moved
-into kv_cache.py, with every older key unchanged)."""
+into kv_cache.py, and the h_ / i_ keys on the commit before the speculative step moved into speculative.py, each time with
+every older key unchanged)."""
 import hashlib
 import json
 import os
@@ -20,6 +23,7 @@ pytestmark = pytest.mark.gpu
 
 from karanta_ocr_amd.config import CONFIGS  # noqa: E402
 from karanta_ocr_amd.engine import Engine, SpecConfig  # noqa: E402
+from karanta_ocr_amd.sampling import RepetitionParams, StepFeatures  # noqa: E402
 from karanta_ocr_amd.weights import random_weights  # noqa: E402
 from tests.launch_trace import canonical, digest, launch_trace, names  # noqa: E402
 from tests.test_gpu_engine import GUIDE_PATTERN  # noqa: E402
@@ -141,9 +145,87 @@ def group_kv8_spec():
     return group_spec(key="g_kv8_spec", kv_cache_dtype="fp8")
 
 
+SPEC_FULL = ("kr_spec_guide_trim", "kr_spec_guide_rows", "kr_spec_guide_advance", "kr_spec_controls_trim", "kr_spec_controls_rows",
+             "kr_spec_controls_count", "kr_logits_adjust_rows", "kr_sample_threshold_rows", "kr_gumbel_argmax_processed_rows",
+             "kr_logits_restore_rows", "kr_logprobs_topk_rows")
+ALL_PASSES = StepFeatures(True, True, True, True, True)
+
+
+def _full_pages(cfg):
+    """One page per feature of a speculative step: greedy, controls + adjustments, a guide, stop entries + repetition."""
+    return [page_of(cfg, 40, variant=0),
+            page_of(cfg, 64, variant=1, temperature=0.7, top_k=5, repetition_penalty=1.1, logit_bias={3: 1.0}, seed=5),
+            page_of(cfg, 100, variant=2, guide=GUIDE_PATTERN),
+            page_of(cfg, 40, variant=3, min_tokens=2, stop_token_ids=(7, 9), repetition=RepetitionParams(8, 2, 5))]
+
+
+def _spec_engine(max_batch, **options):
+    from karanta_ocr_amd.serving import ByteTokenizer
+    eng = _engine("tiny-w512", max_batch=max_batch, speculative=SpecConfig(3, 2, 4, **options))
+    eng.set_vocab(ByteTokenizer(eng.cfg).token_bytes())
+    return eng
+
+
+def _spec_steps(eng, pages, **mode):
+    """The calls of group_spec: one admission, a scripted slot, two speculative steps (eager, then the captured graph) and a
+    plain one.  Returns the step features the admission left."""
+    eng.begin_slots(16, **mode)
+    eng.admit(pages, list(range(len(pages))))
+    eng.set_draft_script(1, [7, 8, 9, 10, 11, 12, 13, 14])
+    step = eng._step
+    eng.decode_steps(2, speculative=True)
+    eng.decode_steps(1)
+    return step
+
+
+def _assert_full(calls, step):
+    """Every pass on: the eleven launches only such a step issues, and the repetition pass last in each speculative step."""
+    got = names(calls)
+    assert step == ALL_PASSES, step
+    assert not set(SPEC_FULL) - set(got), sorted(set(SPEC_FULL) - set(got))
+    ends = [got[i + 1] for i, n in enumerate(got) if n == "kr_spec_guide_advance"]
+    assert len(ends) == 2 and set(ends) == {"kr_repeat_detect"}, ends     # the eager step and the captured one
+
+
+def group_spec_full():
+    """h: the static layout with every option on.  h_spec_full: all five passes; h_spec_mark: a recording step without a trim."""
+    eng, out, seen = _spec_engine(4, guided=True, controls=True, logprobs=True), {}, {}
+    _traced(eng, out, "h_spec_full",
+            lambda: seen.update(step=_spec_steps(eng, _full_pages(eng.cfg), sampling=True, guided=True, logprobs=2)))
+    _assert_full(out["h_spec_full"], seen["step"])
+    assert "kr_spec_propose" in names(out["h_spec_full"]) and "kr_spec_mark" not in names(out["h_spec_full"])
+    warm = [page_of(eng.cfg, LENGTHS[b % 3], variant=b, temperature=0.7, seed=b) for b in range(4)]
+    _traced(eng, out, "h_spec_mark", lambda: _spec_steps(eng, warm, sampling=True, logprobs=2))
+    spec = [n for n in names(out["h_spec_mark"]) if n.startswith("kr_spec_")]
+    assert spec[:2] == ["kr_spec_mark", "kr_spec_propose"] and not any("trim" in n for n in spec), spec
+    assert "kr_logprobs_topk_rows" in names(out["h_spec_mark"]) and "kr_logits_restore_rows" not in names(out["h_spec_mark"])
+    eng.close()
+    return out
+
+
+def group_spec_shared():
+    """i: the dealt layout (nine slots, 32 rows).  i_spec_shared: greedy pages; i_spec_shared_full: every option on — the trims
+    write d_nwant and the row-mapped launches take d_draft_row."""
+    eng, out, seen = _spec_engine(9, share_rows=True), {}, {}
+    greedy = [page_of(eng.cfg, LENGTHS[b % 3], variant=b) for b in range(9)]
+    _traced(eng, out, "i_spec_shared", lambda: _spec_steps(eng, greedy))
+    got = names(out["i_spec_shared"])
+    assert {"kr_spec_lookup", "kr_spec_deal", "kr_spec_accept_rows"} <= set(got) and "kr_spec_propose" not in got
+    eng.close()
+    eng = _spec_engine(9, share_rows=True, guided=True, controls=True, logprobs=True)
+    pages = _full_pages(eng.cfg) + greedy[4:]
+    _traced(eng, out, "i_spec_shared_full",
+            lambda: seen.update(step=_spec_steps(eng, pages, sampling=True, guided=True, logprobs=2)))
+    _assert_full(out["i_spec_shared_full"], seen["step"])
+    got = names(out["i_spec_shared_full"])
+    assert {"kr_spec_lookup", "kr_spec_deal", "kr_spec_accept_rows"} <= set(got) and "kr_spec_propose" not in got
+    eng.close()
+    return out
+
+
 GROUPS = {"tiny": group_tiny, "rows32_bf16": group_rows32_bf16, "rows32_fp8": group_rows32_fp8, "spec": group_spec,
           "kv8_tiny": group_kv8_tiny, "kv8_rows32_bf16": group_kv8_rows32_bf16, "kv8_rows32_fp8": group_kv8_rows32_fp8,
-          "kv8_spec": group_kv8_spec}
+          "kv8_spec": group_kv8_spec, "spec_full": group_spec_full, "spec_shared": group_spec_shared}
 
 
 def _arg_digests(calls):
